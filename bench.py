@@ -8,6 +8,12 @@
                                                             fans out to every device from one call, emb_host.h:258-321)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (launched ranks: RANK /
                                                             WORLD_SIZE in the environment, no further fan-out)
+    python bench.py --gpus 1 ... --full                     (N=1: also the CPU baselines, the cold timing without pre-warm and
+                                                            the bit-exact check of every rotating batch the timed loop wrote)
+    python bench.py --gpus 1 ... --dump-outputs DIR         (N=1: the last timed step's pooled rows as DIR/<name>.npy, float32)
+
+A plain N=1 run sets up, pre-warms, runs the W warm-up and the K timed steps and prints the line; whatever else the
+benchmark measures or checks runs only with --full.
 
 A "step" is one pass of the hot path over one batch of synthetic input: the fused multi-table
 EmbeddingBag(sum) lookup (libpimemb.so, HIP) for the 26 Criteo-Kaggle tables, dim 16 fp32,
@@ -112,7 +118,16 @@ def parse_args():
                          "(emb_queue_*: R x add + ONE flush = one fused launch) instead of one prepared plan per step -- the "
                          "reference's serving shapes (--workload c1: mini-batch 1; --batch 32 / 512) are launch-bound one by one; "
                          "0 = off.  The line also carries the back-to-back figure (R separate launches) it is to be compared with")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also measure and check what the headline figure does not need -- the CPU baselines (oracle and "
+                         "torch CPU EmbeddingBag), the same W / K steps before the pre-warm (value_cold), and every rotating "
+                         "batch's outputs against an in-order torch gather-sum and the oracle (verified).  The prepared-plan path only: --coalesce "
+                         "runs its one-by-one leg and its checks either way, and so does N>1 with all its legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: after the timed steps, write what the last one computed -- the pooled rows a caller receives, one "
+                         "array per table (per request and table with --coalesce) -- as DIR/<name>.npy in float32, at most 64 MB in "
+                         "all (beyond that, the same seeded sample of bags of every table)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     return ap.parse_args()
 
@@ -595,6 +610,29 @@ def cpu_baseline_torch(host_tables, batch, seconds, ncores):
                       f"{el1:.1f} s (1 thread) + {elm:.1f} s ({ncores} threads)"}
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6      # --dump-outputs: every file together, headers included
+
+
+def dump_outputs(out_dir, named, seed=0):
+    """--dump-outputs: `named` = [(name, (bags, dim) tensor)] as the timed path's last step left them, written as
+    out_dir/<name>.npy in float32.  Above DUMP_LIMIT_BYTES in all, every array keeps the same fraction of its bags, picked by
+    a generator seeded with `seed` from (bags, kept) alone: the same bags on every run and every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() * 4 for _, t in named)
+    frac = min(1.0, (DUMP_LIMIT_BYTES - 1024 * len(named)) / max(total, 1))     # (an .npy header takes 128 bytes)
+    picks = {}
+    for name, t in named:
+        a = t.float().cpu().numpy()
+        if frac < 1.0:
+            n = a.shape[0]
+            k = int(n * frac)
+            if (n, k) not in picks:
+                picks[(n, k)] = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+            a = a[picks[(n, k)]]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": out_dir, "arrays": len(named), "bags_kept_fraction": frac, "sample_seed": seed}
+
+
 def verify_last_batch(torch, eng, plan, d_idx, L, n_sample=32, seed=7):
     """What the timed loop left in the output buffers of its LAST batch, checked after the timed region:
     (1) every bag of every table against an independent torch gather on the GPU, summed in index order
@@ -637,7 +675,7 @@ def run_single(args):
     rows_list, dim, B = spec["rows"], spec["dim"], spec["B"]
     T = len(rows_list)
     eng = pel.EmbeddingEngine(device=0, max_tables=T)
-    want_cpu = not args.no_cpu_baseline
+    want_cpu = args.full and not args.no_cpu_baseline
     n_host = T if args.workload in ("c1", "c2") else 2        # c3: 5 GB per table, sample two on the host
     host_tables = make_tables_on_gpu(torch, eng, rows_list, dim, dev, keep_host=n_host if want_cpu else 0,
                                      dtype=spec.get("dtype", "f32"))
@@ -689,8 +727,8 @@ def run_single(args):
         return t_sync, t_event, ev0.elapsed_time(ev1)
 
     # The same W / K shape on the chip as a fresh process finds it (idle clocks), reported next to the headline number:
-    # the driver's default run is W = 5 / K = 20, 0.5 ms in all.
-    cold_sync, _cold_event, cold_ms = timed_region() if args.prewarm_ms > 0 else (None, None, None)
+    # the driver's default run is W = 5 / K = 20, 0.5 ms in all.  (--full only)
+    cold_sync, _cold_event, cold_ms = timed_region() if args.full and args.prewarm_ms > 0 else (None, None, None)
     # Device pre-warm (untimed, before the W warm-up steps): ~0.25 s of the same launches brings the chip to the state a
     # serving loop is in; the W warm-up steps and the EXACTLY K timed steps follow unchanged.
     t_pre = time.perf_counter()
@@ -712,13 +750,18 @@ def run_single(args):
     wall, wall_event, dev_ms = timed_region(graph)
     kernel_us = dev_ms * 1000.0 / args.steps          # avg launch duration on the launch stream
 
-    # what was just timed, checked outside the timed region: every bag of EVERY rotating batch the timed loop wrote (all
+    dumped = None
+    if args.dump_outputs:                # the last timed step's outputs (its plan's buffers: nothing has written them since)
+        last = plans[(args.steps - 1) % len(plans)]
+        dumped = dump_outputs(args.dump_outputs, [("table_%02d" % t, o) for t, o in enumerate(last.outputs)])
+
+    # --full: what was just timed, checked outside the timed region: every bag of EVERY rotating batch the timed loop wrote (all
     # NBATCH plans' output buffers, not only the last one's) bit for bit against an in-order torch gather-sum, plus the
     # oracle on a sample of bags per table
     touched = sorted({(args.steps - 1 - j) % len(plans) for j in range(min(args.steps, len(plans)))}) if args.steps > 0 else [0]
     n_checked = 0
     try:
-        for q in touched:
+        for q in (touched if args.full else []):
             n_checked += verify_last_batch(torch, eng, plans[q], plan_idx[q], spec["L"])
     except AssertionError as ex:
         print(f"bench.py: VERIFICATION FAILED: {ex}", file=sys.stderr, flush=True)
@@ -743,10 +786,12 @@ def run_single(args):
         "value_sync": args.steps * n_bags / wall, "value_event": args.steps * n_bags / wall_event,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": spec.get("dtype", "f32"), "data": "synthetic",
-        "verified": True,
+        # None: not checked (a plain run; --full checks)
+        "verified": True if args.full else None,
         "verify": {"bags_bit_exact_vs_torch_gather": n_checked, "oracle_sample_bags_per_table": 32, "batches_checked": len(touched),
                    "what": "outputs of every rotating batch the timed loop wrote (%d of %d plans), all %d tables, after the timed region"
-                           % (len(touched), len(plans), T)},
+                           % (len(touched), len(plans), T)} if args.full else
+                  {"what": "not checked: a plain run times the steps only (--full checks every rotating batch's outputs)"},
         # the same W warm-up + K timed steps measured BEFORE the device pre-warm (a fresh process, idle clocks): `value` is the
         # warmed figure, this the cold one
         "value_cold": None if cold_sync is None else args.steps * n_bags / cold_sync,
@@ -775,6 +820,8 @@ def run_single(args):
     if launch_id:               # (scalars: a record that keeps only scalar members of `roofline` keeps them)
         result["roofline"].update(kernel_symbol=launch_id["kernel_symbol"], kernel_sha256=launch_id["kernel_sha256"],
                                   launch_signature=launch_id["launch_signature"], device_code_sha256=launch_id["device_code_sha256"])
+    if dumped:
+        result["config"]["dumped_outputs"] = dumped
     if want_cpu:
         result["cpu_baseline"] = cpu_baseline(pel, host_tables, batches[0], args.cpu_seconds)
     # key order as on the N > 1 lines: objects first, scalars after them, the contract's keys last (a record that keeps only the
@@ -868,6 +915,11 @@ def run_coalesced(args):
             for o in rq["plan"].outputs:
                 o.fill_(float("nan"))
     wall_q, dev_q = timed(step_queue)
+    dumped = None
+    if args.dump_outputs:                # the last queued step's R requests (the queue wrote the slot's plan outputs)
+        dumped = dump_outputs(args.dump_outputs, [("request_%d_table_%02d" % (r, t), o)
+                                                  for r, rq in enumerate(slots[(args.steps - 1) % nslots])
+                                                  for t, o in enumerate(rq["plan"].outputs)])
     n_checked = 0
     try:
         for reqs in slots[:min(nslots, args.steps)]:
@@ -900,6 +952,8 @@ def run_coalesced(args):
                    "parallelism": "single"},
         "roofline": roofline_object(alg_bytes * R, dev_q * 1e6 / args.steps, None, None),
     }
+    if dumped:
+        result["config"]["dumped_outputs"] = dumped
     print(json.dumps(result))
     for reqs in slots:
         for rq in reqs:
@@ -980,10 +1034,13 @@ def self_launch(n_ranks: int, argv, script: str | None = None) -> int:
 def main():
     args = parse_args()
     launched = "WORLD_SIZE" in os.environ or "RANK" in os.environ
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    dist = args.gpus > 1 or world > 1 or os.environ.get("PIMEMB_FORCE_DIST") == "1"    # last: 1-rank RCCL rehearsal
+    if args.dump_outputs and dist:
+        sys.exit("bench.py: --dump-outputs is for single-GPU runs (--gpus 1)")
     if args.gpus > 1 and not launched:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if args.gpus > 1 or world > 1 or os.environ.get("PIMEMB_FORCE_DIST") == "1":   # last: 1-rank RCCL rehearsal
+    if dist:
         from importlib import import_module
         import_module("pim-embedding-lookup_amd.dist_bench").run(args, HBM_PEAK_GBS)
     elif args.coalesce > 0:

@@ -299,3 +299,42 @@ def test_the_n_gt_1_line_survives_the_drivers_record():
     res2["config"]["exchange_peer"] = {"skipped": "no fine-grained arena"}
     c2 = db.driver_record_stand_in(json.dumps(db.driver_proof(res2)))["parsed"]["config"]
     assert c2["exchange_peer_skipped"] == "no fine-grained arena" and "exchange_peer_value" not in c2
+
+
+def test_plain_run_options_and_full_switch(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the K steps only: --full (off by default) adds the CPU baselines, the
+    cold timing and the checks of the timed outputs; --dump-outputs names the directory of the last step's outputs."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse_args()
+    assert a.steps == 7 and a.warmup == 3 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "some/dir"])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == "some/dir"
+
+
+def test_dump_outputs_writes_float32_within_the_limit_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per output; above the size limit every array keeps the same seeded bags, so two runs (or two
+    builds) are compared output for output."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(3)
+    outs = [torch.from_numpy(rng.standard_normal((1000, 16)).astype(np.float32)) for _ in range(3)]
+    named = [("table_%02d" % t, o) for t, o in enumerate(outs)]
+    info = bench.dump_outputs(str(tmp_path / "all"), named)
+    assert info["bags_kept_fraction"] == 1.0 and info["arrays"] == 3
+    for t, o in enumerate(outs):
+        got = np.load(tmp_path / "all" / ("table_%02d.npy" % t))
+        assert got.dtype == np.float32 and np.array_equal(got, o.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100_000)          # 3 x 64 kB of rows: a sample has to be kept
+    for d in ("a", "b"):
+        info = bench.dump_outputs(str(tmp_path / d), named)
+        assert 0 < info["bags_kept_fraction"] < 1
+    sizes = sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir())
+    assert sizes <= 100_000
+    for t in range(3):
+        a, b = np.load(tmp_path / "a" / ("table_%02d.npy" % t)), np.load(tmp_path / "b" / ("table_%02d.npy" % t))
+        assert a.dtype == np.float32 and a.shape[1] == 16 and 0 < a.shape[0] < 1000 and np.array_equal(a, b)
+        # the kept rows are rows of the output, in bag order
+        full = outs[t].numpy()
+        pos = [int(np.flatnonzero((full == r).all(axis=1))[0]) for r in a]
+        assert pos == sorted(pos)

@@ -2466,3 +2466,59 @@ def test_big_host_pointer_call_in_two_parts(pel, oracle, dim, bags):
         for t in range(len(bags)):
             assert np.array_equal(outs[t], oracle.c_bag_sum(tabs[t], idx[t], off[t])), (dim, t, itype)
     e.close()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_what_the_last_step_computed(tmp_path):
+    """`bench.py --gpus 1`: a plain run launches exactly K timed steps after its W warm-up ones and checks nothing; the outputs
+    of its last step (--dump-outputs) are the rows of the batch that step used -- gathered here from the same seeded tables and
+    indices, bit for bit -- and equal those of a --full run, whose timed outputs bench.py itself checked.  The plain run spends
+    well under 30 s outside its steps."""
+    import argparse
+    import json
+    import subprocess
+    import sys
+    import time
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    import pim_embedding_lookup_amd as pel
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "PIMEMB_FORCE_DIST"):
+        env.pop(k, None)
+    K, W, B, NB = 5, 2, 4096, 3
+    common = ["--gpus", "1", "--steps", str(K), "--warmup", str(W), "--batch", str(B), "--nbatch", str(NB), "--prewarm-ms", "20"]
+    lines, walls = {}, {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        t0 = time.perf_counter()
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra + ["--dump-outputs", str(tmp_path / mode)],
+                             env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        walls[mode] = time.perf_counter() - t0
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        lines[mode] = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    p, f = lines["plain"], lines["full"]
+    assert p["steps"] == K and p["ms_per_step"] > 0 and p["unit"] == "pooled-lookups/s" and p["dtype"] == "f32"
+    assert p["verified"] is None and p["value_cold"] is None and "cpu_baseline" not in p
+    assert f["verified"] is True and f["verify"]["bags_bit_exact_vs_torch_gather"] == 26 * B * NB and f["value_cold"] is not None
+    # every lookup launch of the process: the pre-warm, then W + K (plain) -- and the cold W + K before the pre-warm (--full)
+    assert sum(p["config"]["launches_by_kind"]) == p["config"]["prewarm_launches"] + W + K
+    assert sum(f["config"]["launches_by_kind"]) == f["config"]["prewarm_launches"] + 2 * (W + K)
+    assert walls["plain"] - (W + K) * p["ms_per_step"] / 1000.0 < 30.0, walls
+    # the last step's batch (step i uses batch i % NB), its rows gathered from the tables bench.py generates
+    spec = bench.workload_spec(pel, argparse.Namespace(workload="c2", batch=B, index_dist=None, index_order="drawn"))
+    idx = bench.make_batches(pel, spec, NB)[(K - 1) % NB][0]
+    others = [bench.make_batches(pel, spec, NB)[j][0] for j in range(NB) if j != (K - 1) % NB]
+    want, other_rows = {}, {}
+
+    class Gather:                 # stands in for the engine: keeps the rows the batches name, not the 2 GB of tables
+        def load_table(self, t, w):
+            want[t] = w[torch.from_numpy(idx[t].astype(np.int64)).to(w.device)].cpu().numpy()
+            other_rows[t] = [w[torch.from_numpy(o[t].astype(np.int64)).to(w.device)].cpu().numpy() for o in others]
+
+    bench.make_tables_on_gpu(torch, Gather(), spec["rows"], spec["dim"], torch.device("cuda", 0))
+    for t in range(26):
+        a = np.load(tmp_path / "plain" / ("table_%02d.npy" % t))
+        b = np.load(tmp_path / "full" / ("table_%02d.npy" % t))
+        assert a.dtype == np.float32 and a.shape == (B, 16) and np.array_equal(a, b), t
+        assert np.array_equal(a, want[t]), t
+        assert not any(np.array_equal(a, o) for o in other_rows[t]), t

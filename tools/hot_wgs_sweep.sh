@@ -8,7 +8,7 @@ out=${1:-gpurun_out/hot_wgs_sweep.log}
 : > "$out"
 for hot in 32 100; do
   for total in 4096 8192 16384 24576 49152; do
-    line=$(PIMEMB_HOT_WGS_TOTAL=$total python3 bench.py --workload c3 --hot-rows $hot --steps 60 --warmup 10 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1)
+    line=$(PIMEMB_HOT_WGS_TOTAL=$total python3 bench.py --workload c3 --hot-rows $hot --steps 60 --warmup 10 --full --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1)
     python3 -c "
 import json, sys
 d = json.loads(sys.argv[1])

@@ -3,7 +3,7 @@
 # usage: run_all_benches.sh <out-dir>      (run from the repository root on a GPU box)
 out=${1:-gpurun_out/benches}
 mkdir -p "$out"
-run() { key=$1; shift; python3 bench.py --no-cpu-baseline "$@" 2>/dev/null | grep '^{' | tail -1 > "$out/bench_$key.json"; }
+run() { key=$1; shift; python3 bench.py --full --no-cpu-baseline "$@" 2>/dev/null | grep '^{' | tail -1 > "$out/bench_$key.json"; }
 run c2
 run c2-zipf --index-dist zipf
 run c1 --workload c1
