@@ -267,6 +267,38 @@ int emb_plan_describe(const emb_plan *p, char *buf, size_t capacity);
  * *avg_us = mean device time per launch. */
 int emb_plan_time(emb_plan *p, void *stream, uint32_t warmup, uint32_t iters, float *avg_us);
 
+/* ---- pooled lookups: nn.EmbeddingBag's mean / max modes, per_sample_weights and padding_idx ------------------------------
+ * One emb_pool_spec per descriptor, in a parallel array.  Results equal torch's CPU F.embedding_bag bit for bit (fp16 tables:
+ * on the rows widened to fp32; output fp32 as always): entries are taken in index order from +0; a weighted sum without
+ * padding is acc = fmaf(w, x, acc), with padding acc = acc + (w * x) with the product rounded on its own; mean is the sum over
+ * the non-padding entries divided (IEEE division) by their count; max starts at the first non-padding row and keeps the first
+ * of equal values (strict >); an empty bag, or one of padding only, gives +0.  NaN ordering is out of scope.
+ *   - per_sample_weights: float[n_indices] in the same memspace as the indices, SUM only (as in torch); or NULL.
+ *   - padding_idx (flags & EMB_POOL_PADDING): a row id in [0, nr_rows) whose entries are skipped (EMB_ERR_INVALID outside).
+ *   - EMB_FIXED32 tables keep plain sum: any other spec on them is EMB_ERR_UNSUPPORTED.
+ * pools == NULL, or a spec of plain SUM without weights or padding, takes exactly emb_lookup_batched's path (same kernels; a
+ * plan's emb_plan_signature equals emb_plan_create's).  Descriptors of one call may mix modes and name a table twice; launches
+ * are grouped by (dtype, dim, pooling mode) and run the bag_pool_* kernels -- never the hot-row kernel.
+ * check: 0 unchecked, 1 as emb_lookup_batched_checked (*n_bad may be NULL), 2 deferred as emb_lookup_batched_checked_deferred
+ * (DEVICE buffers; a HOST call is checked synchronously).  HOST calls stage the weights with the indices.  The ranged, counted
+ * and sharded calls and the request queue stay sum-only. */
+#define EMB_POOL_SUM 0u
+#define EMB_POOL_MEAN 1u
+#define EMB_POOL_MAX 2u
+#define EMB_POOL_PADDING 1u            /* emb_pool_spec.flags: padding_idx is live */
+typedef struct emb_pool_spec {
+    uint32_t mode;                     /* EMB_POOL_* */
+    uint32_t flags;
+    const float *per_sample_weights;   /* float[n_indices], same memspace as the indices, or NULL (SUM only) */
+    int64_t padding_idx;               /* row id in [0, nr_rows) */
+} emb_pool_spec;
+int emb_lookup_pooled(emb_engine *e, const emb_lookup_desc *descs, const emb_pool_spec *pools, uint32_t n_descs,
+                      emb_index_type itype, emb_memspace space, void *stream, uint32_t check, uint64_t *n_bad);
+/* The same as a prepared launch over DEVICE buffers (weights included); emb_plan_bytes adds 4 * n_indices per weighted
+ * descriptor, emb_plan_describe adds pool=<EMB_POOL_*> weighted=<descriptors> padding=<descriptors> to a pooled launch. */
+int emb_plan_create_pooled(emb_engine *e, const emb_lookup_desc *descs, const emb_pool_spec *pools, uint32_t n_descs,
+                           emb_index_type itype, emb_plan **out);
+
 /* Debug-only input check (the reference never checks: an out-of-range index is a wild MRAM read,
  * emb_dpu_lookup.c:113).  Counts indices >= nr_rows and non-monotone / out-of-range offsets over
  * DEVICE or HOST buffers; returns EMB_ERR_RANGE if *n_bad > 0.  (*n_bad, here and below, counts up to 16 777 215 and stays there.) */

@@ -19,6 +19,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <utility>
 #include <unordered_map>
 #include <vector>
@@ -233,6 +234,8 @@ struct PlanGroup {
     uint32_t hot_lds = 0;            // KERNEL_HOT: dynamic LDS bytes (largest hot set of the group)
     uint32_t *cached_xmap = nullptr; // transient launches: map owned by the engine's cache (not in the image)
     bool ranged = false;             // descriptors serve a row range each (emb_lookup_ranged / emb_plan_create_ranged)
+    uint32_t pool = 0;               // 0: plain sum (bag_sum_*); else 1 + EMB_POOL_* of a pooled launch (bag_pool_*)
+    uint32_t n_weighted = 0, n_padding = 0;   // pooled launch: descriptors with per-sample weights / a padding_idx
     size_t desc_off = 0, xmap_off = 0;  // byte offsets of this group's pieces in the launch image
     std::vector<uint32_t> xmap_words;
 };
@@ -434,6 +437,11 @@ int cached_xcd_map(emb_engine *e, PlanGroup &g, uint32_t bpt, const std::vector<
     return EMB_OK;
 }
 
+// A pooling spec that asks for nothing but what emb_lookup_batched does.
+bool is_plain_sum(const emb_pool_spec &ps) {
+    return ps.mode == EMB_POOL_SUM && ps.per_sample_weights == nullptr && ps.flags == 0;
+}
+
 // st_indices / st_offsets / st_out: if non-null, per-descriptor device pointers that replace the
 // caller's (the staged copies of a host-pointer call).
 // row_lo: if non-null, a RANGED launch -- descriptor i serves only the bags whose row falls into
@@ -444,9 +452,11 @@ int cached_xcd_map(emb_engine *e, PlanGroup &g, uint32_t bpt, const std::vector<
 int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_index_type itype,
             const std::vector<const void *> *st_indices, const std::vector<const void *> *st_offsets,
             const std::vector<float *> *st_out, Resolved *r, bool cache_maps = false, const uint64_t *row_lo = nullptr,
-            uint32_t *const *served = nullptr) {
+            uint32_t *const *served = nullptr, const emb_pool_spec *pools = nullptr,
+            const std::vector<const float *> *st_weights = nullptr) {
     if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "bad index type");
-    std::map<std::pair<int, uint32_t>, std::vector<uint32_t>> by_shape;
+    // (dtype, dim, pooling kind): kind 0 = plain sum, the key every call without pooling specs has
+    std::map<std::tuple<int, uint32_t, uint32_t>, std::vector<uint32_t>> by_shape;
     for (uint32_t i = 0; i < n_descs; i++) {
         const emb_lookup_desc &u = descs[i];
         if (u.table_id >= e->tables.size() || e->tables[u.table_id].rows == nullptr)
@@ -467,12 +477,28 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
             if (t.geom.scalar_lanes)
                 return fail(EMB_ERR_UNSUPPORTED, "ranged lookup: desc %u: rows must be 16-byte multiples up to 1 KiB", i);
         }
-        by_shape[{(int)t.dtype, t.dim}].push_back(i);
+        uint32_t pool_kind = 0;
+        if (pools && !is_plain_sum(pools[i])) {
+            const emb_pool_spec &ps = pools[i];
+            if (ps.mode > EMB_POOL_MAX || (ps.flags & ~EMB_POOL_PADDING) != 0)
+                return fail(EMB_ERR_INVALID, "desc %u: bad pooling spec (mode %u, flags 0x%x)", i, ps.mode, ps.flags);
+            if (ps.per_sample_weights != nullptr && ps.mode != EMB_POOL_SUM)
+                return fail(EMB_ERR_INVALID, "desc %u: per_sample_weights need EMB_POOL_SUM (as in torch)", i);
+            if (t.dtype == EMB_FIXED32)
+                return fail(EMB_ERR_UNSUPPORTED, "desc %u: fixed-point tables pool by plain sum only", i);
+            if ((ps.flags & EMB_POOL_PADDING) && (ps.padding_idx < 0 || (uint64_t)ps.padding_idx >= t.nr_rows))
+                return fail(EMB_ERR_INVALID, "desc %u: padding_idx %lld outside table %u (%llu rows)", i, (long long)ps.padding_idx,
+                            u.table_id, (unsigned long long)t.nr_rows);
+            if (row_lo) return fail(EMB_ERR_UNSUPPORTED, "ranged lookups pool by plain sum only");
+            pool_kind = 1u + ps.mode;
+        }
+        by_shape[{(int)t.dtype, t.dim, pool_kind}].push_back(i);
     }
     const size_t isz = index_size(itype);
     for (auto &kv : by_shape) {
         PlanGroup g;
-        g.dtype = (emb_dtype)kv.first.first;
+        g.dtype = (emb_dtype)std::get<0>(kv.first);
+        g.pool = std::get<2>(kv.first);
         g.n = (uint32_t)kv.second.size();
         const Table &t0 = e->tables[descs[kv.second[0]].table_id];
         g.geom = t0.geom;
@@ -489,7 +515,8 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
         }
         g.ranged = row_lo != nullptr;
         if (g.ranged && g.kind == pimemb::KERNEL_GROUP) g.kind = pimemb::KERNEL_WAVEBATCH;    // (small launches too: the predicate lives there)
-        if (g.kind == pimemb::KERNEL_GROUP) {   // pooled launch over tables with a hot-row set: LDS-staged kernel
+        if (g.pool && g.kind == pimemb::KERNEL_WAVEBATCH2) g.kind = pimemb::KERNEL_WAVEBATCH;  // (the pooled family has one wave-batch geometry)
+        if (g.kind == pimemb::KERNEL_GROUP && !g.pool) {   // (a pooled launch never takes the hot-row kernel)   // pooled launch over tables with a hot-row set: LDS-staged kernel
             for (uint32_t i : kv.second) {
                 const Table &t = e->tables[descs[i].table_id];
                 if (t.n_hot && t.hot_lds > g.hot_lds) g.hot_lds = (uint32_t)t.hot_lds;
@@ -516,6 +543,20 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
             d.n_tiles = (uint32_t)tiles;
             if (row_lo) d.pad_[0] = row_lo[i];
             if (row_lo && served) d.pad_[1] = (uint64_t)(uintptr_t)served[i];
+            if (g.pool) {           // the pooling spec rides in pad_ (pimemb_bag_kernels.h: pool_args)
+                const emb_pool_spec &ps = pools[i];
+                const bool weighted = ps.per_sample_weights != nullptr, padded = (ps.flags & EMB_POOL_PADDING) != 0;
+                const uint32_t op = ps.mode == EMB_POOL_MAX ? pimemb::kPoolOpMax
+                                    : !weighted          ? pimemb::kPoolOpAdd
+                                    : padded             ? pimemb::kPoolOpMulAdd
+                                                         : pimemb::kPoolOpFma;
+                d.pad_[0] = (uint64_t)(uintptr_t)(st_weights && weighted ? (*st_weights)[i] : ps.per_sample_weights);
+                d.pad_[1] = padded ? (uint64_t)ps.padding_idx : ~0ull;
+                d.pad_[2] = op | (ps.mode == EMB_POOL_MEAN ? pimemb::kPoolMean : 0u);
+                g.n_weighted += weighted;
+                g.n_padding += padded;
+                if (weighted) r->bytes += u.n_indices * 4;
+            }
             if (g.kind == pimemb::KERNEL_HOT) {
                 d.hot_rows = t.hot_rows;
                 d.hot_hash = t.hot_hash;
@@ -585,7 +626,10 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
 int launch_groups(emb_engine *e, const std::vector<PlanGroup> &groups, emb_index_type itype,
                   hipStream_t s) {
     for (const PlanGroup &g : groups) {
-        if (g.kind == pimemb::KERNEL_HOT)
+        if (g.pool)
+            HIP_TRY(pimemb::launch_bag_pool(g.d_descs, g.n, g.max_tiles, g.dtype, itype, g.geom, g.kind, g.d_xmap, g.xgrid,
+                                            g.xdirect, s));
+        else if (g.kind == pimemb::KERNEL_HOT)
             HIP_TRY(pimemb::launch_bag_sum_hot(g.d_descs, g.n, g.hot_wgs, g.hot_lds, g.dtype, itype, g.geom, s));
         else
             HIP_TRY(pimemb::launch_bag_sum(g.d_descs, g.n, g.max_tiles, g.dtype, itype, g.geom, g.kind, g.d_xmap,
@@ -714,6 +758,7 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // Synchronous, like the reference's lookup (emb_host.h:350 dpu_sync before return).
 struct HostStage {
     std::vector<const void *> d_indices, d_offsets;
+    std::vector<const float *> d_weights;   // pooled calls: staged per-sample weights (nullptr: none)
     std::vector<float *> d_out;
     size_t in_bytes = 0, out_bytes = 0;
     char *h_out = nullptr;  // pinned landing zone for small results (null if not reserved)
@@ -739,7 +784,8 @@ static const size_t kFastPieceBytes = getenv("PIMEMB_FAST_PIECE_BYTES") ? strtou
 static const size_t kSplitInBytes = getenv("PIMEMB_HOST_SPLIT_BYTES") ? strtoull(getenv("PIMEMB_HOST_SPLIT_BYTES"), nullptr, 10) : (1u << 20);
 
 int stage_host_inputs(emb_engine *e, const emb_lookup_desc *descs, uint32_t n, emb_index_type itype,
-                      hipStream_t s, HostStage *hs, bool with_outputs, bool allow_zero_copy = false, bool allow_split = false) {
+                      hipStream_t s, HostStage *hs, bool with_outputs, bool allow_zero_copy = false, bool allow_split = false,
+                      const emb_pool_spec *pools = nullptr) {
     const size_t isz = index_size(itype);
     size_t in_bytes = 0, out_bytes = 0, min_piece = SIZE_MAX;
     for (uint32_t i = 0; i < n; i++) {
@@ -747,6 +793,7 @@ int stage_host_inputs(emb_engine *e, const emb_lookup_desc *descs, uint32_t n, e
             return fail(EMB_ERR_INVALID, "desc %u: table %u is not loaded", i, descs[i].table_id);
         in_bytes += align_up(descs[i].n_indices * isz, 16);
         if (descs[i].offsets) in_bytes += align_up(descs[i].n_bags * isz, 16);
+        if (pools && pools[i].per_sample_weights) in_bytes += align_up(descs[i].n_indices * 4, 16);
         const size_t piece = descs[i].n_bags * (size_t)e->tables[descs[i].table_id].dim * 4;
         out_bytes += align_up(piece, 16);
         if (piece && piece < min_piece) min_piece = piece;
@@ -763,9 +810,10 @@ int stage_host_inputs(emb_engine *e, const emb_lookup_desc *descs, uint32_t n, e
     size_t off = 0;
     hs->d_indices.resize(n);
     hs->d_offsets.resize(n);
+    hs->d_weights.assign(n, nullptr);
     hs->d_out.resize(n);
     std::vector<pimemb::CopyPiece> pack;
-    pack.reserve(2 * n);
+    pack.reserve(3 * n);
     for (uint32_t i = 0; i < n; i++) {
         const emb_lookup_desc &u = descs[i];
         if (u.n_indices && !u.indices) return fail(EMB_ERR_INVALID, "desc %u: indices is NULL", i);
@@ -778,6 +826,11 @@ int stage_host_inputs(emb_engine *e, const emb_lookup_desc *descs, uint32_t n, e
             off += align_up(u.n_bags * isz, 16);
         } else {
             hs->d_offsets[i] = nullptr;
+        }
+        if (pools && pools[i].per_sample_weights) {    // weights travel with the indices
+            pack.push_back({e->h_stage + off, pools[i].per_sample_weights, u.n_indices * 4});
+            hs->d_weights[i] = reinterpret_cast<const float *>(in_base + off);
+            off += align_up(u.n_indices * 4, 16);
         }
     }
     e->copier.copy(pack);
@@ -935,24 +988,26 @@ int lookup_host_split(emb_engine *e, const emb_lookup_desc *descs, uint32_t n, e
 // ~2 extra stream waits per call.  (HIP events between the stages were measured too: they push the
 // small copies onto a slower path, +30 us per call on the reference's presets.)
 int lookup_host(emb_engine *e, const emb_lookup_desc *descs, uint32_t n, emb_index_type itype,
-                hipStream_t s) {
+                hipStream_t s, const emb_pool_spec *pools = nullptr) {
     std::lock_guard<std::mutex> host_lk(e->host_mu);
     const bool timed = e->stage_timing || e->trace_cap != 0;
     HostStage hs;
     const double t0 = now_us();
     {
         std::lock_guard<std::mutex> lk(e->mu);
-        int rc = stage_host_inputs(e, descs, n, itype, s, &hs, true, /*allow_zero_copy=*/true, /*allow_split=*/!timed);
+        // (pooled calls: one part, one stream)
+        int rc = stage_host_inputs(e, descs, n, itype, s, &hs, true, /*allow_zero_copy=*/true, /*allow_split=*/!timed && !pools, pools);
         if (rc) return rc;
     }
     if (hs.h2d_deferred) return lookup_host_split(e, descs, n, itype, s, hs, t0);
     if (timed) HIP_TRY(hipStreamSynchronize(s));
     const double t1 = now_us();
-    if (hs.zero_copy && !timed && hs.out_bytes >= kPipelineBytes && n >= 2)
+    if (hs.zero_copy && !timed && hs.out_bytes >= kPipelineBytes && n >= 2 && !pools)
         return lookup_host_pipelined(e, descs, n, itype, s, hs, t0);
     Resolved r;
     r.stream = s;
-    int rc = resolve(e, descs, n, itype, &hs.d_indices, &hs.d_offsets, &hs.d_out, &r, /*cache_maps=*/true);
+    int rc = resolve(e, descs, n, itype, &hs.d_indices, &hs.d_offsets, &hs.d_out, &r, /*cache_maps=*/true, nullptr, nullptr,
+                     pools, &hs.d_weights);
     if (rc) return rc;
     // descriptor upload ("query copying" in the reference's stage list) + the fused launch
     rc = launch_resolved(e, r, itype, s, hs.zero_copy);
@@ -1333,7 +1388,8 @@ static int validate_on(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_d
 static int checked_launch(emb_engine *e, Resolved &r, emb_index_type itype, hipStream_t s, bool launch, uint64_t *n_bad, bool defer = false);
 
 static int lookup_batched_impl(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_index_type itype,
-                               emb_memspace space, void *stream, bool check, uint64_t *n_bad, bool defer = false) {
+                               emb_memspace space, void *stream, bool check, uint64_t *n_bad, bool defer = false,
+                               const emb_pool_spec *pools = nullptr) {
     if (n_bad) *n_bad = 0;
     if (!e) return fail(EMB_ERR_INVALID, "engine is NULL");
     if (n_descs == 0) return EMB_OK;
@@ -1346,12 +1402,12 @@ static int lookup_batched_impl(emb_engine *e, const emb_lookup_desc *descs, uint
             int vrc = validate_on(e, descs, n_descs, itype, space, s, n_bad);
             if (vrc) return vrc;
         }
-        return lookup_host(e, descs, n_descs, itype, s);
+        return lookup_host(e, descs, n_descs, itype, s, pools);
     }
     Resolved r;
     r.stream = s;
     const double p0 = g_prof.on ? now_us() : 0;
-    int rc = resolve(e, descs, n_descs, itype, nullptr, nullptr, nullptr, &r, /*cache_maps=*/true);
+    int rc = resolve(e, descs, n_descs, itype, nullptr, nullptr, nullptr, &r, /*cache_maps=*/true, nullptr, nullptr, pools);
     if (rc) return rc;
     if (g_prof.on) g_prof.resolve += now_us() - p0;
     // checked: the descriptors are resolved ONCE; the validation kernel and the lookup kernels share one launch image and
@@ -1377,6 +1433,26 @@ int emb_lookup_batched_checked_deferred(emb_engine *e, const emb_lookup_desc *de
 int emb_lookup_batched_checked(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs,
                                emb_index_type itype, emb_memspace space, void *stream, uint64_t *n_bad) {
     return lookup_batched_impl(e, descs, n_descs, itype, space, stream, true, n_bad);
+}
+
+// Pooled specs that all ask for plain sum (or none at all) are today's call, untouched.
+static const emb_pool_spec *live_pools(const emb_pool_spec *pools, uint32_t n_descs) {
+    if (pools)
+        for (uint32_t i = 0; i < n_descs; i++)
+            if (!is_plain_sum(pools[i])) return pools;
+    return nullptr;
+}
+
+int emb_lookup_pooled(emb_engine *e, const emb_lookup_desc *descs, const emb_pool_spec *pools, uint32_t n_descs,
+                      emb_index_type itype, emb_memspace space, void *stream, uint32_t check, uint64_t *n_bad) {
+    if (n_bad) *n_bad = 0;
+    if (!e) return fail(EMB_ERR_INVALID, "engine is NULL");
+    if (check > 2) return fail(EMB_ERR_INVALID, "emb_lookup_pooled: check must be 0, 1 or 2 (got %u)", check);
+    if (n_descs && !descs) return fail(EMB_ERR_INVALID, "descs is NULL");
+    const emb_pool_spec *live = live_pools(pools, n_descs);
+    if (check == 0)        // as emb_lookup_batched: the engine's own flags decide
+        return lookup_batched_impl(e, descs, n_descs, itype, space, stream, e->check_inputs, nullptr, e->defer_check, live);
+    return lookup_batched_impl(e, descs, n_descs, itype, space, stream, true, n_bad, check == 2 && space == EMB_MEM_DEVICE, live);
 }
 
 int emb_lookup(emb_engine *e, uint32_t table_id, const void *indices, uint64_t n_indices,
@@ -1424,7 +1500,7 @@ int emb_lookup_ranged_typed(emb_engine *e, const emb_lookup_desc *descs, const u
 }
 
 static int plan_create(emb_engine *e, const emb_lookup_desc *descs, const uint64_t *row_lo, uint32_t *const *served,
-                       uint32_t n_descs, emb_index_type itype, emb_plan **out);
+                       uint32_t n_descs, emb_index_type itype, emb_plan **out, const emb_pool_spec *pools = nullptr);
 
 int emb_plan_create_ranged(emb_engine *e, const emb_lookup_desc *descs, const uint64_t *row_lo, uint32_t n_descs,
                            emb_plan **out) {
@@ -1449,14 +1525,19 @@ int emb_plan_create(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_desc
     return plan_create(e, descs, nullptr, nullptr, n_descs, itype, out);
 }
 
+int emb_plan_create_pooled(emb_engine *e, const emb_lookup_desc *descs, const emb_pool_spec *pools, uint32_t n_descs,
+                           emb_index_type itype, emb_plan **out) {
+    return plan_create(e, descs, nullptr, nullptr, n_descs, itype, out, live_pools(pools, n_descs));
+}
+
 static int plan_create(emb_engine *e, const emb_lookup_desc *descs, const uint64_t *row_lo, uint32_t *const *served,
-                       uint32_t n_descs, emb_index_type itype, emb_plan **out) {
+                       uint32_t n_descs, emb_index_type itype, emb_plan **out, const emb_pool_spec *pools) {
     if (!e || !out) return fail(EMB_ERR_INVALID, "engine or out is NULL");
     *out = nullptr;
     if (!descs || n_descs == 0) return fail(EMB_ERR_INVALID, "plan needs at least one descriptor");
     DeviceGuard g(e->device);
     Resolved r;
-    int rc = resolve(e, descs, n_descs, itype, nullptr, nullptr, nullptr, &r, false, row_lo, served);
+    int rc = resolve(e, descs, n_descs, itype, nullptr, nullptr, nullptr, &r, false, row_lo, served, pools);
     if (rc) return rc;
     emb_plan *p = new (std::nothrow) emb_plan();
     if (!p) return fail(EMB_ERR_NOMEM, "out of host memory");
@@ -1470,11 +1551,16 @@ static int plan_create(emb_engine *e, const emb_lookup_desc *descs, const uint64
         for (const PlanGroup &g : r.groups) {
             mix(g.kind); mix((uint64_t)g.dtype); mix(g.geom.lanes_per_row); mix(g.geom.chunks); mix(g.geom.scalar_lanes); mix(g.n); mix(g.max_tiles);
             mix(g.xgrid); mix(g.xdirect); mix(g.ranged); mix(g.hot_wgs); mix(g.hot_lds); mix(pimemb::bags_per_tile(g.kind, g.geom));
+            if (g.pool) mix(0x706f6f6c00ull | g.pool);     // (plain-sum groups mix exactly what they always did)
             for (uint32_t w : g.xmap_words) mix(w);
             for (uint32_t i = 0; i < g.n; i++, di++) {
                 const DevDesc &d = r.descs[di];
                 mix(d.n_tiles); mix(d.n_bags); mix(d.n_idx); mix(d.nr_rows); mix(d.fixed_pooling); mix(d.offsets != nullptr); mix(d.n_hot);
-                mix(d.pad_[0]); mix(d.pad_[1] != 0);
+                if (g.pool) {           // pad_ holds the pooling spec: the weights' presence, never their address
+                    mix(d.pad_[0] != 0); mix(d.pad_[1]); mix(d.pad_[2]);
+                } else {
+                    mix(d.pad_[0]); mix(d.pad_[1] != 0);
+                }
             }
         }
         p->signature = h;
@@ -1545,6 +1631,11 @@ int emb_plan_describe(const emb_plan *p, char *buf, size_t capacity) {
                                g.geom.scalar_lanes, (int)g.geom.anydim_vec, (int)g.ranged, g.n, g.d_xmap ? g.xgrid : g.max_tiles * g.n, block);
         if (n < 0 || (size_t)n >= capacity - at) return fail(EMB_ERR_INVALID, "emb_plan_describe: %zu bytes do not hold the text", capacity);
         at += (size_t)n;
+        if (g.pool) {
+            const int m = snprintf(buf + at, capacity - at, " pool=%u weighted=%u padding=%u", g.pool - 1u, g.n_weighted, g.n_padding);
+            if (m < 0 || (size_t)m >= capacity - at) return fail(EMB_ERR_INVALID, "emb_plan_describe: %zu bytes do not hold the text", capacity);
+            at += (size_t)m;
+        }
     }
     return EMB_OK;
 }

@@ -47,6 +47,13 @@ hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max
                           KernelKind kind, const uint32_t *d_xmap, uint32_t xgrid, bool xdirect,
                           hipStream_t stream, bool ranged = false);
 
+// Pooled lookup (emb_lookup_pooled: mean / max, per-sample weights, padding_idx) over descriptors of one dtype (fp32 / fp16)
+// and dim whose pooling spec sits in DevDesc::pad_ (pimemb_bag_kernels.h, bag_pool_*).  kind: KERNEL_WAVEBATCH,
+// KERNEL_GROUP or KERNEL_ANYDIM (no two-batch or hot-row variant).  Pure enqueue.
+hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, emb_dtype dtype,
+                           emb_index_type itype, const LaunchGeom &g, KernelKind kind, const uint32_t *d_xmap,
+                           uint32_t xgrid, bool xdirect, hipStream_t stream);
+
 // Pooled launch with hot rows in LDS: `wgs` persistent workgroups per descriptor, `lds_bytes` of dynamic LDS.
 hipError_t launch_bag_sum_hot(const DevDesc *d_descs, uint32_t n_descs, uint32_t wgs, uint32_t lds_bytes,
                               emb_dtype dtype, emb_index_type itype, const LaunchGeom &g, hipStream_t stream);

@@ -182,6 +182,68 @@ hipError_t launch_anydim(const DevDesc *d, uint32_t n, uint32_t max_tiles, emb_d
     return hipGetLastError();
 }
 
+// ---- pooled lookups (bag_pool_*): fp32 / fp16 tables; one instantiation per (index type, dtype, row width, path) -- the
+// pooling mode, weights and padding are per-descriptor values the kernels branch on (scalar branches) ----------------------
+// The pooled wave-batch kernel under the fp32 64-VGPR cap: its general (multi-index) step also carries a weight per gather
+// in flight, and eight of them spill (21 dwords per lane); four, as Wave2Cfg's general step, do not.  One-hot steps keep all
+// eight rounds' gathers in flight either way.  fp16 rows: the fp16 configuration as it is (4 waves per SIMD, no spill).
+using PoolWaveCfg = BagCfg<64, 4, true, false, 8, 8, 1, false, true, false, kClampInputs>;
+template <int DT> struct PoolWaveCfgOf { using One = PoolWaveCfg; };
+template <> struct PoolWaveCfgOf<EMB_F16> { using One = WaveCfgF16; };
+
+template <typename IdxT, int DT>
+hipError_t launch_pool_lpr(const DevDesc *d, uint32_t n, uint32_t max_tiles, const LaunchGeom &g, KernelKind kind,
+                           const uint32_t *xmap, uint32_t xgrid, bool xdirect, hipStream_t s) {
+    const dim3 grid = xmap ? dim3(xgrid, 1, 1) : dim3(max_tiles, n, 1);
+    const uint32_t chunks = g.chunks | ((xmap && xdirect) ? kXmapDirect : 0u);
+    using One = typename PoolWaveCfgOf<DT>::One;
+    switch (g.lanes_per_row) {
+#define PIMEMB_CASE(L)                                                                                                    \
+    case L:                                                                                                               \
+        if (kind == KERNEL_WAVEBATCH)                                                                                     \
+            hipLaunchKernelGGL((bag_pool_wavebatch_kernel<IdxT, DT, L, One>), grid, dim3(One::kBlock), 0, s, d, chunks, xmap); \
+        else                                                                                                              \
+            hipLaunchKernelGGL((bag_pool_group_kernel<IdxT, DT, L, GroupCfg>), grid, dim3(GroupCfg::kBlock), 0, s, d, chunks, xmap); \
+        break;
+        PIMEMB_CASE(1)
+        PIMEMB_CASE(2)
+        PIMEMB_CASE(4)
+        PIMEMB_CASE(8)
+        PIMEMB_CASE(16)
+        PIMEMB_CASE(32)
+        PIMEMB_CASE(64)
+#undef PIMEMB_CASE
+        default:
+            return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+template <typename IdxT, int DT>
+hipError_t launch_pool_anydim(const DevDesc *d, uint32_t n, uint32_t max_tiles, const LaunchGeom &g, hipStream_t s) {
+    const dim3 grid(max_tiles, n, 1), block(256);
+    if (g.anydim_vec)
+        hipLaunchKernelGGL((bag_pool_anydim_kernel<IdxT, DT, true, kClampInputs>), grid, block, 0, s, d, g.chunks, g.scalar_lanes);
+    else
+        hipLaunchKernelGGL((bag_pool_anydim_kernel<IdxT, DT, false, kClampInputs>), grid, block, 0, s, d, g.chunks, g.scalar_lanes);
+    return hipGetLastError();
+}
+
+template <typename IdxT>
+hipError_t launch_pool_dtype(const DevDesc *d, uint32_t n, uint32_t max_tiles, emb_dtype dtype, const LaunchGeom &g,
+                             KernelKind kind, const uint32_t *xmap, uint32_t xgrid, bool xdirect, hipStream_t s) {
+    if (kind == KERNEL_ANYDIM) {
+        if (g.scalar_lanes == 0 || xmap != nullptr) return hipErrorInvalidValue;
+        if (dtype == EMB_F32) return launch_pool_anydim<IdxT, EMB_F32>(d, n, max_tiles, g, s);
+        if (dtype == EMB_F16) return launch_pool_anydim<IdxT, EMB_F16>(d, n, max_tiles, g, s);
+        return hipErrorInvalidValue;
+    }
+    if (kind != KERNEL_WAVEBATCH && kind != KERNEL_GROUP) return hipErrorInvalidValue;
+    if (dtype == EMB_F32) return launch_pool_lpr<IdxT, EMB_F32>(d, n, max_tiles, g, kind, xmap, xgrid, xdirect, s);
+    if (dtype == EMB_F16) return launch_pool_lpr<IdxT, EMB_F16>(d, n, max_tiles, g, kind, xmap, xgrid, xdirect, s);
+    return hipErrorInvalidValue;
+}
+
 // ---- column scatter for populate_mram-style uploads -----------------------------------------
 __global__ void __launch_bounds__(kBlock)
 scatter_column_kernel(int32_t *__restrict__ table, const int32_t *__restrict__ column,
@@ -1205,6 +1267,16 @@ hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max
     if (itype == EMB_IDX_U32)
         return launch_dtype<uint32_t>(d_descs, n_descs, max_tiles, dtype, g, kind, d_xmap, xgrid, xdirect, ranged, stream);
     return launch_dtype<int64_t>(d_descs, n_descs, max_tiles, dtype, g, kind, d_xmap, xgrid, xdirect, ranged, stream);
+}
+
+hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, emb_dtype dtype,
+                           emb_index_type itype, const LaunchGeom &g, KernelKind kind, const uint32_t *d_xmap,
+                           uint32_t xgrid, bool xdirect, hipStream_t stream) {
+    if (n_descs == 0 || max_tiles == 0) return hipSuccess;
+    if (d_xmap == nullptr && n_descs > 65535u) return hipErrorInvalidValue;
+    return itype == EMB_IDX_U32
+               ? launch_pool_dtype<uint32_t>(d_descs, n_descs, max_tiles, dtype, g, kind, d_xmap, xgrid, xdirect, stream)
+               : launch_pool_dtype<int64_t>(d_descs, n_descs, max_tiles, dtype, g, kind, d_xmap, xgrid, xdirect, stream);
 }
 
 hipError_t launch_bag_sum_hot(const DevDesc *d_descs, uint32_t n_descs, uint32_t wgs, uint32_t lds_bytes,

@@ -25,7 +25,8 @@ class EmbeddingBagCollection:
     """emb_l of a DLRM: T tables of dim m in HBM; forward(lS_o, lS_i) -> list of [B, m]."""
 
     def __init__(self, ln_emb, m_spa: int, device: int = 0, weights=None, seed: int = 0, dtype="f32",
-                 trusted_inputs: bool = False, deferred_check: bool = False):
+                 trusted_inputs: bool = False, deferred_check: bool = False, weighted_pooling: str | None = None,
+                 pooling_weights=None):
         import torch
         self.torch = torch
         self.trusted_inputs = bool(trusted_inputs)     # False: every apply_emb checks its indices first (IndexError)
@@ -48,12 +49,29 @@ class EmbeddingBagCollection:
             self.engine.load_table(k, w)
         self._plans = {}
         self._ids = list(range(len(self.ln_emb)))
+        # DLRM --weighted-pooling: v_W_l[k] is a weight per ROW of table k (ones for "fixed", the checkpoint's for "learned");
+        # a bag entry is weighted by its row's weight, gathered with torch (dlrm_s_pytorch.py: v_W_l[k].gather(0, indices))
+        if weighted_pooling not in (None, "fixed", "learned"):
+            raise ValueError("weighted_pooling must be None, 'fixed' or 'learned'")
+        self.weighted_pooling = weighted_pooling
+        self.v_W_l = None
+        if weighted_pooling is not None:
+            if weighted_pooling == "learned" and pooling_weights is None:
+                raise ValueError("weighted_pooling='learned' needs the per-row weights (pooling_weights / from_checkpoint)")
+            self.v_W_l = [torch.ones(n, dtype=torch.float32, device=self.device) if weighted_pooling == "fixed" else
+                          torch.as_tensor(np.asarray(pooling_weights[k]), dtype=torch.float32).to(self.device).contiguous()
+                          for k, n in enumerate(self.ln_emb)]
+            for k, v in enumerate(self.v_W_l):
+                if v.numel() != self.ln_emb[k]:
+                    raise ValueError(f"table {k}: {v.numel()} pooling weights for {self.ln_emb[k]} rows")
 
     @classmethod
-    def from_checkpoint(cls, path: str, device: int = 0):
-        from .formats import load_dlrm_embedding_weights
+    def from_checkpoint(cls, path: str, device: int = 0, weighted_pooling: str | None = None):
+        from .formats import load_dlrm_embedding_weights, load_dlrm_pooling_weights
         ws = load_dlrm_embedding_weights(path)
-        return cls([w.shape[0] for w in ws], ws[0].shape[1], device=device, weights=ws)
+        vw = load_dlrm_pooling_weights(path, len(ws)) if weighted_pooling == "learned" else None
+        return cls([w.shape[0] for w in ws], ws[0].shape[1], device=device, weights=ws, weighted_pooling=weighted_pooling,
+                   pooling_weights=vw)
 
     def apply_emb(self, lS_o, lS_i):
         """lS_o[k], lS_i[k]: offsets / indices of table k (torch CUDA tensors, int64 or int32, or
@@ -63,10 +81,22 @@ class EmbeddingBagCollection:
             raise ValueError("need one (offsets, indices) pair per table")
         # validated and looked up in ONE engine call; nothing runs on bad input
         check = False if self.trusted_inputs else ("deferred" if self.deferred_check else True)
+        if self.v_W_l is not None:
+            return self._apply_emb_weighted(lS_o, lS_i, check)
         if hasattr(lS_i, "dim") and hasattr(lS_o, "dim") and lS_i.dim() == 2 and lS_o.dim() == 2 and lS_i.is_cuda:
             # DLRM stacks fixed-size batches into [T, N] / [T, B] tensors: one [T, B, m] result, unbound
             return list(self.engine.lookup_stacked(self._ids, lS_i, lS_o, check=check).unbind(0))
         return self.engine.lookup_batched(self._ids, list(lS_i), list(lS_o), check=check)
+
+    def _apply_emb_weighted(self, lS_o, lS_i, check):
+        """--weighted-pooling: per-sample weights v_W_l[k][indices] (gathered by torch on the GPU), then ONE pooled call."""
+        lS_i, lS_o = list(lS_i), list(lS_o)
+        if not all(getattr(i, "is_cuda", False) for i in lS_i):
+            raise TypeError("weighted pooling takes torch CUDA index tensors")
+        if check:      # (a wild index must not reach torch's gather either)
+            self.validate(lS_o, lS_i)
+        ws = [v.gather(0, i.long()) for v, i in zip(self.v_W_l, lS_i)]
+        return self.engine.lookup_pooled(self._ids, lS_i, lS_o, "sum", per_sample_weights=ws, check=check)
 
     def validate(self, lS_o, lS_i) -> None:
         """emb_validate_inputs over one batch: IndexError on an index >= table rows or broken offsets, as
@@ -221,6 +251,7 @@ def main(argv=None):
     ap.add_argument("--load-model", type=str, default="")
     ap.add_argument("--save-model", type=str, default="")
     ap.add_argument("--numpy-rand-seed", type=int, default=123)
+    ap.add_argument("--weighted-pooling", type=str, default=None, choices=["fixed", "learned"])
     args, ignored = ap.parse_known_args(argv)
     if ignored:   # MLP / training / logging flags of the reference command lines (README.md:6,10,14)
         print("ignored (outside the embedding path):", " ".join(ignored))
@@ -237,9 +268,11 @@ def main(argv=None):
     else:
         ln_emb = [int(x) for x in args.arch_embedding_size.split("-")]
     if args.load_model:
-        ebc = EmbeddingBagCollection.from_checkpoint(args.load_model)
+        ebc = EmbeddingBagCollection.from_checkpoint(args.load_model, weighted_pooling=args.weighted_pooling)
     else:
-        ebc = EmbeddingBagCollection(ln_emb, args.arch_sparse_feature_size)
+        if args.weighted_pooling == "learned":
+            raise SystemExit("--weighted-pooling learned needs --load-model (the per-row weights v_W_l come from it)")
+        ebc = EmbeddingBagCollection(ln_emb, args.arch_sparse_feature_size, weighted_pooling=args.weighted_pooling)
     B = args.mini_batch_size
     batches = []
     for b in range(min(args.num_batches, 16)):
@@ -262,6 +295,9 @@ def main(argv=None):
     n_bags = sum(int(x.shape[0]) for x in ly)
     print(f"apply_emb: {len(ebc.ln_emb)} tables, m={ebc.m}, batch {B}: {dt * 1e3:.4f} ms/batch, "
           f"{n_bags / dt:.3e} pooled lookups/s")
+    if ebc.v_W_l is not None:     # (prepared plans hold the sum path only)
+        ebc.close()
+        return 0
     plans = [ebc.prepare(o, i) for o, i in batches]        # same buffers every step: prepared plans
     for p in plans:
         p.launch()

@@ -23,6 +23,7 @@ from . import lib as _l
 
 _NP_TABLE_DTYPES = {np.dtype(np.float32): _l.EMB_F32, np.dtype(np.float16): _l.EMB_F16,
                     np.dtype(np.int32): _l.EMB_FIXED32}
+POOL_MODES = {"sum": _l.EMB_POOL_SUM, "mean": _l.EMB_POOL_MEAN, "max": _l.EMB_POOL_MAX}
 
 
 _MARSHAL = [False]      # False: not looked for yet; None: not built; else the _pimemb_marshal module
@@ -623,15 +624,15 @@ class EmbeddingEngine:
             self._remember_call(key, buf_ptr, n, itype)
         return list(outs)
 
-    def _remember_call(self, key, desc_ptr, n, itype) -> None:
+    def _remember_call(self, key, desc_ptr, n, itype, pools=None) -> None:
         """Second sighting of a call signature: build its plan.  The cache holds plan_cache_size plans; when it is full the
         least recently used one goes -- but at most once per 64 cacheable calls: destroying a plan waits for the device,
         and a caller whose signatures keep changing must not pay that on every call (its recurring signatures keep their
         plans meanwhile)."""
         with self._plan_lock:
-            self._remember_locked(key, desc_ptr, n, itype)
+            self._remember_locked(key, desc_ptr, n, itype, pools)
 
-    def _remember_locked(self, key, desc_ptr, n, itype) -> None:
+    def _remember_locked(self, key, desc_ptr, n, itype, pools=None) -> None:
         if key in self._plan_cache or self._check_inputs:
             return
         h = hash(key)                         # (admission bookkeeping only: a collision costs one early plan, nothing else)
@@ -648,7 +649,9 @@ class EmbeddingEngine:
             victim = min(self._plan_cache, key=lambda k: self._plan_cache[k][1])
             self._plan_cache.pop(victim)[0].destroy()
         p = C.c_void_p()
-        if self._L.emb_plan_create(self._h, desc_ptr, n, itype, C.byref(p)) != _l.EMB_OK:
+        rc = (self._L.emb_plan_create(self._h, desc_ptr, n, itype, C.byref(p)) if pools is None else
+              self._L.emb_plan_create_pooled(self._h, desc_ptr, pools, n, itype, C.byref(p)))
+        if rc != _l.EMB_OK:
             return
         self._plan_cache[key] = [Plan(self, p.value, None, None), self._plan_clock]
 
@@ -755,6 +758,85 @@ class EmbeddingEngine:
         p = C.c_void_p()
         _l.check(self._L.emb_plan_create(self._h, arr, n, itype, C.byref(p)))
         return Plan(self, p.value, results, keep)
+
+    # ---- pooled lookups: nn.EmbeddingBag's mean / max, per_sample_weights, padding_idx (emb_lookup_pooled) ----------
+    def _pools(self, n, descs, modes, per_sample_weights, padding_idx, space):
+        """emb_pool_spec array for a call: `modes` one mode or one per table ("sum" / "mean" / "max" or EMB_POOL_*);
+        `per_sample_weights` None or one float32 array / tensor (or None) per table, placed like the indices;
+        `padding_idx` None, one row id, or one per table (None: no padding).  Returns (array, buffers to keep alive)."""
+        def per_table(v, what):
+            if v is None or isinstance(v, (str, int, np.integer)):
+                return [v] * n
+            v = list(v)
+            if len(v) != n:
+                raise ValueError(f"{what}: one entry per table expected ({n}), got {len(v)}")
+            return v
+        modes, weights, pads = per_table(modes, "modes"), per_table(per_sample_weights, "per_sample_weights"), \
+            per_table(padding_idx, "padding_idx")
+        arr = (_l.EmbPoolSpec * n)()
+        keep = []
+        for i in range(n):
+            m = modes[i]
+            mode = POOL_MODES[m] if isinstance(m, str) else int(m if m is not None else _l.EMB_POOL_SUM)
+            wptr = None
+            if weights[i] is not None:
+                w = weights[i]
+                if _is_torch(w):
+                    if str(w.dtype) != "torch.float32":
+                        raise TypeError("per_sample_weights must be float32")
+                elif not isinstance(w, DeviceBuffer):
+                    w = np.ascontiguousarray(w, dtype=np.float32)
+                wa = _Arg(w)
+                if wa.space != space:
+                    raise TypeError("per_sample_weights must be placed like the indices")
+                if wa.n != descs[i].n_indices:
+                    raise ValueError(f"table {descs[i].table_id}: {wa.n} per_sample_weights for {descs[i].n_indices} indices")
+                wptr = wa.ptr
+                keep.append(wa.keep)
+            flags, pad = (0, 0) if pads[i] is None else (_l.EMB_POOL_PADDING, int(pads[i]))
+            arr[i] = _l.EmbPoolSpec(mode, flags, wptr, pad)
+        return arr, keep
+
+    def lookup_pooled(self, table_ids: Sequence[int], indices: Sequence, offsets: Sequence, modes, per_sample_weights=None,
+                      padding_idx=None, outs: Sequence | None = None, fixed_pooling=0, stream: int | None = None,
+                      check: bool | str = False):
+        """lookup_batched with a pooling spec per table: mode "sum" / "mean" / "max", per-sample weights (sum only) and a
+        padding row id (see _pools) -- nn.EmbeddingBag's arithmetic, bit for bit against torch on the CPU.  All tables in one
+        call (launches grouped by dtype, dim and mode).  check as lookup_batched.  Per-call plans are cached like
+        lookup_batched's; the key holds the descriptors and the pooling specs (mode, padding, weights address), so a sum call
+        never replays a pooled plan or the other way round."""
+        arr, n, itype, space, results, keep = self._descs(table_ids, indices, offsets, outs, fixed_pooling)
+        pools, pkeep = self._pools(n, arr, modes, per_sample_weights, padding_idx, space)
+        if stream is None and space == _l.EMB_MEM_DEVICE:
+            stream = _current_stream_for(*indices)
+        c = 0 if not check else (2 if check == "deferred" else 1)
+        key = None
+        if c == 0 and space == _l.EMB_MEM_DEVICE and self.plan_cache_size:
+            key = ("pooled", bytes(arr), bytes(pools), itype)
+            if self._launch_cached(key, stream):
+                return results
+        bad = C.c_uint64()
+        rc = self._L.emb_lookup_pooled(self._h, arr, pools, n, itype, space, stream, c, C.byref(bad))
+        if rc == _l.EMB_ERR_RANGE:
+            text = self._L.emb_last_error().decode(errors="replace")
+            if c == 2 or "EARLIER" in text:
+                raise IndexError(text)
+            self._raise_range(bad.value)
+        _l.check(rc)
+        if key is not None:
+            self._remember_call(key, arr, n, itype, pools)
+        return results
+
+    def plan_pooled(self, table_ids, indices, offsets, modes, per_sample_weights=None, padding_idx=None, outs=None,
+                    fixed_pooling=0) -> Plan:
+        """plan() for lookup_pooled's calls (device buffers, weights included; graph-capturable like any plan)."""
+        arr, n, itype, space, results, keep = self._descs(table_ids, indices, offsets, outs, fixed_pooling)
+        if space != _l.EMB_MEM_DEVICE:
+            raise TypeError("plans need device-resident buffers (torch CUDA tensors or DeviceBuffer)")
+        pools, pkeep = self._pools(n, arr, modes, per_sample_weights, padding_idx, space)
+        p = C.c_void_p()
+        _l.check(self._L.emb_plan_create_pooled(self._h, arr, pools, n, itype, C.byref(p)))
+        return Plan(self, p.value, results, keep + pkeep)
 
     def validate(self, table_ids, indices, offsets, fixed_pooling=0) -> int:
         """Debug check: number of out-of-range indices / broken offsets (0 = clean)."""

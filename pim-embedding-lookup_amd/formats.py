@@ -65,8 +65,22 @@ def load_dlrm_embedding_weights(path: str):
     return [sd[k].detach().to(torch.float32).contiguous().numpy() for k in keys]
 
 
-def save_dlrm_embedding_weights(path: str, tables) -> None:
+def load_dlrm_pooling_weights(path: str, n_tables: int):
+    """The per-row pooling weights of a DLRM checkpoint trained with --weighted-pooling learned: `v_W_l.<k>` (DLRM's
+    ParameterList v_W_l, one float32 [N_k] vector per table) as numpy arrays in table order."""
+    import torch
+    obj = torch.load(path, map_location="cpu", weights_only=True)
+    sd = obj.get("state_dict", obj) if isinstance(obj, dict) else obj
+    missing = [k for k in range(n_tables) if f"v_W_l.{k}" not in sd]
+    if missing:
+        raise ValueError(f"{path}: no v_W_l.<k> entry for table(s) {missing} (was the model trained with --weighted-pooling learned?)")
+    return [sd[f"v_W_l.{k}"].detach().to(torch.float32).reshape(-1).contiguous().numpy() for k in range(n_tables)]
+
+
+def save_dlrm_embedding_weights(path: str, tables, pooling_weights=None) -> None:
     """Write tables back in the same layout (tests, round trips)."""
     import torch
-    torch.save({"state_dict": {f"emb_l.{k}.weight": torch.as_tensor(np.asarray(t)) for k, t in enumerate(tables)}},
-               path)
+    sd = {f"emb_l.{k}.weight": torch.as_tensor(np.asarray(t)) for k, t in enumerate(tables)}
+    for k, v in enumerate(pooling_weights or []):
+        sd[f"v_W_l.{k}"] = torch.as_tensor(np.asarray(v, dtype=np.float32))
+    torch.save({"state_dict": sd}, path)

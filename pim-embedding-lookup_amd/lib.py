@@ -47,6 +47,12 @@ class EmbCommOp(C.Structure):
 EMB_PLACE_REPLICATED, EMB_PLACE_WHOLE, EMB_PLACE_ROWS = 0, 1, 2
 EMB_SHARD_SELF_VIA_COMM, EMB_SHARD_CHECK_SERVED, EMB_SHARD_PEER_STORES, EMB_SHARD_NO_DIRECT, EMB_SHARD_DEFER_REPORT = 1, 2, 4, 8, 16
 EMB_RANGE_OPEN_END = 1 << 63
+EMB_POOL_SUM, EMB_POOL_MEAN, EMB_POOL_MAX = 0, 1, 2
+EMB_POOL_PADDING = 1
+
+
+class EmbPoolSpec(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("flags", C.c_uint32), ("per_sample_weights", C.c_void_p), ("padding_idx", C.c_int64)]
 
 
 class EmbShardTable(C.Structure):
@@ -136,6 +142,9 @@ SIGNATURES = {
     "emb_lookup_ranged_typed": (C.c_int, [_vp, C.POINTER(EmbLookupDesc), C.POINTER(_u64), C.POINTER(_vp), _u32, C.c_int, _vp]),
     "emb_plan_create_ranged_typed": (C.c_int, [_vp, C.POINTER(EmbLookupDesc), C.POINTER(_u64), C.POINTER(_vp), _u32, C.c_int, C.POINTER(_vp)]),
     "emb_plan_create": (C.c_int, [_vp, C.POINTER(EmbLookupDesc), _u32, C.c_int, _pp]),
+    "emb_lookup_pooled": (C.c_int, [_vp, C.POINTER(EmbLookupDesc), C.POINTER(EmbPoolSpec), _u32, C.c_int, C.c_int, _vp, _u32,
+                                    C.POINTER(_u64)]),
+    "emb_plan_create_pooled": (C.c_int, [_vp, C.POINTER(EmbLookupDesc), C.POINTER(EmbPoolSpec), _u32, C.c_int, _pp]),
     "emb_plan_launch": (C.c_int, [_vp, _vp]),
     "emb_plan_destroy": (C.c_int, [_vp]),
     "emb_plan_bytes": (C.c_int, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),

@@ -7,8 +7,14 @@ exactly that call to populate_mram / lookup.  Here:
     emb_l[k] = EmbeddingBag.from_torch(emb_l[k])          # one table, same forward(input, offsets)
     ebc = FusedEmbeddingBags.from_torch(emb_l)            # all tables, ONE launch per apply_emb
 
-Inference only (the engine has no backward), `mode="sum"` only, no per-sample weights / padding_idx /
-max_norm -- the reference has none of them either.
+Which class does what:
+  EmbeddingBag / FusedEmbeddingBags                   the reference's path: mode="sum" only, no per-sample weights,
+                                                      padding_idx or max_norm (the reference has none of them either,
+                                                      SURVEY.md Appendix B.2); they refuse anything else.
+  PoolingEmbeddingBag / FusedPoolingEmbeddingBags     the rest of nn.EmbeddingBag's inference side: mode "sum" / "mean" /
+                                                      "max", per_sample_weights (sum only, as in torch) and padding_idx,
+                                                      equal to torch's CPU result bit for bit (emb_lookup_pooled).
+Inference only (the engine has no backward); max_norm is not supported by any of them.
 
 Input checking.  The C ABI is as unchecked as the reference (an out-of-range index is a wild read there,
 emb_dpu_lookup.c:113); these modules are what user tensors reach first, so by default every forward goes through
@@ -180,5 +186,120 @@ class FusedEmbeddingBags(torch.nn.Module):
     apply_emb = forward
 
 
-__all__ = ["EmbeddingBag", "FusedEmbeddingBags", "default_engine"]
+class PoolingEmbeddingBag(torch.nn.Module):
+    """One table with nn.EmbeddingBag's pooling options: forward(input, offsets=None, per_sample_weights=None) ->
+    [B, embedding_dim] fp32 for mode "sum" / "mean" / "max", per_sample_weights (mode "sum" only, else NotImplementedError
+    as torch raises), padding_idx (negative values count from the end, as torch normalises them), include_last_offset, 1-D
+    input with offsets or 2-D input.  Same state_dict keys as EmbeddingBag; checking on by default (trusted_inputs,
+    deferred_check as there)."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, mode: str = "mean", sparse: bool = False, _weight=None,
+                 include_last_offset: bool = False, padding_idx: int | None = None, device: int = 0,
+                 engine: EmbeddingEngine | None = None, table_id: int | None = None, dtype=torch.float32,
+                 trusted_inputs: bool = False, deferred_check: bool = False):
+        super().__init__()
+        if mode not in ("sum", "mean", "max"):
+            raise ValueError(f"mode has to be one of sum, mean or max, got {mode!r}")
+        self.num_embeddings, self.embedding_dim = int(num_embeddings), int(embedding_dim)
+        if padding_idx is not None:
+            padding_idx = int(padding_idx)
+            if padding_idx < 0:
+                padding_idx += self.num_embeddings
+            if not 0 <= padding_idx < self.num_embeddings:
+                raise ValueError("padding_idx must be within num_embeddings")     # torch's own check
+        self.mode, self.sparse, self.include_last_offset, self.padding_idx = mode, sparse, include_last_offset, padding_idx
+        self.trusted_inputs, self.deferred_check = bool(trusted_inputs), bool(deferred_check)
+        # the table itself (upload, checkpoint I/O) is an EmbeddingBag held as a plain attribute, not a submodule: the
+        # state_dict key stays "<prefix>weight", as nn.EmbeddingBag's
+        object.__setattr__(self, "_table", EmbeddingBag(num_embeddings, embedding_dim, _weight=_weight,
+                                                        include_last_offset=include_last_offset, device=device, engine=engine,
+                                                        table_id=table_id, dtype=dtype))
+        self.engine, self.table_id, self.device_index = self._table.engine, self._table.table_id, self._table.device_index
+        self._id_list = [self.table_id]
+
+    @classmethod
+    def from_pretrained(cls, embeddings, mode: str = "mean", include_last_offset: bool = False, padding_idx=None, **kw):
+        return cls(embeddings.shape[0], embeddings.shape[1], mode=mode, _weight=embeddings,
+                   include_last_offset=include_last_offset, padding_idx=padding_idx, **kw)
+
+    @classmethod
+    def from_torch(cls, module: torch.nn.EmbeddingBag, **kw):
+        if module.max_norm is not None:
+            raise NotImplementedError("max_norm is not supported")
+        return cls(module.num_embeddings, module.embedding_dim, mode=module.mode, sparse=module.sparse,
+                   _weight=module.weight.detach(), include_last_offset=module.include_last_offset,
+                   padding_idx=module.padding_idx, **kw)
+
+    @property
+    def weight(self):
+        return self.engine.table_tensor(self.table_id)
+
+    def _check(self):
+        return False if self.trusted_inputs else ("deferred" if self.deferred_check else True)
+
+    def forward(self, input, offsets=None, per_sample_weights=None):
+        idx, off = _bags_from(input, offsets, self.include_last_offset)
+        w = _weights_for(per_sample_weights, self.mode, input)
+        return self.engine.lookup_pooled(self._id_list, [idx.contiguous()], [off.contiguous()], self.mode,
+                                         per_sample_weights=None if w is None else [w], padding_idx=self.padding_idx,
+                                         check=self._check())[0]
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        self._table._save_to_state_dict(destination, prefix, keep_vars)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        self._table._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+    def extra_repr(self) -> str:
+        return (f"{self.num_embeddings}, {self.embedding_dim}, mode={self.mode!r}, padding_idx={self.padding_idx}, "
+                f"table_id={self.table_id}, engine=MI355X")
+
+
+def _weights_for(per_sample_weights, mode, input):
+    if per_sample_weights is None:
+        return None
+    if mode != "sum":
+        raise NotImplementedError("embedding_bag: per_sample_weights was not None. per_sample_weights is only supported "
+                                  f"for mode='sum' (got mode='{mode}'). Please open a feature request on GitHub.")
+    if tuple(per_sample_weights.shape) != tuple(input.shape):
+        raise ValueError("embedding_bag: If per_sample_weights ({}) is not None, then it must have the same shape as the "
+                         "input ({})".format(tuple(per_sample_weights.shape), tuple(input.shape)))
+    return per_sample_weights.reshape(-1).float().contiguous()
+
+
+class FusedPoolingEmbeddingBags(torch.nn.Module):
+    """All tables of a model, each with its own mode and padding_idx: forward(lS_o, lS_i, lS_w=None) -> list of [B, m] with
+    ONE engine call (lS_w: per-table per-sample weights or None, sum tables only)."""
+
+    def __init__(self, bags, trusted_inputs: bool | None = None, deferred_check: bool | None = None):
+        super().__init__()
+        self.bags = torch.nn.ModuleList(bags)
+        self.trusted_inputs = all(b.trusted_inputs for b in bags) if trusted_inputs is None else bool(trusted_inputs)
+        self.deferred_check = all(b.deferred_check for b in bags) if deferred_check is None else bool(deferred_check)
+        if len({id(b.engine) for b in self.bags}) != 1:
+            raise ValueError("all tables of a FusedPoolingEmbeddingBags must live in one engine")
+        self.engine = self.bags[0].engine
+        self._ids = [b.table_id for b in self.bags]
+        self._modes = [b.mode for b in self.bags]
+        self._pads = [b.padding_idx for b in self.bags]
+
+    @classmethod
+    def from_torch(cls, emb_l, **kw):
+        return cls([PoolingEmbeddingBag.from_torch(m, **kw) for m in emb_l])
+
+    def forward(self, lS_o, lS_i, lS_w=None):
+        check = False if self.trusted_inputs else ("deferred" if self.deferred_check else True)
+        idx, off, ws = [], [], []
+        for k, (b, i, o) in enumerate(zip(self.bags, lS_i, lS_o)):
+            i1, o1 = _bags_from(i, o, b.include_last_offset)
+            idx.append(i1.contiguous())
+            off.append(o1.contiguous())
+            ws.append(_weights_for(None if lS_w is None else lS_w[k], b.mode, i))
+        return self.engine.lookup_pooled(self._ids, idx, off, self._modes,
+                                         per_sample_weights=None if lS_w is None else ws, padding_idx=self._pads, check=check)
+
+    apply_emb = forward
+
+
+__all__ = ["EmbeddingBag", "FusedEmbeddingBags", "PoolingEmbeddingBag", "FusedPoolingEmbeddingBags", "default_engine"]
 _ = _l  # (lib is imported for its side effect: torch first, then libpimemb.so)
