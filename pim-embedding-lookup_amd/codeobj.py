@@ -238,12 +238,41 @@ def kernel_resources(lib_path: str, arch: str = "gfx950") -> dict[str, dict]:
     return out
 
 
-if __name__ == "__main__":
-    import sys
+def diff_kernels(hashes: dict, res: dict, other_hashes: dict, other_res: dict) -> list[str]:
+    """What a build's device code differs in from another's, one line per kernel: added, removed, machine code (kernel_hashes)
+    or resource figures (kernel_resources) changed.  Empty: the two builds ship the same kernels, byte for byte."""
+    out = []
+    for name in sorted(set(hashes) | set(other_hashes)):
+        if name not in other_hashes:
+            out.append(f"added    {name}")
+        elif name not in hashes:
+            out.append(f"removed  {name}")
+        elif hashes[name] != other_hashes[name]:
+            out.append(f"code     {name}  {other_hashes[name][:12]} -> {hashes[name][:12]}")
+        if name in hashes and name in other_hashes and res.get(name) != other_res.get(name):
+            was, now = other_res.get(name) or {}, res.get(name) or {}
+            moved = ", ".join(f"{k} {was.get(k)} -> {now.get(k)}" for k in sorted(set(was) | set(now)) if was.get(k) != now.get(k))
+            out.append(f"resource {name}  {moved}")
+    return out
+
+
+def main(argv: list[str]) -> int:
+    """codeobj [LIB [OTHER]]: the kernels of LIB (default: the in-tree library; an object file will do); with OTHER, only what
+    differs from it, and exit status 1 if anything does -- the check that a refactor left the machine code alone."""
     from .build import LIB_PATH
-    path = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else LIB_PATH
+    path = argv[0] if argv and not argv[0].startswith("-") else LIB_PATH
     res, hashes = kernel_resources(path), kernel_hashes(path)
+    if len(argv) > 1:
+        lines = diff_kernels(hashes, res, kernel_hashes(argv[1]), kernel_resources(argv[1]))
+        print("\n".join(lines + [f"{len(hashes)} kernels in {path}, {len(lines)} differences from {argv[1]}"]))
+        return 1 if lines else 0
     print("gfx950 code object sha256", device_code_sha256(path))
     for name in sorted(res):
         r = res[name]
         print(f"{r['vgpr']:4d} vgpr {r['vgpr_spill']:3d} spill {r['sgpr']:4d} sgpr {r['lds']:6d} lds {r['scratch']:5d} scratch  {hashes.get(name, '?')[:12]}  {name}")
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main(sys.argv[1:]))

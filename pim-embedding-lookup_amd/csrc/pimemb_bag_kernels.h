@@ -28,6 +28,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -35,6 +36,18 @@
 #include "pimemb.h"
 
 namespace pimemb {
+
+// The 32 bytes behind the fixed fields of a DevDesc mean what the launch needs them to mean; each launch kind reads ONE of
+// these views.
+struct RangedView {         // ranged launch (bag_sum_wavebatch_kernel<..., RANGED>; launch_bag_sum(..., ranged))
+    uint64_t row_lo;        // first row of the range this descriptor serves | kRangeOpenEnd
+    uint32_t *served;       // counter in HBM the launch adds the number of bags it served to, or nullptr
+};
+struct PoolView {           // pooled launch (bag_pool_*: pool_args)
+    const float *weights;   // per-sample weights, or nullptr
+    uint64_t padding_row;   // padding row id, ~0: none
+    uint64_t op;            // pooling op (kPoolOp*) | kPoolMean
+};
 
 // One table's share of a fused launch as the kernel sees it (HBM-resident array, 128 B each: a
 // workgroup fetches its descriptor with scalar loads).
@@ -53,9 +66,16 @@ struct alignas(64) DevDesc {
     const uint64_t *hot_hash; // open-addressing table: entry = (slot << 32) | row id, empty = ~0
     uint32_t n_hot;
     uint32_t hot_log2;        // log2 of the hash table size
-    uint64_t pad_[4];
+    union {                   // (words first: `DevDesc d{}` zeroes all of it)
+        uint64_t words[4];    // raw: a plain launch leaves them zero; the plan signature and the tuners' own kernels read them
+        RangedView ranged;
+        PoolView pool;
+    };
 };
 static_assert(sizeof(DevDesc) == 128, "DevDesc is two 64-byte lines");
+static_assert(offsetof(DevDesc, words) == 88 && offsetof(DevDesc, ranged.row_lo) == 88 && offsetof(DevDesc, ranged.served) == 96 &&
+              offsetof(DevDesc, pool.weights) == 88 && offsetof(DevDesc, pool.padding_row) == 96 && offsetof(DevDesc, pool.op) == 104,
+              "the views overlay words[0..2]: engine, kernels, tuners and the host-side stub agree on these offsets");
 
 using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -256,7 +276,7 @@ struct XcdSegDev {
     uint32_t desc, tile0, slot_begin, slot_end;
 };
 constexpr uint32_t kXmapDirect = 0x80000000u;   // flag in the `chunks` kernel argument: xmap is a per-workgroup table
-constexpr uint64_t kRangeOpenEnd = 1ull << 63;  // flag in DevDesc::pad_[0] of a ranged launch (EMB_RANGE_OPEN_END, pimemb.h)
+constexpr uint64_t kRangeOpenEnd = 1ull << 63;  // flag in RangedView::row_lo (EMB_RANGE_OPEN_END, pimemb.h)
 
 __device__ __forceinline__ bool decode_block(const uint32_t *__restrict__ xmap, uint32_t direct,
                                              uint32_t *desc_i, uint32_t *tile) {
@@ -368,6 +388,55 @@ struct NoProbe {
     __device__ __forceinline__ uint32_t operator()(uint64_t) const { return 0u; }
 };
 
+// ---- what the bag kernels share below their entry points -------------------------------------------------------------------
+// Each piece is used where it leaves the kernel's machine code as it was (the counter profiles are tied to it, and the
+// kernels are tuned to the register: DESIGN.md section 3.2b); a site that keeps its own text says so.
+
+// One descriptor as a kernel's locals: typed pointers and the counts, fetched once per workgroup (scalar loads).
+// (bag_pool_wavebatch_kernel and the three any-dim kernels spell these out: built from a DescView their code object changes.)
+template <typename IdxT>
+struct DescView {
+    const char *__restrict__ weights;
+    const IdxT *__restrict__ indices;
+    const IdxT *__restrict__ offsets;
+    float *__restrict__ out;
+    uint64_t n_idx, n_bags, last_row;
+    uint32_t fixed_pooling, n_tiles;
+    __device__ __forceinline__ explicit DescView(const DevDesc *dp)
+        : weights(static_cast<const char *>(dp->weights)), indices(static_cast<const IdxT *>(dp->indices)),
+          offsets(static_cast<const IdxT *>(dp->offsets)), out(dp->out), n_idx(dp->n_idx), n_bags(dp->n_bags),
+          last_row(dp->nr_rows - 1), fixed_pooling(dp->fixed_pooling), n_tiles(dp->n_tiles) {}
+};
+
+// Where a thread sits among the LPR-lane groups of its wavefront, and what a row of `chunks` 16-byte pieces means to it.
+// (The two wave-batch kernels; the three lane-group kernels -- sum, hot, pooled -- spell it out: with a LaneGeom the code
+// object of some of their instantiations changes.)
+template <int LPR, class Ops>
+struct LaneGeom {
+    uint32_t lane, wave;             // lane of the wavefront, wavefront of the workgroup
+    uint32_t sub, grp;               // piece of the row this lane owns, lane group of the wavefront
+    uint32_t row_bytes, out_stride;  // bytes of a table row, floats of a pooled row
+    const char *__restrict__ wsub;   // this lane's piece of row 0
+    __device__ __forceinline__ LaneGeom(const char *weights, uint32_t chunks)
+        : lane(threadIdx.x & 63u), wave(threadIdx.x >> 6), sub(lane & (LPR - 1)), grp(lane / LPR), row_bytes(chunks * 16u),
+          out_stride(chunks * Ops::kFloatsPerLane), wsub(weights + sub * 16u) {}
+};
+
+// Bounds [p, e) of bag `bag` < n_bags: from the offsets array (the last bag ends at n_idx), else bag * fixed_pooling.
+// (Plain arguments, not a DescView: the any-dim kernels have none.  bag_sum_group_kernel spells it out.)
+template <bool NT, bool CLAMP, typename IdxT>
+__device__ __forceinline__ void bag_range(const IdxT *__restrict__ offsets, uint64_t n_bags, uint64_t n_idx, uint32_t fixed_pooling,
+                                          uint64_t bag, uint64_t &p, uint64_t &e) {
+    if (offsets != nullptr) {
+        p = (uint64_t)load_meta<NT>(offsets + bag);
+        e = (bag + 1 < n_bags) ? (uint64_t)load_meta<NT>(offsets + bag + 1) : n_idx;
+    } else {
+        p = bag * fixed_pooling;
+        e = p + fixed_pooling;
+    }
+    if (CLAMP && e > n_idx) e = n_idx;
+}
+
 // ---- v1: one lane group per bag, no cross-lane traffic (kept as the A/B baseline) -------------
 template <typename IdxT, int DT, int LPR, class Cfg>
 __global__ void __launch_bounds__(Cfg::kBlock)
@@ -381,39 +450,35 @@ bag_sum_group_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg,
     uint32_t desc_i, tile;
     if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
     const uint32_t chunks = chunks_arg & ~kXmapDirect;
-    const DevDesc *dp = descs + desc_i;
-    const char *__restrict__ weights = static_cast<const char *>(dp->weights);
-    const IdxT *__restrict__ indices = static_cast<const IdxT *>(dp->indices);
-    const IdxT *__restrict__ offsets = static_cast<const IdxT *>(dp->offsets);
-    float *__restrict__ out = dp->out;
-    const uint64_t n_idx = dp->n_idx, n_bags = dp->n_bags, last_row = dp->nr_rows - 1;
-    const uint32_t fixed_pooling = dp->fixed_pooling, n_tiles = dp->n_tiles;
+    const DescView<IdxT> t(descs + desc_i);
 
+    // (a LaneGeom here changes the code object of 30 of this kernel's 42 instantiations)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
     const uint32_t row_bytes = chunks * 16u;
     const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
-    const char *__restrict__ wsub = weights + sub * 16u;
+    const char *__restrict__ wsub = t.weights + sub * 16u;
 
-    if (tile < n_tiles) {
+    if (tile < t.n_tiles) {
         const uint64_t bag = (uint64_t)tile * BAGS_PER_TILE + wave * BPW + grp;
         const bool live = sub < chunks;
-        if (bag >= n_bags) return;                     // whole lane group leaves together
+        if (bag >= t.n_bags) return;                   // whole lane group leaves together
         uint64_t p, e;
-        if (offsets != nullptr) {
-            p = (uint64_t)load_meta<Cfg::kNtMeta>(offsets + bag);
-            e = (bag + 1 < n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(offsets + bag + 1) : n_idx;
+        // (bag_range() spelled out: calling it changes the code object of 28 of the 42 instantiations, same registers, no spill)
+        if (t.offsets != nullptr) {
+            p = (uint64_t)load_meta<Cfg::kNtMeta>(t.offsets + bag);
+            e = (bag + 1 < t.n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(t.offsets + bag + 1) : t.n_idx;
         } else {
-            p = bag * fixed_pooling;
-            e = p + fixed_pooling;
+            p = bag * t.fixed_pooling;
+            e = p + t.fixed_pooling;
         }
-        if (Cfg::kClamp && e > n_idx) e = n_idx;
+        if (Cfg::kClamp && e > t.n_idx) e = t.n_idx;
         typename Ops::Acc acc = Ops::zero();
-        walk_bag<IdxT, LPR, Cfg, Ops>(indices, p, e, sub, grp, live, acc, NoProbe{},
+        walk_bag<IdxT, LPR, Cfg, Ops>(t.indices, p, e, sub, grp, live, acc, NoProbe{},
                                       [&](uint64_t r, uint32_t) -> u32x4 {
-                                          return load_row<Cfg::kNtRow>(wsub + clamp_row<Cfg::kClamp, IdxT>(r, last_row) * row_bytes);
+                                          return load_row<Cfg::kNtRow>(wsub + clamp_row<Cfg::kClamp, IdxT>(r, t.last_row) * row_bytes);
                                       });
-        store_row<Ops, Cfg, LPR>(acc, out + bag * out_stride, sub, grp, chunks, live);
+        store_row<Ops, Cfg, LPR>(acc, t.out + bag * out_stride, sub, grp, chunks, live);
     }
 }
 
@@ -453,14 +518,7 @@ bag_sum_anydim_kernel(const DevDesc *__restrict__ descs, uint32_t dim, uint32_t 
     const uint64_t bag = (uint64_t)blockIdx.x * (256u / lanes) + threadIdx.x / lanes;
     if (blockIdx.x >= dp->n_tiles || bag >= n_bags) return;
     uint64_t p0, e;
-    if (offsets != nullptr) {
-        p0 = (uint64_t)offsets[bag];
-        e = (bag + 1 < n_bags) ? (uint64_t)offsets[bag + 1] : n_idx;
-    } else {
-        p0 = bag * dp->fixed_pooling;
-        e = p0 + dp->fixed_pooling;
-    }
-    if (CLAMP && e > n_idx) e = n_idx;
+    bag_range<false, CLAMP>(offsets, n_bags, n_idx, dp->fixed_pooling, bag, p0, e);
     for (uint32_t col = threadIdx.x & (lanes - 1); col < dim; col += lanes) {
         typename E::Acc acc = 0;
         for (uint64_t p = p0; p < e; p++) {
@@ -494,14 +552,7 @@ bag_sum_anydim_vec_kernel(const DevDesc *__restrict__ descs, uint32_t dim, uint3
     const uint64_t bag = (uint64_t)blockIdx.x * (256u / lanes) + threadIdx.x / lanes;
     if (blockIdx.x >= dp->n_tiles || bag >= n_bags) return;
     uint64_t p0, e;
-    if (offsets != nullptr) {
-        p0 = (uint64_t)offsets[bag];
-        e = (bag + 1 < n_bags) ? (uint64_t)offsets[bag + 1] : n_idx;
-    } else {
-        p0 = bag * dp->fixed_pooling;
-        e = p0 + dp->fixed_pooling;
-    }
-    if (CLAMP && e > n_idx) e = n_idx;
+    bag_range<false, CLAMP>(offsets, n_bags, n_idx, dp->fixed_pooling, bag, p0, e);
     const uint32_t row_bytes = dim * ESZ, pieces = (dim + EP - 1) / EP;
     for (uint32_t piece = threadIdx.x & (lanes - 1); piece < pieces; piece += lanes) {
         const uint32_t n_el = (dim - piece * EP < EP) ? dim - piece * EP : EP;
@@ -515,7 +566,7 @@ bag_sum_anydim_vec_kernel(const DevDesc *__restrict__ descs, uint32_t dim, uint3
             return v;
         };
         typename Ops::Acc acc = Ops::zero();
-        uint64_t p = p0;
+        uint64_t p = p0;      // (walk_bag's non-shuffle loop, spelled out: a call of walk_bag changes the code object of 2 of 6 instantiations)
         for (; p + U <= e; p += U) {
             uint64_t r[U];
 #pragma unroll
@@ -558,10 +609,18 @@ bag_sum_anydim_vec_kernel(const DevDesc *__restrict__ descs, uint32_t dim, uint3
 #define PIMEMB_LPR32_ONEHOT_INFLIGHT 8
 #endif
 
+// (1-KiB rows, LPR = 64: eight rounds in flight = 8 KiB per wavefront and two registers more than the 64-VGPR cap of the
+// fp32 configurations holds -- 12 bytes of scratch per lane; PIMEMB_LPR64_ONEHOT_INFLIGHT picks the depth for that row width)
+template <int LPR, class Cfg>
+constexpr uint32_t onehot_rounds_in_flight() {      // of the LPR rounds of a 64-bag wave batch (both wave-batch kernels)
+    constexpr uint32_t depth = (LPR == 64) ? (uint32_t)PIMEMB_LPR64_ONEHOT_INFLIGHT : (LPR == 32) ? (uint32_t)PIMEMB_LPR32_ONEHOT_INFLIGHT : (uint32_t)Cfg::kOneHot;
+    return ((uint32_t)LPR < depth) ? (uint32_t)LPR : depth;
+}
+
 // ---- v2: wave batches of 64 bags, coalesced bounds, shuffle-distributed, one-hot fast path -------
 // RANGED (the sharded lookup's direct path, pimemb_shard.cpp): one index per bag, and a descriptor serves only the bags
-// whose row falls into [row_lo, row_lo + nr_rows) (row_lo in DevDesc::pad_[0]): out[b] = W[idx[b] - row_lo]; the other bags
-// are left untouched -- another shard of the table writes them, straight into the same output (pad_[1], if not null: a
+// whose row falls into [row_lo, row_lo + nr_rows) (DevDesc::ranged.row_lo): out[b] = W[idx[b] - row_lo]; the other bags
+// are left untouched -- another shard of the table writes them, straight into the same output (DevDesc::ranged.served, if not null: a
 // uint32 counter in HBM the launch adds the number of bags it served to).  A shard scans the
 // requester's RAW index array (its own, or a peer's through its mapping): no router, no counts, no un-router.  A whole
 // table is the range [0, nr_rows), so replicated tables and shards share ONE launch of the tuned kernel.
@@ -575,40 +634,28 @@ bag_sum_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg,
     constexpr uint32_t ROUNDS = LPR;        // rounds per 64-bag wave batch
     constexpr uint32_t NB = Cfg::kBatches;  // wave batches per step
     constexpr int U = Cfg::kUnroll;
-    // (1-KiB rows, LPR = 64: eight rounds in flight = 8 KiB per wavefront and two registers more than the 64-VGPR cap of the
-    // fp32 configurations holds -- 12 bytes of scratch per lane; PIMEMB_LPR64_ONEHOT_INFLIGHT picks the depth for that row width)
-    constexpr uint32_t kInFlight = (LPR == 64) ? (uint32_t)PIMEMB_LPR64_ONEHOT_INFLIGHT : (LPR == 32) ? (uint32_t)PIMEMB_LPR32_ONEHOT_INFLIGHT : (uint32_t)Cfg::kOneHot;
-    constexpr uint32_t RU = (ROUNDS < kInFlight) ? ROUNDS : kInFlight;
+    constexpr uint32_t RU = onehot_rounds_in_flight<LPR, Cfg>();
 
     uint32_t desc_i, tile;
     if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
     const uint32_t chunks = chunks_arg & ~kXmapDirect;
     const DevDesc *dp = descs + desc_i;
-    const char *__restrict__ weights = static_cast<const char *>(dp->weights);
-    const IdxT *__restrict__ indices = static_cast<const IdxT *>(dp->indices);
-    const IdxT *__restrict__ offsets = static_cast<const IdxT *>(dp->offsets);
-    float *__restrict__ out = dp->out;
-    const uint64_t n_idx = dp->n_idx, n_bags = dp->n_bags, last_row = dp->nr_rows - 1;
-    const uint32_t fixed_pooling = dp->fixed_pooling, n_tiles = dp->n_tiles;
+    const DescView<IdxT> t(dp);
 
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
-    const uint32_t row_bytes = chunks * 16u;
-    const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
-    const char *__restrict__ wsub = weights + sub * 16u;
-    const bool lane_live = sub < chunks;
+    const LaneGeom<LPR, Ops> ln(t.weights, chunks);
+    const bool lane_live = ln.sub < chunks;
     uint64_t row_lo = 0;
     bool open_end = false;               // RANGED: ids at or beyond the end of this range are this descriptor's to ZERO (EMB_RANGE_OPEN_END)
     uint32_t *served_ctr = nullptr;      // RANGED: where this descriptor's launch adds the number of bags it served (or null)
     if constexpr (RANGED) {
-        row_lo = dp->pad_[0] & ~kRangeOpenEnd;
-        open_end = (dp->pad_[0] & kRangeOpenEnd) != 0;
-        served_ctr = reinterpret_cast<uint32_t *>(dp->pad_[1]);
+        row_lo = dp->ranged.row_lo & ~kRangeOpenEnd;
+        open_end = (dp->ranged.row_lo & kRangeOpenEnd) != 0;
+        served_ctr = dp->ranged.served;
     }
 
-    if (tile < n_tiles) {
-        const uint64_t step_base = ((uint64_t)tile * kWaves + wave) * (64u * NB);
-        if (step_base >= n_bags) return;  // wave-uniform
+    if (tile < t.n_tiles) {
+        const uint64_t step_base = ((uint64_t)tile * kWaves + ln.wave) * (64u * NB);
+        if (step_base >= t.n_bags) return;  // wave-uniform
 
         // lane l of batch q holds the bounds of bag step_base + 64q + l (past-the-end = empty)
         uint64_t st[NB];
@@ -621,24 +668,24 @@ bag_sum_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg,
         if constexpr (Cfg::kSpeculate) {
 #pragma unroll
             for (uint32_t q = 0; q < NB; q++) {
-                const uint64_t mb = step_base + 64u * q + lane;
+                const uint64_t mb = step_base + 64u * q + ln.lane;
                 spec[q] = 0;
-                if (mb < n_idx) spec[q] = load_meta<Cfg::kNtMeta>(indices + mb);
+                if (mb < t.n_idx) spec[q] = load_meta<Cfg::kNtMeta>(t.indices + mb);
             }
         }
 #pragma unroll
         for (uint32_t q = 0; q < NB; q++) {
-            const uint64_t mb = step_base + 64u * q + lane;
-            uint64_t en;
-            if (offsets != nullptr) {
-                st[q] = (mb < n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(offsets + mb) : n_idx;
-                en = (mb + 1 < n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(offsets + mb + 1) : n_idx;
+            const uint64_t mb = step_base + 64u * q + ln.lane;
+            uint64_t en;    // (this block as a function shared with bag_pool_wavebatch_kernel: 18 instantiations here, 28 there change)
+            if (t.offsets != nullptr) {
+                st[q] = (mb < t.n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(t.offsets + mb) : t.n_idx;
+                en = (mb + 1 < t.n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(t.offsets + mb + 1) : t.n_idx;
             } else {
-                st[q] = (mb < n_bags ? mb : n_bags) * fixed_pooling;
-                en = (mb + 1 < n_bags ? mb + 1 : n_bags) * fixed_pooling;
+                st[q] = (mb < t.n_bags ? mb : t.n_bags) * t.fixed_pooling;
+                en = (mb + 1 < t.n_bags ? mb + 1 : t.n_bags) * t.fixed_pooling;
             }
             if (Cfg::kClamp) {                       // malformed offsets: keep [st, en) inside [0, n_idx]
-                if (en > n_idx) en = n_idx;
+                if (en > t.n_idx) en = t.n_idx;
                 if (st[q] > en) st[q] = en;
             }
             len[q] = (uint32_t)(en - st[q]);
@@ -653,17 +700,17 @@ bag_sum_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg,
             for (uint32_t q = 0; q < NB; q++) {
                 my[q] = 0;
                 if constexpr (Cfg::kSpeculate) {
-                    const uint64_t mb = step_base + 64u * q + lane;
-                    if (len[q]) my[q] = (st[q] == mb) ? spec[q] : load_meta<Cfg::kNtMeta>(indices + st[q]);
+                    const uint64_t mb = step_base + 64u * q + ln.lane;
+                    if (len[q]) my[q] = (st[q] == mb) ? spec[q] : load_meta<Cfg::kNtMeta>(t.indices + st[q]);
                 } else {
-                    if (len[q]) my[q] = load_meta<Cfg::kNtMeta>(indices + st[q]);
+                    if (len[q]) my[q] = load_meta<Cfg::kNtMeta>(t.indices + st[q]);
                 }
                 if constexpr (RANGED) {     // row ids relative to this shard; a bag of another shard counts as empty
                     const uint64_t id = (uint64_t)my[q];               // (a negative int64 id: huge, beyond every range)
                     const uint64_t r = id - row_lo;                    // (wraps far out of range below row_lo)
                     // len: 1 = served here; 2 = an id no range holds, and this descriptor answers for the open end: the bag's
                     // pooled row is written as zeros (not served, not counted); 0 = some other shard's bag, left alone
-                    if (r > last_row) len[q] = (len[q] && open_end && id >= row_lo) ? 2u : 0u;
+                    if (r > t.last_row) len[q] = (len[q] && open_end && id >= row_lo) ? 2u : 0u;
                     my[q] = (IdxT)r;
                 }
             }
@@ -679,7 +726,7 @@ bag_sum_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg,
 #pragma unroll
                     for (uint32_t q = 0; q < NB; q++) n += (uint32_t)__popcll(__ballot(len[q] == 1u));
                     uint32_t *slot = served_ctr + (size_t)(blockIdx.x % EMB_SERVED_LANES) * (EMB_SERVED_STRIDE / 4u);
-                    if (lane == 0 && n) (void)__hip_atomic_fetch_add(slot, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (ln.lane == 0 && n) (void)__hip_atomic_fetch_add(slot, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
 #pragma unroll
@@ -691,32 +738,33 @@ bag_sum_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg,
                 for (uint32_t q = 0; q < NB; q++)
 #pragma unroll
                     for (uint32_t jj = 0; jj < RU; jj++) {
-                        const uint32_t src = (j0 + jj) * BPR + grp;
-                        const uint64_t r = clamp_row<Cfg::kClamp, IdxT>(shfl_index<IdxT>(my[q], src), last_row);
+                        const uint32_t src = (j0 + jj) * BPR + ln.grp;
+                        const uint64_t r = clamp_row<Cfg::kClamp, IdxT>(shfl_index<IdxT>(my[q], src), t.last_row);
                         const uint32_t l = shfl_u32(len[q], src);
                         has[q][jj] = RANGED ? l == 1u : l != 0u;
                         zero_it[q][jj] = RANGED && l == 2u;
                         v[q][jj] = u32x4{0u, 0u, 0u, 0u};
-                        if (has[q][jj] && lane_live) v[q][jj] = load_row<Cfg::kNtRow>(wsub + r * row_bytes);
+                        if (has[q][jj] && lane_live) v[q][jj] = load_row<Cfg::kNtRow>(ln.wsub + r * ln.row_bytes);
                     }
 #pragma unroll
                 for (uint32_t q = 0; q < NB; q++)
 #pragma unroll
                     for (uint32_t jj = 0; jj < RU; jj++) {
-                        const uint64_t bag = step_base + 64u * q + (j0 + jj) * BPR + grp;
+                        const uint64_t bag = step_base + 64u * q + (j0 + jj) * BPR + ln.grp;
                         // (RANGED: only the bags this shard holds the row of are written)
-                        const bool wr = RANGED ? (has[q][jj] || zero_it[q][jj]) : bag < n_bags;
+                        const bool wr = RANGED ? (has[q][jj] || zero_it[q][jj]) : bag < t.n_bags;
+                        // (store_row alone, which covers both cases, changes the code object of 50 instantiations)
                         if constexpr (!Ops::kGroupStore) {
                             if (wr && lane_live) {
                                 typename Ops::Acc acc = Ops::zero();
                                 if (has[q][jj]) Ops::add(acc, v[q][jj]);
                                 Ops::template store<Cfg::kNtStore>(
-                                    acc, out + bag * out_stride + sub * Ops::kFloatsPerLane);
+                                    acc, t.out + bag * ln.out_stride + ln.sub * Ops::kFloatsPerLane);
                             }
                         } else {   // all lanes take part in the group store's shuffles
                             typename Ops::Acc acc = Ops::zero();
                             if (has[q][jj] && lane_live) Ops::add(acc, v[q][jj]);
-                            store_row<Ops, Cfg, LPR>(acc, out + bag * out_stride, sub, grp, chunks,
+                            store_row<Ops, Cfg, LPR>(acc, t.out + bag * ln.out_stride, ln.sub, ln.grp, chunks,
                                                      wr && lane_live);
                         }
                     }
@@ -725,38 +773,39 @@ bag_sum_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg,
         }
         if constexpr (RANGED) return;      // (the host hands a ranged launch fixed_pooling 1 only: every step is one-hot)
 
-        // general step: each round, a lane group walks its bag in index order
+        // general step: each round, a lane group walks its bag in index order (walk_bag's non-shuffle loop, spelled out: a call of
+        // walk_bag changes the code object of 46 instantiations)
 #pragma unroll 1
         for (uint32_t q = 0; q < NB; q++) {
 #pragma unroll 1
             for (uint32_t j = 0; j < ROUNDS; j++) {
-                const uint32_t src = j * BPR + grp;
+                const uint32_t src = j * BPR + ln.grp;
                 uint64_t p = shfl_u64(st[q], src);
                 const uint64_t e = p + shfl_u32(len[q], src);
                 const uint64_t bag = step_base + 64u * q + src;
                 // (no early `continue`: every lane must reach the next round's shuffles)
                 typename Ops::Acc acc = Ops::zero();
-                if (bag < n_bags && lane_live) {
+                if (bag < t.n_bags && lane_live) {
                     for (; p + U <= e; p += U) {
                         uint64_t r[U];
 #pragma unroll
-                        for (int k = 0; k < U; k++) r[k] = (uint64_t)load_meta<Cfg::kNtMeta>(indices + p + k);
+                        for (int k = 0; k < U; k++) r[k] = (uint64_t)load_meta<Cfg::kNtMeta>(t.indices + p + k);
                         u32x4 v[U];
 #pragma unroll
                         for (int k = 0; k < U; k++)
-                            v[k] = load_row<Cfg::kNtRow>(wsub + clamp_row<Cfg::kClamp, IdxT>(r[k], last_row) * row_bytes);
+                            v[k] = load_row<Cfg::kNtRow>(ln.wsub + clamp_row<Cfg::kClamp, IdxT>(r[k], t.last_row) * ln.row_bytes);
 #pragma unroll
                         for (int k = 0; k < U; k++) Ops::add(acc, v[k]);
                     }
                     for (; p < e; p++) {
-                        const uint64_t r = clamp_row<Cfg::kClamp, IdxT>((uint64_t)load_meta<Cfg::kNtMeta>(indices + p), last_row);
-                        Ops::add(acc, load_row<Cfg::kNtRow>(wsub + r * row_bytes));
+                        const uint64_t r = clamp_row<Cfg::kClamp, IdxT>((uint64_t)load_meta<Cfg::kNtMeta>(t.indices + p), t.last_row);
+                        Ops::add(acc, load_row<Cfg::kNtRow>(ln.wsub + r * ln.row_bytes));
                     }
                     if constexpr (!Ops::kGroupStore)
-                        Ops::template store<Cfg::kNtStore>(acc, out + bag * out_stride + sub * Ops::kFloatsPerLane);
+                        Ops::template store<Cfg::kNtStore>(acc, t.out + bag * ln.out_stride + ln.sub * Ops::kFloatsPerLane);
                 }
                 if constexpr (Ops::kGroupStore)
-                    store_row<Ops, Cfg, LPR>(acc, out + bag * out_stride, sub, grp, chunks, bag < n_bags && lane_live);
+                    store_row<Ops, Cfg, LPR>(acc, t.out + bag * ln.out_stride, ln.sub, ln.grp, chunks, bag < t.n_bags && lane_live);
             }
         }
     }
@@ -800,20 +849,15 @@ bag_sum_hot_kernel(const DevDesc *__restrict__ descs, uint32_t chunks) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
     const DevDesc *dp = descs + blockIdx.y;
-    const char *__restrict__ weights = static_cast<const char *>(dp->weights);
-    const IdxT *__restrict__ indices = static_cast<const IdxT *>(dp->indices);
-    const IdxT *__restrict__ offsets = static_cast<const IdxT *>(dp->offsets);
-    float *__restrict__ out = dp->out;
-    const uint64_t n_idx = dp->n_idx, n_bags = dp->n_bags;
-    const uint32_t fixed_pooling = dp->fixed_pooling, n_tiles = dp->n_tiles;
+    const DescView<IdxT> t(dp);
     const uint32_t n_hot = dp->n_hot, hot_log2 = dp->hot_log2;
-    const uint64_t last_row = dp->nr_rows - 1;
 
+    // (a LaneGeom here changes the code object of 8 of this kernel's 42 instantiations)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
     const uint32_t row_bytes = chunks * 16u;
     const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
-    const char *__restrict__ wsub = weights + sub * 16u;
+    const char *__restrict__ wsub = t.weights + sub * 16u;
 
     // stage hot rows + hash into LDS (rows first: 16-byte aligned pieces)
     u32x4 *lrows = reinterpret_cast<u32x4 *>(lds_raw);
@@ -833,25 +877,18 @@ bag_sum_hot_kernel(const DevDesc *__restrict__ descs, uint32_t chunks) {
     // one gathered row piece: LDS if the row is hot, L2/HBM otherwise
     auto fetch = [&](uint64_t r, uint32_t tok) -> u32x4 {
         if (tok & 0x80000000u) return lsub[(tok & 0x7fffffffu) * chunks];
-        return load_row<Cfg::kNtRow>(wsub + clamp_row<Cfg::kClamp, IdxT>(r, last_row) * row_bytes);
+        return load_row<Cfg::kNtRow>(wsub + clamp_row<Cfg::kClamp, IdxT>(r, t.last_row) * row_bytes);
     };
 
     const bool live = sub < chunks;
-    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    for (uint32_t tile = blockIdx.x; tile < t.n_tiles; tile += gridDim.x) {
         const uint64_t bag = (uint64_t)tile * BAGS_PER_TILE + wave * BPW + grp;
-        if (bag < n_bags) {                            // (no `continue`: lane groups stay whole for the shuffles)
+        if (bag < t.n_bags) {                          // (no `continue`: lane groups stay whole for the shuffles)
             uint64_t p, e;
-            if (offsets != nullptr) {
-                p = (uint64_t)load_meta<Cfg::kNtMeta>(offsets + bag);
-                e = (bag + 1 < n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(offsets + bag + 1) : n_idx;
-            } else {
-                p = bag * fixed_pooling;
-                e = p + fixed_pooling;
-            }
-            if (Cfg::kClamp && e > n_idx) e = n_idx;
+            bag_range<Cfg::kNtMeta, Cfg::kClamp>(t.offsets, t.n_bags, t.n_idx, t.fixed_pooling, bag, p, e);
             typename Ops::Acc acc = Ops::zero();
-            walk_bag<IdxT, LPR, Cfg, Ops>(indices, p, e, sub, grp, live, acc, probe, fetch);
-            store_row<Ops, Cfg, LPR>(acc, out + bag * out_stride, sub, grp, chunks, live);
+            walk_bag<IdxT, LPR, Cfg, Ops>(t.indices, p, e, sub, grp, live, acc, probe, fetch);
+            store_row<Ops, Cfg, LPR>(acc, t.out + bag * out_stride, sub, grp, chunks, live);
         }
     }
 }
@@ -868,8 +905,7 @@ bag_sum_hot_kernel(const DevDesc *__restrict__ descs, uint32_t chunks) {
 //                                                                  included -- v_max_f32 would not keep it; empty -> +0)
 // Padding entries are skipped before their row is gathered.  hipcc contracts a * b + c into an FMA by default, so the
 // unfused rule lives under `fp contract(off)` and the fused one is an explicit fma.
-// DevDesc::pad_ of a pooled launch: [0] per-sample weights (const float *, or 0), [1] padding row id (~0: none),
-// [2] pooling op (kPoolOp*) | kPoolMean.
+// The pooling spec of a descriptor rides in DevDesc::pool (PoolView).
 constexpr uint32_t kPoolOpAdd = 0, kPoolOpFma = 1, kPoolOpMulAdd = 2, kPoolOpMax = 3;
 constexpr uint32_t kPoolMean = 0x100u;
 
@@ -882,10 +918,10 @@ struct PoolArgs {
 
 __device__ __forceinline__ PoolArgs pool_args(const DevDesc *dp) {
     PoolArgs a;
-    a.psw = reinterpret_cast<const float *>(dp->pad_[0]);
-    a.pad = dp->pad_[1];
-    a.op = (uint32_t)dp->pad_[2] & 0xffu;
-    a.mean = (dp->pad_[2] & kPoolMean) != 0;
+    a.psw = dp->pool.weights;
+    a.pad = dp->pool.padding_row;
+    a.op = (uint32_t)dp->pool.op & 0xffu;
+    a.mean = (dp->pool.op & kPoolMean) != 0;
     return a;
 }
 
@@ -932,6 +968,8 @@ __device__ __forceinline__ void pool_finish(Acc &acc, uint32_t cnt, bool mean) {
 
 // Walk one bag [p, e) in index order for a lane that owns a 16-byte piece of the row: kUnroll indices (and weights) are
 // loaded, padding entries dropped, the remaining rows gathered together, then taken in order.
+// (bag_pool_anydim_kernel has its own copy of the load / drop-padding step: as a function of U entries, or of one, shared by
+// the two, it changes the code object of all 64 pooled kernels.)
 template <typename IdxT, int DT, class Cfg>
 __device__ __forceinline__ void pool_walk(const IdxT *__restrict__ indices, const PoolArgs &a, uint64_t p, uint64_t e,
                                           const char *__restrict__ wsub, uint32_t row_bytes, uint64_t last_row,
@@ -981,38 +1019,27 @@ bag_pool_group_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg, co
     if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
     const uint32_t chunks = chunks_arg & ~kXmapDirect;
     const DevDesc *dp = descs + desc_i;
-    const char *__restrict__ weights = static_cast<const char *>(dp->weights);
-    const IdxT *__restrict__ indices = static_cast<const IdxT *>(dp->indices);
-    const IdxT *__restrict__ offsets = static_cast<const IdxT *>(dp->offsets);
-    float *__restrict__ out = dp->out;
-    const uint64_t n_idx = dp->n_idx, n_bags = dp->n_bags, last_row = dp->nr_rows - 1;
-    const uint32_t fixed_pooling = dp->fixed_pooling, n_tiles = dp->n_tiles;
+    const DescView<IdxT> t(dp);
     const PoolArgs a = pool_args(dp);
 
+    // (a LaneGeom here changes the code object of this kernel's 4 one-lane-per-row instantiations)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
     const uint32_t row_bytes = chunks * 16u;
     const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
-    const char *__restrict__ wsub = weights + sub * 16u;
+    const char *__restrict__ wsub = t.weights + sub * 16u;
 
-    if (tile < n_tiles) {
+    if (tile < t.n_tiles) {
         const uint64_t bag = (uint64_t)tile * BAGS_PER_TILE + wave * BPW + grp;
         const bool live = sub < chunks;
-        if (bag >= n_bags) return;                     // whole lane group leaves together
+        if (bag >= t.n_bags) return;                   // whole lane group leaves together
         uint64_t p, e;
-        if (offsets != nullptr) {
-            p = (uint64_t)load_meta<Cfg::kNtMeta>(offsets + bag);
-            e = (bag + 1 < n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(offsets + bag + 1) : n_idx;
-        } else {
-            p = bag * fixed_pooling;
-            e = p + fixed_pooling;
-        }
-        if (Cfg::kClamp && e > n_idx) e = n_idx;
+        bag_range<Cfg::kNtMeta, Cfg::kClamp>(t.offsets, t.n_bags, t.n_idx, t.fixed_pooling, bag, p, e);
         typename Ops::Acc acc = Ops::zero();
         uint32_t cnt = 0;
-        if (live) pool_walk<IdxT, DT, Cfg>(indices, a, p, e, wsub, row_bytes, last_row, acc, cnt);
+        if (live) pool_walk<IdxT, DT, Cfg>(t.indices, a, p, e, wsub, row_bytes, t.last_row, acc, cnt);
         pool_finish<DT>(acc, cnt, a.mean);
-        store_row<Ops, Cfg, LPR>(acc, out + bag * out_stride, sub, grp, chunks, live);
+        store_row<Ops, Cfg, LPR>(acc, t.out + bag * out_stride, sub, grp, chunks, live);
     }
 }
 
@@ -1027,13 +1054,13 @@ bag_pool_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg
     constexpr uint32_t kWaves = Cfg::kBlock / 64;
     constexpr uint32_t BPR = 64 / LPR;      // bags per round
     constexpr uint32_t ROUNDS = LPR;        // rounds per 64-bag wave batch
-    constexpr uint32_t kInFlight = (LPR == 64) ? (uint32_t)PIMEMB_LPR64_ONEHOT_INFLIGHT : (LPR == 32) ? (uint32_t)PIMEMB_LPR32_ONEHOT_INFLIGHT : (uint32_t)Cfg::kOneHot;
-    constexpr uint32_t RU = (ROUNDS < kInFlight) ? ROUNDS : kInFlight;
+    constexpr uint32_t RU = onehot_rounds_in_flight<LPR, Cfg>();
 
     uint32_t desc_i, tile;
     if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
     const uint32_t chunks = chunks_arg & ~kXmapDirect;
     const DevDesc *dp = descs + desc_i;
+    // (a DescView here changes the code object of the two fp32 two-lanes-per-row instantiations)
     const char *__restrict__ weights = static_cast<const char *>(dp->weights);
     const IdxT *__restrict__ indices = static_cast<const IdxT *>(dp->indices);
     const IdxT *__restrict__ offsets = static_cast<const IdxT *>(dp->offsets);
@@ -1041,27 +1068,22 @@ bag_pool_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg
     const uint64_t n_idx = dp->n_idx, n_bags = dp->n_bags, last_row = dp->nr_rows - 1;
     const uint32_t fixed_pooling = dp->fixed_pooling, n_tiles = dp->n_tiles;
     const PoolArgs a = pool_args(dp);
-
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
-    const uint32_t row_bytes = chunks * 16u;
-    const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
-    const char *__restrict__ wsub = weights + sub * 16u;
-    const bool lane_live = sub < chunks;
+    const LaneGeom<LPR, Ops> ln(weights, chunks);
+    const bool lane_live = ln.sub < chunks;
 
     if (tile >= n_tiles) return;
-    const uint64_t step_base = ((uint64_t)tile * kWaves + wave) * 64u;
+    const uint64_t step_base = ((uint64_t)tile * kWaves + ln.wave) * 64u;
     if (step_base >= n_bags) return;  // wave-uniform
 
     // lane l holds the bounds of bag step_base + l (past-the-end = empty)
-    const uint64_t mb = step_base + lane;
+    const uint64_t mb = step_base + ln.lane;
     IdxT spec = 0;
     float spec_w = 1.f;
     if (mb < n_idx) {
         spec = load_meta<Cfg::kNtMeta>(indices + mb);
         if (a.psw != nullptr) spec_w = load_meta<Cfg::kNtMeta>(a.psw + mb);
     }
-    uint64_t st, en;
+    uint64_t st, en;    // (shared with bag_sum_wavebatch_kernel's block as a function: every instantiation changes)
     if (offsets != nullptr) {
         st = (mb < n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(offsets + mb) : n_idx;
         en = (mb + 1 < n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(offsets + mb + 1) : n_idx;
@@ -1090,25 +1112,21 @@ bag_pool_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg
             bool has[RU];
 #pragma unroll
             for (uint32_t jj = 0; jj < RU; jj++) {
-                const uint32_t src = (j0 + jj) * BPR + grp;
+                const uint32_t src = (j0 + jj) * BPR + ln.grp;
                 const uint64_t r = clamp_row<Cfg::kClamp, IdxT>(shfl_index<IdxT>(my, src), last_row);
                 has[jj] = shfl_u32(len, src) != 0u;
                 v[jj] = u32x4{0u, 0u, 0u, 0u};
-                if (has[jj] && lane_live) v[jj] = load_row<Cfg::kNtRow>(wsub + r * row_bytes);
+                if (has[jj] && lane_live) v[jj] = load_row<Cfg::kNtRow>(ln.wsub + r * ln.row_bytes);
             }
 #pragma unroll
             for (uint32_t jj = 0; jj < RU; jj++) {
-                const uint32_t src = (j0 + jj) * BPR + grp;
+                const uint32_t src = (j0 + jj) * BPR + ln.grp;
                 const uint64_t bag = step_base + src;
                 const float w = shfl_f32(my_w, src);
                 typename Ops::Acc acc = Ops::zero();
                 if (has[jj] && lane_live) pool_combine<DT>(acc, v[jj], w, a.op, true);
-                if constexpr (!Ops::kGroupStore) {
-                    if (bag < n_bags && lane_live)
-                        Ops::template store<Cfg::kNtStore>(acc, out + bag * out_stride + sub * Ops::kFloatsPerLane);
-                } else {   // all lanes take part in the group store's shuffles
-                    store_row<Ops, Cfg, LPR>(acc, out + bag * out_stride, sub, grp, chunks, bag < n_bags && lane_live);
-                }
+                // (all lanes take part in a group store's shuffles)
+                store_row<Ops, Cfg, LPR>(acc, out + bag * ln.out_stride, ln.sub, ln.grp, chunks, bag < n_bags && lane_live);
             }
         }
         return;
@@ -1117,21 +1135,16 @@ bag_pool_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg
     // general step: each round, a lane group walks its bag in index order
 #pragma unroll 1
     for (uint32_t j = 0; j < ROUNDS; j++) {
-        const uint32_t src = j * BPR + grp;
+        const uint32_t src = j * BPR + ln.grp;
         const uint64_t p = shfl_u64(st, src);
         const uint64_t e = p + shfl_u32(len, src);
         const uint64_t bag = step_base + src;
         // (no early `continue`: every lane must reach the next round's shuffles)
         typename Ops::Acc acc = Ops::zero();
         uint32_t cnt = 0;
-        if (bag < n_bags && lane_live) pool_walk<IdxT, DT, Cfg>(indices, a, p, e, wsub, row_bytes, last_row, acc, cnt);
+        if (bag < n_bags && lane_live) pool_walk<IdxT, DT, Cfg>(indices, a, p, e, ln.wsub, ln.row_bytes, last_row, acc, cnt);
         pool_finish<DT>(acc, cnt, a.mean);
-        if constexpr (!Ops::kGroupStore) {
-            if (bag < n_bags && lane_live)
-                Ops::template store<Cfg::kNtStore>(acc, out + bag * out_stride + sub * Ops::kFloatsPerLane);
-        } else {
-            store_row<Ops, Cfg, LPR>(acc, out + bag * out_stride, sub, grp, chunks, bag < n_bags && lane_live);
-        }
+        store_row<Ops, Cfg, LPR>(acc, out + bag * ln.out_stride, ln.sub, ln.grp, chunks, bag < n_bags && lane_live);
     }
 }
 
@@ -1153,14 +1166,7 @@ bag_pool_anydim_kernel(const DevDesc *__restrict__ descs, uint32_t dim, uint32_t
     if (blockIdx.x >= dp->n_tiles || bag >= n_bags) return;
     const PoolArgs a = pool_args(dp);
     uint64_t p0, e;
-    if (offsets != nullptr) {
-        p0 = (uint64_t)offsets[bag];
-        e = (bag + 1 < n_bags) ? (uint64_t)offsets[bag + 1] : n_idx;
-    } else {
-        p0 = bag * dp->fixed_pooling;
-        e = p0 + dp->fixed_pooling;
-    }
-    if (CLAMP && e > n_idx) e = n_idx;
+    bag_range<false, CLAMP>(offsets, n_bags, n_idx, dp->fixed_pooling, bag, p0, e);
     const uint32_t row_bytes = dim * ESZ, units = (dim + EP - 1) / EP;
     for (uint32_t unit = threadIdx.x & (lanes - 1); unit < units; unit += lanes) {
         const uint32_t n_el = (dim - unit * EP < EP) ? dim - unit * EP : EP;

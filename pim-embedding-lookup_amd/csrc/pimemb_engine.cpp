@@ -541,18 +541,18 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
             d.nr_rows = t.nr_rows;
             d.fixed_pooling = u.offsets ? 0u : u.fixed_pooling;
             d.n_tiles = (uint32_t)tiles;
-            if (row_lo) d.pad_[0] = row_lo[i];
-            if (row_lo && served) d.pad_[1] = (uint64_t)(uintptr_t)served[i];
-            if (g.pool) {           // the pooling spec rides in pad_ (pimemb_bag_kernels.h: pool_args)
+            if (row_lo) d.ranged.row_lo = row_lo[i];
+            if (row_lo && served) d.ranged.served = served[i];
+            if (g.pool) {           // the pooling spec rides in DevDesc::pool (pimemb_bag_kernels.h: pool_args)
                 const emb_pool_spec &ps = pools[i];
                 const bool weighted = ps.per_sample_weights != nullptr, padded = (ps.flags & EMB_POOL_PADDING) != 0;
                 const uint32_t op = ps.mode == EMB_POOL_MAX ? pimemb::kPoolOpMax
                                     : !weighted          ? pimemb::kPoolOpAdd
                                     : padded             ? pimemb::kPoolOpMulAdd
                                                          : pimemb::kPoolOpFma;
-                d.pad_[0] = (uint64_t)(uintptr_t)(st_weights && weighted ? (*st_weights)[i] : ps.per_sample_weights);
-                d.pad_[1] = padded ? (uint64_t)ps.padding_idx : ~0ull;
-                d.pad_[2] = op | (ps.mode == EMB_POOL_MEAN ? pimemb::kPoolMean : 0u);
+                d.pool.weights = st_weights && weighted ? (*st_weights)[i] : ps.per_sample_weights;
+                d.pool.padding_row = padded ? (uint64_t)ps.padding_idx : ~0ull;
+                d.pool.op = op | (ps.mode == EMB_POOL_MEAN ? pimemb::kPoolMean : 0u);
                 g.n_weighted += weighted;
                 g.n_padding += padded;
                 if (weighted) r->bytes += u.n_indices * 4;
@@ -1556,10 +1556,10 @@ static int plan_create(emb_engine *e, const emb_lookup_desc *descs, const uint64
             for (uint32_t i = 0; i < g.n; i++, di++) {
                 const DevDesc &d = r.descs[di];
                 mix(d.n_tiles); mix(d.n_bags); mix(d.n_idx); mix(d.nr_rows); mix(d.fixed_pooling); mix(d.offsets != nullptr); mix(d.n_hot);
-                if (g.pool) {           // pad_ holds the pooling spec: the weights' presence, never their address
-                    mix(d.pad_[0] != 0); mix(d.pad_[1]); mix(d.pad_[2]);
+                if (g.pool) {           // the pooling spec: the weights' presence, never their address
+                    mix(d.pool.weights != nullptr); mix(d.pool.padding_row); mix(d.pool.op);
                 } else {
-                    mix(d.pad_[0]); mix(d.pad_[1] != 0);
+                    mix(d.ranged.row_lo); mix(d.ranged.served != nullptr);
                 }
             }
         }

@@ -48,7 +48,7 @@ hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max
                           hipStream_t stream, bool ranged = false);
 
 // Pooled lookup (emb_lookup_pooled: mean / max, per-sample weights, padding_idx) over descriptors of one dtype (fp32 / fp16)
-// and dim whose pooling spec sits in DevDesc::pad_ (pimemb_bag_kernels.h, bag_pool_*).  kind: KERNEL_WAVEBATCH,
+// and dim whose pooling spec sits in DevDesc::pool (pimemb_bag_kernels.h, bag_pool_*).  kind: KERNEL_WAVEBATCH,
 // KERNEL_GROUP or KERNEL_ANYDIM (no two-batch or hot-row variant).  Pure enqueue.
 hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, emb_dtype dtype,
                            emb_index_type itype, const LaunchGeom &g, KernelKind kind, const uint32_t *d_xmap,
@@ -59,8 +59,8 @@ hipError_t launch_bag_sum_hot(const DevDesc *d_descs, uint32_t n_descs, uint32_t
                               emb_dtype dtype, emb_index_type itype, const LaunchGeom &g, hipStream_t stream);
 
 // ranged (wave-batch kinds, one index per bag): a descriptor serves only the bags whose row falls into
-// [row_lo, row_lo + nr_rows) -- row_lo in DevDesc::pad_[0] -- as out[b] = W[idx[b] - row_lo]; other bags are left untouched
-// (kRangeOpenEnd in pad_[0]: bags whose id lies at or beyond the end of the range are written as zero rows).
+// [row_lo, row_lo + nr_rows) -- DevDesc::ranged.row_lo -- as out[b] = W[idx[b] - row_lo]; other bags are left untouched
+// (kRangeOpenEnd in row_lo: bags whose id lies at or beyond the end of the range are written as zero rows).
 
 // Scatter an int32 column (device buffer, nr_rows entries) into column `col` of a row-major
 // [nr_rows][dim] int32 table: the inverse of alloc_buffers' split (emb_host.h:116-118).

@@ -1,6 +1,7 @@
 // pimemb_kernels.hip -- instantiates the bag kernels of pimemb_bag_kernels.h for the library and
 // holds the two small helper kernels (column scatter, input validation).  gfx950 only.
 #include <cstdlib>
+#include <type_traits>
 
 #include "pimemb_internal.h"
 #include "pimemb_peer.h"
@@ -47,139 +48,73 @@ template <> struct WaveCfgOf<EMB_F16> { using One = WaveCfgF16; using Two = Wave
 using HotCfg = BagCfg<1024, 8, true, false, 8, 1, 1, false, false, /*IDX_SHUFFLE*/ true, kClampInputs>;
 constexpr int kBlock = 256;  // helper kernels below
 
+// ---- host dispatch: runtime (index type, dtype, lanes per row) -> template arguments, ONE switch each -----------------------
+// A launcher hands these a generic lambda, receives the choice as a type / an integral constant and names its kernel: which
+// kernel, which block size, which dynamic LDS is all a launcher spells out.  What is instantiated is what the lambdas name --
+// no kernel for a combination that is never launched (each costs build time).
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// f(IdxT{}, Int<DT>{}) -> hipError_t.  FIXED32: the family has fixed-point kernels (the pooled one has none: invalid there).
+template <bool FIXED32, class F>
+hipError_t with_types(emb_index_type itype, emb_dtype dtype, F &&f) {
+    auto with_index = [&](auto dt) { return itype == EMB_IDX_U32 ? f(uint32_t{}, dt) : f(int64_t{}, dt); };
+    switch (dtype) {
+        case EMB_F32: return with_index(Int<EMB_F32>{});
+        case EMB_F16: return with_index(Int<EMB_F16>{});
+        case EMB_FIXED32:
+            if constexpr (FIXED32) return with_index(Int<EMB_FIXED32>{});
+            break;
+    }
+    return hipErrorInvalidValue;
+}
+
+// f(Int<L>{}) enqueues the kernel for rows of L 16-byte lanes (geometry_for: a power of two up to 64).
+template <class F>
+hipError_t with_lanes_per_row(uint32_t lanes_per_row, F &&f) {
+    switch (lanes_per_row) {
+        case 1: f(Int<1>{}); break;
+        case 2: f(Int<2>{}); break;
+        case 4: f(Int<4>{}); break;
+        case 8: f(Int<8>{}); break;
+        case 16: f(Int<16>{}); break;
+        case 32: f(Int<32>{}); break;
+        case 64: f(Int<64>{}); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// Grid and `chunks` argument of the kernels that decode their workgroup through decode_block (2-D grid, or the XCD map).
+struct MappedLaunch {
+    dim3 grid;
+    uint32_t chunks;
+    MappedLaunch(uint32_t n, uint32_t max_tiles, const LaunchGeom &g, const uint32_t *xmap, uint32_t xgrid, bool xdirect)
+        : grid(xmap ? dim3(xgrid, 1, 1) : dim3(max_tiles, n, 1)), chunks(g.chunks | ((xmap && xdirect) ? kXmapDirect : 0u)) {}
+};
+
 template <typename IdxT, int DT, int L>
-void launch_one(const DevDesc *d, uint32_t n, uint32_t max_tiles, const LaunchGeom &g_in, KernelKind kind,
-                const uint32_t *xmap, uint32_t xgrid, bool xdirect, bool ranged, hipStream_t s) {
-    const dim3 grid = xmap ? dim3(xgrid, 1, 1) : dim3(max_tiles, n, 1);
-    struct { uint32_t chunks; } g{g_in.chunks | ((xmap && xdirect) ? kXmapDirect : 0u)};
+void launch_sum(const DevDesc *d, const MappedLaunch &m, KernelKind kind, const uint32_t *xmap, bool ranged, hipStream_t s) {
     using One = typename WaveCfgOf<DT>::One;
     using Two = typename WaveCfgOf<DT>::Two;
     // developer A/B (tools/onehot_occupancy_sweep.sh): bytes of dynamic LDS per workgroup of the one-batch wave-batch launch -- LDS the
     // kernel never touches, reserved to CAP how many of its wavefronts a CU holds at once (160 KB per CU)
     static const uint32_t lds_pad = getenv("PIMEMB_WAVEBATCH_LDS_PAD") ? (uint32_t)atoi(getenv("PIMEMB_WAVEBATCH_LDS_PAD")) : 0u;
-    if (ranged) {      // launch_bag_sum lets the two wave-batch kinds through only (uint32 and int64 indices alike)
+    auto wavebatch = [&](auto ranged_c) {
+        constexpr bool RANGED = decltype(ranged_c)::value;
         if (kind == KERNEL_WAVEBATCH)
-            hipLaunchKernelGGL((bag_sum_wavebatch_kernel<IdxT, DT, L, One, true>), grid, dim3(One::kBlock), lds_pad, s, d, g.chunks, xmap);
-        else if constexpr (L <= 4)
-            hipLaunchKernelGGL((bag_sum_wavebatch_kernel<IdxT, DT, L, Two, true>), grid, dim3(Two::kBlock), 0, s, d, g.chunks, xmap);
-        return;
-    }
-    if (kind == KERNEL_WAVEBATCH) {
-        hipLaunchKernelGGL((bag_sum_wavebatch_kernel<IdxT, DT, L, One>), grid, dim3(One::kBlock), lds_pad, s, d, g.chunks, xmap);
-    } else if (kind == KERNEL_WAVEBATCH2) {
+            hipLaunchKernelGGL((bag_sum_wavebatch_kernel<IdxT, DT, L, One, RANGED>), m.grid, dim3(One::kBlock), lds_pad, s, d, m.chunks, xmap);
         // choose_kernel hands out the two-batch geometry for <= 4 lanes per row only; wider rows are not
         // instantiated (they would spill under the 64-VGPR cap and are never launched)
-        if constexpr (L <= 4)
-            hipLaunchKernelGGL((bag_sum_wavebatch_kernel<IdxT, DT, L, Two>), grid, dim3(Two::kBlock), 0, s, d, g.chunks, xmap);
-    } else
-        hipLaunchKernelGGL((bag_sum_group_kernel<IdxT, DT, L, GroupCfg>), grid, dim3(GroupCfg::kBlock), 0,
-                           s, d, g.chunks, xmap);
-}
-
-template <typename IdxT, int DT>
-hipError_t launch_lpr(const DevDesc *d, uint32_t n, uint32_t max_tiles, const LaunchGeom &g,
-                      KernelKind kind, const uint32_t *xmap, uint32_t xgrid, bool xdirect, bool ranged, hipStream_t s) {
-    switch (g.lanes_per_row) {
-#define PIMEMB_CASE(L)                                                          \
-    case L:                                                                     \
-        launch_one<IdxT, DT, L>(d, n, max_tiles, g, kind, xmap, xgrid, xdirect, ranged, s); \
-        break;
-        PIMEMB_CASE(1)
-        PIMEMB_CASE(2)
-        PIMEMB_CASE(4)
-        PIMEMB_CASE(8)
-        PIMEMB_CASE(16)
-        PIMEMB_CASE(32)
-        PIMEMB_CASE(64)
-#undef PIMEMB_CASE
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-template <typename IdxT>
-hipError_t launch_dtype(const DevDesc *d, uint32_t n, uint32_t max_tiles, emb_dtype dtype,
-                        const LaunchGeom &g, KernelKind kind, const uint32_t *xmap, uint32_t xgrid,
-                        bool xdirect, bool ranged, hipStream_t s) {
-    switch (dtype) {
-        case EMB_F32:
-            return launch_lpr<IdxT, EMB_F32>(d, n, max_tiles, g, kind, xmap, xgrid, xdirect, ranged, s);
-        case EMB_F16:
-            return launch_lpr<IdxT, EMB_F16>(d, n, max_tiles, g, kind, xmap, xgrid, xdirect, ranged, s);
-        case EMB_FIXED32:
-            return launch_lpr<IdxT, EMB_FIXED32>(d, n, max_tiles, g, kind, xmap, xgrid, xdirect, ranged, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <typename IdxT, int DT>
-hipError_t launch_hot_lpr(const DevDesc *d, uint32_t n, uint32_t wgs, uint32_t lds, const LaunchGeom &g, hipStream_t s) {
-    const dim3 grid(wgs, n, 1), block(HotCfg::kBlock);
-    switch (g.lanes_per_row) {
-#define PIMEMB_CASE(L)                                                                                       \
-    case L:                                                                                                  \
-        hipLaunchKernelGGL((bag_sum_hot_kernel<IdxT, DT, L, HotCfg>), grid, block, lds, s, d, g.chunks);     \
-        break;
-        PIMEMB_CASE(1)
-        PIMEMB_CASE(2)
-        PIMEMB_CASE(4)
-        PIMEMB_CASE(8)
-        PIMEMB_CASE(16)
-        PIMEMB_CASE(32)
-        PIMEMB_CASE(64)
-#undef PIMEMB_CASE
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-template <typename IdxT>
-hipError_t launch_hot_dtype(const DevDesc *d, uint32_t n, uint32_t wgs, uint32_t lds, emb_dtype dtype,
-                            const LaunchGeom &g, hipStream_t s) {
-    switch (dtype) {
-        case EMB_F32: return launch_hot_lpr<IdxT, EMB_F32>(d, n, wgs, lds, g, s);
-        case EMB_F16: return launch_hot_lpr<IdxT, EMB_F16>(d, n, wgs, lds, g, s);
-        case EMB_FIXED32: return launch_hot_lpr<IdxT, EMB_FIXED32>(d, n, wgs, lds, g, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <typename IdxT>
-hipError_t launch_anydim(const DevDesc *d, uint32_t n, uint32_t max_tiles, emb_dtype dtype, const LaunchGeom &g,
-                         hipStream_t s) {
-    const dim3 grid(max_tiles, n, 1), block(256);
-    if (g.anydim_vec) {
-        switch (dtype) {
-            case EMB_F32:
-                hipLaunchKernelGGL((bag_sum_anydim_vec_kernel<IdxT, EMB_F32, kClampInputs>), grid, block, 0, s, d, g.chunks, g.scalar_lanes);
-                break;
-            case EMB_F16:
-                hipLaunchKernelGGL((bag_sum_anydim_vec_kernel<IdxT, EMB_F16, kClampInputs>), grid, block, 0, s, d, g.chunks, g.scalar_lanes);
-                break;
-            case EMB_FIXED32:
-                hipLaunchKernelGGL((bag_sum_anydim_vec_kernel<IdxT, EMB_FIXED32, kClampInputs>), grid, block, 0, s, d, g.chunks, g.scalar_lanes);
-                break;
-            default:
-                return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (dtype) {
-        case EMB_F32:
-            hipLaunchKernelGGL((bag_sum_anydim_kernel<IdxT, EMB_F32, kClampInputs>), grid, block, 0, s, d, g.chunks, g.scalar_lanes);
-            break;
-        case EMB_F16:
-            hipLaunchKernelGGL((bag_sum_anydim_kernel<IdxT, EMB_F16, kClampInputs>), grid, block, 0, s, d, g.chunks, g.scalar_lanes);
-            break;
-        case EMB_FIXED32:
-            hipLaunchKernelGGL((bag_sum_anydim_kernel<IdxT, EMB_FIXED32, kClampInputs>), grid, block, 0, s, d, g.chunks, g.scalar_lanes);
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+        else if constexpr (L <= 4)
+            hipLaunchKernelGGL((bag_sum_wavebatch_kernel<IdxT, DT, L, Two, RANGED>), m.grid, dim3(Two::kBlock), 0, s, d, m.chunks, xmap);
+    };
+    if (ranged)        // launch_bag_sum lets the two wave-batch kinds through only (uint32 and int64 indices alike)
+        wavebatch(std::true_type{});
+    else if (kind == KERNEL_WAVEBATCH || kind == KERNEL_WAVEBATCH2)
+        wavebatch(std::false_type{});
+    else
+        hipLaunchKernelGGL((bag_sum_group_kernel<IdxT, DT, L, GroupCfg>), m.grid, dim3(GroupCfg::kBlock), 0, s, d, m.chunks, xmap);
 }
 
 // ---- pooled lookups (bag_pool_*): fp32 / fp16 tables; one instantiation per (index type, dtype, row width, path) -- the
@@ -190,59 +125,6 @@ hipError_t launch_anydim(const DevDesc *d, uint32_t n, uint32_t max_tiles, emb_d
 using PoolWaveCfg = BagCfg<64, 4, true, false, 8, 8, 1, false, true, false, kClampInputs>;
 template <int DT> struct PoolWaveCfgOf { using One = PoolWaveCfg; };
 template <> struct PoolWaveCfgOf<EMB_F16> { using One = WaveCfgF16; };
-
-template <typename IdxT, int DT>
-hipError_t launch_pool_lpr(const DevDesc *d, uint32_t n, uint32_t max_tiles, const LaunchGeom &g, KernelKind kind,
-                           const uint32_t *xmap, uint32_t xgrid, bool xdirect, hipStream_t s) {
-    const dim3 grid = xmap ? dim3(xgrid, 1, 1) : dim3(max_tiles, n, 1);
-    const uint32_t chunks = g.chunks | ((xmap && xdirect) ? kXmapDirect : 0u);
-    using One = typename PoolWaveCfgOf<DT>::One;
-    switch (g.lanes_per_row) {
-#define PIMEMB_CASE(L)                                                                                                    \
-    case L:                                                                                                               \
-        if (kind == KERNEL_WAVEBATCH)                                                                                     \
-            hipLaunchKernelGGL((bag_pool_wavebatch_kernel<IdxT, DT, L, One>), grid, dim3(One::kBlock), 0, s, d, chunks, xmap); \
-        else                                                                                                              \
-            hipLaunchKernelGGL((bag_pool_group_kernel<IdxT, DT, L, GroupCfg>), grid, dim3(GroupCfg::kBlock), 0, s, d, chunks, xmap); \
-        break;
-        PIMEMB_CASE(1)
-        PIMEMB_CASE(2)
-        PIMEMB_CASE(4)
-        PIMEMB_CASE(8)
-        PIMEMB_CASE(16)
-        PIMEMB_CASE(32)
-        PIMEMB_CASE(64)
-#undef PIMEMB_CASE
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-template <typename IdxT, int DT>
-hipError_t launch_pool_anydim(const DevDesc *d, uint32_t n, uint32_t max_tiles, const LaunchGeom &g, hipStream_t s) {
-    const dim3 grid(max_tiles, n, 1), block(256);
-    if (g.anydim_vec)
-        hipLaunchKernelGGL((bag_pool_anydim_kernel<IdxT, DT, true, kClampInputs>), grid, block, 0, s, d, g.chunks, g.scalar_lanes);
-    else
-        hipLaunchKernelGGL((bag_pool_anydim_kernel<IdxT, DT, false, kClampInputs>), grid, block, 0, s, d, g.chunks, g.scalar_lanes);
-    return hipGetLastError();
-}
-
-template <typename IdxT>
-hipError_t launch_pool_dtype(const DevDesc *d, uint32_t n, uint32_t max_tiles, emb_dtype dtype, const LaunchGeom &g,
-                             KernelKind kind, const uint32_t *xmap, uint32_t xgrid, bool xdirect, hipStream_t s) {
-    if (kind == KERNEL_ANYDIM) {
-        if (g.scalar_lanes == 0 || xmap != nullptr) return hipErrorInvalidValue;
-        if (dtype == EMB_F32) return launch_pool_anydim<IdxT, EMB_F32>(d, n, max_tiles, g, s);
-        if (dtype == EMB_F16) return launch_pool_anydim<IdxT, EMB_F16>(d, n, max_tiles, g, s);
-        return hipErrorInvalidValue;
-    }
-    if (kind != KERNEL_WAVEBATCH && kind != KERNEL_GROUP) return hipErrorInvalidValue;
-    if (dtype == EMB_F32) return launch_pool_lpr<IdxT, EMB_F32>(d, n, max_tiles, g, kind, xmap, xgrid, xdirect, s);
-    if (dtype == EMB_F16) return launch_pool_lpr<IdxT, EMB_F16>(d, n, max_tiles, g, kind, xmap, xgrid, xdirect, s);
-    return hipErrorInvalidValue;
-}
 
 // ---- column scatter for populate_mram-style uploads -----------------------------------------
 __global__ void __launch_bounds__(kBlock)
@@ -1259,14 +1141,20 @@ hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max
     if (d_xmap == nullptr && n_descs > 65535u) return hipErrorInvalidValue;
     if (ranged && ((kind != KERNEL_WAVEBATCH && kind != KERNEL_WAVEBATCH2) || (kind == KERNEL_WAVEBATCH2 && g.lanes_per_row > 4)))
         return hipErrorInvalidValue;
-    if (kind == KERNEL_ANYDIM) {
-        if (g.scalar_lanes == 0 || d_xmap != nullptr) return hipErrorInvalidValue;
-        return itype == EMB_IDX_U32 ? launch_anydim<uint32_t>(d_descs, n_descs, max_tiles, dtype, g, stream)
-                                    : launch_anydim<int64_t>(d_descs, n_descs, max_tiles, dtype, g, stream);
-    }
-    if (itype == EMB_IDX_U32)
-        return launch_dtype<uint32_t>(d_descs, n_descs, max_tiles, dtype, g, kind, d_xmap, xgrid, xdirect, ranged, stream);
-    return launch_dtype<int64_t>(d_descs, n_descs, max_tiles, dtype, g, kind, d_xmap, xgrid, xdirect, ranged, stream);
+    if (kind == KERNEL_ANYDIM && (g.scalar_lanes == 0 || d_xmap != nullptr)) return hipErrorInvalidValue;
+    const MappedLaunch m(n_descs, max_tiles, g, d_xmap, xgrid, xdirect);
+    return with_types<true>(itype, dtype, [&](auto idx, auto dt) {
+        using IdxT = decltype(idx);
+        constexpr int DT = decltype(dt)::value;
+        if (kind == KERNEL_ANYDIM) {
+            if (g.anydim_vec)
+                hipLaunchKernelGGL((bag_sum_anydim_vec_kernel<IdxT, DT, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
+            else
+                hipLaunchKernelGGL((bag_sum_anydim_kernel<IdxT, DT, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
+            return hipGetLastError();
+        }
+        return with_lanes_per_row(g.lanes_per_row, [&](auto l) { launch_sum<IdxT, DT, decltype(l)::value>(d_descs, m, kind, d_xmap, ranged, stream); });
+    });
 }
 
 hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, emb_dtype dtype,
@@ -1274,17 +1162,40 @@ hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t ma
                            uint32_t xgrid, bool xdirect, hipStream_t stream) {
     if (n_descs == 0 || max_tiles == 0) return hipSuccess;
     if (d_xmap == nullptr && n_descs > 65535u) return hipErrorInvalidValue;
-    return itype == EMB_IDX_U32
-               ? launch_pool_dtype<uint32_t>(d_descs, n_descs, max_tiles, dtype, g, kind, d_xmap, xgrid, xdirect, stream)
-               : launch_pool_dtype<int64_t>(d_descs, n_descs, max_tiles, dtype, g, kind, d_xmap, xgrid, xdirect, stream);
+    if (kind == KERNEL_ANYDIM ? (g.scalar_lanes == 0 || d_xmap != nullptr) : (kind != KERNEL_WAVEBATCH && kind != KERNEL_GROUP))
+        return hipErrorInvalidValue;
+    const MappedLaunch m(n_descs, max_tiles, g, d_xmap, xgrid, xdirect);
+    return with_types<false>(itype, dtype, [&](auto idx, auto dt) {
+        using IdxT = decltype(idx);
+        constexpr int DT = decltype(dt)::value;
+        using One = typename PoolWaveCfgOf<DT>::One;
+        if (kind == KERNEL_ANYDIM) {
+            if (g.anydim_vec)
+                hipLaunchKernelGGL((bag_pool_anydim_kernel<IdxT, DT, true, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
+            else
+                hipLaunchKernelGGL((bag_pool_anydim_kernel<IdxT, DT, false, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
+            return hipGetLastError();
+        }
+        return with_lanes_per_row(g.lanes_per_row, [&](auto l) {
+            constexpr int L = decltype(l)::value;
+            if (kind == KERNEL_WAVEBATCH)
+                hipLaunchKernelGGL((bag_pool_wavebatch_kernel<IdxT, DT, L, One>), m.grid, dim3(One::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+            else
+                hipLaunchKernelGGL((bag_pool_group_kernel<IdxT, DT, L, GroupCfg>), m.grid, dim3(GroupCfg::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+        });
+    });
 }
 
 hipError_t launch_bag_sum_hot(const DevDesc *d_descs, uint32_t n_descs, uint32_t wgs, uint32_t lds_bytes,
                               emb_dtype dtype, emb_index_type itype, const LaunchGeom &g, hipStream_t stream) {
     if (n_descs == 0 || wgs == 0) return hipSuccess;
     if (n_descs > 65535u || lds_bytes > kHotLdsBudget || g.scalar_lanes) return hipErrorInvalidValue;
-    return itype == EMB_IDX_U32 ? launch_hot_dtype<uint32_t>(d_descs, n_descs, wgs, lds_bytes, dtype, g, stream)
-                                : launch_hot_dtype<int64_t>(d_descs, n_descs, wgs, lds_bytes, dtype, g, stream);
+    return with_types<true>(itype, dtype, [&](auto idx, auto dt) {
+        return with_lanes_per_row(g.lanes_per_row, [&](auto l) {
+            hipLaunchKernelGGL((bag_sum_hot_kernel<decltype(idx), decltype(dt)::value, decltype(l)::value, HotCfg>), dim3(wgs, n_descs, 1),
+                               dim3(HotCfg::kBlock), lds_bytes, stream, d_descs, g.chunks);
+        });
+    });
 }
 
 hipError_t launch_scatter_column(int32_t *table, const int32_t *column, uint64_t nr_rows,

@@ -174,7 +174,7 @@ void emulate_route_counts(const RouteBagParamsMirror &rp, uint64_t n_bags, uint3
 
 // The COUNTED ranged lookup of a checked shard's direct path: no row is gathered here, but the per-descriptor counters of
 // served bags steer host control flow (the requester compares their sum with its bag count), so they are produced: the
-// number of indices inside [row_lo, row_lo + nr_rows), added to the counter the descriptor names in pad_[1].
+// number of indices inside [row_lo, row_lo + nr_rows), added to the counter the descriptor names in DevDesc::ranged.served.
 void emulate_ranged_counts(void **args, dim3 grid, bool idx64) {
     using pimemb::DevDesc;
     const DevDesc *descs = arg<const DevDesc *>(args, 0);
@@ -195,9 +195,9 @@ void emulate_ranged_counts(void **args, dim3 grid, bool idx64) {
     ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
     for (uint32_t d : ids) {
         const DevDesc &dd = descs[d];
-        uint32_t *ctr = reinterpret_cast<uint32_t *>(dd.pad_[1]);
+        uint32_t *ctr = dd.ranged.served;
         if (!ctr || dd.n_tiles == 0) continue;
-        const uint64_t row_lo = dd.pad_[0] & ~pimemb::kRangeOpenEnd;      // (the open end's bags are zeroed, never counted)
+        const uint64_t row_lo = dd.ranged.row_lo & ~pimemb::kRangeOpenEnd;      // (the open end's bags are zeroed, never counted)
         uint32_t n = 0;
         for (uint64_t b = 0; b < dd.n_bags; b++) {
             const uint64_t id = idx64 ? (uint64_t)static_cast<const int64_t *>(dd.indices)[b] : (uint64_t)static_cast<const uint32_t *>(dd.indices)[b];

@@ -180,6 +180,26 @@ def test_code_object_reader_names_every_kernel_of_a_launch():
     assert "IlLi0ELi32E" in codeobj.kernel_of_launch(lib, dict(kind=0, dtype=0, itype=1, lanes_per_row=32, ranged=1))[0]
 
 
+def test_code_object_comparison_reports_what_moved(capsys):
+    """`python -m pim-embedding-lookup_amd.codeobj LIB OTHER`: a library against itself differs in nothing (exit status 0);
+    one kernel whose hash or register count moved, one that left and one that came are each reported."""
+    from importlib import import_module
+    codeobj = import_module("pim-embedding-lookup_amd.codeobj")
+    lib = os.path.join(ROOT, "pim-embedding-lookup_amd", "lib", "libpimemb.so")
+    assert codeobj.main([lib, lib]) == 0
+    assert "0 differences" in capsys.readouterr().out
+    hashes, res = codeobj.kernel_hashes(lib), codeobj.kernel_resources(lib)
+    assert codeobj.diff_kernels(hashes, res, hashes, res) == []
+    moved, gone = sorted(hashes)[:2]
+    other_hashes = dict(hashes, **{moved: "0" * 64}, extra_kernel="1" * 64)
+    del other_hashes[gone]
+    other_res = dict(res, **{moved: dict(res[moved], vgpr=res[moved]["vgpr"] + 1)})
+    lines = codeobj.diff_kernels(hashes, res, other_hashes, other_res)
+    assert sorted(l.split()[0] + " " + l.split()[1] for l in lines) == sorted(
+        ["code " + moved, "resource " + moved, "added " + gone, "removed extra_kernel"])
+    assert "vgpr %d -> %d" % (res[moved]["vgpr"] + 1, res[moved]["vgpr"]) in "\n".join(lines)
+
+
 def test_roofline_object_names_the_roof_that_binds():
     """every line carries `binding` and a `frac_binding` <= 1 on THAT roof; the algorithmic HBM `frac` stays."""
     # c2: HBM-side traffic 114 MB in 20 us = 0.71 of 8 TB/s; L2 0.33: HBM binds

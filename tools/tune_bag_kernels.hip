@@ -221,7 +221,7 @@ int main(int argc, char **argv) {
                     d.nr_rows = hi - lo;
                     d.fixed_pooling = 0;
                     d.n_tiles = tiles[v];
-                    d.pad_[0] = lo;
+                    d.ranged.row_lo = lo;
                     hd.push_back(d);
                     desc_bytes[v].push_back((hi - lo) * D * 4);
                 }

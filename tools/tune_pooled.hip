@@ -268,7 +268,7 @@ bag_sum_stream_kernel(const DevDesc *__restrict__ descs, uint32_t chunks, uint32
 // Zipf(1.2) over 10 M rows names its hottest row in 18.5 % of all gathers, the top two in 26.5 %, the top four in 35 %.  Those
 // gathers hit the L1, but an L1 hit still goes through the texture-address unit and the L1's 64 B/clk -- the two things the
 // pooled Zipf launch is bound by.  Here every lane keeps its 16-byte piece of the K hottest rows of
-// the descriptor's table in 4 K registers (row ids in DevDesc::pad_[2..3], rows = the first K of the compact hot copy the
+// the descriptor's table in 4 K registers (row ids in DevDesc::words[2..3], rows = the first K of the compact hot copy the
 // engine already keeps for the LDS path); a gather whose row id equals one of them is a register select, its lanes are
 // masked out of the load.  Same bits: the register copy holds the table's own bits, the adds stay in index order.
 template <typename IdxT, int DT, int LPR, class Cfg, int K>
@@ -300,7 +300,7 @@ bag_sum_reghot_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg, co
     // the K hottest rows of this table: ids (0xffffffff = none) and this lane's piece of each
     uint32_t hid[K];
     u32x4 hrow[K];
-    const uint32_t *ids = reinterpret_cast<const uint32_t *>(&dp->pad_[2]);
+    const uint32_t *ids = reinterpret_cast<const uint32_t *>(&dp->words[2]);
     const u32x4 *hot = static_cast<const u32x4 *>(dp->hot_rows);
 #pragma unroll
     for (int k = 0; k < K; k++) {
@@ -602,7 +602,7 @@ build_done:
                 hd[t].nr_rows = rows;
                 hd[t].n_tiles = tiles[v];
                 if (vars[v].reghot) {
-                    uint32_t *ids32 = reinterpret_cast<uint32_t *>(&hd[t].pad_[2]);
+                    uint32_t *ids32 = reinterpret_cast<uint32_t *>(&hd[t].words[2]);
                     for (uint32_t k = 0; k < 4; k++)
                         ids32[k] = k < vars[v].hot ? (uint32_t)(((uint64_t)k * 2654435761ull + 12345ull + t) % rows) : 0xffffffffu;
                 }
