@@ -48,8 +48,10 @@ extern "C" {
 typedef enum emb_dtype {
     EMB_F32 = 0,     /* fp32 rows, fp32 accumulate: nn.EmbeddingBag(sum) parity target */
     EMB_F16 = 1,     /* fp16 rows, fp32 accumulate (BASELINE config C5) */
-    EMB_FIXED32 = 2  /* int32 x1e9 fixed point, int32 wrap-around accumulate, out = (float)acc/1e9:
+    EMB_FIXED32 = 2, /* int32 x1e9 fixed point, int32 wrap-around accumulate, out = (float)acc/1e9:
                         the reference's own arithmetic, emb_dpu_lookup.c:114 + emb_host.h:210 */
+    EMB_BF16 = 3     /* bfloat16 rows (2 bytes: the upper 16 bits of an fp32), fp32 accumulate: every row is widened
+                        exactly, so results equal the fp32 lookup over the widened table bit for bit */
 } emb_dtype;
 
 /* width of indices AND offsets: uint32 at the reference ABI (emb_host.h:234), int64 at torch's */
@@ -268,8 +270,8 @@ int emb_plan_describe(const emb_plan *p, char *buf, size_t capacity);
 int emb_plan_time(emb_plan *p, void *stream, uint32_t warmup, uint32_t iters, float *avg_us);
 
 /* ---- pooled lookups: nn.EmbeddingBag's mean / max modes, per_sample_weights and padding_idx ------------------------------
- * One emb_pool_spec per descriptor, in a parallel array.  Results equal torch's CPU F.embedding_bag bit for bit (fp16 tables:
- * on the rows widened to fp32; output fp32 as always): entries are taken in index order from +0; a weighted sum without
+ * One emb_pool_spec per descriptor, in a parallel array.  Results equal torch's CPU F.embedding_bag bit for bit (fp16 and
+ * bf16 tables: on the rows widened to fp32; output fp32 as always): entries are taken in index order from +0; a weighted sum without
  * padding is acc = fmaf(w, x, acc), with padding acc = acc + (w * x) with the product rounded on its own; mean is the sum over
  * the non-padding entries divided (IEEE division) by their count; max starts at the first non-padding row and keeps the first
  * of equal values (strict >); an empty bag, or one of padding only, gives +0.  NaN ordering is out of scope.

@@ -9,7 +9,7 @@ CSRC_DIR = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb.so")
 MARSHAL_PATH = os.path.join(PKG_DIR, "lib", "_pimemb_marshal.so")
 SOURCES = ["pimemb_kernels.hip", "pimemb_engine.cpp", "pimemb_compat.cpp", "pimemb_comm.cpp", "pimemb_shard.cpp", "pimemb_peer.cpp", "pimemb_peer.h", "pimemb_internal.h", "pimemb_torch_marshal.cpp",
-           "pimemb_bag_kernels.h", "pimemb_xcd_map.h", "pimemb_hot_rows.h", "pimemb_hostcopy.h", "Makefile",
+           "pimemb_bag_kernels.h", "pimemb_pool_kernels.inc", "pimemb_xcd_map.h", "pimemb_hot_rows.h", "pimemb_hostcopy.h", "Makefile",
            os.path.join("..", "..", "include", "pimemb.h")]
 
 

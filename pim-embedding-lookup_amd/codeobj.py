@@ -119,14 +119,16 @@ def symbol_fragments(launch: dict) -> list[str]:
     """Fragments of the mangled name of the kernel instantiation one launch of a plan runs (Plan.describe() record): enough to
     pick it out of kernel_hashes().  The template heads are pimemb_kernels.hip's: bag_sum_<family>_kernel<IdxT, DT, LPR, Cfg
     [, RANGED]>, the any-dim kernels <IdxT, DT, CLAMP>; a pooled launch (a record with `pool`, emb_plan_create_pooled) runs
-    bag_pool_<family>_kernel<IdxT, DT, LPR, Cfg> or bag_pool_anydim_kernel<IdxT, DT, VEC, CLAMP>."""
+    bag_pool_<family>_kernel<IdxT, DT, LPR, Cfg> or bag_pool_anydim_kernel<IdxT, DT, VEC, CLAMP> -- for bf16 tables (dtype 3) the
+    same under the name bag_bf16pool_*."""
     idx = "j" if launch["itype"] == 0 else "l"
     kind, dt, lpr = launch["kind"], launch["dtype"], launch["lanes_per_row"]
     if "pool" in launch:
+        pool = "bag_bf16pool" if dt == 3 else "bag_pool"
         if kind == 3:
-            return ["bag_pool_anydim_kernelI%sLi%dELb%dE" % (idx, dt, 1 if launch.get("anydim_vec") else 0)]
+            return ["%s_anydim_kernelI%sLi%dELb%dE" % (pool, idx, dt, 1 if launch.get("anydim_vec") else 0)]
         family = "group" if kind == 1 else "wavebatch"
-        return ["bag_pool_%s_kernelI%sLi%dELi%dENS_6BagCfgI" % (family, idx, dt, lpr)]
+        return ["%s_%s_kernelI%sLi%dELi%dENS_6BagCfgI" % (pool, family, idx, dt, lpr)]
     if kind == 3:
         return ["bag_sum_anydim_vec_kernelI%sLi%dE" % (idx, dt)] if launch.get("anydim_vec") else ["bag_sum_anydim_kernelI%sLi%dE" % (idx, dt)]
     if kind == 1:

@@ -81,6 +81,7 @@ using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using f32x8 = __attribute__((ext_vector_type(8))) float;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 // Compile-time knobs of the bag kernels.
 template <int BLOCK = 256, int UNROLL = 8, bool NT_STORE = false, bool NT_META = false,
@@ -156,6 +157,30 @@ struct RowOps<EMB_F16> {
     static __device__ __forceinline__ void add(Acc &a, u32x4 raw) {
         a += __builtin_convertvector(__builtin_bit_cast(f16x8, raw), f32x8);
     }
+    template <bool NT>
+    static __device__ __forceinline__ void store(const Acc &a, float *dst) {
+        store_f32x4<NT>(dst, f32x4{a[0], a[1], a[2], a[3]});
+        store_f32x4<NT>(dst + 4, f32x4{a[4], a[5], a[6], a[7]});
+    }
+};
+
+// bfloat16 rows: a bf16 is the upper half of an fp32, so widening is integer work on the raw dwords and exact for every bit
+// pattern (denormals, NaN payloads).  Dword i of a piece holds elements 2i (low half: v_lshlrev_b32 16) and 2i + 1 (high half:
+// v_and_b32 0xffff0000), and the accumulator takes them in row order (store_row relies on it).  Written as ONE vector conversion,
+// which the backend lowers to exactly those shifts and masks: spelled out as shifts, masks and a re-ordering shuffle the machine
+// work is the same, but it is five IR operations where the fp16 conversion is one, too many for the compiler to speculate, and
+// the one-hot paths then keep a branch around every gathered row (+2..4 % per launch: profiles/bf16/README.md).
+__device__ __forceinline__ f32x8 widen_bf16x8(u32x4 raw) {
+    return __builtin_convertvector(__builtin_bit_cast(bf16x8, raw), f32x8);
+}
+
+template <>
+struct RowOps<EMB_BF16> {
+    using Acc = f32x8;
+    static constexpr uint32_t kFloatsPerLane = 8;
+    static constexpr bool kGroupStore = true;      // 32 B of output per lane, as fp16 rows: see RowOps<EMB_F16>
+    static __device__ __forceinline__ Acc zero() { return Acc{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; }
+    static __device__ __forceinline__ void add(Acc &a, u32x4 raw) { a += widen_bf16x8(raw); }
     template <bool NT>
     static __device__ __forceinline__ void store(const Acc &a, float *dst) {
         store_f32x4<NT>(dst, f32x4{a[0], a[1], a[2], a[3]});
@@ -497,6 +522,12 @@ template <> struct ElemOps<EMB_F32> {
 template <> struct ElemOps<EMB_F16> {
     using Elem = _Float16; using Acc = float;
     static __device__ __forceinline__ void add(Acc &a, Elem v) { a = a + (float)v; }
+    static __device__ __forceinline__ float out(Acc a) { return a; }
+};
+template <> struct ElemOps<EMB_BF16> {
+    using Elem = uint16_t; using Acc = float;      // (the raw bits)
+    static __device__ __forceinline__ float widen(Elem v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
+    static __device__ __forceinline__ void add(Acc &a, Elem v) { a = a + widen(v); }
     static __device__ __forceinline__ float out(Acc a) { return a; }
 };
 template <> struct ElemOps<EMB_FIXED32> {
@@ -896,7 +927,7 @@ bag_sum_hot_kernel(const DevDesc *__restrict__ descs, uint32_t chunks) {
 // ---- pooled lookups: mean / max pooling, per-sample weights, padding_idx (emb_lookup_pooled) -------------------------
 // A family of its own (bag_pool_*), so that every bag_sum_* kernel above keeps its machine code.  Each output element is
 // still owned by ONE lane that takes the bag's entries in index order, and the arithmetic is spelled out so that the result
-// equals torch's CPU EmbeddingBag bit for bit (fp16 rows are widened to fp32 first):
+// equals torch's CPU EmbeddingBag bit for bit (fp16 and bf16 rows are widened to fp32 first):
 //   sum              acc = +0; acc = acc + x
 //   weighted sum     acc = fma(w, x, acc)                         (no padding_idx: torch's fused per-sample-weight kernel)
 //   ... + padding    acc = acc + round(w * x)                     (padding_idx given: torch takes the unfused path)
@@ -950,6 +981,10 @@ template <> struct PoolRow<EMB_F16> {
     static __device__ __forceinline__ f32x8 widen(u32x4 raw) {
         return __builtin_convertvector(__builtin_bit_cast(f16x8, raw), f32x8);
     }
+};
+template <> struct PoolRow<EMB_BF16> {
+    static constexpr int K = 8;
+    static __device__ __forceinline__ f32x8 widen(u32x4 raw) { return widen_bf16x8(raw); }
 };
 
 template <int DT, class Acc>
@@ -1006,239 +1041,16 @@ __device__ __forceinline__ void pool_walk(const IdxT *__restrict__ indices, cons
     }
 }
 
-// Lane-group path (ragged bags, rows of 16-byte multiples up to 1 KiB): one lane group per bag, as bag_sum_group_kernel.
-template <typename IdxT, int DT, int LPR, class Cfg>
-__global__ void __launch_bounds__(Cfg::kBlock)
-bag_pool_group_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg, const uint32_t *__restrict__ xmap) {
-    using Ops = RowOps<DT>;
-    constexpr uint32_t kWaves = Cfg::kBlock / 64;
-    constexpr uint32_t BPW = 64 / LPR;
-    constexpr uint32_t BAGS_PER_TILE = BPW * kWaves;
-
-    uint32_t desc_i, tile;
-    if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
-    const uint32_t chunks = chunks_arg & ~kXmapDirect;
-    const DevDesc *dp = descs + desc_i;
-    const DescView<IdxT> t(dp);
-    const PoolArgs a = pool_args(dp);
-
-    // (a LaneGeom here changes the code object of this kernel's 4 one-lane-per-row instantiations)
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
-    const uint32_t row_bytes = chunks * 16u;
-    const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
-    const char *__restrict__ wsub = t.weights + sub * 16u;
-
-    if (tile < t.n_tiles) {
-        const uint64_t bag = (uint64_t)tile * BAGS_PER_TILE + wave * BPW + grp;
-        const bool live = sub < chunks;
-        if (bag >= t.n_bags) return;                   // whole lane group leaves together
-        uint64_t p, e;
-        bag_range<Cfg::kNtMeta, Cfg::kClamp>(t.offsets, t.n_bags, t.n_idx, t.fixed_pooling, bag, p, e);
-        typename Ops::Acc acc = Ops::zero();
-        uint32_t cnt = 0;
-        if (live) pool_walk<IdxT, DT, Cfg>(t.indices, a, p, e, wsub, row_bytes, t.last_row, acc, cnt);
-        pool_finish<DT>(acc, cnt, a.mean);
-        store_row<Ops, Cfg, LPR>(acc, t.out + bag * out_stride, sub, grp, chunks, live);
-    }
-}
-
-// Wave-batch path (big batches): 64 bags per wavefront with coalesced bounds, as bag_sum_wavebatch_kernel (one batch per
-// step).  One-hot steps -- DLRM's weighted pooling on Criteo shapes -- load the bag's index AND its weight coalesced (both
-// speculatively, in the shadow of the bounds), issue every round's gather before the first store and store non-temporally;
-// a padding entry makes its bag empty.  Longer bags: each round a lane group walks its bag (pool_walk).
-template <typename IdxT, int DT, int LPR, class Cfg>
-__global__ void __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves)
-bag_pool_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg, const uint32_t *__restrict__ xmap) {
-    using Ops = RowOps<DT>;
-    constexpr uint32_t kWaves = Cfg::kBlock / 64;
-    constexpr uint32_t BPR = 64 / LPR;      // bags per round
-    constexpr uint32_t ROUNDS = LPR;        // rounds per 64-bag wave batch
-    constexpr uint32_t RU = onehot_rounds_in_flight<LPR, Cfg>();
-
-    uint32_t desc_i, tile;
-    if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
-    const uint32_t chunks = chunks_arg & ~kXmapDirect;
-    const DevDesc *dp = descs + desc_i;
-    // (a DescView here changes the code object of the two fp32 two-lanes-per-row instantiations)
-    const char *__restrict__ weights = static_cast<const char *>(dp->weights);
-    const IdxT *__restrict__ indices = static_cast<const IdxT *>(dp->indices);
-    const IdxT *__restrict__ offsets = static_cast<const IdxT *>(dp->offsets);
-    float *__restrict__ out = dp->out;
-    const uint64_t n_idx = dp->n_idx, n_bags = dp->n_bags, last_row = dp->nr_rows - 1;
-    const uint32_t fixed_pooling = dp->fixed_pooling, n_tiles = dp->n_tiles;
-    const PoolArgs a = pool_args(dp);
-    const LaneGeom<LPR, Ops> ln(weights, chunks);
-    const bool lane_live = ln.sub < chunks;
-
-    if (tile >= n_tiles) return;
-    const uint64_t step_base = ((uint64_t)tile * kWaves + ln.wave) * 64u;
-    if (step_base >= n_bags) return;  // wave-uniform
-
-    // lane l holds the bounds of bag step_base + l (past-the-end = empty)
-    const uint64_t mb = step_base + ln.lane;
-    IdxT spec = 0;
-    float spec_w = 1.f;
-    if (mb < n_idx) {
-        spec = load_meta<Cfg::kNtMeta>(indices + mb);
-        if (a.psw != nullptr) spec_w = load_meta<Cfg::kNtMeta>(a.psw + mb);
-    }
-    uint64_t st, en;    // (shared with bag_sum_wavebatch_kernel's block as a function: every instantiation changes)
-    if (offsets != nullptr) {
-        st = (mb < n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(offsets + mb) : n_idx;
-        en = (mb + 1 < n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(offsets + mb + 1) : n_idx;
-    } else {
-        st = (mb < n_bags ? mb : n_bags) * fixed_pooling;
-        en = (mb + 1 < n_bags ? mb + 1 : n_bags) * fixed_pooling;
-    }
-    if (Cfg::kClamp) {
-        if (en > n_idx) en = n_idx;
-        if (st > en) st = en;
-    }
-    uint32_t len = (uint32_t)(en - st);
-
-    if (__all(len <= 1u)) {
-        IdxT my = 0;
-        float my_w = 1.f;
-        if (len) {
-            const bool at_spec = st == mb;
-            my = at_spec ? spec : load_meta<Cfg::kNtMeta>(indices + st);
-            if (a.psw != nullptr) my_w = at_spec ? spec_w : load_meta<Cfg::kNtMeta>(a.psw + st);
-            if ((uint64_t)my == a.pad) len = 0;     // the bag's only entry is padding: an empty bag
-        }
-#pragma unroll
-        for (uint32_t j0 = 0; j0 < ROUNDS; j0 += RU) {
-            u32x4 v[RU];
-            bool has[RU];
-#pragma unroll
-            for (uint32_t jj = 0; jj < RU; jj++) {
-                const uint32_t src = (j0 + jj) * BPR + ln.grp;
-                const uint64_t r = clamp_row<Cfg::kClamp, IdxT>(shfl_index<IdxT>(my, src), last_row);
-                has[jj] = shfl_u32(len, src) != 0u;
-                v[jj] = u32x4{0u, 0u, 0u, 0u};
-                if (has[jj] && lane_live) v[jj] = load_row<Cfg::kNtRow>(ln.wsub + r * ln.row_bytes);
-            }
-#pragma unroll
-            for (uint32_t jj = 0; jj < RU; jj++) {
-                const uint32_t src = (j0 + jj) * BPR + ln.grp;
-                const uint64_t bag = step_base + src;
-                const float w = shfl_f32(my_w, src);
-                typename Ops::Acc acc = Ops::zero();
-                if (has[jj] && lane_live) pool_combine<DT>(acc, v[jj], w, a.op, true);
-                // (all lanes take part in a group store's shuffles)
-                store_row<Ops, Cfg, LPR>(acc, out + bag * ln.out_stride, ln.sub, ln.grp, chunks, bag < n_bags && lane_live);
-            }
-        }
-        return;
-    }
-
-    // general step: each round, a lane group walks its bag in index order
-#pragma unroll 1
-    for (uint32_t j = 0; j < ROUNDS; j++) {
-        const uint32_t src = j * BPR + ln.grp;
-        const uint64_t p = shfl_u64(st, src);
-        const uint64_t e = p + shfl_u32(len, src);
-        const uint64_t bag = step_base + src;
-        // (no early `continue`: every lane must reach the next round's shuffles)
-        typename Ops::Acc acc = Ops::zero();
-        uint32_t cnt = 0;
-        if (bag < n_bags && lane_live) pool_walk<IdxT, DT, Cfg>(indices, a, p, e, ln.wsub, ln.row_bytes, last_row, acc, cnt);
-        pool_finish<DT>(acc, cnt, a.mean);
-        store_row<Ops, Cfg, LPR>(acc, out + bag * ln.out_stride, ln.sub, ln.grp, chunks, bag < n_bags && lane_live);
-    }
-}
-
-// Any-dim path: rows that are not 16-byte multiples or wider than 1 KiB, as bag_sum_anydim[_vec]_kernel.  VEC: one thread
-// per 16-byte piece of a 4-byte-multiple row (a partial last piece dword by dword), else one thread per element.
-template <typename IdxT, int DT, bool VEC, bool CLAMP>
-__global__ void __launch_bounds__(256)
-bag_pool_anydim_kernel(const DevDesc *__restrict__ descs, uint32_t dim, uint32_t lanes) {
-    constexpr uint32_t EP = VEC ? (uint32_t)PoolRow<DT>::K : 1u;    // elements per unit
-    constexpr uint32_t ESZ = (DT == EMB_F16) ? 2u : 4u;
-    constexpr int U = 4;
-    const DevDesc *dp = descs + blockIdx.y;
-    const char *__restrict__ weights = static_cast<const char *>(dp->weights);
-    const IdxT *__restrict__ indices = static_cast<const IdxT *>(dp->indices);
-    const IdxT *__restrict__ offsets = static_cast<const IdxT *>(dp->offsets);
-    float *__restrict__ out = dp->out;
-    const uint64_t n_idx = dp->n_idx, n_bags = dp->n_bags, last_row = dp->nr_rows - 1;
-    const uint64_t bag = (uint64_t)blockIdx.x * (256u / lanes) + threadIdx.x / lanes;
-    if (blockIdx.x >= dp->n_tiles || bag >= n_bags) return;
-    const PoolArgs a = pool_args(dp);
-    uint64_t p0, e;
-    bag_range<false, CLAMP>(offsets, n_bags, n_idx, dp->fixed_pooling, bag, p0, e);
-    const uint32_t row_bytes = dim * ESZ, units = (dim + EP - 1) / EP;
-    for (uint32_t unit = threadIdx.x & (lanes - 1); unit < units; unit += lanes) {
-        const uint32_t n_el = (dim - unit * EP < EP) ? dim - unit * EP : EP;
-        const char *__restrict__ wp = weights + unit * EP * ESZ;
-        float acc[EP];
-#pragma unroll
-        for (uint32_t c = 0; c < EP; c++) acc[c] = 0.f;
-        uint32_t cnt = 0;
-        for (uint64_t p = p0; p < e; p += U) {
-            const uint64_t left = e - p;
-            uint64_t r[U];
-            float w[U];
-            bool use[U];
-#pragma unroll
-            for (int k = 0; k < U; k++) {
-                use[k] = (uint64_t)k < left;
-                r[k] = 0;
-                w[k] = 1.f;
-                if (use[k]) {
-                    r[k] = (uint64_t)indices[p + k];
-                    if (a.psw != nullptr) w[k] = a.psw[p + k];
-                }
-                use[k] = use[k] && r[k] != a.pad;
-            }
-            float x[U][EP];
-#pragma unroll
-            for (int k = 0; k < U; k++) {
-                const char *src = wp + clamp_row<CLAMP, IdxT>(r[k], last_row) * row_bytes;
-                if constexpr (VEC) {
-                    u32x4 v = {0u, 0u, 0u, 0u};
-                    if (use[k]) {
-                        if (n_el == EP) {
-                            v = *reinterpret_cast<const u32x4_a4 *>(src);
-                        } else {                         // partial last piece: whole dwords only
-                            const uint32_t n_dw = n_el * ESZ / 4u;
-                            for (uint32_t d = 0; d < n_dw; d++) v[d] = reinterpret_cast<const uint32_t *>(src)[d];
-                        }
-                    }
-                    const auto f = PoolRow<DT>::widen(v);
-#pragma unroll
-                    for (uint32_t c = 0; c < EP; c++) x[k][c] = f[c];
-                } else {
-                    x[k][0] = 0.f;
-                    if (use[k]) {
-                        if constexpr (DT == EMB_F16) x[k][0] = (float)*reinterpret_cast<const _Float16 *>(src);
-                        else x[k][0] = *reinterpret_cast<const float *>(src);
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < U; k++)
-                if (use[k]) {
-#pragma unroll
-                    for (uint32_t c = 0; c < EP; c++) acc[c] = pool_op1(acc[c], x[k][c], w[k], a.op, cnt == 0u);
-                    cnt++;
-                }
-        }
-#pragma unroll
-        for (uint32_t c = 0; c < EP; c++) acc[c] = pool_finish1(acc[c], cnt, a.mean);
-        float *o = out + bag * dim + unit * EP;
-        bool stored = false;
-        if constexpr (VEC) {
-            if (n_el == EP) {
-#pragma unroll
-                for (uint32_t c = 0; c < EP; c += 4)
-                    *reinterpret_cast<f32x4_a4 *>(o + c) = f32x4{acc[c], acc[c + 1], acc[c + 2], acc[c + 3]};
-                stored = true;
-            }
-        }
-        if (!stored)
-            for (uint32_t c = 0; c < n_el; c++) o[c] = acc[c];
-    }
-}
+// The kernels themselves: pimemb_pool_kernels.inc, compiled under two sets of names.  bag_pool_* are the fp32 and fp16
+// instantiations.  bf16 tables enter through bag_bf16pool_*, the same text with the same template arguments:
+// tests/test_pooling_abi.py pins the SET of bag_pool_* kernels in the code object (64: index width x fp32 / fp16 x row widths
+// x paths, plus the any-dim ones) and is not a file that adding a dtype may edit, so that set stays what the test pins;
+// launch_bag_pool (pimemb_kernels.hip) and codeobj.symbol_fragments know both names.
+#define PIMEMB_POOL_KERNEL(path) bag_pool_##path##_kernel
+#include "pimemb_pool_kernels.inc"
+#undef PIMEMB_POOL_KERNEL
+#define PIMEMB_POOL_KERNEL(path) bag_bf16pool_##path##_kernel
+#include "pimemb_pool_kernels.inc"
+#undef PIMEMB_POOL_KERNEL
 
 }  // namespace pimemb

@@ -60,7 +60,7 @@ double now_us() {
     return duration<double, std::micro>(steady_clock::now().time_since_epoch()).count();
 }
 
-size_t elem_size(emb_dtype d) { return d == EMB_F16 ? 2 : 4; }
+size_t elem_size(emb_dtype d) { return (d == EMB_F16 || d == EMB_BF16) ? 2 : 4; }
 size_t index_size(emb_index_type t) { return t == EMB_IDX_I64 ? 8 : 4; }
 
 struct Table {

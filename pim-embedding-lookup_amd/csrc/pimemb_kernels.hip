@@ -44,6 +44,14 @@ using WaveCfgF16 = BagCfg<64, 8, true, false, 8, PIMEMB_F16_MINW, 1, false, true
 using Wave2CfgF16 = BagCfg<128, 4, true, false, 8, PIMEMB_F16_MINW, 2, false, true, false, kClampInputs>;
 template <int DT> struct WaveCfgOf { using One = WaveCfg; using Two = Wave2Cfg; };
 template <> struct WaveCfgOf<EMB_F16> { using One = WaveCfgF16; using Two = Wave2CfgF16; };
+// bf16 rows: the same bytes, accumulator and group store as fp16 rows, so the same configurations.  Other occupancies were
+// tried on MI355X and change nothing that matters (tools/bf16_probe.py, profiles/bf16/README.md); -DPIMEMB_BF16_MINW=n repeats it.
+#ifndef PIMEMB_BF16_MINW
+#define PIMEMB_BF16_MINW PIMEMB_F16_MINW
+#endif
+using WaveCfgBF16 = BagCfg<64, 8, true, false, 8, PIMEMB_BF16_MINW, 1, false, true, false, kClampInputs>;
+using Wave2CfgBF16 = BagCfg<128, 4, true, false, 8, PIMEMB_BF16_MINW, 2, false, true, false, kClampInputs>;
+template <> struct WaveCfgOf<EMB_BF16> { using One = WaveCfgBF16; using Two = Wave2CfgBF16; };
 // pooled launches over tables with a hot-row set: persistent 1024-thread workgroups stage the set into LDS
 using HotCfg = BagCfg<1024, 8, true, false, 8, 1, 1, false, false, /*IDX_SHUFFLE*/ true, kClampInputs>;
 constexpr int kBlock = 256;  // helper kernels below
@@ -62,6 +70,7 @@ hipError_t with_types(emb_index_type itype, emb_dtype dtype, F &&f) {
     switch (dtype) {
         case EMB_F32: return with_index(Int<EMB_F32>{});
         case EMB_F16: return with_index(Int<EMB_F16>{});
+        case EMB_BF16: return with_index(Int<EMB_BF16>{});
         case EMB_FIXED32:
             if constexpr (FIXED32) return with_index(Int<EMB_FIXED32>{});
             break;
@@ -117,14 +126,15 @@ void launch_sum(const DevDesc *d, const MappedLaunch &m, KernelKind kind, const 
         hipLaunchKernelGGL((bag_sum_group_kernel<IdxT, DT, L, GroupCfg>), m.grid, dim3(GroupCfg::kBlock), 0, s, d, m.chunks, xmap);
 }
 
-// ---- pooled lookups (bag_pool_*): fp32 / fp16 tables; one instantiation per (index type, dtype, row width, path) -- the
+// ---- pooled lookups (bag_pool_*): fp32 / fp16 / bf16 tables; one instantiation per (index type, dtype, row width, path) -- the
 // pooling mode, weights and padding are per-descriptor values the kernels branch on (scalar branches) ----------------------
 // The pooled wave-batch kernel under the fp32 64-VGPR cap: its general (multi-index) step also carries a weight per gather
 // in flight, and eight of them spill (21 dwords per lane); four, as Wave2Cfg's general step, do not.  One-hot steps keep all
-// eight rounds' gathers in flight either way.  fp16 rows: the fp16 configuration as it is (4 waves per SIMD, no spill).
+// eight rounds' gathers in flight either way.  fp16 and bf16 rows: the fp16 configuration as it is (4 waves per SIMD, no spill).
 using PoolWaveCfg = BagCfg<64, 4, true, false, 8, 8, 1, false, true, false, kClampInputs>;
 template <int DT> struct PoolWaveCfgOf { using One = PoolWaveCfg; };
 template <> struct PoolWaveCfgOf<EMB_F16> { using One = WaveCfgF16; };
+template <> struct PoolWaveCfgOf<EMB_BF16> { using One = WaveCfgBF16; };
 
 // ---- column scatter for populate_mram-style uploads -----------------------------------------
 __global__ void __launch_bounds__(kBlock)
@@ -1081,8 +1091,8 @@ hipError_t launch_widen_words(const WidenArgs &a, hipStream_t stream) {
 }
 
 int geometry_for(emb_dtype dtype, uint32_t dim, LaunchGeom *g) {
-    uint32_t elem = (dtype == EMB_F16) ? 2u : 4u;
-    if (dtype != EMB_F32 && dtype != EMB_F16 && dtype != EMB_FIXED32) return EMB_ERR_INVALID;
+    uint32_t elem = (dtype == EMB_F16 || dtype == EMB_BF16) ? 2u : 4u;
+    if (dtype != EMB_F32 && dtype != EMB_F16 && dtype != EMB_FIXED32 && dtype != EMB_BF16) return EMB_ERR_INVALID;
     uint64_t row_bytes = (uint64_t)dim * elem;
     if (dim == 0) return EMB_ERR_UNSUPPORTED;
     g->anydim_vec = false;
@@ -1169,19 +1179,34 @@ hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t ma
         using IdxT = decltype(idx);
         constexpr int DT = decltype(dt)::value;
         using One = typename PoolWaveCfgOf<DT>::One;
+        constexpr bool BF16 = DT == EMB_BF16;       // bf16 tables: the same bodies under the bag_bf16pool_* names (pimemb_bag_kernels.h)
         if (kind == KERNEL_ANYDIM) {
+            auto anydim = [&](auto vec) {
+                constexpr bool VEC = decltype(vec)::value;
+                if constexpr (BF16)
+                    hipLaunchKernelGGL((bag_bf16pool_anydim_kernel<IdxT, DT, VEC, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
+                else
+                    hipLaunchKernelGGL((bag_pool_anydim_kernel<IdxT, DT, VEC, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
+            };
             if (g.anydim_vec)
-                hipLaunchKernelGGL((bag_pool_anydim_kernel<IdxT, DT, true, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
+                anydim(std::true_type{});
             else
-                hipLaunchKernelGGL((bag_pool_anydim_kernel<IdxT, DT, false, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
+                anydim(std::false_type{});
             return hipGetLastError();
         }
         return with_lanes_per_row(g.lanes_per_row, [&](auto l) {
             constexpr int L = decltype(l)::value;
-            if (kind == KERNEL_WAVEBATCH)
-                hipLaunchKernelGGL((bag_pool_wavebatch_kernel<IdxT, DT, L, One>), m.grid, dim3(One::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
-            else
-                hipLaunchKernelGGL((bag_pool_group_kernel<IdxT, DT, L, GroupCfg>), m.grid, dim3(GroupCfg::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+            if constexpr (BF16) {
+                if (kind == KERNEL_WAVEBATCH)
+                    hipLaunchKernelGGL((bag_bf16pool_wavebatch_kernel<IdxT, DT, L, One>), m.grid, dim3(One::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+                else
+                    hipLaunchKernelGGL((bag_bf16pool_group_kernel<IdxT, DT, L, GroupCfg>), m.grid, dim3(GroupCfg::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+            } else {
+                if (kind == KERNEL_WAVEBATCH)
+                    hipLaunchKernelGGL((bag_pool_wavebatch_kernel<IdxT, DT, L, One>), m.grid, dim3(One::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+                else
+                    hipLaunchKernelGGL((bag_pool_group_kernel<IdxT, DT, L, GroupCfg>), m.grid, dim3(GroupCfg::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+            }
         });
     });
 }

@@ -44,8 +44,10 @@ class EmbeddingBagCollection:
             else:  # DLRM init: U(-sqrt(1/n), sqrt(1/n))
                 a = float(np.sqrt(1.0 / n))
                 w = torch.empty((n, self.m), dtype=torch.float32, device=self.device).uniform_(-a, a, generator=g)
-            if dtype == "f16":
-                w = w.to(torch.float16)
+            if dtype not in ("f32", "f16", "bf16"):
+                raise ValueError("dtype must be 'f32', 'f16' or 'bf16'")
+            if dtype != "f32":
+                w = w.to(torch.float16 if dtype == "f16" else torch.bfloat16)
             self.engine.load_table(k, w)
         self._plans = {}
         self._ids = list(range(len(self.ln_emb)))

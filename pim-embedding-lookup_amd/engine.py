@@ -310,10 +310,12 @@ class EmbeddingEngine:
     # ---- tables (populate_mram's job, emb_host.h:136) ------------------------------------------
     def load_table(self, table_id: int, rows, dtype: int | None = None) -> None:
         """rows: [nr_rows, dim] numpy float32/float16/int32 (int32 = x1e9 fixed point) or a torch
-        tensor (CPU or CUDA) of those dtypes."""
+        tensor (CPU or CUDA) of those dtypes or of torch.bfloat16.  numpy has no bfloat16: a uint16 array
+        holds bf16 bits (formats.to_bf16_bits) when -- and only when -- dtype=EMB_BF16 says so."""
         if _is_torch(rows):
             import torch
-            tmap = {torch.float32: _l.EMB_F32, torch.float16: _l.EMB_F16, torch.int32: _l.EMB_FIXED32}
+            tmap = {torch.float32: _l.EMB_F32, torch.float16: _l.EMB_F16, torch.int32: _l.EMB_FIXED32,
+                    torch.bfloat16: _l.EMB_BF16}
             dt = tmap[rows.dtype] if dtype is None else dtype
             if not rows.is_contiguous():
                 rows = rows.contiguous()
@@ -366,12 +368,14 @@ class EmbeddingEngine:
         through it changes what lookups return (and leaves any hot-row copy stale)."""
         import torch
         ptr, n, d, dt = self.table_info(table_id)
-        typestr = {_l.EMB_F32: "<f4", _l.EMB_F16: "<f2", _l.EMB_FIXED32: "<i4"}[dt]
+        # (the CUDA array interface has no bfloat16 typestr: the bits travel as uint16 and are viewed as bf16)
+        typestr = {_l.EMB_F32: "<f4", _l.EMB_F16: "<f2", _l.EMB_FIXED32: "<i4", _l.EMB_BF16: "<u2"}[dt]
 
         class _View:
             __cuda_array_interface__ = {"shape": (n, d), "typestr": typestr, "data": (ptr, False), "version": 2,
                                         "strides": None}
-        return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+        view = torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+        return view.view(torch.bfloat16) if dt == _l.EMB_BF16 else view
 
     def table_info(self, table_id: int):
         ptr, n, d, dt = C.c_void_p(), C.c_uint64(), C.c_uint32(), C.c_int()

@@ -16,6 +16,21 @@ from __future__ import annotations
 import numpy as np
 
 
+def to_bf16_bits(x) -> np.ndarray:
+    """float32 array -> the uint16 bits of its bfloat16 rounding (nearest, ties to even -- what
+    `tensor.to(torch.bfloat16)` gives); NaN stays NaN (quiet bit set, sign and upper payload kept).  numpy has no bfloat16:
+    EmbeddingEngine.load_table takes such an array with dtype=EMB_BF16."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    rounded = (u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)   # (wraps only for NaNs)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    return np.where(nan, (u >> np.uint32(16)) | np.uint32(0x0040), rounded).astype(np.uint16)
+
+
+def from_bf16_bits(bits) -> np.ndarray:
+    """uint16 bfloat16 bits -> float32, exact for every pattern (a bf16 is the upper half of an fp32)."""
+    return (np.ascontiguousarray(bits, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
 class CriteoKaggleNpz:
     """Categorical side of a processed Criteo-Kaggle file as embedding-lookup batches."""
 
