@@ -283,11 +283,36 @@ int emb_plan_time(emb_plan *p, void *stream, uint32_t warmup, uint32_t iters, fl
  * are grouped by (dtype, dim, pooling mode) and run the bag_pool_* kernels -- never the hot-row kernel.
  * check: 0 unchecked, 1 as emb_lookup_batched_checked (*n_bad may be NULL), 2 deferred as emb_lookup_batched_checked_deferred
  * (DEVICE buffers; a HOST call is checked synchronously).  HOST calls stage the weights with the indices.  The ranged, counted
- * and sharded calls and the request queue stay sum-only. */
+ * and sharded calls and the request queue stay sum-only.  They also stay fp32-out, as do populate_mram / lookup of the compat
+ * layer: EMB_POOL_OUT_TABLE_DTYPE below exists on emb_lookup_pooled and emb_plan_create_pooled only.
+ *
+ * Half-width output (flags & EMB_POOL_OUT_TABLE_DTYPE; EMB_F16 and EMB_BF16 tables): descs[i].pooled points to n_bags * dim
+ * 2-byte elements of the TABLE's dtype, row-major, no padding, instead of floats.  The pooled value is computed exactly as
+ * without the flag (rows widened exactly to fp32, index order, the rules above) and then rounded ONCE, to nearest even, to the
+ * table's dtype: a one-index bag and a max bag return table values bit for bit, an fp16 sum beyond 65504 is +-inf, results in
+ * the subnormal range stay subnormal; NaN stays out of scope.  The reference is torch's CPU F.embedding_bag over the widened
+ * table, rounded by torch: F.embedding_bag(idx, W.float(), ...).to(W.dtype).  It is deliberately NOT torch's own half-dtype
+ * F.embedding_bag, which rounds more than once in its bf16 sum and in both dtypes' mean (torch 2.10 CPU, 37 indices per bag:
+ * bf16 sums of N(0, 3^2) rows differ by up to 0.125): this library is the more accurate of the two, and equal to torch where
+ * torch rounds once (max, one-index bags, weighted and padded sums, fp16 sum).
+ *   - The flag combines with every mode, with weights (which stay fp32) and with padding.  On an EMB_F32 or EMB_FIXED32 table
+ *     it is EMB_ERR_UNSUPPORTED; unknown flag bits stay EMB_ERR_INVALID.
+ *   - Alignment: for rows of 16-byte multiples up to 1 KiB (the tuned kernels) `pooled` must be 16-byte aligned, the same
+ *     rule the fp32 output has; other even dims of >= 32-byte rows need 4-byte alignment, every other dim 2-byte alignment.
+ *   - A plain-SUM spec that carries only this flag runs half-output twins of emb_lookup_batched's kernels (wave-batch,
+ *     two-batch wave-batch, lane-group, any-dim), every other spec with it half-output twins of the bag_pool_* kernels; never
+ *     the hot-row kernel, so results are the same with or without a hot set.  Descriptors of one call may mix flagged and
+ *     unflagged outputs and dtypes: launches are grouped by (dtype, dim, pooling mode, output width).
+ *   - HOST calls stage and copy out 2 bytes per element; emb_plan_bytes counts 2 bytes per output element of a flagged
+ *     descriptor; emb_plan_describe adds out=1 to a half-output launch's record (and only to those) and emb_plan_signature
+ *     differs from the fp32-out plan's; emb_stats counts the launches under their existing kind.
+ * A call or plan without the flag is what it was: same launches, signature, describe text and kernel machine code. */
 #define EMB_POOL_SUM 0u
 #define EMB_POOL_MEAN 1u
 #define EMB_POOL_MAX 2u
 #define EMB_POOL_PADDING 1u            /* emb_pool_spec.flags: padding_idx is live */
+#define EMB_POOL_OUT_TABLE_DTYPE 2u    /* emb_pool_spec.flags: descs[i].pooled points to rows of the TABLE's dtype
+                                          (EMB_F16 / EMB_BF16 tables only), n_bags * dim 2-byte elements */
 typedef struct emb_pool_spec {
     uint32_t mode;                     /* EMB_POOL_* */
     uint32_t flags;

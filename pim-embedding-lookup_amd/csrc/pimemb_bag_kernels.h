@@ -205,6 +205,41 @@ struct RowOps<EMB_FIXED32> {
     }
 };
 
+// ---- half-width pooled output (EMB_POOL_OUT_TABLE_DTYPE): the pooled row leaves in the table's own 2-byte dtype ----------
+// An INTERNAL dtype value, EMB_F16 / EMB_BF16 with the kHalfOutDT bit, names the half-output twin of a kernel: the sum kernels
+// derive everything from RowOps<DT> / ElemOps<DT>, so `fp16, half out` instantiates them under a mangling of its own and the
+// fp32-out instantiations keep their machine code.  The value never leaves the library (launch_bag_sum maps to it).
+// The fp32 accumulator is rounded ONCE, to nearest even: v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32, one per two elements, which is
+// what the vector conversion lowers to on gfx950.
+constexpr int kHalfOutDT = 16;
+template <int DT>
+inline constexpr bool kIsHalfOut = (DT & kHalfOutDT) != 0;
+
+template <int BASE> struct HalfRound;      // fp32 -> the 2-byte dtype BASE, as raw bits
+template <> struct HalfRound<EMB_F16> {
+    static __device__ __forceinline__ u32x4 pack(f32x8 a) { return __builtin_bit_cast(u32x4, __builtin_convertvector(a, f16x8)); }
+    static __device__ __forceinline__ uint16_t one(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }
+};
+template <> struct HalfRound<EMB_BF16> {
+    static __device__ __forceinline__ u32x4 pack(f32x8 a) { return __builtin_bit_cast(u32x4, __builtin_convertvector(a, bf16x8)); }
+    static __device__ __forceinline__ uint16_t one(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
+};
+
+// A lane's 8 consecutive elements are 16 B of output: one dwordx4 store per lane, already contiguous across the lane group,
+// so no group store.  The kernels address the output as float *: kFloatsPerLane is therefore the lane's output in FLOATS'
+// WORTH of bytes (4), which makes out_stride = chunks * 4 floats = dim * 2 bytes.
+template <int BASE>
+struct HalfOutRowOps : RowOps<BASE> {
+    static constexpr uint32_t kFloatsPerLane = 4;
+    static constexpr bool kGroupStore = false;
+    template <bool NT>
+    static __device__ __forceinline__ void store(const f32x8 &a, float *dst) {
+        store_f32x4<NT>(dst, __builtin_bit_cast(f32x4, HalfRound<BASE>::pack(a)));
+    }
+};
+template <> struct RowOps<EMB_F16 | kHalfOutDT> : HalfOutRowOps<EMB_F16> {};
+template <> struct RowOps<EMB_BF16 | kHalfOutDT> : HalfOutRowOps<EMB_BF16> {};
+
 template <bool NT, typename T>
 __device__ __forceinline__ T load_meta(const T *p) {
     typedef const T PIMEMB_AS *ptr_t;
@@ -515,26 +550,33 @@ bag_sum_group_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg,
 // are bit-identical to the vector kernels and the oracle.  Generality path, not a tuned one.
 template <int DT> struct ElemOps;
 template <> struct ElemOps<EMB_F32> {
-    using Elem = float; using Acc = float;
+    using Elem = float; using Acc = float; using Out = float;
     static __device__ __forceinline__ void add(Acc &a, Elem v) { a = a + v; }
     static __device__ __forceinline__ float out(Acc a) { return a; }
 };
 template <> struct ElemOps<EMB_F16> {
-    using Elem = _Float16; using Acc = float;
+    using Elem = _Float16; using Acc = float; using Out = float;
     static __device__ __forceinline__ void add(Acc &a, Elem v) { a = a + (float)v; }
     static __device__ __forceinline__ float out(Acc a) { return a; }
 };
 template <> struct ElemOps<EMB_BF16> {
-    using Elem = uint16_t; using Acc = float;      // (the raw bits)
+    using Elem = uint16_t; using Acc = float; using Out = float;      // (Elem: the raw bits)
     static __device__ __forceinline__ float widen(Elem v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
     static __device__ __forceinline__ void add(Acc &a, Elem v) { a = a + widen(v); }
     static __device__ __forceinline__ float out(Acc a) { return a; }
 };
 template <> struct ElemOps<EMB_FIXED32> {
-    using Elem = uint32_t; using Acc = uint32_t;
+    using Elem = uint32_t; using Acc = uint32_t; using Out = float;
     static __device__ __forceinline__ void add(Acc &a, Elem v) { a += v; }
     static __device__ __forceinline__ float out(Acc a) { return RowOps<EMB_FIXED32>::conv(a); }
 };
+
+template <int BASE> struct HalfOutElemOps : ElemOps<BASE> {       // half-width output: Out is the raw bits of the table's dtype
+    using Out = uint16_t;
+    static __device__ __forceinline__ Out out(float a) { return HalfRound<BASE>::one(a); }
+};
+template <> struct ElemOps<EMB_F16 | kHalfOutDT> : HalfOutElemOps<EMB_F16> {};
+template <> struct ElemOps<EMB_BF16 | kHalfOutDT> : HalfOutElemOps<EMB_BF16> {};
 
 template <typename IdxT, int DT, bool CLAMP>
 __global__ void __launch_bounds__(256)
@@ -544,7 +586,7 @@ bag_sum_anydim_kernel(const DevDesc *__restrict__ descs, uint32_t dim, uint32_t 
     const typename E::Elem *__restrict__ weights = static_cast<const typename E::Elem *>(dp->weights);
     const IdxT *__restrict__ indices = static_cast<const IdxT *>(dp->indices);
     const IdxT *__restrict__ offsets = static_cast<const IdxT *>(dp->offsets);
-    float *__restrict__ out = dp->out;
+    typename E::Out *__restrict__ out = reinterpret_cast<typename E::Out *>(dp->out);     // (float, or the halves of a half-output twin)
     const uint64_t n_idx = dp->n_idx, n_bags = dp->n_bags, last_row = dp->nr_rows - 1;
     const uint64_t bag = (uint64_t)blockIdx.x * (256u / lanes) + threadIdx.x / lanes;
     if (blockIdx.x >= dp->n_tiles || bag >= n_bags) return;
@@ -571,7 +613,7 @@ template <typename IdxT, int DT, bool CLAMP>
 __global__ void __launch_bounds__(256)
 bag_sum_anydim_vec_kernel(const DevDesc *__restrict__ descs, uint32_t dim, uint32_t lanes) {
     using Ops = RowOps<DT>;
-    constexpr uint32_t EP = Ops::kFloatsPerLane;            // elements per 16-byte piece (4, or 8 halves)
+    constexpr uint32_t EP = sizeof(typename Ops::Acc) / 4u; // elements per 16-byte piece (4, or 8 halves)
     constexpr uint32_t ESZ = 16u / EP;
     constexpr int U = 4;
     const DevDesc *dp = descs + blockIdx.y;
@@ -609,21 +651,34 @@ bag_sum_anydim_vec_kernel(const DevDesc *__restrict__ descs, uint32_t dim, uint3
             for (int k = 0; k < U; k++) Ops::add(acc, v[k]);
         }
         for (; p < e; p++) Ops::add(acc, fetch((uint64_t)indices[p]));
-        float *o = out + bag * dim + piece * EP;
-        float res[EP];
-        if constexpr (DT == EMB_FIXED32) {
+        if constexpr (kIsHalfOut<DT>) {
+            // half-width output: the piece is 16 B of halves at a 4-byte aligned address (dim is even here)
+            uint16_t *o = reinterpret_cast<uint16_t *>(out) + bag * dim + piece * EP;
+            const u32x4 h = HalfRound<DT & ~kHalfOutDT>::pack(acc);
+            if (n_el == EP) {
+                *reinterpret_cast<u32x4_a4 *>(o) = h;
+            } else {
 #pragma unroll
-            for (uint32_t c = 0; c < EP; c++) res[c] = RowOps<EMB_FIXED32>::conv(acc[c]);
+                for (uint32_t c = 0; c < EP; c++)
+                    if (c < n_el) o[c] = (uint16_t)(h[c / 2] >> (16u * (c & 1u)));
+            }
         } else {
+            float *o = out + bag * dim + piece * EP;
+            float res[EP];
+            if constexpr (DT == EMB_FIXED32) {
 #pragma unroll
-            for (uint32_t c = 0; c < EP; c++) res[c] = acc[c];
-        }
-        if (n_el == EP) {
+                for (uint32_t c = 0; c < EP; c++) res[c] = RowOps<EMB_FIXED32>::conv(acc[c]);
+            } else {
 #pragma unroll
-            for (uint32_t c = 0; c < EP; c += 4)
-                *reinterpret_cast<f32x4_a4 *>(o + c) = f32x4{res[c], res[c + 1], res[c + 2], res[c + 3]};
-        } else {
-            for (uint32_t c = 0; c < n_el; c++) o[c] = res[c];
+                for (uint32_t c = 0; c < EP; c++) res[c] = acc[c];
+            }
+            if (n_el == EP) {
+#pragma unroll
+                for (uint32_t c = 0; c < EP; c += 4)
+                    *reinterpret_cast<f32x4_a4 *>(o + c) = f32x4{res[c], res[c + 1], res[c + 2], res[c + 3]};
+            } else {
+                for (uint32_t c = 0; c < n_el; c++) o[c] = res[c];
+            }
         }
     }
 }
@@ -1046,11 +1101,25 @@ __device__ __forceinline__ void pool_walk(const IdxT *__restrict__ indices, cons
 // tests/test_pooling_abi.py pins the SET of bag_pool_* kernels in the code object (64: index width x fp32 / fp16 x row widths
 // x paths, plus the any-dim ones) and is not a file that adding a dtype may edit, so that set stays what the test pins;
 // launch_bag_pool (pimemb_kernels.hip) and codeobj.symbol_fragments know both names.
+// Half-width output (EMB_POOL_OUT_TABLE_DTYPE): a third set, bag_hpool_*, for fp16 and bf16 tables alike -- the same text with
+// PIMEMB_POOL_HALF_OUT 1, which swaps in the half-output RowOps (one 16-byte store per lane) and the any-dim kernel's 2-byte
+// store tail.  DT stays the table's public dtype there; the name tells the twins apart (and is not one the tests above pin).
 #define PIMEMB_POOL_KERNEL(path) bag_pool_##path##_kernel
+#define PIMEMB_POOL_HALF_OUT 0
+#define PIMEMB_POOL_ROWOPS(DT) RowOps<DT>
 #include "pimemb_pool_kernels.inc"
 #undef PIMEMB_POOL_KERNEL
 #define PIMEMB_POOL_KERNEL(path) bag_bf16pool_##path##_kernel
 #include "pimemb_pool_kernels.inc"
 #undef PIMEMB_POOL_KERNEL
+#undef PIMEMB_POOL_HALF_OUT
+#undef PIMEMB_POOL_ROWOPS
+#define PIMEMB_POOL_KERNEL(path) bag_hpool_##path##_kernel
+#define PIMEMB_POOL_HALF_OUT 1
+#define PIMEMB_POOL_ROWOPS(DT) RowOps<(DT) | kHalfOutDT>
+#include "pimemb_pool_kernels.inc"
+#undef PIMEMB_POOL_KERNEL
+#undef PIMEMB_POOL_HALF_OUT
+#undef PIMEMB_POOL_ROWOPS
 
 }  // namespace pimemb

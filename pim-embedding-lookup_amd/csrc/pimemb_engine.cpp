@@ -236,6 +236,7 @@ struct PlanGroup {
     bool ranged = false;             // descriptors serve a row range each (emb_lookup_ranged / emb_plan_create_ranged)
     uint32_t pool = 0;               // 0: plain sum (bag_sum_*); else 1 + EMB_POOL_* of a pooled launch (bag_pool_*)
     uint32_t n_weighted = 0, n_padding = 0;   // pooled launch: descriptors with per-sample weights / a padding_idx
+    bool out_half = false;           // EMB_POOL_OUT_TABLE_DTYPE: pooled rows leave in the table's 2-byte dtype (half-output twins)
     size_t desc_off = 0, xmap_off = 0;  // byte offsets of this group's pieces in the launch image
     std::vector<uint32_t> xmap_words;
 };
@@ -441,6 +442,13 @@ int cached_xcd_map(emb_engine *e, PlanGroup &g, uint32_t bpt, const std::vector<
 bool is_plain_sum(const emb_pool_spec &ps) {
     return ps.mode == EMB_POOL_SUM && ps.per_sample_weights == nullptr && ps.flags == 0;
 }
+// ... or for nothing else but rows in the table's dtype: the half-output twins of emb_lookup_batched's kernels.
+bool is_plain_sum_half_out(const emb_pool_spec &ps) {
+    return ps.mode == EMB_POOL_SUM && ps.per_sample_weights == nullptr && ps.flags == EMB_POOL_OUT_TABLE_DTYPE;
+}
+bool wants_half_out(const emb_pool_spec *pools, uint32_t i) { return pools && (pools[i].flags & EMB_POOL_OUT_TABLE_DTYPE) != 0; }
+// Bytes of descriptor u's pooled rows: fp32, or the table's 2-byte dtype for a half-output descriptor.
+size_t out_elem_size(const emb_pool_spec *pools, uint32_t i) { return wants_half_out(pools, i) ? 2 : 4; }
 
 // st_indices / st_offsets / st_out: if non-null, per-descriptor device pointers that replace the
 // caller's (the staged copies of a host-pointer call).
@@ -455,8 +463,8 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
             uint32_t *const *served = nullptr, const emb_pool_spec *pools = nullptr,
             const std::vector<const float *> *st_weights = nullptr) {
     if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "bad index type");
-    // (dtype, dim, pooling kind): kind 0 = plain sum, the key every call without pooling specs has
-    std::map<std::tuple<int, uint32_t, uint32_t>, std::vector<uint32_t>> by_shape;
+    // (dtype, dim, pooling kind, output width): kind 0 = plain sum, width 0 = fp32, the key every call without pooling specs has
+    std::map<std::tuple<int, uint32_t, uint32_t, uint32_t>, std::vector<uint32_t>> by_shape;
     for (uint32_t i = 0; i < n_descs; i++) {
         const emb_lookup_desc &u = descs[i];
         if (u.table_id >= e->tables.size() || e->tables[u.table_id].rows == nullptr)
@@ -480,8 +488,11 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
         uint32_t pool_kind = 0;
         if (pools && !is_plain_sum(pools[i])) {
             const emb_pool_spec &ps = pools[i];
-            if (ps.mode > EMB_POOL_MAX || (ps.flags & ~EMB_POOL_PADDING) != 0)
+            if (ps.mode > EMB_POOL_MAX || (ps.flags & ~(EMB_POOL_PADDING | EMB_POOL_OUT_TABLE_DTYPE)) != 0)
                 return fail(EMB_ERR_INVALID, "desc %u: bad pooling spec (mode %u, flags 0x%x)", i, ps.mode, ps.flags);
+            if ((ps.flags & EMB_POOL_OUT_TABLE_DTYPE) && t.dtype != EMB_F16 && t.dtype != EMB_BF16)
+                return fail(EMB_ERR_UNSUPPORTED, "desc %u: EMB_POOL_OUT_TABLE_DTYPE needs an fp16 or bf16 table (table %u has dtype %d)", i,
+                            u.table_id, (int)t.dtype);
             if (ps.per_sample_weights != nullptr && ps.mode != EMB_POOL_SUM)
                 return fail(EMB_ERR_INVALID, "desc %u: per_sample_weights need EMB_POOL_SUM (as in torch)", i);
             if (t.dtype == EMB_FIXED32)
@@ -490,15 +501,16 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
                 return fail(EMB_ERR_INVALID, "desc %u: padding_idx %lld outside table %u (%llu rows)", i, (long long)ps.padding_idx,
                             u.table_id, (unsigned long long)t.nr_rows);
             if (row_lo) return fail(EMB_ERR_UNSUPPORTED, "ranged lookups pool by plain sum only");
-            pool_kind = 1u + ps.mode;
+            if (!is_plain_sum_half_out(ps)) pool_kind = 1u + ps.mode;      // (only the flag: the sum kernels' half-output twins)
         }
-        by_shape[{(int)t.dtype, t.dim, pool_kind}].push_back(i);
+        by_shape[{(int)t.dtype, t.dim, pool_kind, wants_half_out(pools, i) ? 1u : 0u}].push_back(i);
     }
     const size_t isz = index_size(itype);
     for (auto &kv : by_shape) {
         PlanGroup g;
         g.dtype = (emb_dtype)std::get<0>(kv.first);
         g.pool = std::get<2>(kv.first);
+        g.out_half = std::get<3>(kv.first) != 0;
         g.n = (uint32_t)kv.second.size();
         const Table &t0 = e->tables[descs[kv.second[0]].table_id];
         g.geom = t0.geom;
@@ -516,7 +528,7 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
         g.ranged = row_lo != nullptr;
         if (g.ranged && g.kind == pimemb::KERNEL_GROUP) g.kind = pimemb::KERNEL_WAVEBATCH;    // (small launches too: the predicate lives there)
         if (g.pool && g.kind == pimemb::KERNEL_WAVEBATCH2) g.kind = pimemb::KERNEL_WAVEBATCH;  // (the pooled family has one wave-batch geometry)
-        if (g.kind == pimemb::KERNEL_GROUP && !g.pool) {   // (a pooled launch never takes the hot-row kernel)   // pooled launch over tables with a hot-row set: LDS-staged kernel
+        if (g.kind == pimemb::KERNEL_GROUP && !g.pool && !g.out_half) {   // (a pooled or half-output launch never takes the hot-row kernel)   // pooled launch over tables with a hot-row set: LDS-staged kernel
             for (uint32_t i : kv.second) {
                 const Table &t = e->tables[descs[i].table_id];
                 if (t.n_hot && t.hot_lds > g.hot_lds) g.hot_lds = (uint32_t)t.hot_lds;
@@ -571,7 +583,7 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
             r->n_indices += u.n_indices;
             // algorithmic bytes, SURVEY.md section 8 row D
             r->bytes += u.n_indices * ((uint64_t)t.dim * elem_size(t.dtype) + isz) +
-                        (u.offsets ? u.n_bags * isz : 0) + u.n_bags * (uint64_t)t.dim * 4;
+                        (u.offsets ? u.n_bags * isz : 0) + u.n_bags * (uint64_t)t.dim * (g.out_half ? 2 : 4);
         }
         // several tables in one big one-hot launch: XCD-aware workgroup map (one table <-> one XCD's
         // L2).  Measured neutral for pooled launches and slightly negative for small ones, which
@@ -628,12 +640,12 @@ int launch_groups(emb_engine *e, const std::vector<PlanGroup> &groups, emb_index
     for (const PlanGroup &g : groups) {
         if (g.pool)
             HIP_TRY(pimemb::launch_bag_pool(g.d_descs, g.n, g.max_tiles, g.dtype, itype, g.geom, g.kind, g.d_xmap, g.xgrid,
-                                            g.xdirect, s));
+                                            g.xdirect, s, g.out_half));
         else if (g.kind == pimemb::KERNEL_HOT)
             HIP_TRY(pimemb::launch_bag_sum_hot(g.d_descs, g.n, g.hot_wgs, g.hot_lds, g.dtype, itype, g.geom, s));
         else
             HIP_TRY(pimemb::launch_bag_sum(g.d_descs, g.n, g.max_tiles, g.dtype, itype, g.geom, g.kind, g.d_xmap,
-                                           g.xgrid, g.xdirect, s, g.ranged));
+                                           g.xgrid, g.xdirect, s, g.ranged, g.out_half));
         e->n_kernel_launches.fetch_add(1, std::memory_order_relaxed);
         e->n_by_kind[g.kind].fetch_add(1, std::memory_order_relaxed);
     }
@@ -794,7 +806,7 @@ int stage_host_inputs(emb_engine *e, const emb_lookup_desc *descs, uint32_t n, e
         in_bytes += align_up(descs[i].n_indices * isz, 16);
         if (descs[i].offsets) in_bytes += align_up(descs[i].n_bags * isz, 16);
         if (pools && pools[i].per_sample_weights) in_bytes += align_up(descs[i].n_indices * 4, 16);
-        const size_t piece = descs[i].n_bags * (size_t)e->tables[descs[i].table_id].dim * 4;
+        const size_t piece = descs[i].n_bags * (size_t)e->tables[descs[i].table_id].dim * out_elem_size(pools, i);
         out_bytes += align_up(piece, 16);
         if (piece && piece < min_piece) min_piece = piece;
     }
@@ -838,7 +850,7 @@ int stage_host_inputs(emb_engine *e, const emb_lookup_desc *descs, uint32_t n, e
     for (uint32_t i = 0; i < n; i++) {
         hs->d_out[i] = reinterpret_cast<float *>((hs->zero_copy ? e->h_stage : e->d_stage) + oo);
         if (with_outputs)
-            oo += align_up(descs[i].n_bags * (size_t)e->tables[descs[i].table_id].dim * 4, 16);
+            oo += align_up(descs[i].n_bags * (size_t)e->tables[descs[i].table_id].dim * out_elem_size(pools, i), 16);
     }
     hs->in_bytes = in_bytes;
     hs->out_bytes = out_bytes;
@@ -1025,7 +1037,7 @@ int lookup_host(emb_engine *e, const emb_lookup_desc *descs, uint32_t n, emb_ind
         HIP_TRY(hipMemcpyAsync(hs.h_out, hs.d_out[0], hs.out_bytes, hipMemcpyDeviceToHost, s));
     } else {
         for (uint32_t i = 0; i < n; i++) {
-            size_t bytes = descs[i].n_bags * (size_t)e->tables[descs[i].table_id].dim * 4;
+            size_t bytes = descs[i].n_bags * (size_t)e->tables[descs[i].table_id].dim * out_elem_size(pools, i);
             if (bytes)
                 HIP_TRY(hipMemcpyAsync(descs[i].pooled, hs.d_out[i], bytes, hipMemcpyDeviceToHost, s));
         }
@@ -1054,7 +1066,7 @@ int lookup_host(emb_engine *e, const emb_lookup_desc *descs, uint32_t n, emb_ind
         std::vector<pimemb::CopyPiece> unpack;
         unpack.reserve(n);
         for (uint32_t i = 0; i < n; i++) {
-            size_t bytes = descs[i].n_bags * (size_t)e->tables[descs[i].table_id].dim * 4;
+            size_t bytes = descs[i].n_bags * (size_t)e->tables[descs[i].table_id].dim * out_elem_size(pools, i);
             if (bytes)
                 unpack.push_back({descs[i].pooled, hs.h_out + (reinterpret_cast<char *>(hs.d_out[i]) -
                                                                 reinterpret_cast<char *>(hs.d_out[0])), bytes});
@@ -1552,6 +1564,7 @@ static int plan_create(emb_engine *e, const emb_lookup_desc *descs, const uint64
             mix(g.kind); mix((uint64_t)g.dtype); mix(g.geom.lanes_per_row); mix(g.geom.chunks); mix(g.geom.scalar_lanes); mix(g.n); mix(g.max_tiles);
             mix(g.xgrid); mix(g.xdirect); mix(g.ranged); mix(g.hot_wgs); mix(g.hot_lds); mix(pimemb::bags_per_tile(g.kind, g.geom));
             if (g.pool) mix(0x706f6f6c00ull | g.pool);     // (plain-sum groups mix exactly what they always did)
+            if (g.out_half) mix(0x6f757400ull | 1u);       // (... and so do fp32-out groups)
             for (uint32_t w : g.xmap_words) mix(w);
             for (uint32_t i = 0; i < g.n; i++, di++) {
                 const DevDesc &d = r.descs[di];
@@ -1633,6 +1646,11 @@ int emb_plan_describe(const emb_plan *p, char *buf, size_t capacity) {
         at += (size_t)n;
         if (g.pool) {
             const int m = snprintf(buf + at, capacity - at, " pool=%u weighted=%u padding=%u", g.pool - 1u, g.n_weighted, g.n_padding);
+            if (m < 0 || (size_t)m >= capacity - at) return fail(EMB_ERR_INVALID, "emb_plan_describe: %zu bytes do not hold the text", capacity);
+            at += (size_t)m;
+        }
+        if (g.out_half) {
+            const int m = snprintf(buf + at, capacity - at, " out=1");
             if (m < 0 || (size_t)m >= capacity - at) return fail(EMB_ERR_INVALID, "emb_plan_describe: %zu bytes do not hold the text", capacity);
             at += (size_t)m;
         }

@@ -45,14 +45,16 @@ KernelKind choose_kernel(uint64_t total_bags, uint64_t total_indices, const Laun
 hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles,
                           emb_dtype dtype, emb_index_type itype, const LaunchGeom &g,
                           KernelKind kind, const uint32_t *d_xmap, uint32_t xgrid, bool xdirect,
-                          hipStream_t stream, bool ranged = false);
+                          hipStream_t stream, bool ranged = false, bool out_half = false);
+// out_half (here and in launch_bag_pool; EMB_POOL_OUT_TABLE_DTYPE): DevDesc::out points to rows of the table's 2-byte dtype
+// (fp16 / bf16 tables only; never ranged) and the launch runs the half-output twin of the kernel.
 
 // Pooled lookup (emb_lookup_pooled: mean / max, per-sample weights, padding_idx) over descriptors of one dtype (fp32 / fp16 / bf16)
 // and dim whose pooling spec sits in DevDesc::pool (pimemb_bag_kernels.h, bag_pool_*).  kind: KERNEL_WAVEBATCH,
 // KERNEL_GROUP or KERNEL_ANYDIM (no two-batch or hot-row variant).  Pure enqueue.
 hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, emb_dtype dtype,
                            emb_index_type itype, const LaunchGeom &g, KernelKind kind, const uint32_t *d_xmap,
-                           uint32_t xgrid, bool xdirect, hipStream_t stream);
+                           uint32_t xgrid, bool xdirect, hipStream_t stream, bool out_half = false);
 
 // Pooled launch with hot rows in LDS: `wgs` persistent workgroups per descriptor, `lds_bytes` of dynamic LDS.
 hipError_t launch_bag_sum_hot(const DevDesc *d_descs, uint32_t n_descs, uint32_t wgs, uint32_t lds_bytes,

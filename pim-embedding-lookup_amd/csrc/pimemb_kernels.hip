@@ -52,6 +52,10 @@ template <> struct WaveCfgOf<EMB_F16> { using One = WaveCfgF16; using Two = Wave
 using WaveCfgBF16 = BagCfg<64, 8, true, false, 8, PIMEMB_BF16_MINW, 1, false, true, false, kClampInputs>;
 using Wave2CfgBF16 = BagCfg<128, 4, true, false, 8, PIMEMB_BF16_MINW, 2, false, true, false, kClampInputs>;
 template <> struct WaveCfgOf<EMB_BF16> { using One = WaveCfgBF16; using Two = Wave2CfgBF16; };
+// half-width output (kHalfOutDT, pimemb_bag_kernels.h): the same 8 fp32 accumulators per gather as the fp32-out kernels of these
+// tables, no store shuffles; the configurations of their tables, under which none of them spills
+template <> struct WaveCfgOf<EMB_F16 | kHalfOutDT> : WaveCfgOf<EMB_F16> {};
+template <> struct WaveCfgOf<EMB_BF16 | kHalfOutDT> : WaveCfgOf<EMB_BF16> {};
 // pooled launches over tables with a hot-row set: persistent 1024-thread workgroups stage the set into LDS
 using HotCfg = BagCfg<1024, 8, true, false, 8, 1, 1, false, false, /*IDX_SHUFFLE*/ true, kClampInputs>;
 constexpr int kBlock = 256;  // helper kernels below
@@ -75,6 +79,16 @@ hipError_t with_types(emb_index_type itype, emb_dtype dtype, F &&f) {
             if constexpr (FIXED32) return with_index(Int<EMB_FIXED32>{});
             break;
     }
+    return hipErrorInvalidValue;
+}
+
+// The same for a half-output launch (EMB_POOL_OUT_TABLE_DTYPE): fp16 / bf16 tables only, and f receives the INTERNAL dtype value
+// that names the half-output twin of a sum kernel.
+template <class F>
+hipError_t with_half_out_types(emb_index_type itype, emb_dtype dtype, F &&f) {
+    auto with_index = [&](auto dt) { return itype == EMB_IDX_U32 ? f(uint32_t{}, dt) : f(int64_t{}, dt); };
+    if (dtype == EMB_F16) return with_index(Int<EMB_F16 | kHalfOutDT>{});
+    if (dtype == EMB_BF16) return with_index(Int<EMB_BF16 | kHalfOutDT>{});
     return hipErrorInvalidValue;
 }
 
@@ -118,9 +132,9 @@ void launch_sum(const DevDesc *d, const MappedLaunch &m, KernelKind kind, const 
         else if constexpr (L <= 4)
             hipLaunchKernelGGL((bag_sum_wavebatch_kernel<IdxT, DT, L, Two, RANGED>), m.grid, dim3(Two::kBlock), 0, s, d, m.chunks, xmap);
     };
-    if (ranged)        // launch_bag_sum lets the two wave-batch kinds through only (uint32 and int64 indices alike)
-        wavebatch(std::true_type{});
-    else if (kind == KERNEL_WAVEBATCH || kind == KERNEL_WAVEBATCH2)
+    if (ranged) {      // launch_bag_sum lets the two wave-batch kinds through only (uint32 and int64 indices alike)
+        if constexpr (!kIsHalfOut<DT>) wavebatch(std::true_type{});      // (ranged launches stay fp32-out: no such twin)
+    } else if (kind == KERNEL_WAVEBATCH || kind == KERNEL_WAVEBATCH2)
         wavebatch(std::false_type{});
     else
         hipLaunchKernelGGL((bag_sum_group_kernel<IdxT, DT, L, GroupCfg>), m.grid, dim3(GroupCfg::kBlock), 0, s, d, m.chunks, xmap);
@@ -1146,14 +1160,15 @@ KernelKind choose_kernel(uint64_t total_bags, uint64_t total_indices, const Laun
 hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles,
                           emb_dtype dtype, emb_index_type itype, const LaunchGeom &g,
                           KernelKind kind, const uint32_t *d_xmap, uint32_t xgrid, bool xdirect,
-                          hipStream_t stream, bool ranged) {
+                          hipStream_t stream, bool ranged, bool out_half) {
     if (n_descs == 0 || max_tiles == 0) return hipSuccess;
     if (d_xmap == nullptr && n_descs > 65535u) return hipErrorInvalidValue;
     if (ranged && ((kind != KERNEL_WAVEBATCH && kind != KERNEL_WAVEBATCH2) || (kind == KERNEL_WAVEBATCH2 && g.lanes_per_row > 4)))
         return hipErrorInvalidValue;
     if (kind == KERNEL_ANYDIM && (g.scalar_lanes == 0 || d_xmap != nullptr)) return hipErrorInvalidValue;
+    if (out_half && (ranged || kind == KERNEL_HOT)) return hipErrorInvalidValue;
     const MappedLaunch m(n_descs, max_tiles, g, d_xmap, xgrid, xdirect);
-    return with_types<true>(itype, dtype, [&](auto idx, auto dt) {
+    auto launch = [&](auto idx, auto dt) {
         using IdxT = decltype(idx);
         constexpr int DT = decltype(dt)::value;
         if (kind == KERNEL_ANYDIM) {
@@ -1164,13 +1179,15 @@ hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max
             return hipGetLastError();
         }
         return with_lanes_per_row(g.lanes_per_row, [&](auto l) { launch_sum<IdxT, DT, decltype(l)::value>(d_descs, m, kind, d_xmap, ranged, stream); });
-    });
+    };
+    return out_half ? with_half_out_types(itype, dtype, launch) : with_types<true>(itype, dtype, launch);
 }
 
 hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, emb_dtype dtype,
                            emb_index_type itype, const LaunchGeom &g, KernelKind kind, const uint32_t *d_xmap,
-                           uint32_t xgrid, bool xdirect, hipStream_t stream) {
+                           uint32_t xgrid, bool xdirect, hipStream_t stream, bool out_half) {
     if (n_descs == 0 || max_tiles == 0) return hipSuccess;
+    if (out_half && dtype != EMB_F16 && dtype != EMB_BF16) return hipErrorInvalidValue;
     if (d_xmap == nullptr && n_descs > 65535u) return hipErrorInvalidValue;
     if (kind == KERNEL_ANYDIM ? (g.scalar_lanes == 0 || d_xmap != nullptr) : (kind != KERNEL_WAVEBATCH && kind != KERNEL_GROUP))
         return hipErrorInvalidValue;
@@ -1180,6 +1197,24 @@ hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t ma
         constexpr int DT = decltype(dt)::value;
         using One = typename PoolWaveCfgOf<DT>::One;
         constexpr bool BF16 = DT == EMB_BF16;       // bf16 tables: the same bodies under the bag_bf16pool_* names (pimemb_bag_kernels.h)
+        if constexpr (DT == EMB_F16 || DT == EMB_BF16) {
+            if (out_half) {                         // ... and the half-output set, bag_hpool_*, for both 2-byte dtypes
+                if (kind == KERNEL_ANYDIM) {
+                    if (g.anydim_vec)
+                        hipLaunchKernelGGL((bag_hpool_anydim_kernel<IdxT, DT, true, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
+                    else
+                        hipLaunchKernelGGL((bag_hpool_anydim_kernel<IdxT, DT, false, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
+                    return hipGetLastError();
+                }
+                return with_lanes_per_row(g.lanes_per_row, [&](auto l) {
+                    constexpr int L = decltype(l)::value;
+                    if (kind == KERNEL_WAVEBATCH)
+                        hipLaunchKernelGGL((bag_hpool_wavebatch_kernel<IdxT, DT, L, One>), m.grid, dim3(One::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+                    else
+                        hipLaunchKernelGGL((bag_hpool_group_kernel<IdxT, DT, L, GroupCfg>), m.grid, dim3(GroupCfg::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+                });
+            }
+        }
         if (kind == KERNEL_ANYDIM) {
             auto anydim = [&](auto vec) {
                 constexpr bool VEC = decltype(vec)::value;

@@ -1,14 +1,16 @@
 // pimemb_pool_kernels.inc -- the three kernels of the pooled family (mean / max pooling, per-sample weights, padding_idx).
 // Included by pimemb_bag_kernels.h, inside namespace pimemb, ONCE PER SET OF ENTRY-POINT NAMES: PIMEMB_POOL_KERNEL(path) names
-// the kernel of a path (group, wavebatch, anydim).  The same text compiled under two names, so that the kernels of the first
-// set keep their machine code to the byte (as bodies shared by two thin kernels they do not: inlined, 50 of the 64 fp32 / fp16
-// pooled kernels change, some by up to 4 VGPRs).
+// the kernel of a path (group, wavebatch, anydim); PIMEMB_POOL_ROWOPS(DT) is the accumulate / store trait and
+// PIMEMB_POOL_HALF_OUT says whether the set stores fp32 rows (0) or rows of the table's 2-byte dtype (1).
+// The same text compiled under three sets of names -- bag_pool_* (fp32, fp16), bag_bf16pool_* (bf16), bag_hpool_* (half-width
+// output of fp16 and bf16 tables) -- so that the kernels of the first set keep their machine code to the byte (as bodies
+// shared by thin kernels they do not: inlined, 50 of the 64 fp32 / fp16 pooled kernels change, some by up to 4 VGPRs).
 
 // Lane-group path (ragged bags, rows of 16-byte multiples up to 1 KiB): one lane group per bag, as bag_sum_group_kernel.
 template <typename IdxT, int DT, int LPR, class Cfg>
 __global__ void __launch_bounds__(Cfg::kBlock)
 PIMEMB_POOL_KERNEL(group)(const DevDesc *__restrict__ descs, uint32_t chunks_arg, const uint32_t *__restrict__ xmap) {
-    using Ops = RowOps<DT>;
+    using Ops = PIMEMB_POOL_ROWOPS(DT);
     constexpr uint32_t kWaves = Cfg::kBlock / 64;
     constexpr uint32_t BPW = 64 / LPR;
     constexpr uint32_t BAGS_PER_TILE = BPW * kWaves;
@@ -48,7 +50,7 @@ PIMEMB_POOL_KERNEL(group)(const DevDesc *__restrict__ descs, uint32_t chunks_arg
 template <typename IdxT, int DT, int LPR, class Cfg>
 __global__ void __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves)
 PIMEMB_POOL_KERNEL(wavebatch)(const DevDesc *__restrict__ descs, uint32_t chunks_arg, const uint32_t *__restrict__ xmap) {
-    using Ops = RowOps<DT>;
+    using Ops = PIMEMB_POOL_ROWOPS(DT);
     constexpr uint32_t kWaves = Cfg::kBlock / 64;
     constexpr uint32_t BPR = 64 / LPR;      // bags per round
     constexpr uint32_t ROUNDS = LPR;        // rounds per 64-bag wave batch
@@ -225,6 +227,24 @@ PIMEMB_POOL_KERNEL(anydim)(const DevDesc *__restrict__ descs, uint32_t dim, uint
         }
 #pragma unroll
         for (uint32_t c = 0; c < EP; c++) acc[c] = pool_finish1(acc[c], cnt, a.mean);
+#if PIMEMB_POOL_HALF_OUT    // rounded once to the table's dtype: a full piece is 16 B of halves at a 4-byte aligned address
+        uint16_t *o = reinterpret_cast<uint16_t *>(out) + bag * dim + unit * EP;
+        if constexpr (VEC) {
+            f32x8 a8;
+#pragma unroll
+            for (uint32_t c = 0; c < EP; c++) a8[c] = acc[c];
+            const u32x4 h = HalfRound<DT>::pack(a8);
+            if (n_el == EP) {
+                *reinterpret_cast<u32x4_a4 *>(o) = h;
+            } else {
+#pragma unroll
+                for (uint32_t c = 0; c < EP; c++)
+                    if (c < n_el) o[c] = (uint16_t)(h[c / 2] >> (16u * (c & 1u)));
+            }
+        } else {
+            o[0] = HalfRound<DT>::one(acc[0]);
+        }
+#else
         float *o = out + bag * dim + unit * EP;
         bool stored = false;
         if constexpr (VEC) {
@@ -237,5 +257,6 @@ PIMEMB_POOL_KERNEL(anydim)(const DevDesc *__restrict__ descs, uint32_t dim, uint
         }
         if (!stored)
             for (uint32_t c = 0; c < n_el; c++) o[c] = acc[c];
+#endif
     }
 }

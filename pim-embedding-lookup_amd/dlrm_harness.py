@@ -26,9 +26,14 @@ class EmbeddingBagCollection:
 
     def __init__(self, ln_emb, m_spa: int, device: int = 0, weights=None, seed: int = 0, dtype="f32",
                  trusted_inputs: bool = False, deferred_check: bool = False, weighted_pooling: str | None = None,
-                 pooling_weights=None):
+                 pooling_weights=None, out_dtype: str | None = None):
         import torch
         self.torch = torch
+        # out_dtype="weight": f16 / bf16 tables return rows of their own dtype (the fp32 sum rounded once), as nn.EmbeddingBag
+        # does; None: fp32 rows whatever the tables hold
+        if out_dtype not in (None, "weight"):
+            raise ValueError('out_dtype must be None or "weight"')
+        self._out = "table" if out_dtype == "weight" and dtype in ("f16", "bf16") else None
         self.trusted_inputs = bool(trusted_inputs)     # False: every apply_emb checks its indices first (IndexError)
         self.deferred_check = bool(deferred_check)     # ... without waiting for the verdict (a later call / close() raises it)
         self.device = torch.device("cuda", device)
@@ -85,10 +90,10 @@ class EmbeddingBagCollection:
         check = False if self.trusted_inputs else ("deferred" if self.deferred_check else True)
         if self.v_W_l is not None:
             return self._apply_emb_weighted(lS_o, lS_i, check)
-        if hasattr(lS_i, "dim") and hasattr(lS_o, "dim") and lS_i.dim() == 2 and lS_o.dim() == 2 and lS_i.is_cuda:
+        if self._out is None and hasattr(lS_i, "dim") and hasattr(lS_o, "dim") and lS_i.dim() == 2 and lS_o.dim() == 2 and lS_i.is_cuda:
             # DLRM stacks fixed-size batches into [T, N] / [T, B] tensors: one [T, B, m] result, unbound
             return list(self.engine.lookup_stacked(self._ids, lS_i, lS_o, check=check).unbind(0))
-        return self.engine.lookup_batched(self._ids, list(lS_i), list(lS_o), check=check)
+        return self.engine.lookup_batched(self._ids, list(lS_i), list(lS_o), check=check, out_dtype=self._out)
 
     def _apply_emb_weighted(self, lS_o, lS_i, check):
         """--weighted-pooling: per-sample weights v_W_l[k][indices] (gathered by torch on the GPU), then ONE pooled call."""
@@ -98,7 +103,7 @@ class EmbeddingBagCollection:
         if check:      # (a wild index must not reach torch's gather either)
             self.validate(lS_o, lS_i)
         ws = [v.gather(0, i.long()) for v, i in zip(self.v_W_l, lS_i)]
-        return self.engine.lookup_pooled(self._ids, lS_i, lS_o, "sum", per_sample_weights=ws, check=check)
+        return self.engine.lookup_pooled(self._ids, lS_i, lS_o, "sum", per_sample_weights=ws, check=check, out_dtype=self._out)
 
     def validate(self, lS_o, lS_i) -> None:
         """emb_validate_inputs over one batch: IndexError on an index >= table rows or broken offsets, as
@@ -113,7 +118,7 @@ class EmbeddingBagCollection:
         """For callers that reuse the SAME device tensors every step (static-shape serving, hipGraph
         capture): a prepared plan over these buffers.  plan.launch() enqueues the lookup (3-4 us of host
         time), plan.outputs are its fixed output tensors.  The caller keeps the inputs alive."""
-        plan = self.engine.plan(self._ids, list(lS_i), list(lS_o))
+        plan = self.engine.plan(self._ids, list(lS_i), list(lS_o), out_dtype=self._out)
         self._plans[id(plan)] = plan
         return plan
 

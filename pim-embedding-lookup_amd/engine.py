@@ -24,6 +24,10 @@ from . import lib as _l
 _NP_TABLE_DTYPES = {np.dtype(np.float32): _l.EMB_F32, np.dtype(np.float16): _l.EMB_F16,
                     np.dtype(np.int32): _l.EMB_FIXED32}
 POOL_MODES = {"sum": _l.EMB_POOL_SUM, "mean": _l.EMB_POOL_MEAN, "max": _l.EMB_POOL_MAX}
+# out_dtype="table" (EMB_POOL_OUT_TABLE_DTYPE): what a half-width output buffer has to be, by table dtype.  numpy has no
+# bfloat16: bf16 rows come back as uint16 bits (formats.from_bf16_bits reads them).
+_HALF_OUT_NP = {_l.EMB_F16: np.dtype(np.float16), _l.EMB_BF16: np.dtype(np.uint16)}
+_HALF_OUT_TORCH = {_l.EMB_F16: "torch.float16", _l.EMB_BF16: "torch.bfloat16"}
 
 
 _MARSHAL = [False]      # False: not looked for yet; None: not built; else the _pimemb_marshal module
@@ -64,6 +68,38 @@ def _index_type_of(dtype) -> int:
     if name == "int64":
         return _l.EMB_IDX_I64
     raise TypeError(f"indices/offsets must be uint32/int32 or int64, got {dtype}")
+
+
+def _check_half_out(out, table_dtype: int | None = None, table_id=None) -> None:
+    """TypeError unless `out` can hold half-width rows: of the table dtype (EMB_F16 / EMB_BF16) when it is known, else of any
+    2-byte table dtype.  The one place that says what such a buffer is."""
+    name = str(getattr(out, "dtype", type(out).__name__))
+    if table_dtype is None:
+        ok = name.replace("torch.", "") in ("float16", "bfloat16", "uint16")
+        want = "a 2-byte table dtype"
+    else:
+        want = _HALF_OUT_TORCH[table_dtype] if _is_torch(out) else str(_HALF_OUT_NP[table_dtype])
+        ok = name == want
+    if not ok:
+        where = "" if table_id is None else f"table {table_id}: "
+        raise TypeError(f'{where}out_dtype="table" needs an output of {want}, got {name}')
+
+
+def _half_out_list(out_dtype, n: int, outs=None) -> list | None:
+    """out_dtype of a call -> None (fp32 rows everywhere) or one bool per table.  None | "table" | one of those per table.
+    Caller-supplied `outs` that cannot be half-width rows of any table are refused here, before anything else is touched
+    (_descs checks them against their table's dtype)."""
+    if out_dtype is None:
+        return None
+    per = [out_dtype] * n if isinstance(out_dtype, str) else list(out_dtype)
+    if len(per) != n or any(v not in (None, "table") for v in per):
+        raise ValueError('out_dtype must be None or "table" (or one of those per table)')
+    half = [v == "table" for v in per]
+    if outs is not None:
+        for h, o in zip(half, outs):
+            if h:
+                _check_half_out(o)
+    return half if any(half) else None
 
 
 class DeviceBuffer:
@@ -159,7 +195,7 @@ class Plan:
 
     def describe(self) -> list[dict]:
         """One dict per kernel launch of the plan: kind, dtype, itype, lanes_per_row, chunks, scalar_lanes, anydim_vec, ranged,
-        descs, grid, bags_per_tile (emb_plan_describe)."""
+        descs, grid, bags_per_tile; pool, weighted, padding for a pooled launch; out=1 for a half-output one (emb_plan_describe)."""
         buf = C.create_string_buffer(4096)
         _l.check(self.engine._L.emb_plan_describe(self._p, buf, len(buf)))
         return [{k: int(v) for k, v in (kv.split("=") for kv in rec.split())} for rec in buf.value.decode().split(";") if rec]
@@ -383,17 +419,21 @@ class EmbeddingEngine:
         return ptr.value, n.value, d.value, dt.value
 
     # ---- lookups (lookup's job, emb_host.h:234) ------------------------------------------------
-    def _alloc_out(self, like, n_bags: int, dim: int):
+    def _alloc_out(self, like, n_bags: int, dim: int, half_of: int | None = None):
+        """half_of: the table dtype (EMB_F16 / EMB_BF16) whose 2-byte rows the buffer holds, or None for fp32 rows."""
+        np_dt = np.dtype(np.float32) if half_of is None else _HALF_OUT_NP[half_of]
         if isinstance(like, DeviceBuffer):
-            return DeviceBuffer(self, n_bags * dim * 4, np.float32, (n_bags, dim))
+            return DeviceBuffer(self, n_bags * dim * np_dt.itemsize, np_dt, (n_bags, dim))
         if _is_torch(like):
             import torch
-            return torch.empty((n_bags, dim), dtype=torch.float32, device=like.device)
-        return np.empty((n_bags, dim), dtype=np.float32)
+            dt = torch.float32 if half_of is None else (torch.float16 if half_of == _l.EMB_F16 else torch.bfloat16)
+            return torch.empty((n_bags, dim), dtype=dt, device=like.device)
+        return np.empty((n_bags, dim), dtype=np_dt)
 
-    def _descs(self, table_ids, indices, offsets, outs, fixed_pooling, want_outputs=True):
+    def _descs(self, table_ids, indices, offsets, outs, fixed_pooling, want_outputs=True, half=None):
         """ctypes descriptor array for a batched call.  want_outputs=False (validation) leaves
-        `pooled` NULL and allocates nothing."""
+        `pooled` NULL and allocates nothing.  half: None, or one bool per table -- that table's rows leave in its own 2-byte
+        dtype (out_dtype="table"): outputs are allocated so, and caller-supplied ones of another dtype are a TypeError."""
         n = len(table_ids)
         if not (len(indices) == n and len(offsets) == n):
             raise ValueError("table_ids, indices and offsets must have equal length")
@@ -421,9 +461,12 @@ class EmbeddingEngine:
                 raise TypeError("all tables of one batched lookup must share index width and placement")
             out_ptr = None
             if want_outputs:
-                dim = self._tables[t][1]
-                out = outs[i] if outs is not None else self._alloc_out(indices[i], n_bags, dim)
+                dim, tdt = self._tables[t][1], self._tables[t][2]
+                half_of = tdt if half is not None and half[i] and tdt in _HALF_OUT_NP else None   # (another table dtype: the C call refuses)
+                out = outs[i] if outs is not None else self._alloc_out(indices[i], n_bags, dim, half_of)
                 ua = _Arg(out)
+                if half_of is not None and outs is not None:
+                    _check_half_out(out, half_of, t)
                 if ua.space != space:
                     raise TypeError("output placement must match the inputs")
                 out_ptr = ua.ptr
@@ -730,12 +773,19 @@ class EmbeddingEngine:
                                             itype, _l.EMB_MEM_DEVICE, stream))
 
     def lookup_batched(self, table_ids: Sequence[int], indices: Sequence, offsets: Sequence,
-                       outs: Sequence | None = None, fixed_pooling=0, stream: int | None = None, check: bool | str = False):
+                       outs: Sequence | None = None, fixed_pooling=0, stream: int | None = None, check: bool | str = False,
+                       out_dtype=None):
         """All tables in one fused launch; returns the list of pooled [B_t, D] outputs
         (the `apply_emb` contract: one [B, D] per table).  check=True: indices / offsets are validated on the GPU
         first (emb_lookup_batched_checked) and IndexError is raised, like nn.EmbeddingBag, before anything is launched.
         check="deferred": validated all the same and a finding still keeps the lookup from running, but the call does not wait
-        for the verdict (see _checked_call / check_report)."""
+        for the verdict (see _checked_call / check_report).
+        out_dtype="table" (or one of None / "table" per table): fp16 / bf16 tables return rows of their own dtype, the fp32
+        sum rounded once (EMB_POOL_OUT_TABLE_DTYPE): torch.float16 / torch.bfloat16 tensors, np.float16 arrays, np.uint16
+        bits for bf16 on the numpy path.  Outputs passed in must have that dtype (TypeError otherwise)."""
+        if _half_out_list(out_dtype, len(table_ids), outs) is not None:
+            return self.lookup_pooled(table_ids, indices, offsets, "sum", outs=outs, fixed_pooling=fixed_pooling, stream=stream,
+                                      check=check, out_dtype=out_dtype)
         if not fixed_pooling and len(table_ids) and _is_torch(indices[0]):
             res = self._lookup_batched_cuda(table_ids, indices, offsets, outs, stream, check)
             if res is not None:
@@ -750,12 +800,18 @@ class EmbeddingEngine:
         return results
 
     def lookup(self, table_id: int, indices, offsets, out=None, fixed_pooling: int = 0,
-               stream: int | None = None, check: bool = False):
+               stream: int | None = None, check: bool = False, out_dtype=None):
         """lookup(table_id, offsets, indices) -> pooled_rows for one table."""
         return self.lookup_batched([table_id], [indices], [offsets], None if out is None else [out],
-                                   fixed_pooling, stream, check)[0]
+                                   fixed_pooling, stream, check, out_dtype)[0]
 
-    def plan(self, table_ids, indices, offsets, outs=None, fixed_pooling=0) -> Plan:
+    def plan(self, table_ids, indices, offsets, outs=None, fixed_pooling=0, modes=None, per_sample_weights=None,
+             padding_idx=None, out_dtype=None) -> Plan:
+        """A prepared launch of lookup_batched's call; with modes / per_sample_weights / padding_idx / out_dtype, of
+        lookup_pooled's (plan_pooled)."""
+        if modes is not None or per_sample_weights is not None or padding_idx is not None or out_dtype is not None:
+            return self.plan_pooled(table_ids, indices, offsets, "sum" if modes is None else modes, per_sample_weights, padding_idx,
+                                    outs, fixed_pooling, out_dtype)
         arr, n, itype, space, results, keep = self._descs(table_ids, indices, offsets, outs, fixed_pooling)
         if space != _l.EMB_MEM_DEVICE:
             raise TypeError("plans need device-resident buffers (torch CUDA tensors or DeviceBuffer)")
@@ -764,10 +820,11 @@ class EmbeddingEngine:
         return Plan(self, p.value, results, keep)
 
     # ---- pooled lookups: nn.EmbeddingBag's mean / max, per_sample_weights, padding_idx (emb_lookup_pooled) ----------
-    def _pools(self, n, descs, modes, per_sample_weights, padding_idx, space):
+    def _pools(self, n, descs, modes, per_sample_weights, padding_idx, space, half=None):
         """emb_pool_spec array for a call: `modes` one mode or one per table ("sum" / "mean" / "max" or EMB_POOL_*);
         `per_sample_weights` None or one float32 array / tensor (or None) per table, placed like the indices;
-        `padding_idx` None, one row id, or one per table (None: no padding).  Returns (array, buffers to keep alive)."""
+        `padding_idx` None, one row id, or one per table (None: no padding); `half` None or one bool per table
+        (EMB_POOL_OUT_TABLE_DTYPE).  Returns (array, buffers to keep alive)."""
         def per_table(v, what):
             if v is None or isinstance(v, (str, int, np.integer)):
                 return [v] * n
@@ -798,19 +855,23 @@ class EmbeddingEngine:
                 wptr = wa.ptr
                 keep.append(wa.keep)
             flags, pad = (0, 0) if pads[i] is None else (_l.EMB_POOL_PADDING, int(pads[i]))
+            if half is not None and half[i]:
+                flags |= _l.EMB_POOL_OUT_TABLE_DTYPE
             arr[i] = _l.EmbPoolSpec(mode, flags, wptr, pad)
         return arr, keep
 
     def lookup_pooled(self, table_ids: Sequence[int], indices: Sequence, offsets: Sequence, modes, per_sample_weights=None,
                       padding_idx=None, outs: Sequence | None = None, fixed_pooling=0, stream: int | None = None,
-                      check: bool | str = False):
+                      check: bool | str = False, out_dtype=None):
         """lookup_batched with a pooling spec per table: mode "sum" / "mean" / "max", per-sample weights (sum only) and a
         padding row id (see _pools) -- nn.EmbeddingBag's arithmetic, bit for bit against torch on the CPU.  All tables in one
         call (launches grouped by dtype, dim and mode).  check as lookup_batched.  Per-call plans are cached like
-        lookup_batched's; the key holds the descriptors and the pooling specs (mode, padding, weights address), so a sum call
-        never replays a pooled plan or the other way round."""
-        arr, n, itype, space, results, keep = self._descs(table_ids, indices, offsets, outs, fixed_pooling)
-        pools, pkeep = self._pools(n, arr, modes, per_sample_weights, padding_idx, space)
+        lookup_batched's; the key holds the descriptors and the pooling specs (mode, flags, padding, weights address), so a sum
+        call never replays a pooled plan, nor an fp32-out call a half-out one, or the other way round.  out_dtype as
+        lookup_batched's."""
+        half = _half_out_list(out_dtype, len(table_ids), outs)
+        arr, n, itype, space, results, keep = self._descs(table_ids, indices, offsets, outs, fixed_pooling, half=half)
+        pools, pkeep = self._pools(n, arr, modes, per_sample_weights, padding_idx, space, half)
         if stream is None and space == _l.EMB_MEM_DEVICE:
             stream = _current_stream_for(*indices)
         c = 0 if not check else (2 if check == "deferred" else 1)
@@ -832,12 +893,13 @@ class EmbeddingEngine:
         return results
 
     def plan_pooled(self, table_ids, indices, offsets, modes, per_sample_weights=None, padding_idx=None, outs=None,
-                    fixed_pooling=0) -> Plan:
+                    fixed_pooling=0, out_dtype=None) -> Plan:
         """plan() for lookup_pooled's calls (device buffers, weights included; graph-capturable like any plan)."""
-        arr, n, itype, space, results, keep = self._descs(table_ids, indices, offsets, outs, fixed_pooling)
+        half = _half_out_list(out_dtype, len(table_ids), outs)
+        arr, n, itype, space, results, keep = self._descs(table_ids, indices, offsets, outs, fixed_pooling, half=half)
         if space != _l.EMB_MEM_DEVICE:
             raise TypeError("plans need device-resident buffers (torch CUDA tensors or DeviceBuffer)")
-        pools, pkeep = self._pools(n, arr, modes, per_sample_weights, padding_idx, space)
+        pools, pkeep = self._pools(n, arr, modes, per_sample_weights, padding_idx, space, half)
         p = C.c_void_p()
         _l.check(self._L.emb_plan_create_pooled(self._h, arr, pools, n, itype, C.byref(p)))
         return Plan(self, p.value, results, keep + pkeep)

@@ -49,6 +49,7 @@ EMB_SHARD_SELF_VIA_COMM, EMB_SHARD_CHECK_SERVED, EMB_SHARD_PEER_STORES, EMB_SHAR
 EMB_RANGE_OPEN_END = 1 << 63
 EMB_POOL_SUM, EMB_POOL_MEAN, EMB_POOL_MAX = 0, 1, 2
 EMB_POOL_PADDING = 1
+EMB_POOL_OUT_TABLE_DTYPE = 2      # emb_pool_spec.flags: pooled rows in the table's own 2-byte dtype (fp16 / bf16 tables)
 
 
 class EmbPoolSpec(C.Structure):

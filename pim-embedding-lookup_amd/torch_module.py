@@ -16,6 +16,10 @@ Which class does what:
                                                       equal to torch's CPU result bit for bit (emb_lookup_pooled).
 Inference only (the engine has no backward); max_norm is not supported by any of them.
 
+Output dtype.  By default every module returns fp32 rows, whatever the table holds.  `out_dtype="weight"` makes a module
+with an fp16 / bf16 weight return the weight's dtype, as nn.EmbeddingBag does: the fp32 pooled value rounded once (the
+engine's out_dtype="table", EMB_POOL_OUT_TABLE_DTYPE).  The fused modules follow their bags unless told otherwise.
+
 Input checking.  The C ABI is as unchecked as the reference (an out-of-range index is a wild read there,
 emb_dpu_lookup.c:113); these modules are what user tensors reach first, so by default every forward goes through
 emb_lookup_batched_checked: indices / offsets are validated on the GPU first and IndexError is raised, like
@@ -63,6 +67,13 @@ def _new_table_id(device: int) -> int:
         return t
 
 
+def _engine_out_dtype(out_dtype, table_dtype):
+    """A module's out_dtype (None: fp32 rows; "weight": the weight's dtype) -> the engine's (None | "table")."""
+    if out_dtype not in (None, "weight"):
+        raise ValueError(f'out_dtype has to be None or "weight", got {out_dtype!r}')
+    return "table" if out_dtype == "weight" and table_dtype in (torch.float16, torch.bfloat16) else None
+
+
 def _bags_from(input, offsets, include_last_offset: bool):
     """torch's calling conventions -> (1-D indices, 1-D bag starts)."""
     if input.dim() == 2:
@@ -80,15 +91,19 @@ def _bags_from(input, offsets, include_last_offset: bool):
 
 
 class EmbeddingBag(torch.nn.Module):
-    """One table.  forward(input, offsets) -> [B, embedding_dim] fp32, like nn.EmbeddingBag(mode="sum")."""
+    """One table.  forward(input, offsets) -> [B, embedding_dim] fp32, like nn.EmbeddingBag(mode="sum"); with
+    out_dtype="weight" in the weight's dtype."""
 
     def __init__(self, num_embeddings: int, embedding_dim: int, mode: str = "sum", sparse: bool = False,
                  _weight=None, include_last_offset: bool = False, device: int = 0, engine: EmbeddingEngine | None = None,
-                 table_id: int | None = None, dtype=torch.float32, trusted_inputs: bool = False, deferred_check: bool = False):
+                 table_id: int | None = None, dtype=torch.float32, trusted_inputs: bool = False, deferred_check: bool = False,
+                 out_dtype: str | None = None):
         super().__init__()
         self.trusted_inputs = bool(trusted_inputs)
         self.deferred_check = bool(deferred_check)
         self._table_dtype = dtype
+        self.out_dtype = out_dtype
+        self._engine_out = _engine_out_dtype(out_dtype, dtype)
         if mode != "sum":
             raise NotImplementedError("only mode='sum' (the reference pools by summation, emb_dpu_lookup.c:114)")
         self.num_embeddings, self.embedding_dim = int(num_embeddings), int(embedding_dim)
@@ -128,7 +143,7 @@ class EmbeddingBag(torch.nn.Module):
         idx, off = _bags_from(input, offsets, self.include_last_offset)
         idx, off = idx.contiguous(), off.contiguous()
         check = False if self.trusted_inputs else ("deferred" if self.deferred_check else True)
-        return self.engine.lookup_batched(self._id_list, [idx], [off], check=check)[0]
+        return self.engine.lookup_batched(self._id_list, [idx], [off], check=check, out_dtype=self._engine_out)[0]
 
     # ---- checkpoints: the same key and shape as nn.EmbeddingBag ("<prefix>weight", [num_embeddings, dim]) ----
     def _save_to_state_dict(self, destination, prefix, keep_vars):
@@ -156,12 +171,13 @@ class EmbeddingBag(torch.nn.Module):
 class FusedEmbeddingBags(torch.nn.Module):
     """All tables of a model: forward(lS_o, lS_i) -> list of [B, m] with ONE fused launch (apply_emb)."""
 
-    def __init__(self, bags, trusted_inputs: bool | None = None, deferred_check: bool | None = None):
+    def __init__(self, bags, trusted_inputs: bool | None = None, deferred_check: bool | None = None, out_dtype: str | None = None):
         super().__init__()
         self.bags = torch.nn.ModuleList(bags)
         # unchecked only if every table says so (or the caller does); the same for the deferred verdict
         self.trusted_inputs = all(b.trusted_inputs for b in bags) if trusted_inputs is None else bool(trusted_inputs)
         self.deferred_check = all(b.deferred_check for b in bags) if deferred_check is None else bool(deferred_check)
+        self._outs = _fused_out_dtypes(bags, out_dtype)
         engines = {id(b.engine) for b in self.bags}
         if len(engines) != 1:
             raise ValueError("all tables of a FusedEmbeddingBags must live in one engine")
@@ -174,21 +190,28 @@ class FusedEmbeddingBags(torch.nn.Module):
 
     def forward(self, lS_o, lS_i):
         check = False if self.trusted_inputs else ("deferred" if self.deferred_check else True)
-        if hasattr(lS_i, "dim") and lS_i.dim() == 2 and hasattr(lS_o, "dim") and lS_o.dim() == 2 and lS_i.is_cuda:
-            return list(self.engine.lookup_stacked(self._ids, lS_i, lS_o, check=check).unbind(0))
+        if self._outs is None and hasattr(lS_i, "dim") and lS_i.dim() == 2 and hasattr(lS_o, "dim") and lS_o.dim() == 2 and lS_i.is_cuda:
+            return list(self.engine.lookup_stacked(self._ids, lS_i, lS_o, check=check).unbind(0))      # (one fp32 [T, B, dim] tensor)
         idx, off = [], []
         for b, i, o in zip(self.bags, lS_i, lS_o):
             i1, o1 = _bags_from(i, o, b.include_last_offset)
             idx.append(i1.contiguous())
             off.append(o1.contiguous())
-        return self.engine.lookup_batched(self._ids, idx, off, check=check)
+        return self.engine.lookup_batched(self._ids, idx, off, check=check, out_dtype=self._outs)
 
     apply_emb = forward
 
 
+def _fused_out_dtypes(bags, out_dtype):
+    """The engine's out_dtype list of a fused module: each bag's own, or out_dtype="weight" for every bag; None when all
+    rows leave as fp32."""
+    outs = [b._engine_out if out_dtype is None else _engine_out_dtype(out_dtype, b._table_dtype) for b in bags]
+    return outs if any(o is not None for o in outs) else None
+
+
 class PoolingEmbeddingBag(torch.nn.Module):
     """One table with nn.EmbeddingBag's pooling options: forward(input, offsets=None, per_sample_weights=None) ->
-    [B, embedding_dim] fp32 for mode "sum" / "mean" / "max", per_sample_weights (mode "sum" only, else NotImplementedError
+    [B, embedding_dim] fp32 (out_dtype="weight": the weight's dtype) for mode "sum" / "mean" / "max", per_sample_weights (mode "sum" only, else NotImplementedError
     as torch raises), padding_idx (negative values count from the end, as torch normalises them), include_last_offset, 1-D
     input with offsets or 2-D input.  Same state_dict keys as EmbeddingBag; checking on by default (trusted_inputs,
     deferred_check as there)."""
@@ -196,8 +219,10 @@ class PoolingEmbeddingBag(torch.nn.Module):
     def __init__(self, num_embeddings: int, embedding_dim: int, mode: str = "mean", sparse: bool = False, _weight=None,
                  include_last_offset: bool = False, padding_idx: int | None = None, device: int = 0,
                  engine: EmbeddingEngine | None = None, table_id: int | None = None, dtype=torch.float32,
-                 trusted_inputs: bool = False, deferred_check: bool = False):
+                 trusted_inputs: bool = False, deferred_check: bool = False, out_dtype: str | None = None):
         super().__init__()
+        self.out_dtype, self._table_dtype = out_dtype, dtype
+        self._engine_out = _engine_out_dtype(out_dtype, dtype)
         if mode not in ("sum", "mean", "max"):
             raise ValueError(f"mode has to be one of sum, mean or max, got {mode!r}")
         self.num_embeddings, self.embedding_dim = int(num_embeddings), int(embedding_dim)
@@ -242,7 +267,7 @@ class PoolingEmbeddingBag(torch.nn.Module):
         w = _weights_for(per_sample_weights, self.mode, input)
         return self.engine.lookup_pooled(self._id_list, [idx.contiguous()], [off.contiguous()], self.mode,
                                          per_sample_weights=None if w is None else [w], padding_idx=self.padding_idx,
-                                         check=self._check())[0]
+                                         check=self._check(), out_dtype=self._engine_out)[0]
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         self._table._save_to_state_dict(destination, prefix, keep_vars)
@@ -271,11 +296,12 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
     """All tables of a model, each with its own mode and padding_idx: forward(lS_o, lS_i, lS_w=None) -> list of [B, m] with
     ONE engine call (lS_w: per-table per-sample weights or None, sum tables only)."""
 
-    def __init__(self, bags, trusted_inputs: bool | None = None, deferred_check: bool | None = None):
+    def __init__(self, bags, trusted_inputs: bool | None = None, deferred_check: bool | None = None, out_dtype: str | None = None):
         super().__init__()
         self.bags = torch.nn.ModuleList(bags)
         self.trusted_inputs = all(b.trusted_inputs for b in bags) if trusted_inputs is None else bool(trusted_inputs)
         self.deferred_check = all(b.deferred_check for b in bags) if deferred_check is None else bool(deferred_check)
+        self._outs = _fused_out_dtypes(bags, out_dtype)
         if len({id(b.engine) for b in self.bags}) != 1:
             raise ValueError("all tables of a FusedPoolingEmbeddingBags must live in one engine")
         self.engine = self.bags[0].engine
@@ -296,7 +322,8 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             off.append(o1.contiguous())
             ws.append(_weights_for(None if lS_w is None else lS_w[k], b.mode, i))
         return self.engine.lookup_pooled(self._ids, idx, off, self._modes,
-                                         per_sample_weights=None if lS_w is None else ws, padding_idx=self._pads, check=check)
+                                         per_sample_weights=None if lS_w is None else ws, padding_idx=self._pads, check=check,
+                                         out_dtype=self._outs)
 
     apply_emb = forward
 
