@@ -53,6 +53,20 @@ typedef enum emb_dtype {
     EMB_BF16 = 3     /* bfloat16 rows (2 bytes: the upper 16 bits of an fp32), fp32 accumulate: every row is widened
                         exactly, so results equal the fp32 lookup over the widened table bit for bit */
 } emb_dtype;
+/* FP8 tables (OCP 8-bit floating point, 1 byte per element).  Defined OUTSIDE the enum on purpose: the enum's body is pinned at
+ * its four members (a test reads it from this header), and values 4-7 stay EMB_ERR_INVALID.  C++ callers: the values lie
+ * outside the enum's own range, so they are no constant expressions there (no case label, no template argument), and an
+ * emb_dtype OBJECT that holds one has no defined read (-fsanitize=enum reports it): pass the macros as arguments, keep the
+ * value in an int (emb_table_info's *dtype: copy its bytes).  The library itself does so.
+ * Every fp8 bit pattern widens EXACTLY to fp32, so -- as for EMB_BF16 -- results equal the fp32 lookup over the widened table
+ * bit for bit: fp32 accumulate in index order from +0, fp32 out.  EMB_POOL_OUT_TABLE_DTYPE on an fp8 table is
+ * EMB_ERR_UNSUPPORTED: the pooled row stays fp32, an fp8 output would round it lossily.  emb_load_table_column stays
+ * fixed-point only.  NaN patterns are out of scope, as everywhere in this header.
+ * Speed, measured on MI355X (profiles/fp8/README.md): pooled launches gain (dim 128, 32 indices per bag: 0.72 of the bf16 time) and
+ * a table takes half the HBM of a 2-byte one; ONE-HOT launches, which are paced by their fp32 stores, are currently SLOWER than
+ * with EMB_BF16 tables (1.4x - 1.8x at dims 16 - 64, 1.0x - 1.15x at dims 128 - 256).  Choose fp8 for pooled lookups and for capacity. */
+#define EMB_F8_E4M3 ((emb_dtype)8) /* OCP e4m3fn: 4 exponent bits (bias 7), 3 mantissa bits, no infinities, 0x7f / 0xff are NaN */
+#define EMB_F8_E5M2 ((emb_dtype)9) /* OCP e5m2: 5 exponent bits (bias 15), 2 mantissa bits: the upper byte of an fp16 */
 
 /* width of indices AND offsets: uint32 at the reference ABI (emb_host.h:234), int64 at torch's */
 typedef enum emb_index_type { EMB_IDX_U32 = 0, EMB_IDX_I64 = 1 } emb_index_type;
@@ -312,7 +326,8 @@ int emb_plan_time(emb_plan *p, void *stream, uint32_t warmup, uint32_t iters, fl
 #define EMB_POOL_MAX 2u
 #define EMB_POOL_PADDING 1u            /* emb_pool_spec.flags: padding_idx is live */
 #define EMB_POOL_OUT_TABLE_DTYPE 2u    /* emb_pool_spec.flags: descs[i].pooled points to rows of the TABLE's dtype
-                                          (EMB_F16 / EMB_BF16 tables only), n_bags * dim 2-byte elements */
+                                          (EMB_F16 / EMB_BF16 tables only -- EMB_ERR_UNSUPPORTED on any other, the fp8
+                                          ones included --), n_bags * dim 2-byte elements */
 typedef struct emb_pool_spec {
     uint32_t mode;                     /* EMB_POOL_* */
     uint32_t flags;

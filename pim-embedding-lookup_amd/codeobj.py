@@ -120,14 +120,14 @@ def symbol_fragments(launch: dict) -> list[str]:
     pick it out of kernel_hashes().  The template heads are pimemb_kernels.hip's: bag_sum_<family>_kernel<IdxT, DT, LPR, Cfg
     [, RANGED]>, the any-dim kernels <IdxT, DT, CLAMP>; a pooled launch (a record with `pool`, emb_plan_create_pooled) runs
     bag_pool_<family>_kernel<IdxT, DT, LPR, Cfg> or bag_pool_anydim_kernel<IdxT, DT, VEC, CLAMP> -- for bf16 tables (dtype 3) the
-    same under the name bag_bf16pool_*.  A half-output launch (a record with out=1, EMB_POOL_OUT_TABLE_DTYPE) runs the twin of
+    same under the name bag_bf16pool_*, for fp8 tables (dtype 8 / 9) under bag_f8pool_*.  A half-output launch (a record with out=1, EMB_POOL_OUT_TABLE_DTYPE) runs the twin of
     that kernel: a pooled one under the name bag_hpool_* (fp16 and bf16 tables alike), a sum one the same bag_sum_* template
     with the internal dtype value DT | 16 (pimemb_bag_kernels.h: kHalfOutDT)."""
     idx = "j" if launch["itype"] == 0 else "l"
     kind, dt, lpr = launch["kind"], launch["dtype"], launch["lanes_per_row"]
     half = bool(launch.get("out"))
     if "pool" in launch:
-        pool = "bag_hpool" if half else "bag_bf16pool" if dt == 3 else "bag_pool"
+        pool = "bag_hpool" if half else "bag_bf16pool" if dt == 3 else "bag_f8pool" if dt in (8, 9) else "bag_pool"
         if kind == 3:
             return ["%s_anydim_kernelI%sLi%dELb%dE" % (pool, idx, dt, 1 if launch.get("anydim_vec") else 0)]
         family = "group" if kind == 1 else "wavebatch"

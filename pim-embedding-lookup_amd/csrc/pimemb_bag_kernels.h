@@ -82,6 +82,20 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using f32x8 = __attribute__((ext_vector_type(8))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+// The fp8 table dtypes as template arguments and case labels: pimemb.h spells EMB_F8_E4M3 / EMB_F8_E5M2 as casts to emb_dtype
+// outside the enum's range, which C++ does not take as constant expressions -- the same values as plain ints.
+constexpr int kF8E4M3 = 8, kF8E5M2 = 9;
+template <int DT>
+inline constexpr bool kIsF8 = DT == kF8E4M3 || DT == kF8E5M2;
+
+// Bytes of one table element of dtype `dt` (a public emb_dtype value): THE place that knows it -- geometry_for, the engine's
+// and the shard's byte counts and the any-dim kernels all ask here.
+__host__ __device__ constexpr uint32_t elem_bytes(int dt) {
+    return (dt == kF8E4M3 || dt == kF8E5M2) ? 1u : (dt == EMB_F16 || dt == EMB_BF16) ? 2u : 4u;
+}
 
 // Compile-time knobs of the bag kernels.
 template <int BLOCK = 256, int UNROLL = 8, bool NT_STORE = false, bool NT_META = false,
@@ -187,6 +201,62 @@ struct RowOps<EMB_BF16> {
         store_f32x4<NT>(dst + 4, f32x4{a[4], a[5], a[6], a[7]});
     }
 };
+
+// FP8 rows (OCP e4m3fn / e5m2): a lane's 16-byte piece is 16 elements, widened by the packed hardware conversions
+// v_cvt_pk_f32_fp8 / v_cvt_pk_f32_bf8 -- two elements per instruction, low and high word of each dword (SDWA word select), eight
+// instructions per piece, exact for every non-NaN bit pattern (subnormals, signed zeros, e5m2 infinities).  e5m2 could also be
+// widened as the upper byte of an fp16 (zero-extend, shift, v_cvt_f32_f16): four v_perm_b32 and sixteen conversions per piece
+// against eight, so the hardware conversion it is.  The accumulator takes the elements in row order (store_row relies on it).
+template <int DT> struct F8Widen;
+template <> struct F8Widen<kF8E4M3> {
+    static __device__ __forceinline__ f32x2 two(uint32_t w, bool hi) { return hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false); }
+    static __device__ __forceinline__ float one(uint8_t b) { return __builtin_amdgcn_cvt_f32_fp8((int)b, 0); }
+};
+template <> struct F8Widen<kF8E5M2> {
+    static __device__ __forceinline__ f32x2 two(uint32_t w, bool hi) { return hi ? __builtin_amdgcn_cvt_pk_f32_bf8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_bf8((int)w, false); }
+    static __device__ __forceinline__ float one(uint8_t b) { return __builtin_amdgcn_cvt_f32_bf8((int)b, 0); }
+};
+template <int DT>
+__device__ __forceinline__ f32x16 widen_f8x16(u32x4 raw) {
+    using W = F8Widen<DT>;
+    const f32x4 q0 = __builtin_shufflevector(W::two(raw[0], false), W::two(raw[0], true), 0, 1, 2, 3);
+    const f32x4 q1 = __builtin_shufflevector(W::two(raw[1], false), W::two(raw[1], true), 0, 1, 2, 3);
+    const f32x4 q2 = __builtin_shufflevector(W::two(raw[2], false), W::two(raw[2], true), 0, 1, 2, 3);
+    const f32x4 q3 = __builtin_shufflevector(W::two(raw[3], false), W::two(raw[3], true), 0, 1, 2, 3);
+    const f32x8 h0 = __builtin_shufflevector(q0, q1, 0, 1, 2, 3, 4, 5, 6, 7), h1 = __builtin_shufflevector(q2, q3, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+}
+
+// Wide fp8 rows (>= 8 lanes): a lane owns 64 B of output, four 16-byte pieces at a 64-byte lane stride.  1: store_row re-deals
+// the pieces inside the lane group (16 ds_bpermute per store instruction) so that every instruction writes a contiguous run,
+// non-temporally, as for fp16 rows; 0: four plain stores per lane, merged by the L2.  Measured on MI355X (profiles/fp8/README.md),
+// us per launch, plain -> re-dealt: one-hot dim 128 177.6 -> 108.5, dim 256 330.7 -> 213.2, pooled dim 128 14.6 -> 12.6.
+#ifndef PIMEMB_F8_WIDE_REDEAL
+#define PIMEMB_F8_WIDE_REDEAL 1
+#endif
+// Narrow fp8 rows (<= 4 lanes) store plainly, four 16-byte pieces per lane.  1: those stores are non-temporal (an A/B of the
+// one-hot launches' store pattern, profiles/fp8/README.md); 0, the default: ordinary stores that the L2 merges, as fp16's narrow rows.
+#ifndef PIMEMB_F8_NARROW_NT
+#define PIMEMB_F8_NARROW_NT 0
+#endif
+
+template <int DT>
+struct F8RowOps {
+    using Acc = f32x16;
+    static constexpr uint32_t kFloatsPerLane = 16;
+    static constexpr bool kGroupStore = true;       // 64 B of output per lane: store_row decides how they leave
+    static constexpr bool kGroupRedeal = PIMEMB_F8_WIDE_REDEAL != 0;
+    static constexpr bool kNarrowNt = PIMEMB_F8_NARROW_NT != 0;
+    static __device__ __forceinline__ Acc zero() { return Acc{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; }
+    static __device__ __forceinline__ void add(Acc &a, u32x4 raw) { a += widen_f8x16<DT>(raw); }
+    template <bool NT>
+    static __device__ __forceinline__ void store(const Acc &a, float *dst) {
+#pragma unroll
+        for (int c = 0; c < 16; c += 4) store_f32x4<NT>(dst + c, f32x4{a[c], a[c + 1], a[c + 2], a[c + 3]});
+    }
+};
+template <> struct RowOps<kF8E4M3> : F8RowOps<kF8E4M3> {};
+template <> struct RowOps<kF8E5M2> : F8RowOps<kF8E5M2> {};
 
 template <>
 struct RowOps<EMB_FIXED32> {
@@ -295,20 +365,30 @@ __device__ __forceinline__ float shfl_f32(float v, uint32_t src) {
 
 // Store one pooled row held by a lane group.  `row` = out + bag * out_stride (the row's first float);
 // `valid`: this lane owns a piece of a real bag.  Ops without kGroupStore: every lane stores its own
-// 16 bytes (already contiguous across the group).  kGroupStore (fp16 tables: 32 B of output per lane):
-// the row is 2*chunks 16-byte pieces, lane s holds pieces 2s and 2s+1; instruction 1 lets lane j write
-// piece j, instruction 2 piece LPR + j, both fetched from the owning lane with ds_bpermute -- EVERY lane
+// 16 bytes (already contiguous across the group).  kGroupStore (2-byte tables: 32 B of output per lane, PPL = 2 pieces;
+// fp8 tables: 64 B, PPL = 4): the row is PPL*chunks 16-byte pieces, lane s holds pieces PPL*s .. PPL*s + PPL-1; instruction i
+// lets lane j write piece i*LPR + j, fetched from the owning lane with ds_bpermute -- EVERY lane
 // of the group must call this (the shuffles read the neighbours' registers).
+template <class Ops, class = void>
+struct GroupRedeal { static constexpr bool value = true; };      // (Ops that say nothing re-deal: the 2-byte tables)
+template <class Ops>
+struct GroupRedeal<Ops, std::void_t<decltype(Ops::kGroupRedeal)>> { static constexpr bool value = Ops::kGroupRedeal; };
+
+template <class Ops, class = void>
+struct NarrowNt { static constexpr bool value = false; };
+template <class Ops>
+struct NarrowNt<Ops, std::void_t<decltype(Ops::kNarrowNt)>> { static constexpr bool value = Ops::kNarrowNt; };
+
 template <class Ops, class Cfg, int LPR>
 __device__ __forceinline__ void store_row(const typename Ops::Acc &acc, float *__restrict__ row, uint32_t sub,
                                           uint32_t grp, uint32_t chunks, bool valid) {
     if constexpr (!Ops::kGroupStore) {
         if (valid) Ops::template store<Cfg::kNtStore>(acc, row + sub * Ops::kFloatsPerLane);
-    } else if constexpr (LPR <= 4) {
+    } else if constexpr (LPR <= 4 || !GroupRedeal<Ops>::value) {
         // narrow rows: the shuffles cost more than they save (fp16 dim 16 one-hot: 42 us with them, 21 us
-        // without); two plain 16-byte stores per lane instead, which the L2 merges into full lines
-        if (valid) Ops::template store<false>(acc, row + sub * Ops::kFloatsPerLane);
-    } else {
+        // without); plain 16-byte stores per lane instead, which the L2 merges into full lines
+        if (valid) Ops::template store<NarrowNt<Ops>::value && Cfg::kNtStore>(acc, row + sub * Ops::kFloatsPerLane);
+    } else if constexpr (Ops::kFloatsPerLane == 8) {
         const uint32_t pieces = 2u * chunks;
 #pragma unroll
         for (uint32_t inst = 0; inst < 2; inst++) {
@@ -320,6 +400,34 @@ __device__ __forceinline__ void store_row(const typename Ops::Acc &acc, float *_
             for (int c = 0; c < 4; c++) {
                 const float lo_c = shfl_f32(acc[c], src), hi_c = shfl_f32(acc[4 + c], src);
                 v[c] = hi ? hi_c : lo_c;
+            }
+            // (validity is uniform over a lane group except for lanes beyond `chunks`, whose own
+            // `valid` is false but which still write pieces of the row when p < pieces)
+            const bool bag_ok = __shfl((int)valid, (int)(grp * LPR), 64) != 0;
+            if (bag_ok && p < pieces) store_f32x4<Cfg::kNtStore>(row + 4u * p, v);
+        }
+    } else {
+        // any number of pieces per lane (a power of two; the 2-piece case above keeps its own text, and with it the machine code
+        // of the fp16 / bf16 kernels): LPR is a multiple of PPL here, so a lane wants the SAME piece number p % PPL of its
+        // source lane in every instruction
+        constexpr uint32_t PPL = Ops::kFloatsPerLane / 4u;
+        static_assert((PPL & (PPL - 1u)) == 0u && LPR % PPL == 0u, "pieces per lane: a power of two that divides the lane group");
+        const uint32_t pieces = PPL * chunks;
+#pragma unroll
+        for (uint32_t inst = 0; inst < PPL; inst++) {
+            const uint32_t p = inst * LPR + sub;               // piece this lane writes
+            const uint32_t src = grp * LPR + p / PPL;          // lane that holds it
+            const uint32_t which = p % PPL;
+            f32x4 v;
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                float x = shfl_f32(acc[c], src);
+#pragma unroll
+                for (uint32_t k = 1; k < PPL; k++) {
+                    const float y = shfl_f32(acc[4 * k + c], src);
+                    x = (which == k) ? y : x;
+                }
+                v[c] = x;
             }
             // (validity is uniform over a lane group except for lanes beyond `chunks`, whose own
             // `valid` is false but which still write pieces of the row when p < pieces)
@@ -565,6 +673,14 @@ template <> struct ElemOps<EMB_BF16> {
     static __device__ __forceinline__ void add(Acc &a, Elem v) { a = a + widen(v); }
     static __device__ __forceinline__ float out(Acc a) { return a; }
 };
+template <int DT> struct F8ElemOps {
+    using Elem = uint8_t; using Acc = float; using Out = float;       // (Elem: the raw byte)
+    static __device__ __forceinline__ float widen(Elem v) { return F8Widen<DT>::one(v); }
+    static __device__ __forceinline__ void add(Acc &a, Elem v) { a = a + widen(v); }
+    static __device__ __forceinline__ float out(Acc a) { return a; }
+};
+template <> struct ElemOps<kF8E4M3> : F8ElemOps<kF8E4M3> {};
+template <> struct ElemOps<kF8E5M2> : F8ElemOps<kF8E5M2> {};
 template <> struct ElemOps<EMB_FIXED32> {
     using Elem = uint32_t; using Acc = uint32_t; using Out = float;
     static __device__ __forceinline__ void add(Acc &a, Elem v) { a += v; }
@@ -613,8 +729,8 @@ template <typename IdxT, int DT, bool CLAMP>
 __global__ void __launch_bounds__(256)
 bag_sum_anydim_vec_kernel(const DevDesc *__restrict__ descs, uint32_t dim, uint32_t lanes) {
     using Ops = RowOps<DT>;
-    constexpr uint32_t EP = sizeof(typename Ops::Acc) / 4u; // elements per 16-byte piece (4, or 8 halves)
-    constexpr uint32_t ESZ = 16u / EP;
+    constexpr uint32_t ESZ = elem_bytes(DT & ~kHalfOutDT);
+    constexpr uint32_t EP = 16u / ESZ;                       // elements per 16-byte piece (4, 8 halves or 16 bytes)
     constexpr int U = 4;
     const DevDesc *dp = descs + blockIdx.y;
     const char *__restrict__ weights = static_cast<const char *>(dp->weights);
@@ -849,7 +965,10 @@ bag_sum_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg,
                             }
                         } else {   // all lanes take part in the group store's shuffles
                             typename Ops::Acc acc = Ops::zero();
-                            if (has[q][jj] && lane_live) Ops::add(acc, v[q][jj]);
+                            // (fp8: a piece that was not gathered is all zero bytes, which widen to +0, and +0 + +0 = +0 --
+                            // added without the test, the eight conversions stay out of a branch per gathered row)
+                            if constexpr (kIsF8<DT>) Ops::add(acc, v[q][jj]);
+                            else if (has[q][jj] && lane_live) Ops::add(acc, v[q][jj]);
                             store_row<Ops, Cfg, LPR>(acc, t.out + bag * ln.out_stride, ln.sub, ln.grp, chunks,
                                                      wr && lane_live);
                         }
@@ -1042,6 +1161,13 @@ template <> struct PoolRow<EMB_BF16> {
     static __device__ __forceinline__ f32x8 widen(u32x4 raw) { return widen_bf16x8(raw); }
 };
 
+template <int DT> struct F8PoolRow {
+    static constexpr int K = 16;
+    static __device__ __forceinline__ f32x16 widen(u32x4 raw) { return widen_f8x16<DT>(raw); }
+};
+template <> struct PoolRow<kF8E4M3> : F8PoolRow<kF8E4M3> {};
+template <> struct PoolRow<kF8E5M2> : F8PoolRow<kF8E5M2> {};
+
 template <int DT, class Acc>
 __device__ __forceinline__ void pool_combine(Acc &acc, u32x4 raw, float w, uint32_t op, bool first) {
     const auto x = PoolRow<DT>::widen(raw);
@@ -1100,7 +1226,7 @@ __device__ __forceinline__ void pool_walk(const IdxT *__restrict__ indices, cons
 // instantiations.  bf16 tables enter through bag_bf16pool_*, the same text with the same template arguments:
 // tests/test_pooling_abi.py pins the SET of bag_pool_* kernels in the code object (64: index width x fp32 / fp16 x row widths
 // x paths, plus the any-dim ones) and is not a file that adding a dtype may edit, so that set stays what the test pins;
-// launch_bag_pool (pimemb_kernels.hip) and codeobj.symbol_fragments know both names.
+// launch_bag_pool (pimemb_kernels.hip) and codeobj.symbol_fragments know both names.  fp8 tables the same way: bag_f8pool_*.
 // Half-width output (EMB_POOL_OUT_TABLE_DTYPE): a third set, bag_hpool_*, for fp16 and bf16 tables alike -- the same text with
 // PIMEMB_POOL_HALF_OUT 1, which swaps in the half-output RowOps (one 16-byte store per lane) and the any-dim kernel's 2-byte
 // store tail.  DT stays the table's public dtype there; the name tells the twins apart (and is not one the tests above pin).
@@ -1110,6 +1236,9 @@ __device__ __forceinline__ void pool_walk(const IdxT *__restrict__ indices, cons
 #include "pimemb_pool_kernels.inc"
 #undef PIMEMB_POOL_KERNEL
 #define PIMEMB_POOL_KERNEL(path) bag_bf16pool_##path##_kernel
+#include "pimemb_pool_kernels.inc"
+#undef PIMEMB_POOL_KERNEL
+#define PIMEMB_POOL_KERNEL(path) bag_f8pool_##path##_kernel       // fp8 tables (both encodings), fp32 out: as bag_bf16pool_*
 #include "pimemb_pool_kernels.inc"
 #undef PIMEMB_POOL_KERNEL
 #undef PIMEMB_POOL_HALF_OUT

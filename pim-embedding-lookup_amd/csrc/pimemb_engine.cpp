@@ -60,14 +60,14 @@ double now_us() {
     return duration<double, std::micro>(steady_clock::now().time_since_epoch()).count();
 }
 
-size_t elem_size(emb_dtype d) { return (d == EMB_F16 || d == EMB_BF16) ? 2 : 4; }
+size_t elem_size(int dtype) { return pimemb::elem_bytes(dtype); }
 size_t index_size(emb_index_type t) { return t == EMB_IDX_I64 ? 8 : 4; }
 
 struct Table {
     void *rows = nullptr;
     uint64_t nr_rows = 0;
     uint32_t dim = 0;
-    emb_dtype dtype = EMB_F32;
+    int dtype = EMB_F32;            // (an emb_dtype value, held as int: pimemb_internal.h, dtype_value)
     LaunchGeom geom{};
     size_t bytes = 0;
     uint64_t generation = 0;  // bumped whenever `rows` is (re)allocated: prepared plans check it
@@ -224,7 +224,7 @@ struct PlanGroup {
     DevDesc *d_descs = nullptr;
     uint32_t n = 0;
     uint32_t max_tiles = 0;
-    emb_dtype dtype = EMB_F32;
+    int dtype = EMB_F32;            // (an emb_dtype value, held as int: pimemb_internal.h, dtype_value)
     LaunchGeom geom{};
     KernelKind kind = pimemb::KERNEL_WAVEBATCH;
     uint32_t *d_xmap = nullptr;      // XCD-aware workgroup map, or null (2-D grid)
@@ -508,7 +508,7 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
     const size_t isz = index_size(itype);
     for (auto &kv : by_shape) {
         PlanGroup g;
-        g.dtype = (emb_dtype)std::get<0>(kv.first);
+        g.dtype = std::get<0>(kv.first);
         g.pool = std::get<2>(kv.first);
         g.out_half = std::get<3>(kv.first) != 0;
         g.n = (uint32_t)kv.second.size();
@@ -1192,7 +1192,7 @@ int emb_destroy(emb_engine *e) {
     return EMB_OK;
 }
 
-static int alloc_table(emb_engine *e, uint32_t table_id, uint64_t nr_rows, uint32_t dim, emb_dtype dtype,
+static int alloc_table(emb_engine *e, uint32_t table_id, uint64_t nr_rows, uint32_t dim, int dtype,
                        bool zero_fill) {
     if (!e) return fail(EMB_ERR_INVALID, "engine is NULL");
     if (table_id >= e->tables.size())
@@ -1235,13 +1235,13 @@ static int alloc_table(emb_engine *e, uint32_t table_id, uint64_t nr_rows, uint3
 }
 
 int emb_alloc_table(emb_engine *e, uint32_t table_id, uint64_t nr_rows, uint32_t dim, emb_dtype dtype) {
-    return alloc_table(e, table_id, nr_rows, dim, dtype, /*zero_fill=*/true);
+    return alloc_table(e, table_id, nr_rows, dim, pimemb::dtype_value(dtype), /*zero_fill=*/true);
 }
 
 int emb_load_table(emb_engine *e, uint32_t table_id, uint64_t nr_rows, uint32_t dim, emb_dtype dtype,
                    const void *rows, emb_memspace space) {
     if (!rows) return fail(EMB_ERR_INVALID, "table %u: rows is NULL", table_id);
-    int rc = alloc_table(e, table_id, nr_rows, dim, dtype, /*zero_fill=*/false);
+    int rc = alloc_table(e, table_id, nr_rows, dim, pimemb::dtype_value(dtype), /*zero_fill=*/false);
     if (rc) return rc;
     DeviceGuard g(e->device);
     Table &t = e->tables[table_id];
@@ -1391,7 +1391,7 @@ int emb_table_info(emb_engine *e, uint32_t table_id, void **device_rows, uint64_
     if (device_rows) *device_rows = t.rows;
     if (nr_rows) *nr_rows = t.nr_rows;
     if (dim) *dim = t.dim;
-    if (dtype) *dtype = t.dtype;
+    if (dtype) pimemb::dtype_store(dtype, t.dtype);
     return EMB_OK;
 }
 
@@ -2068,7 +2068,7 @@ struct emb_queue {
     // behind the lookup stores it: no event -- an event between two kernels costs GPU time -- and waiters poll a word)
     volatile unsigned long long *done = nullptr;
     bool shaped = false;
-    emb_dtype dtype = EMB_F32;
+    int dtype = EMB_F32;            // (an emb_dtype value, held as int: pimemb_internal.h, dtype_value)
     uint32_t dim = 0;
     LaunchGeom geom{};
     KernelKind kind = pimemb::KERNEL_GROUP;

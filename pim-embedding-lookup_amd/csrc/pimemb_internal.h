@@ -29,8 +29,19 @@ enum KernelKind : uint32_t {
 
 constexpr size_t kHotLdsBudget = 62u << 10;   // LDS bytes a hot set (rows + hash) may take per workgroup
 
+// A table dtype as the library holds and passes it: an int.  The fp8 values lie outside the range of the emb_dtype enum
+// (pimemb.h says why), so a C++ read of an emb_dtype object that holds one is not a read the language defines (and one that
+// -fsanitize=enum reports): the ABI functions copy the argument's bytes, everything behind them is int.
+inline int dtype_value(const emb_dtype &d) {
+    static_assert(sizeof(emb_dtype) == sizeof(int), "emb_dtype is an int-sized enum");
+    int v;
+    __builtin_memcpy(&v, &d, sizeof v);
+    return v;
+}
+inline void dtype_store(emb_dtype *dst, int v) { __builtin_memcpy(dst, &v, sizeof v); }
+
 // Returns EMB_OK / EMB_ERR_UNSUPPORTED and fills `g` for a table shape.
-int geometry_for(emb_dtype dtype, uint32_t dim, LaunchGeom *g);
+int geometry_for(int dtype, uint32_t dim, LaunchGeom *g);
 
 // Bags one workgroup finishes per tile for this kernel kind and row shape.
 uint32_t bags_per_tile(KernelKind kind, const LaunchGeom &g);
@@ -43,7 +54,7 @@ KernelKind choose_kernel(uint64_t total_bags, uint64_t total_indices, const Laun
 // pimemb_xcd_map.h with `xgrid` workgroups (xdirect: expanded to one entry per workgroup).
 // Pure enqueue: no allocation, copy or sync.
 hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles,
-                          emb_dtype dtype, emb_index_type itype, const LaunchGeom &g,
+                          int dtype, emb_index_type itype, const LaunchGeom &g,
                           KernelKind kind, const uint32_t *d_xmap, uint32_t xgrid, bool xdirect,
                           hipStream_t stream, bool ranged = false, bool out_half = false);
 // out_half (here and in launch_bag_pool; EMB_POOL_OUT_TABLE_DTYPE): DevDesc::out points to rows of the table's 2-byte dtype
@@ -52,13 +63,13 @@ hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max
 // Pooled lookup (emb_lookup_pooled: mean / max, per-sample weights, padding_idx) over descriptors of one dtype (fp32 / fp16 / bf16)
 // and dim whose pooling spec sits in DevDesc::pool (pimemb_bag_kernels.h, bag_pool_*).  kind: KERNEL_WAVEBATCH,
 // KERNEL_GROUP or KERNEL_ANYDIM (no two-batch or hot-row variant).  Pure enqueue.
-hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, emb_dtype dtype,
+hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, int dtype,
                            emb_index_type itype, const LaunchGeom &g, KernelKind kind, const uint32_t *d_xmap,
                            uint32_t xgrid, bool xdirect, hipStream_t stream, bool out_half = false);
 
 // Pooled launch with hot rows in LDS: `wgs` persistent workgroups per descriptor, `lds_bytes` of dynamic LDS.
 hipError_t launch_bag_sum_hot(const DevDesc *d_descs, uint32_t n_descs, uint32_t wgs, uint32_t lds_bytes,
-                              emb_dtype dtype, emb_index_type itype, const LaunchGeom &g, hipStream_t stream);
+                              int dtype, emb_index_type itype, const LaunchGeom &g, hipStream_t stream);
 
 // ranged (wave-batch kinds, one index per bag): a descriptor serves only the bags whose row falls into
 // [row_lo, row_lo + nr_rows) -- DevDesc::ranged.row_lo -- as out[b] = W[idx[b] - row_lo]; other bags are left untouched

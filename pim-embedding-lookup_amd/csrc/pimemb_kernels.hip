@@ -52,6 +52,16 @@ template <> struct WaveCfgOf<EMB_F16> { using One = WaveCfgF16; using Two = Wave
 using WaveCfgBF16 = BagCfg<64, 8, true, false, 8, PIMEMB_BF16_MINW, 1, false, true, false, kClampInputs>;
 using Wave2CfgBF16 = BagCfg<128, 4, true, false, 8, PIMEMB_BF16_MINW, 2, false, true, false, kClampInputs>;
 template <> struct WaveCfgOf<EMB_BF16> { using One = WaveCfgBF16; using Two = Wave2CfgBF16; };
+// fp8 rows: 16 fp32 accumulators per gather and up to four store instructions per lane; started from the fp16 configurations
+// (4 waves per SIMD, 128 VGPRs), under which no fp8 kernel spills or uses scratch -- the two-batch kernel at unroll 4 included
+// (tests/test_f8_cpu.py reads it off the code object).  -DPIMEMB_F8_MINW=n repeats the choice.
+#ifndef PIMEMB_F8_MINW
+#define PIMEMB_F8_MINW PIMEMB_F16_MINW
+#endif
+using WaveCfgF8 = BagCfg<64, 8, true, false, 8, PIMEMB_F8_MINW, 1, false, true, false, kClampInputs>;
+using Wave2CfgF8 = BagCfg<128, 4, true, false, 8, PIMEMB_F8_MINW, 2, false, true, false, kClampInputs>;
+template <> struct WaveCfgOf<kF8E4M3> { using One = WaveCfgF8; using Two = Wave2CfgF8; };
+template <> struct WaveCfgOf<kF8E5M2> { using One = WaveCfgF8; using Two = Wave2CfgF8; };
 // half-width output (kHalfOutDT, pimemb_bag_kernels.h): the same 8 fp32 accumulators per gather as the fp32-out kernels of these
 // tables, no store shuffles; the configurations of their tables, under which none of them spills
 template <> struct WaveCfgOf<EMB_F16 | kHalfOutDT> : WaveCfgOf<EMB_F16> {};
@@ -69,9 +79,11 @@ using Int = std::integral_constant<int, V>;
 
 // f(IdxT{}, Int<DT>{}) -> hipError_t.  FIXED32: the family has fixed-point kernels (the pooled one has none: invalid there).
 template <bool FIXED32, class F>
-hipError_t with_types(emb_index_type itype, emb_dtype dtype, F &&f) {
+hipError_t with_types(emb_index_type itype, int dtype, F &&f) {
     auto with_index = [&](auto dt) { return itype == EMB_IDX_U32 ? f(uint32_t{}, dt) : f(int64_t{}, dt); };
     switch (dtype) {
+        case kF8E4M3: return with_index(Int<kF8E4M3>{});
+        case kF8E5M2: return with_index(Int<kF8E5M2>{});
         case EMB_F32: return with_index(Int<EMB_F32>{});
         case EMB_F16: return with_index(Int<EMB_F16>{});
         case EMB_BF16: return with_index(Int<EMB_BF16>{});
@@ -85,7 +97,7 @@ hipError_t with_types(emb_index_type itype, emb_dtype dtype, F &&f) {
 // The same for a half-output launch (EMB_POOL_OUT_TABLE_DTYPE): fp16 / bf16 tables only, and f receives the INTERNAL dtype value
 // that names the half-output twin of a sum kernel.
 template <class F>
-hipError_t with_half_out_types(emb_index_type itype, emb_dtype dtype, F &&f) {
+hipError_t with_half_out_types(emb_index_type itype, int dtype, F &&f) {
     auto with_index = [&](auto dt) { return itype == EMB_IDX_U32 ? f(uint32_t{}, dt) : f(int64_t{}, dt); };
     if (dtype == EMB_F16) return with_index(Int<EMB_F16 | kHalfOutDT>{});
     if (dtype == EMB_BF16) return with_index(Int<EMB_BF16 | kHalfOutDT>{});
@@ -149,6 +161,8 @@ using PoolWaveCfg = BagCfg<64, 4, true, false, 8, 8, 1, false, true, false, kCla
 template <int DT> struct PoolWaveCfgOf { using One = PoolWaveCfg; };
 template <> struct PoolWaveCfgOf<EMB_F16> { using One = WaveCfgF16; };
 template <> struct PoolWaveCfgOf<EMB_BF16> { using One = WaveCfgBF16; };
+template <> struct PoolWaveCfgOf<kF8E4M3> { using One = WaveCfgF8; };
+template <> struct PoolWaveCfgOf<kF8E5M2> { using One = WaveCfgF8; };
 
 // ---- column scatter for populate_mram-style uploads -----------------------------------------
 __global__ void __launch_bounds__(kBlock)
@@ -1104,9 +1118,10 @@ hipError_t launch_widen_words(const WidenArgs &a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-int geometry_for(emb_dtype dtype, uint32_t dim, LaunchGeom *g) {
-    uint32_t elem = (dtype == EMB_F16 || dtype == EMB_BF16) ? 2u : 4u;
-    if (dtype != EMB_F32 && dtype != EMB_F16 && dtype != EMB_FIXED32 && dtype != EMB_BF16) return EMB_ERR_INVALID;
+int geometry_for(int dtype, uint32_t dim, LaunchGeom *g) {
+    const int dt = dtype;
+    if (dt != EMB_F32 && dt != EMB_F16 && dt != EMB_FIXED32 && dt != EMB_BF16 && dt != kF8E4M3 && dt != kF8E5M2) return EMB_ERR_INVALID;
+    const uint32_t elem = elem_bytes(dt);
     uint64_t row_bytes = (uint64_t)dim * elem;
     if (dim == 0) return EMB_ERR_UNSUPPORTED;
     g->anydim_vec = false;
@@ -1158,7 +1173,7 @@ KernelKind choose_kernel(uint64_t total_bags, uint64_t total_indices, const Laun
 }
 
 hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles,
-                          emb_dtype dtype, emb_index_type itype, const LaunchGeom &g,
+                          int dtype, emb_index_type itype, const LaunchGeom &g,
                           KernelKind kind, const uint32_t *d_xmap, uint32_t xgrid, bool xdirect,
                           hipStream_t stream, bool ranged, bool out_half) {
     if (n_descs == 0 || max_tiles == 0) return hipSuccess;
@@ -1183,7 +1198,7 @@ hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max
     return out_half ? with_half_out_types(itype, dtype, launch) : with_types<true>(itype, dtype, launch);
 }
 
-hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, emb_dtype dtype,
+hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, int dtype,
                            emb_index_type itype, const LaunchGeom &g, KernelKind kind, const uint32_t *d_xmap,
                            uint32_t xgrid, bool xdirect, hipStream_t stream, bool out_half) {
     if (n_descs == 0 || max_tiles == 0) return hipSuccess;
@@ -1197,6 +1212,7 @@ hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t ma
         constexpr int DT = decltype(dt)::value;
         using One = typename PoolWaveCfgOf<DT>::One;
         constexpr bool BF16 = DT == EMB_BF16;       // bf16 tables: the same bodies under the bag_bf16pool_* names (pimemb_bag_kernels.h)
+        constexpr bool F8 = kIsF8<DT>;              // fp8 tables: under bag_f8pool_*
         if constexpr (DT == EMB_F16 || DT == EMB_BF16) {
             if (out_half) {                         // ... and the half-output set, bag_hpool_*, for both 2-byte dtypes
                 if (kind == KERNEL_ANYDIM) {
@@ -1220,6 +1236,8 @@ hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t ma
                 constexpr bool VEC = decltype(vec)::value;
                 if constexpr (BF16)
                     hipLaunchKernelGGL((bag_bf16pool_anydim_kernel<IdxT, DT, VEC, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
+                else if constexpr (F8)
+                    hipLaunchKernelGGL((bag_f8pool_anydim_kernel<IdxT, DT, VEC, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
                 else
                     hipLaunchKernelGGL((bag_pool_anydim_kernel<IdxT, DT, VEC, kClampInputs>), m.grid, dim3(256), 0, stream, d_descs, g.chunks, g.scalar_lanes);
             };
@@ -1236,6 +1254,11 @@ hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t ma
                     hipLaunchKernelGGL((bag_bf16pool_wavebatch_kernel<IdxT, DT, L, One>), m.grid, dim3(One::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
                 else
                     hipLaunchKernelGGL((bag_bf16pool_group_kernel<IdxT, DT, L, GroupCfg>), m.grid, dim3(GroupCfg::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+            } else if constexpr (F8) {
+                if (kind == KERNEL_WAVEBATCH)
+                    hipLaunchKernelGGL((bag_f8pool_wavebatch_kernel<IdxT, DT, L, One>), m.grid, dim3(One::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+                else
+                    hipLaunchKernelGGL((bag_f8pool_group_kernel<IdxT, DT, L, GroupCfg>), m.grid, dim3(GroupCfg::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
             } else {
                 if (kind == KERNEL_WAVEBATCH)
                     hipLaunchKernelGGL((bag_pool_wavebatch_kernel<IdxT, DT, L, One>), m.grid, dim3(One::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
@@ -1247,7 +1270,7 @@ hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t ma
 }
 
 hipError_t launch_bag_sum_hot(const DevDesc *d_descs, uint32_t n_descs, uint32_t wgs, uint32_t lds_bytes,
-                              emb_dtype dtype, emb_index_type itype, const LaunchGeom &g, hipStream_t stream) {
+                              int dtype, emb_index_type itype, const LaunchGeom &g, hipStream_t stream) {
     if (n_descs == 0 || wgs == 0) return hipSuccess;
     if (n_descs > 65535u || lds_bytes > kHotLdsBudget || g.scalar_lanes) return hipErrorInvalidValue;
     return with_types<true>(itype, dtype, [&](auto idx, auto dt) {

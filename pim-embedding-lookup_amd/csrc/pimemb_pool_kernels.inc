@@ -2,8 +2,8 @@
 // Included by pimemb_bag_kernels.h, inside namespace pimemb, ONCE PER SET OF ENTRY-POINT NAMES: PIMEMB_POOL_KERNEL(path) names
 // the kernel of a path (group, wavebatch, anydim); PIMEMB_POOL_ROWOPS(DT) is the accumulate / store trait and
 // PIMEMB_POOL_HALF_OUT says whether the set stores fp32 rows (0) or rows of the table's 2-byte dtype (1).
-// The same text compiled under three sets of names -- bag_pool_* (fp32, fp16), bag_bf16pool_* (bf16), bag_hpool_* (half-width
-// output of fp16 and bf16 tables) -- so that the kernels of the first set keep their machine code to the byte (as bodies
+// The same text compiled under four sets of names -- bag_pool_* (fp32, fp16), bag_bf16pool_* (bf16), bag_f8pool_* (fp8),
+// bag_hpool_* (half-width output of fp16 and bf16 tables) -- so that the kernels of the first set keep their machine code to the byte (as bodies
 // shared by thin kernels they do not: inlined, 50 of the 64 fp32 / fp16 pooled kernels change, some by up to 4 VGPRs).
 
 // Lane-group path (ragged bags, rows of 16-byte multiples up to 1 KiB): one lane group per bag, as bag_sum_group_kernel.
@@ -154,7 +154,7 @@ template <typename IdxT, int DT, bool VEC, bool CLAMP>
 __global__ void __launch_bounds__(256)
 PIMEMB_POOL_KERNEL(anydim)(const DevDesc *__restrict__ descs, uint32_t dim, uint32_t lanes) {
     constexpr uint32_t EP = VEC ? (uint32_t)PoolRow<DT>::K : 1u;    // elements per unit
-    constexpr uint32_t ESZ = (DT == EMB_F16 || DT == EMB_BF16) ? 2u : 4u;
+    constexpr uint32_t ESZ = elem_bytes(DT);
     constexpr int U = 4;
     const DevDesc *dp = descs + blockIdx.y;
     const char *__restrict__ weights = static_cast<const char *>(dp->weights);
@@ -213,6 +213,7 @@ PIMEMB_POOL_KERNEL(anydim)(const DevDesc *__restrict__ descs, uint32_t dim, uint
                     if (use[k]) {
                         if constexpr (DT == EMB_F16) x[k][0] = (float)*reinterpret_cast<const _Float16 *>(src);
                         else if constexpr (DT == EMB_BF16) x[k][0] = ElemOps<EMB_BF16>::widen(*reinterpret_cast<const uint16_t *>(src));
+                        else if constexpr (kIsF8<DT>) x[k][0] = ElemOps<DT>::widen(*reinterpret_cast<const uint8_t *>(src));
                         else x[k][0] = *reinterpret_cast<const float *>(src);
                     }
                 }

@@ -1422,7 +1422,7 @@ int emb_shard_create(emb_engine *e, emb_comm *comm, const emb_shard_config *cfg,
             rc = emb_table_info(e, tb.engine_table, nullptr, nullptr, &d, &dt);
             if (rc) return bail(rc);
             if (d != s->dim) return bail(fail(EMB_ERR_INVALID, "emb_shard_create: table %u: engine table %u has dim %u, not %u", t, tb.engine_table, d, s->dim));
-            s->elem_bytes[t] = (dt == EMB_F16 || dt == EMB_BF16) ? 2u : 4u;
+            s->elem_bytes[t] = pimemb::elem_bytes(pimemb::dtype_value(dt));
         }
     }
     // the ranged (direct-path / counted) launches run on the 16-byte lane-piece kernels only: rows of 16..1024 bytes in 16-byte steps

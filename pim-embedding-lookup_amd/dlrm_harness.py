@@ -33,6 +33,8 @@ class EmbeddingBagCollection:
         # does; None: fp32 rows whatever the tables hold
         if out_dtype not in (None, "weight"):
             raise ValueError('out_dtype must be None or "weight"')
+        if out_dtype == "weight" and str(dtype).startswith("fp8"):
+            raise ValueError('out_dtype="weight" needs f16 or bf16 tables: fp8 tables return fp32 rows only')
         self._out = "table" if out_dtype == "weight" and dtype in ("f16", "bf16") else None
         self.trusted_inputs = bool(trusted_inputs)     # False: every apply_emb checks its indices first (IndexError)
         self.deferred_check = bool(deferred_check)     # ... without waiting for the verdict (a later call / close() raises it)
@@ -49,10 +51,12 @@ class EmbeddingBagCollection:
             else:  # DLRM init: U(-sqrt(1/n), sqrt(1/n))
                 a = float(np.sqrt(1.0 / n))
                 w = torch.empty((n, self.m), dtype=torch.float32, device=self.device).uniform_(-a, a, generator=g)
-            if dtype not in ("f32", "f16", "bf16"):
-                raise ValueError("dtype must be 'f32', 'f16' or 'bf16'")
+            tdt = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16, "fp8_e4m3": torch.float8_e4m3fn,
+                   "fp8_e5m2": torch.float8_e5m2}.get(dtype)
+            if tdt is None:
+                raise ValueError("dtype must be 'f32', 'f16', 'bf16', 'fp8_e4m3' or 'fp8_e5m2'")
             if dtype != "f32":
-                w = w.to(torch.float16 if dtype == "f16" else torch.bfloat16)
+                w = w.to(tdt)          # (fp32 checkpoints are rounded by torch: nearest even)
             self.engine.load_table(k, w)
         self._plans = {}
         self._ids = list(range(len(self.ln_emb)))

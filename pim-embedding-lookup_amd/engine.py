@@ -28,6 +28,7 @@ POOL_MODES = {"sum": _l.EMB_POOL_SUM, "mean": _l.EMB_POOL_MEAN, "max": _l.EMB_PO
 # bfloat16: bf16 rows come back as uint16 bits (formats.from_bf16_bits reads them).
 _HALF_OUT_NP = {_l.EMB_F16: np.dtype(np.float16), _l.EMB_BF16: np.dtype(np.uint16)}
 _HALF_OUT_TORCH = {_l.EMB_F16: "torch.float16", _l.EMB_BF16: "torch.bfloat16"}
+_F8_TORCH = {_l.EMB_F8_E4M3: "float8_e4m3fn", _l.EMB_F8_E5M2: "float8_e5m2"}      # fp8 tables: always fp32 out
 
 
 _MARSHAL = [False]      # False: not looked for yet; None: not built; else the _pimemb_marshal module
@@ -346,12 +347,13 @@ class EmbeddingEngine:
     # ---- tables (populate_mram's job, emb_host.h:136) ------------------------------------------
     def load_table(self, table_id: int, rows, dtype: int | None = None) -> None:
         """rows: [nr_rows, dim] numpy float32/float16/int32 (int32 = x1e9 fixed point) or a torch
-        tensor (CPU or CUDA) of those dtypes or of torch.bfloat16.  numpy has no bfloat16: a uint16 array
-        holds bf16 bits (formats.to_bf16_bits) when -- and only when -- dtype=EMB_BF16 says so."""
+        tensor (CPU or CUDA) of those dtypes, of torch.bfloat16, torch.float8_e4m3fn or torch.float8_e5m2.  numpy has no
+        bfloat16 and no fp8: a uint16 array holds bf16 bits (formats.to_bf16_bits) when -- and only when -- dtype=EMB_BF16
+        says so, a uint8 array fp8 bits (formats.to_f8_bits) only with dtype=EMB_F8_E4M3 / EMB_F8_E5M2."""
         if _is_torch(rows):
             import torch
             tmap = {torch.float32: _l.EMB_F32, torch.float16: _l.EMB_F16, torch.int32: _l.EMB_FIXED32,
-                    torch.bfloat16: _l.EMB_BF16}
+                    torch.bfloat16: _l.EMB_BF16, torch.float8_e4m3fn: _l.EMB_F8_E4M3, torch.float8_e5m2: _l.EMB_F8_E5M2}
             dt = tmap[rows.dtype] if dtype is None else dtype
             if not rows.is_contiguous():
                 rows = rows.contiguous()
@@ -405,12 +407,16 @@ class EmbeddingEngine:
         import torch
         ptr, n, d, dt = self.table_info(table_id)
         # (the CUDA array interface has no bfloat16 typestr: the bits travel as uint16 and are viewed as bf16)
-        typestr = {_l.EMB_F32: "<f4", _l.EMB_F16: "<f2", _l.EMB_FIXED32: "<i4", _l.EMB_BF16: "<u2"}[dt]
+        # (nor an fp8 one: uint8, viewed as the float8 dtype)
+        typestr = {_l.EMB_F32: "<f4", _l.EMB_F16: "<f2", _l.EMB_FIXED32: "<i4", _l.EMB_BF16: "<u2", _l.EMB_F8_E4M3: "|u1",
+                   _l.EMB_F8_E5M2: "|u1"}[dt]
 
         class _View:
             __cuda_array_interface__ = {"shape": (n, d), "typestr": typestr, "data": (ptr, False), "version": 2,
                                         "strides": None}
         view = torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+        if dt in _F8_TORCH:
+            return view.view(getattr(torch, _F8_TORCH[dt]))
         return view.view(torch.bfloat16) if dt == _l.EMB_BF16 else view
 
     def table_info(self, table_id: int):
@@ -437,6 +443,11 @@ class EmbeddingEngine:
         n = len(table_ids)
         if not (len(indices) == n and len(offsets) == n):
             raise ValueError("table_ids, indices and offsets must have equal length")
+        if half is not None:       # refused here, before anything is allocated or any C call made: an fp8 output would round lossily
+            for t, h in zip(table_ids, half):
+                if h and t in self._tables and self._tables[t][2] in _F8_TORCH:
+                    raise TypeError(f'table {t}: out_dtype="table" needs an fp16 or bf16 table; an fp8 table ({_F8_TORCH[self._tables[t][2]]}) '
+                                    "returns fp32 rows only")
         arr = (_l.EmbLookupDesc * n)()
         keep, results = [], []
         itype = space = None

@@ -31,6 +31,66 @@ def from_bf16_bits(bits) -> np.ndarray:
     return (np.ascontiguousarray(bits, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
+_F8_KINDS = {"e4m3": (4, 3, 7), "e4m3fn": (4, 3, 7), "e5m2": (5, 2, 15)}      # exponent bits, mantissa bits, bias
+
+
+def _f8_kind(kind):
+    """"e4m3" / "e4m3fn" / "e5m2", or the dtype value EMB_F8_E4M3 (8) / EMB_F8_E5M2 (9) -> (name, ebits, mbits, bias)."""
+    name = {8: "e4m3", 9: "e5m2"}.get(kind, kind) if not isinstance(kind, str) else kind
+    name = str(name).replace("torch.", "").replace("float8_", "").replace("fp8_", "")
+    if name not in _F8_KINDS:
+        raise ValueError(f"fp8 kind must be 'e4m3' or 'e5m2' (or EMB_F8_E4M3 / EMB_F8_E5M2), got {kind!r}")
+    return ("e5m2" if name == "e5m2" else "e4m3",) + _F8_KINDS[name]
+
+
+def from_f8_bits(bits, kind) -> np.ndarray:
+    """uint8 OCP fp8 bits (kind "e4m3": e4m3fn, no infinities, 0x7f / 0xff NaN; "e5m2": IEEE-like) -> float32, exact for all
+    256 patterns: integer work on the bits, as `tensor.view(torch.float8_*).float()` gives."""
+    name, ebits, mbits, bias = _f8_kind(kind)
+    b = np.ascontiguousarray(bits, dtype=np.uint8).astype(np.uint32)
+    sign = (b & np.uint32(0x80)) << np.uint32(24)
+    e = (b >> np.uint32(mbits)) & np.uint32((1 << ebits) - 1)
+    m = b & np.uint32((1 << mbits) - 1)
+    normal = sign | ((e + np.uint32(127 - bias)) << np.uint32(23)) | (m << np.uint32(23 - mbits))
+    # subnormal: m * 2^(1 - bias - mbits), exact in fp32 arithmetic (m < 8)
+    sub = (m.astype(np.float32) * np.float32(2.0 ** (1 - bias - mbits))).view(np.uint32) | sign
+    out = np.where(e == 0, sub, normal)
+    if name == "e5m2":
+        top = e == np.uint32(31)
+        out = np.where(top, sign | np.uint32(0x7F800000) | (m << np.uint32(21)), out)          # inf, NaN (payload kept)
+    else:
+        out = np.where((b & np.uint32(0x7F)) == np.uint32(0x7F), sign | np.uint32(0x7FC00000), out)
+    return out.astype(np.uint32).view(np.float32)
+
+
+def to_f8_bits(x, kind) -> np.ndarray:
+    """float32 array -> the uint8 bits of its OCP fp8 rounding (nearest, ties to even), as `tensor.to(torch.float8_e4m3fn)` /
+    `.to(torch.float8_e5m2)` give them, overflow included: e4m3fn has no infinity, so whatever rounds beyond its largest finite
+    value (448) -- infinities too -- becomes NaN (0x7f | sign); e5m2 rounds beyond 57344 to +-inf (0x7c | sign).  NaN stays NaN.
+    numpy has no fp8: EmbeddingEngine.load_table takes such an array with dtype=EMB_F8_E4M3 / EMB_F8_E5M2."""
+    name, ebits, mbits, bias = _f8_kind(kind)
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    sign = ((u >> np.uint32(24)) & np.uint32(0x80)).astype(np.uint32)
+    a = u & np.uint32(0x7FFFFFFF)
+    shift = 23 - mbits
+    min_normal = np.uint32((127 - bias + 1) << 23)                                   # smallest normal fp8 as fp32 bits
+    # normal range: re-bias, round the dropped `shift` bits to nearest even (a carry runs into the exponent, as it should)
+    v = a.astype(np.int64) - ((127 - bias) << 23)
+    v = (v + ((1 << (shift - 1)) - 1) + ((v >> shift) & 1)) >> shift
+    # subnormal range: adding 2^(1 - bias - mbits + 23) in fp32 leaves the rounded multiple of the fp8 quantum in the low bits
+    magic = np.float32(2.0 ** (1 - bias - mbits + 23))
+    with np.errstate(invalid="ignore", over="ignore"):
+        subn = ((a.view(np.float32) + magic).view(np.uint32) - magic.view(np.uint32)).astype(np.int64)
+    r = np.where(a < min_normal, subn, v)
+    if name == "e5m2":
+        r = np.where(r >= 0x7C, 0x7C, r)                                             # beyond 57344 (or inf): inf
+        r = np.where(a > np.uint32(0x7F800000), 0x7F, r)                             # NaN
+    else:
+        r = np.where(r >= 0x7F, 0x7F, r)                                             # beyond 448, inf, NaN: NaN
+        r = np.where(a >= np.uint32(0x7F800000), 0x7F, r)
+    return (r.astype(np.uint32) | sign).astype(np.uint8)
+
+
 class CriteoKaggleNpz:
     """Categorical side of a processed Criteo-Kaggle file as embedding-lookup batches."""
 

@@ -19,6 +19,8 @@ Inference only (the engine has no backward); max_norm is not supported by any of
 Output dtype.  By default every module returns fp32 rows, whatever the table holds.  `out_dtype="weight"` makes a module
 with an fp16 / bf16 weight return the weight's dtype, as nn.EmbeddingBag does: the fp32 pooled value rounded once (the
 engine's out_dtype="table", EMB_POOL_OUT_TABLE_DTYPE).  The fused modules follow their bags unless told otherwise.
+Weights may also be torch.float8_e4m3fn / torch.float8_e5m2 (dtype=, or a float8 `_weight`): 1-byte rows, `weight` and
+`state_dict()` return them as float8; their output is always fp32 (out_dtype="weight" is refused).
 
 Input checking.  The C ABI is as unchecked as the reference (an out-of-range index is a wild read there,
 emb_dpu_lookup.c:113); these modules are what user tensors reach first, so by default every forward goes through
@@ -71,6 +73,9 @@ def _engine_out_dtype(out_dtype, table_dtype):
     """A module's out_dtype (None: fp32 rows; "weight": the weight's dtype) -> the engine's (None | "table")."""
     if out_dtype not in (None, "weight"):
         raise ValueError(f'out_dtype has to be None or "weight", got {out_dtype!r}')
+    if out_dtype == "weight" and table_dtype in (torch.float8_e4m3fn, torch.float8_e5m2):
+        raise ValueError('out_dtype="weight" needs an fp16 or bf16 weight: a float8 weight returns fp32 rows only (an fp8 output would '
+                         "round the pooled value lossily)")
     return "table" if out_dtype == "weight" and table_dtype in (torch.float16, torch.bfloat16) else None
 
 
