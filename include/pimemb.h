@@ -67,6 +67,27 @@ typedef enum emb_dtype {
  * with EMB_BF16 tables (1.4x - 1.8x at dims 16 - 64, 1.0x - 1.15x at dims 128 - 256).  Choose fp8 for pooled lookups and for capacity. */
 #define EMB_F8_E4M3 ((emb_dtype)8) /* OCP e4m3fn: 4 exponent bits (bias 7), 3 mantissa bits, no infinities, 0x7f / 0xff are NaN */
 #define EMB_F8_E5M2 ((emb_dtype)9) /* OCP e5m2: 5 exponent bits (bias 15), 2 mantissa bits: the upper byte of an fp16 */
+/* MXFP4 tables (OCP Microscaling v1.0: blocks of 32 E2M1 elements share one E8M0 power-of-two scale, 4.25 bits per element).
+ * Outside the enum like the fp8 values, and held the same way by C++ callers.  dim must be a multiple of 32 (else
+ * EMB_ERR_INVALID) of at most 2048 (else EMB_ERR_UNSUPPORTED).  A ROW -- in emb_load_table's buffer, in device memory
+ * (emb_table_info) and in Python's table_tensor alike, loading is a straight copy -- is EMB_MXFP4_ROW_STRIDE(dim) bytes:
+ *   [0, dim/2)               the elements: byte j holds element 2j in its low nibble, element 2j+1 in its high nibble; a nibble is
+ *                            sign (bit 3), two exponent bits, one mantissa bit: +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, no inf, no NaN
+ *   [dim/2, dim/2 + dim/32)  the scales: byte b is the E8M0 scale 2^(s - 127) of elements 32b .. 32b+31; s = 0xFF makes the
+ *                            block's 32 elements NaN
+ *   up to the stride         zero padding, never read as data
+ * An element's value e2m1 * 2^(s - 127) is exact in fp32 (denormals kept), so -- as for fp8 -- results equal the fp32 lookup
+ * over the dequantised table bit for bit: fp32 accumulate in index order from +0, fp32 out.
+ * Served by the lane-group kernels only: emb_lookup / emb_lookup_batched (checked and deferred too), emb_lookup_pooled (every
+ * mode, weights, padding_idx), their plans and the request queue.  EMB_ERR_UNSUPPORTED (emb_last_error names MXFP4): the ranged /
+ * counted / typed lookups and their plans, emb_shard_create over an engine whose rank holds such a table, emb_set_hot_rows /
+ * emb_learn_hot_rows, emb_load_table_column, EMB_POOL_OUT_TABLE_DTYPE.
+ * Speed, measured on MI355X (profiles/mxfp4/README.md): choose MXFP4 for CAPACITY (a dim-128 row is 80 bytes against fp8's 128).
+ * Pooled launches (dim 128, 32 indices per bag) take 0.95 of the bf16 time but 1.29x the fp8 time; one-hot launches 1.5x - 1.9x
+ * the bf16 time. */
+#define EMB_MXFP4 ((emb_dtype)10)
+#define EMB_MXFP4_ROW_BYTES(dim) ((dim) / 2u + (dim) / 32u)                       /* elements + scales */
+#define EMB_MXFP4_ROW_STRIDE(dim) ((EMB_MXFP4_ROW_BYTES(dim) + 15u) & ~15u)       /* 32 / 48 / 80 / 144 / 272 / 1088 bytes at dim 32 / 64 / 128 / 256 / 512 / 2048 */
 
 /* width of indices AND offsets: uint32 at the reference ABI (emb_host.h:234), int64 at torch's */
 typedef enum emb_index_type { EMB_IDX_U32 = 0, EMB_IDX_I64 = 1 } emb_index_type;

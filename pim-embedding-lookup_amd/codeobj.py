@@ -122,10 +122,15 @@ def symbol_fragments(launch: dict) -> list[str]:
     bag_pool_<family>_kernel<IdxT, DT, LPR, Cfg> or bag_pool_anydim_kernel<IdxT, DT, VEC, CLAMP> -- for bf16 tables (dtype 3) the
     same under the name bag_bf16pool_*, for fp8 tables (dtype 8 / 9) under bag_f8pool_*.  A half-output launch (a record with out=1, EMB_POOL_OUT_TABLE_DTYPE) runs the twin of
     that kernel: a pooled one under the name bag_hpool_* (fp16 and bf16 tables alike), a sum one the same bag_sum_* template
-    with the internal dtype value DT | 16 (pimemb_bag_kernels.h: kHalfOutDT)."""
+    with the internal dtype value DT | 16 (pimemb_bag_kernels.h: kHalfOutDT).  MXFP4 tables (dtype 10) have two kernel
+    templates of their own, without a DT argument."""
     idx = "j" if launch["itype"] == 0 else "l"
     kind, dt, lpr = launch["kind"], launch["dtype"], launch["lanes_per_row"]
     half = bool(launch.get("out"))
+    if dt == 10:        # MXFP4: kernels of their own, lane-group only -- bag_mx4sum_group_kernel / bag_mx4pool_group_kernel<IdxT, LPR, Cfg>
+        if kind != 1 or half or launch.get("ranged"):
+            raise LookupError("an MXFP4 launch runs the lane-group kernels only: %s" % (launch,))
+        return ["bag_mx4%s_group_kernelI%sLi%dENS_6BagCfgI" % ("pool" if "pool" in launch else "sum", idx, lpr)]
     if "pool" in launch:
         pool = "bag_hpool" if half else "bag_bf16pool" if dt == 3 else "bag_f8pool" if dt in (8, 9) else "bag_pool"
         if kind == 3:

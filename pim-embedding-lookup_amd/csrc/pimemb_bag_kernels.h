@@ -97,6 +97,16 @@ __host__ __device__ constexpr uint32_t elem_bytes(int dt) {
     return (dt == kF8E4M3 || dt == kF8E5M2) ? 1u : (dt == EMB_F16 || dt == EMB_BF16) ? 2u : 4u;
 }
 
+// MXFP4 tables (EMB_MXFP4, the same way an int).  A row is no run of like elements: chunks = dim / 32 16-byte pieces of 32
+// E2M1 elements each, then one E8M0 scale byte per piece, padded to a 16-byte multiple (pimemb.h has the layout).
+constexpr int kMXFP4 = 10;
+using f32x32 = __attribute__((ext_vector_type(32))) float;
+// Bytes from one row of a table to the next: THE place that knows it -- table sizes, a plan's algorithmic bytes and the MXFP4
+// kernels ask here (elem_bytes cannot say it for MXFP4).
+__host__ __device__ constexpr uint64_t row_stride_bytes(int dt, uint32_t dim) {
+    return dt == kMXFP4 ? (uint64_t)EMB_MXFP4_ROW_STRIDE(dim) : (uint64_t)dim * elem_bytes(dt);
+}
+
 // Compile-time knobs of the bag kernels.
 template <int BLOCK = 256, int UNROLL = 8, bool NT_STORE = false, bool NT_META = false,
           int ONEHOT_INFLIGHT = 8, int MIN_WAVES = 1, int BATCHES = 1, bool NT_ROW = false,
@@ -257,6 +267,76 @@ struct F8RowOps {
 };
 template <> struct RowOps<kF8E4M3> : F8RowOps<kF8E4M3> {};
 template <> struct RowOps<kF8E5M2> : F8RowOps<kF8E5M2> {};
+
+// MXFP4 rows: a lane's 16-byte piece is exactly one MX block -- 32 E2M1 elements -- and comes with the block's E8M0 scale byte
+// from the row's tail.  Widened by v_cvt_scalef32_pk_f32_fp4: two elements (one byte) per instruction, the byte picked by op_sel,
+// sixteen instructions per piece.
+// PIMEMB_MX4_HW_SCALE 1: the scale travels as the instruction's scale operand, s << 23 (the fp32 whose exponent field is s).
+// 0: the instruction widens with scale 1.0 and the element is multiplied by 2^(s - 127) in fp32 (exact: an E2M1 value has two
+// significant bits; 2^-127 is the fp32 denormal 0x00400000, s = 0xFF a NaN) -- for hardware whose scale operand departs from
+// the contract somewhere.  MI355X does not: over all 16 nibbles x 256 scale bytes (tests/test_gpu_mxfp4.py) the instruction takes
+// the exponent field alone (s = 0 is 2^-127), keeps results that are fp32 denormals, reads the low nibble first and gives NaN
+// for s = 0xFF, so 1 ships.
+#ifndef PIMEMB_MX4_HW_SCALE
+#define PIMEMB_MX4_HW_SCALE 1
+#endif
+// 1: the pooled row leaves by non-temporal stores; 0, the default: ordinary stores.  A lane owns 128 contiguous bytes of output,
+// a whole line.  Measured on MI355X (profiles/mxfp4/README.md), us per launch, ordinary -> non-temporal: pooled dim 128 16.7 -> 26.8,
+// one-hot dim 32 48 -> 226, dim 128 182 -> 952.
+#ifndef PIMEMB_MX4_NT_STORE
+#define PIMEMB_MX4_NT_STORE 0
+#endif
+struct Mx4Piece {
+    u32x4 raw;      // 32 elements, element 2j in the low nibble of byte j
+    uint32_t s;     // the block's E8M0 scale byte
+};
+__device__ __forceinline__ uint32_t load_mx4_scale(const char *p) {
+    typedef const uint8_t PIMEMB_AS *ptr_t;
+    return (uint32_t)*(ptr_t)(reinterpret_cast<const uint8_t *>(p));
+}
+__device__ __forceinline__ f32x32 widen_mx4x32(const Mx4Piece &pc) {
+#if PIMEMB_MX4_HW_SCALE
+    const float scale = __builtin_bit_cast(float, pc.s << 23);
+#else
+    const float scale = 1.0f;
+    const float mul = __builtin_bit_cast(float, pc.s == 0u ? 0x00400000u : pc.s == 0xffu ? 0x7fc00000u : pc.s << 23);
+#endif
+    f32x32 out;
+#define PIMEMB_MX4_BYTE(d, b)                                                                              \
+    {                                                                                                      \
+        const f32x2 v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(pc.raw[d], scale, b);                     \
+        out[8 * (d) + 2 * (b)] = v[0];                                                                     \
+        out[8 * (d) + 2 * (b) + 1] = v[1];                                                                 \
+    }
+#define PIMEMB_MX4_DWORD(d) PIMEMB_MX4_BYTE(d, 0) PIMEMB_MX4_BYTE(d, 1) PIMEMB_MX4_BYTE(d, 2) PIMEMB_MX4_BYTE(d, 3)
+    PIMEMB_MX4_DWORD(0) PIMEMB_MX4_DWORD(1) PIMEMB_MX4_DWORD(2) PIMEMB_MX4_DWORD(3)
+#undef PIMEMB_MX4_DWORD
+#undef PIMEMB_MX4_BYTE
+#if !PIMEMB_MX4_HW_SCALE
+    out *= mul;
+#endif
+    return out;
+}
+template <>
+struct RowOps<kMXFP4> {
+    using Acc = f32x32;
+    static constexpr uint32_t kFloatsPerLane = 32;
+    static constexpr bool kGroupStore = true;       // 128 B of output per lane ...
+    static constexpr bool kGroupRedeal = false;     // ... a whole line of its own: eight plain 16-byte stores, no re-deal
+    static constexpr bool kNarrowNt = PIMEMB_MX4_NT_STORE != 0;
+    static __device__ __forceinline__ Acc zero() {
+        Acc a;
+#pragma unroll
+        for (int c = 0; c < 32; c++) a[c] = 0.f;
+        return a;
+    }
+    static __device__ __forceinline__ void add(Acc &a, const Mx4Piece &pc) { a += widen_mx4x32(pc); }
+    template <bool NT>
+    static __device__ __forceinline__ void store(const Acc &a, float *dst) {
+#pragma unroll
+        for (int c = 0; c < 32; c += 4) store_f32x4<NT>(dst + c, f32x4{a[c], a[c + 1], a[c + 2], a[c + 3]});
+    }
+};
 
 template <>
 struct RowOps<EMB_FIXED32> {
@@ -490,8 +570,9 @@ __device__ __forceinline__ void walk_bag(const IdxT *__restrict__ indices, uint6
                                          uint32_t grp, bool live, typename Ops::Acc &acc, Probe &&probe,
                                          Fetch &&fetch) {
     // probe(row) -> 32-bit token computed ONCE per index (e.g. the LDS slot of a hot row);
-    // fetch(row, token) -> the lane's 16-byte piece of that row.
+    // fetch(row, token) -> the lane's 16-byte piece of that row (whatever Ops::add takes).
     constexpr int U = Cfg::kUnroll;
+    using Piece = decltype(fetch(uint64_t{}, uint32_t{}));   // u32x4: 16 bytes of a row; MXFP4: with the block's scale (Mx4Piece)
     constexpr bool kProbe = std::remove_reference_t<Probe>::kUsed;
     if constexpr (!Cfg::kIdxShuffle) {
         if (!live) return;
@@ -499,7 +580,7 @@ __device__ __forceinline__ void walk_bag(const IdxT *__restrict__ indices, uint6
             uint64_t r[U];
 #pragma unroll
             for (int k = 0; k < U; k++) r[k] = (uint64_t)load_meta<Cfg::kNtMeta>(indices + p + k);
-            u32x4 v[U];
+            Piece v[U];
 #pragma unroll
             for (int k = 0; k < U; k++) v[k] = fetch(r[k], probe(r[k]));
 #pragma unroll
@@ -533,7 +614,7 @@ __device__ __forceinline__ void walk_bag(const IdxT *__restrict__ indices, uint6
                     t[j] = kProbe ? shfl_u32(tok[(IPL == 1) ? 0 : q / LPR], src) : 0u;
                 }
                 if (live) {
-                    u32x4 v[U];
+                    Piece v[U];
 #pragma unroll
                     for (int j = 0; j < U; j++) v[j] = fetch(r[j], t[j]);
 #pragma unroll
@@ -1250,5 +1331,132 @@ __device__ __forceinline__ void pool_walk(const IdxT *__restrict__ indices, cons
 #undef PIMEMB_POOL_KERNEL
 #undef PIMEMB_POOL_HALF_OUT
 #undef PIMEMB_POOL_ROWOPS
+
+// ---- MXFP4 tables: the lane-group kernels, sum and pooled ------------------------------------------------------------------
+// Kernels of their own, not instantiations of the ones above: a row is `chunks` 16-byte pieces FOLLOWED by `chunks` scale bytes,
+// so the row stride is not chunks * 16, a gather is a 16-byte load plus a byte load (lane `sub`: row + 16 * sub and
+// row + 16 * chunks + sub -- for dims <= 224 inside the cache lines the pieces bring in anyway), and a lane accumulates 32 floats.
+// Everything else is the lane-group kernels': one lane group per bag, indices loaded as a window and broadcast by shuffle, each
+// output element summed by one lane in index order from +0.  The lanes of a group beyond `chunks` (dim 96: 3 of 4) gather nothing.
+__host__ __device__ constexpr uint32_t mx4_row_stride(uint32_t chunks) { return (chunks * 17u + 15u) & ~15u; }
+static_assert(mx4_row_stride(1) == EMB_MXFP4_ROW_STRIDE(32u) && mx4_row_stride(4) == EMB_MXFP4_ROW_STRIDE(128u) &&
+              mx4_row_stride(64) == EMB_MXFP4_ROW_STRIDE(2048u), "the kernels' row stride is the header's");
+
+template <typename IdxT, int LPR, class Cfg>
+__global__ void __launch_bounds__(Cfg::kBlock)
+bag_mx4sum_group_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg, const uint32_t *__restrict__ xmap) {
+    using Ops = RowOps<kMXFP4>;
+    constexpr uint32_t kWaves = Cfg::kBlock / 64;
+    constexpr uint32_t BPW = 64 / LPR;
+    constexpr uint32_t BAGS_PER_TILE = BPW * kWaves;
+
+    uint32_t desc_i, tile;
+    if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
+    const uint32_t chunks = chunks_arg & ~kXmapDirect;
+    const DescView<IdxT> t(descs + desc_i);
+
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
+    const uint32_t row_stride = mx4_row_stride(chunks);
+    const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
+    const char *__restrict__ wsub = t.weights + sub * 16u;              // this lane's block of row 0 ...
+    const char *__restrict__ ssub = t.weights + chunks * 16u + sub;     // ... and that block's scale
+
+    if (tile < t.n_tiles) {
+        const uint64_t bag = (uint64_t)tile * BAGS_PER_TILE + wave * BPW + grp;
+        const bool live = sub < chunks;
+        if (bag >= t.n_bags) return;                   // whole lane group leaves together
+        uint64_t p, e;
+        bag_range<Cfg::kNtMeta, Cfg::kClamp>(t.offsets, t.n_bags, t.n_idx, t.fixed_pooling, bag, p, e);
+        typename Ops::Acc acc = Ops::zero();
+        walk_bag<IdxT, LPR, Cfg, Ops>(t.indices, p, e, sub, grp, live, acc, NoProbe{}, [&](uint64_t r, uint32_t) -> Mx4Piece {
+            const uint64_t at = clamp_row<Cfg::kClamp, IdxT>(r, t.last_row) * row_stride;
+            return Mx4Piece{load_row<Cfg::kNtRow>(wsub + at), load_mx4_scale(ssub + at)};
+        });
+        store_row<Ops, Cfg, LPR>(acc, t.out + bag * out_stride, sub, grp, chunks, live);
+    }
+}
+
+// pool_walk for MXFP4 rows: kUnroll indices (and weights) loaded, padding entries dropped, the remaining blocks and scales
+// gathered together, then taken in order.
+template <typename IdxT, class Cfg>
+__device__ __forceinline__ void mx4_pool_walk(const IdxT *__restrict__ indices, const PoolArgs &a, uint64_t p, uint64_t e,
+                                              const char *__restrict__ wsub, const char *__restrict__ ssub, uint32_t row_stride,
+                                              uint64_t last_row, f32x32 &acc, uint32_t &cnt) {
+    constexpr int U = Cfg::kUnroll;
+    for (; p < e; p += U) {
+        const uint64_t left = e - p;
+        uint64_t r[U];
+        float w[U];
+        bool use[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            use[k] = (uint64_t)k < left;
+            r[k] = 0;
+            w[k] = 1.f;
+            if (use[k]) {
+                r[k] = (uint64_t)load_meta<Cfg::kNtMeta>(indices + p + k);
+                if (a.psw != nullptr) w[k] = load_meta<Cfg::kNtMeta>(a.psw + p + k);
+            }
+            use[k] = use[k] && r[k] != a.pad;
+        }
+        Mx4Piece v[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            v[k] = Mx4Piece{u32x4{0u, 0u, 0u, 0u}, 0u};
+            if (use[k]) {
+                const uint64_t at = clamp_row<Cfg::kClamp, IdxT>(r[k], last_row) * row_stride;
+                v[k] = Mx4Piece{load_row<Cfg::kNtRow>(wsub + at), load_mx4_scale(ssub + at)};
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < U; k++)
+            if (use[k]) {
+                const f32x32 x = widen_mx4x32(v[k]);
+#pragma unroll
+                for (int c = 0; c < 32; c++) acc[c] = pool_op1(acc[c], x[c], w[k], a.op, cnt == 0u);
+                cnt++;
+            }
+    }
+}
+
+template <typename IdxT, int LPR, class Cfg>
+__global__ void __launch_bounds__(Cfg::kBlock)
+bag_mx4pool_group_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg, const uint32_t *__restrict__ xmap) {
+    using Ops = RowOps<kMXFP4>;
+    constexpr uint32_t kWaves = Cfg::kBlock / 64;
+    constexpr uint32_t BPW = 64 / LPR;
+    constexpr uint32_t BAGS_PER_TILE = BPW * kWaves;
+
+    uint32_t desc_i, tile;
+    if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
+    const uint32_t chunks = chunks_arg & ~kXmapDirect;
+    const DevDesc *dp = descs + desc_i;
+    const DescView<IdxT> t(dp);
+    const PoolArgs a = pool_args(dp);
+
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
+    const uint32_t row_stride = mx4_row_stride(chunks);
+    const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
+    const char *__restrict__ wsub = t.weights + sub * 16u;
+    const char *__restrict__ ssub = t.weights + chunks * 16u + sub;
+
+    if (tile < t.n_tiles) {
+        const uint64_t bag = (uint64_t)tile * BAGS_PER_TILE + wave * BPW + grp;
+        const bool live = sub < chunks;
+        if (bag >= t.n_bags) return;                   // whole lane group leaves together
+        uint64_t p, e;
+        bag_range<Cfg::kNtMeta, Cfg::kClamp>(t.offsets, t.n_bags, t.n_idx, t.fixed_pooling, bag, p, e);
+        typename Ops::Acc acc = Ops::zero();
+        uint32_t cnt = 0;
+        if (live) mx4_pool_walk<IdxT, Cfg>(t.indices, a, p, e, wsub, ssub, row_stride, t.last_row, acc, cnt);
+        if (a.mean && cnt > 1u) {
+#pragma unroll
+            for (int c = 0; c < 32; c++) acc[c] = pool_finish1(acc[c], cnt, true);
+        }
+        store_row<Ops, Cfg, LPR>(acc, t.out + bag * out_stride, sub, grp, chunks, live);
+    }
+}
 
 }  // namespace pimemb

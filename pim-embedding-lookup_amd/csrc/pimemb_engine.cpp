@@ -60,7 +60,7 @@ double now_us() {
     return duration<double, std::micro>(steady_clock::now().time_since_epoch()).count();
 }
 
-size_t elem_size(int dtype) { return pimemb::elem_bytes(dtype); }
+size_t row_stride(int dtype, uint32_t dim) { return (size_t)pimemb::row_stride_bytes(dtype, dim); }   // bytes from one row to the next
 size_t index_size(emb_index_type t) { return t == EMB_IDX_I64 ? 8 : 4; }
 
 struct Table {
@@ -484,12 +484,17 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
                 return fail(EMB_ERR_INVALID, "ranged lookup: desc %u: one index per bag only (offsets NULL, fixed_pooling 1)", i);
             if (t.geom.scalar_lanes)
                 return fail(EMB_ERR_UNSUPPORTED, "ranged lookup: desc %u: rows must be 16-byte multiples up to 1 KiB", i);
+            if (t.dtype == pimemb::kMXFP4)
+                return fail(EMB_ERR_UNSUPPORTED, "ranged lookup: desc %u: table %u is MXFP4, which the lane-group kernels serve only "
+                            "(no ranged, counted or typed lookup)", i, u.table_id);
         }
         uint32_t pool_kind = 0;
         if (pools && !is_plain_sum(pools[i])) {
             const emb_pool_spec &ps = pools[i];
             if (ps.mode > EMB_POOL_MAX || (ps.flags & ~(EMB_POOL_PADDING | EMB_POOL_OUT_TABLE_DTYPE)) != 0)
                 return fail(EMB_ERR_INVALID, "desc %u: bad pooling spec (mode %u, flags 0x%x)", i, ps.mode, ps.flags);
+            if ((ps.flags & EMB_POOL_OUT_TABLE_DTYPE) && t.dtype == pimemb::kMXFP4)
+                return fail(EMB_ERR_UNSUPPORTED, "desc %u: EMB_POOL_OUT_TABLE_DTYPE: table %u is MXFP4, whose pooled rows are fp32 only", i, u.table_id);
             if ((ps.flags & EMB_POOL_OUT_TABLE_DTYPE) && t.dtype != EMB_F16 && t.dtype != EMB_BF16)
                 return fail(EMB_ERR_UNSUPPORTED, "desc %u: EMB_POOL_OUT_TABLE_DTYPE needs an fp16 or bf16 table (table %u has dtype %d)", i,
                             u.table_id, (int)t.dtype);
@@ -525,6 +530,7 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
             if (force && g.kind != pimemb::KERNEL_ANYDIM && group_idx <= 2 * group_bags)
                 g.kind = force[0] == 'g' ? pimemb::KERNEL_GROUP : pimemb::KERNEL_WAVEBATCH;
         }
+        if (g.dtype == pimemb::kMXFP4) g.kind = pimemb::KERNEL_GROUP;      // (whatever the shape: MXFP4 has the lane-group kernels only)
         g.ranged = row_lo != nullptr;
         if (g.ranged && g.kind == pimemb::KERNEL_GROUP) g.kind = pimemb::KERNEL_WAVEBATCH;    // (small launches too: the predicate lives there)
         if (g.pool && g.kind == pimemb::KERNEL_WAVEBATCH2) g.kind = pimemb::KERNEL_WAVEBATCH;  // (the pooled family has one wave-batch geometry)
@@ -582,7 +588,7 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
             r->n_bags += u.n_bags;
             r->n_indices += u.n_indices;
             // algorithmic bytes, SURVEY.md section 8 row D
-            r->bytes += u.n_indices * ((uint64_t)t.dim * elem_size(t.dtype) + isz) +
+            r->bytes += u.n_indices * ((uint64_t)row_stride(t.dtype, t.dim) + isz) +
                         (u.offsets ? u.n_bags * isz : 0) + u.n_bags * (uint64_t)t.dim * (g.out_half ? 2 : 4);
         }
         // several tables in one big one-hot launch: XCD-aware workgroup map (one table <-> one XCD's
@@ -1200,13 +1206,17 @@ static int alloc_table(emb_engine *e, uint32_t table_id, uint64_t nr_rows, uint3
     if (nr_rows == 0) return fail(EMB_ERR_INVALID, "table %u: nr_rows is 0", table_id);
     LaunchGeom geom;
     int rc = pimemb::geometry_for(dtype, dim, &geom);
+    if (dtype == pimemb::kMXFP4 && rc == EMB_ERR_INVALID)
+        return fail(rc, "table %u: MXFP4 rows are blocks of 32 elements: dim %u is no multiple of 32", table_id, dim);
+    if (dtype == pimemb::kMXFP4 && rc == EMB_ERR_UNSUPPORTED)
+        return fail(rc, "table %u: MXFP4 tables take dim 32 .. 2048 (64 lanes per row), not %u", table_id, dim);
     if (rc == EMB_ERR_UNSUPPORTED)
         return fail(rc, "table %u: dim %u of dtype %d is not supported (dim must be > 0)", table_id, dim, (int)dtype);
     if (rc) return fail(rc, "table %u: bad dtype %d", table_id, (int)dtype);
     DeviceGuard g(e->device);
     std::lock_guard<std::mutex> lk(e->mu);
     Table &t = e->tables[table_id];
-    size_t bytes = (size_t)nr_rows * dim * elem_size(dtype);
+    size_t bytes = (size_t)nr_rows * row_stride(dtype, dim);
     if (t.n_hot) {   // (re)loading a table invalidates its hot-row copy
         HIP_TRY(hipDeviceSynchronize());
         clear_hot(t);
@@ -1256,6 +1266,8 @@ int emb_load_table_column(emb_engine *e, uint32_t table_id, uint32_t col, const 
     if (table_id >= e->tables.size() || !e->tables[table_id].rows)
         return fail(EMB_ERR_INVALID, "table %u is not allocated", table_id);
     Table &t = e->tables[table_id];
+    if (t.dtype == pimemb::kMXFP4)
+        return fail(EMB_ERR_UNSUPPORTED, "emb_load_table_column: table %u is MXFP4: a row interleaves 32-element blocks and their scales, it has no columns to load", table_id);
     if (t.dtype != EMB_FIXED32) return fail(EMB_ERR_INVALID, "table %u is not EMB_FIXED32", table_id);
     if (col >= t.dim) return fail(EMB_ERR_INVALID, "table %u: col %u >= dim %u", table_id, col, t.dim);
     if (nr_rows > t.nr_rows)
@@ -1290,6 +1302,8 @@ int emb_set_hot_rows(emb_engine *e, uint32_t table_id, const uint64_t *row_ids, 
     if (table_id >= e->tables.size() || !e->tables[table_id].rows)
         return fail(EMB_ERR_INVALID, "table %u is not loaded", table_id);
     if (n_rows && !row_ids) return fail(EMB_ERR_INVALID, "row_ids is NULL");
+    if (e->tables[table_id].dtype == pimemb::kMXFP4)
+        return fail(EMB_ERR_UNSUPPORTED, "emb_set_hot_rows: table %u is MXFP4, which has no hot-row kernel", table_id);
     DeviceGuard g(e->device);
     std::lock_guard<std::mutex> lk(e->mu);
     Table &t = e->tables[table_id];
@@ -1329,6 +1343,8 @@ int emb_learn_hot_rows(emb_engine *e, uint32_t table_id, const void *indices, ui
     if (table_id >= e->tables.size() || !e->tables[table_id].rows) return fail(EMB_ERR_INVALID, "table %u is not loaded", table_id);
     if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "bad index type");
     if (n_indices && !indices) return fail(EMB_ERR_INVALID, "emb_learn_hot_rows: indices is NULL");
+    if (e->tables[table_id].dtype == pimemb::kMXFP4)
+        return fail(EMB_ERR_UNSUPPORTED, "emb_learn_hot_rows: table %u is MXFP4, which has no hot-row kernel", table_id);
     if (n_chosen) *n_chosen = 0;
     if (share) *share = 0.f;
     // the sample: up to four evenly spaced runs of 65 536 ids (the whole array when it is that small) -- bags are independent
@@ -2261,7 +2277,7 @@ int emb_queue_flush(emb_queue *q, void *stream, uint32_t *n_requests) {
     KernelKind kind = q->kind;
     uint32_t max_tiles = g.max_tiles;
     if (kind == pimemb::KERNEL_GROUP) {
-        kind = pimemb::choose_kernel(g.bags, g.idx, q->geom);
+        kind = q->dtype == pimemb::kMXFP4 ? pimemb::KERNEL_GROUP : pimemb::choose_kernel(g.bags, g.idx, q->geom);   // (MXFP4: lane-group only)
         if (kind != pimemb::KERNEL_GROUP) {
             const uint32_t bpt = pimemb::bags_per_tile(kind, q->geom);
             max_tiles = 0;

@@ -66,6 +66,17 @@ template <> struct WaveCfgOf<kF8E5M2> { using One = WaveCfgF8; using Two = Wave2
 // tables, no store shuffles; the configurations of their tables, under which none of them spills
 template <> struct WaveCfgOf<EMB_F16 | kHalfOutDT> : WaveCfgOf<EMB_F16> {};
 template <> struct WaveCfgOf<EMB_BF16 | kHalfOutDT> : WaveCfgOf<EMB_BF16> {};
+// MXFP4 rows (bag_mx4sum_group_kernel / bag_mx4pool_group_kernel): 32 fp32 accumulators per lane, and every gather in flight
+// holds five registers (16 bytes + the scale byte).  The lane-group configuration as it is -- eight gathers in flight, no
+// occupancy asked for beyond one 256-thread workgroup per CU: the compiler lands every MXFP4 kernel at 119-126 VGPRs (four
+// wavefronts per SIMD, as the fp8 kernels), none spills or uses scratch (tests/test_mxfp4_cpu.py reads it off the code object).
+// Unroll 4 saves nothing: 96-130 VGPRs, one kernel then over the 128 of the fourth wavefront, and measured on MI355X it loses at
+// the pooled point (dim 128, 32 per bag: 19.45 us against 16.72; profiles/mxfp4/README.md).  -DPIMEMB_MX4_UNROLL=n repeats it.
+#ifndef PIMEMB_MX4_UNROLL
+#define PIMEMB_MX4_UNROLL 8
+#endif
+using Mx4GroupCfg = BagCfg<256, PIMEMB_MX4_UNROLL, true, false, 8, 1, 1, false, false, /*IDX_SHUFFLE*/ true, kClampInputs>;
+static_assert(Mx4GroupCfg::kBlock == GroupCfg::kBlock, "bags_per_tile(KERNEL_GROUP) is one figure for every dtype");
 // pooled launches over tables with a hot-row set: persistent 1024-thread workgroups stage the set into LDS
 using HotCfg = BagCfg<1024, 8, true, false, 8, 1, 1, false, false, /*IDX_SHUFFLE*/ true, kClampInputs>;
 constexpr int kBlock = 256;  // helper kernels below
@@ -1120,6 +1131,16 @@ hipError_t launch_widen_words(const WidenArgs &a, hipStream_t stream) {
 
 int geometry_for(int dtype, uint32_t dim, LaunchGeom *g) {
     const int dt = dtype;
+    if (dt == kMXFP4) {      // one 16-byte piece per 32-element block, 1..64 lanes per row; no any-dim path
+        if (dim % 32u != 0u) return EMB_ERR_INVALID;
+        if (dim == 0 || dim > 2048u) return EMB_ERR_UNSUPPORTED;
+        g->anydim_vec = false;
+        g->scalar_lanes = 0;
+        g->chunks = dim / 32u;
+        g->lanes_per_row = 1;
+        while (g->lanes_per_row < g->chunks) g->lanes_per_row <<= 1;
+        return EMB_OK;
+    }
     if (dt != EMB_F32 && dt != EMB_F16 && dt != EMB_FIXED32 && dt != EMB_BF16 && dt != kF8E4M3 && dt != kF8E5M2) return EMB_ERR_INVALID;
     const uint32_t elem = elem_bytes(dt);
     uint64_t row_bytes = (uint64_t)dim * elem;
@@ -1183,6 +1204,16 @@ hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max
     if (kind == KERNEL_ANYDIM && (g.scalar_lanes == 0 || d_xmap != nullptr)) return hipErrorInvalidValue;
     if (out_half && (ranged || kind == KERNEL_HOT)) return hipErrorInvalidValue;
     const MappedLaunch m(n_descs, max_tiles, g, d_xmap, xgrid, xdirect);
+    if (dtype == kMXFP4) {      // the lane-group kernel only: no wave-batch, ranged, hot-row or half-output twin
+        if (kind != KERNEL_GROUP || ranged || out_half || g.scalar_lanes) return hipErrorInvalidValue;
+        return with_lanes_per_row(g.lanes_per_row, [&](auto l) {
+            constexpr int L = decltype(l)::value;
+            if (itype == EMB_IDX_U32)
+                hipLaunchKernelGGL((bag_mx4sum_group_kernel<uint32_t, L, Mx4GroupCfg>), m.grid, dim3(Mx4GroupCfg::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+            else
+                hipLaunchKernelGGL((bag_mx4sum_group_kernel<int64_t, L, Mx4GroupCfg>), m.grid, dim3(Mx4GroupCfg::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+        });
+    }
     auto launch = [&](auto idx, auto dt) {
         using IdxT = decltype(idx);
         constexpr int DT = decltype(dt)::value;
@@ -1207,6 +1238,16 @@ hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t ma
     if (kind == KERNEL_ANYDIM ? (g.scalar_lanes == 0 || d_xmap != nullptr) : (kind != KERNEL_WAVEBATCH && kind != KERNEL_GROUP))
         return hipErrorInvalidValue;
     const MappedLaunch m(n_descs, max_tiles, g, d_xmap, xgrid, xdirect);
+    if (dtype == kMXFP4) {      // the lane-group kernel only
+        if (kind != KERNEL_GROUP || g.scalar_lanes) return hipErrorInvalidValue;
+        return with_lanes_per_row(g.lanes_per_row, [&](auto l) {
+            constexpr int L = decltype(l)::value;
+            if (itype == EMB_IDX_U32)
+                hipLaunchKernelGGL((bag_mx4pool_group_kernel<uint32_t, L, Mx4GroupCfg>), m.grid, dim3(Mx4GroupCfg::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+            else
+                hipLaunchKernelGGL((bag_mx4pool_group_kernel<int64_t, L, Mx4GroupCfg>), m.grid, dim3(Mx4GroupCfg::kBlock), 0, stream, d_descs, m.chunks, d_xmap);
+        });
+    }
     return with_types<false>(itype, dtype, [&](auto idx, auto dt) {
         using IdxT = decltype(idx);
         constexpr int DT = decltype(dt)::value;

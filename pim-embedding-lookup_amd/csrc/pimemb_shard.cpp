@@ -1422,6 +1422,8 @@ int emb_shard_create(emb_engine *e, emb_comm *comm, const emb_shard_config *cfg,
             rc = emb_table_info(e, tb.engine_table, nullptr, nullptr, &d, &dt);
             if (rc) return bail(rc);
             if (d != s->dim) return bail(fail(EMB_ERR_INVALID, "emb_shard_create: table %u: engine table %u has dim %u, not %u", t, tb.engine_table, d, s->dim));
+            if (pimemb::dtype_value(dt) == pimemb::kMXFP4)      // (the sharded step's ranged and routed launches have no MXFP4 kernel)
+                return bail(fail(EMB_ERR_UNSUPPORTED, "emb_shard_create: table %u: engine table %u is MXFP4, which sharded lookups do not serve", t, tb.engine_table));
             s->elem_bytes[t] = pimemb::elem_bytes(pimemb::dtype_value(dt));
         }
     }

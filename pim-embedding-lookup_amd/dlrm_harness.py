@@ -33,6 +33,8 @@ class EmbeddingBagCollection:
         # does; None: fp32 rows whatever the tables hold
         if out_dtype not in (None, "weight"):
             raise ValueError('out_dtype must be None or "weight"')
+        if out_dtype == "weight" and dtype == "mxfp4":
+            raise ValueError('out_dtype="weight" needs f16 or bf16 tables: mxfp4 tables return fp32 rows only')
         if out_dtype == "weight" and str(dtype).startswith("fp8"):
             raise ValueError('out_dtype="weight" needs f16 or bf16 tables: fp8 tables return fp32 rows only')
         self._out = "table" if out_dtype == "weight" and dtype in ("f16", "bf16") else None
@@ -53,8 +55,13 @@ class EmbeddingBagCollection:
                 w = torch.empty((n, self.m), dtype=torch.float32, device=self.device).uniform_(-a, a, generator=g)
             tdt = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16, "fp8_e4m3": torch.float8_e4m3fn,
                    "fp8_e5m2": torch.float8_e5m2}.get(dtype)
+            if dtype == "mxfp4":       # fp32 checkpoints are quantised by the OCP MX rule (formats.to_mxfp4); m a multiple of 32
+                from .formats import to_mxfp4
+                from .lib import EMB_MXFP4
+                self.engine.load_table(k, to_mxfp4(w.float().cpu().numpy()), dtype=EMB_MXFP4)
+                continue
             if tdt is None:
-                raise ValueError("dtype must be 'f32', 'f16', 'bf16', 'fp8_e4m3' or 'fp8_e5m2'")
+                raise ValueError("dtype must be 'f32', 'f16', 'bf16', 'fp8_e4m3', 'fp8_e5m2' or 'mxfp4'")
             if dtype != "f32":
                 w = w.to(tdt)          # (fp32 checkpoints are rounded by torch: nearest even)
             self.engine.load_table(k, w)

@@ -349,7 +349,12 @@ class EmbeddingEngine:
         """rows: [nr_rows, dim] numpy float32/float16/int32 (int32 = x1e9 fixed point) or a torch
         tensor (CPU or CUDA) of those dtypes, of torch.bfloat16, torch.float8_e4m3fn or torch.float8_e5m2.  numpy has no
         bfloat16 and no fp8: a uint16 array holds bf16 bits (formats.to_bf16_bits) when -- and only when -- dtype=EMB_BF16
-        says so, a uint8 array fp8 bits (formats.to_f8_bits) only with dtype=EMB_F8_E4M3 / EMB_F8_E5M2."""
+        says so, a uint8 array fp8 bits (formats.to_f8_bits) only with dtype=EMB_F8_E4M3 / EMB_F8_E5M2.
+        MXFP4 (dtype=EMB_MXFP4): a uint8 array or tensor of FUSED rows [nr_rows, EMB_MXFP4_ROW_STRIDE(dim)] (formats.to_mxfp4),
+        or the pair (elements [nr_rows, dim/2], scales [nr_rows, dim/32]) -- uint8 arrays or tensors, or torch.float4_e2m1fn_x2 /
+        torch.float8_e8m0fnu tensors (CPU or device), which need no dtype=.  Plain uint8 without dtype= stays refused."""
+        if isinstance(rows, (tuple, list)) and len(rows) == 2:
+            rows, dtype = self._fuse_mxfp4_pair(rows[0], rows[1], dtype), _l.EMB_MXFP4
         if _is_torch(rows):
             import torch
             tmap = {torch.float32: _l.EMB_F32, torch.float16: _l.EMB_F16, torch.int32: _l.EMB_FIXED32,
@@ -367,9 +372,37 @@ class EmbeddingEngine:
             space, ptr, shape = _l.EMB_MEM_HOST, rows.ctypes.data, rows.shape
         if len(shape) != 2:
             raise ValueError("table must be 2-D [nr_rows, dim]")
+        if dt == _l.EMB_MXFP4:      # fused rows: their width is the row stride, which names the dim
+            from .formats import mxfp4_dim_of_stride
+            if str(rows.dtype).replace("torch.", "") != "uint8":
+                raise TypeError(f"an MXFP4 table is uint8 fused rows or an (elements, scales) pair, not {rows.dtype}")
+            shape = (shape[0], mxfp4_dim_of_stride(shape[1]))
         _l.check(self._L.emb_load_table(self._h, table_id, shape[0], shape[1], dt, ptr, space))
         self._tables[table_id] = (shape[0], shape[1], dt)
         self._same_dim.clear()
+
+    @staticmethod
+    def _fuse_mxfp4_pair(elements, scales, dtype):
+        """(elements, scales) -> fused MXFP4 rows: a uint8 numpy array, or a uint8 tensor on the pair's device."""
+        if dtype not in (None, _l.EMB_MXFP4):
+            raise TypeError("an (elements, scales) pair is an MXFP4 table: dtype is EMB_MXFP4 or left out")
+        from .formats import mxfp4_join, mxfp4_row_stride
+        if not (_is_torch(elements) and _is_torch(scales)):
+            if _is_torch(elements) or _is_torch(scales):
+                raise TypeError("MXFP4 pair: both numpy arrays or both torch tensors")
+            if dtype is None:
+                raise TypeError("a pair of plain uint8 arrays is an MXFP4 table only when dtype=EMB_MXFP4 says so")
+            return mxfp4_join(elements, scales)
+        import torch
+        typed = elements.dtype == torch.float4_e2m1fn_x2 and scales.dtype == torch.float8_e8m0fnu
+        if not typed and not (elements.dtype == torch.uint8 and scales.dtype == torch.uint8 and dtype == _l.EMB_MXFP4):
+            raise TypeError("MXFP4 pair: torch.float4_e2m1fn_x2 elements with torch.float8_e8m0fnu scales, or two uint8 tensors "
+                            f"with dtype=EMB_MXFP4; got {elements.dtype} and {scales.dtype}")
+        el, sc = elements.contiguous().view(torch.uint8), scales.contiguous().view(torch.uint8)
+        if el.dim() != 2 or sc.dim() != 2 or el.shape[0] != sc.shape[0] or sc.shape[1] == 0 or el.shape[1] != 16 * sc.shape[1] or el.device != sc.device:
+            raise ValueError(f"MXFP4 pair: elements [rows, dim/2] and scales [rows, dim/32] on one device, got {tuple(el.shape)} and {tuple(sc.shape)}")
+        pad = mxfp4_row_stride(2 * el.shape[1]) - el.shape[1] - sc.shape[1]
+        return torch.cat([el, sc, torch.zeros((el.shape[0], pad), dtype=torch.uint8, device=el.device)], dim=1)
 
     def alloc_table(self, table_id: int, nr_rows: int, dim: int, dtype: int) -> None:
         _l.check(self._L.emb_alloc_table(self._h, table_id, nr_rows, dim, dtype))
@@ -406,10 +439,13 @@ class EmbeddingEngine:
         through it changes what lookups return (and leaves any hot-row copy stale)."""
         import torch
         ptr, n, d, dt = self.table_info(table_id)
+        if dt == _l.EMB_MXFP4:      # the fused rows as they lie in HBM: uint8 [nr_rows, row stride] (formats.from_mxfp4 reads them)
+            from .formats import mxfp4_row_stride
+            d = mxfp4_row_stride(d)
         # (the CUDA array interface has no bfloat16 typestr: the bits travel as uint16 and are viewed as bf16)
         # (nor an fp8 one: uint8, viewed as the float8 dtype)
         typestr = {_l.EMB_F32: "<f4", _l.EMB_F16: "<f2", _l.EMB_FIXED32: "<i4", _l.EMB_BF16: "<u2", _l.EMB_F8_E4M3: "|u1",
-                   _l.EMB_F8_E5M2: "|u1"}[dt]
+                   _l.EMB_F8_E5M2: "|u1", _l.EMB_MXFP4: "|u1"}[dt]
 
         class _View:
             __cuda_array_interface__ = {"shape": (n, d), "typestr": typestr, "data": (ptr, False), "version": 2,
@@ -445,6 +481,8 @@ class EmbeddingEngine:
             raise ValueError("table_ids, indices and offsets must have equal length")
         if half is not None:       # refused here, before anything is allocated or any C call made: an fp8 output would round lossily
             for t, h in zip(table_ids, half):
+                if h and t in self._tables and self._tables[t][2] == _l.EMB_MXFP4:
+                    raise TypeError(f'table {t}: out_dtype="table" needs an fp16 or bf16 table; an MXFP4 table returns fp32 rows only')
                 if h and t in self._tables and self._tables[t][2] in _F8_TORCH:
                     raise TypeError(f'table {t}: out_dtype="table" needs an fp16 or bf16 table; an fp8 table ({_F8_TORCH[self._tables[t][2]]}) '
                                     "returns fp32 rows only")

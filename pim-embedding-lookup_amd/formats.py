@@ -91,6 +91,98 @@ def to_f8_bits(x, kind) -> np.ndarray:
     return (r.astype(np.uint32) | sign).astype(np.uint8)
 
 
+# ---- MXFP4 (OCP Microscaling v1.0): blocks of 32 E2M1 elements under one E8M0 scale; EMB_MXFP4 tables ------------------------
+# A fused row, as pimemb.h lays it out: dim/2 element bytes (element 2j in the low nibble of byte j), dim/32 scale bytes, zero
+# padding up to a multiple of 16.
+_E2M1 = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], dtype=np.float64)
+_E2M1_MIDS = np.array([0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0], dtype=np.float64)      # between code k and code k + 1
+
+
+def mxfp4_row_bytes(dim: int) -> int:
+    return dim // 2 + dim // 32
+
+
+def mxfp4_row_stride(dim: int) -> int:
+    """Bytes from one fused row to the next (EMB_MXFP4_ROW_STRIDE): 32 / 48 / 80 / 144 / 272 / 1088 at dim 32 / 64 / 128 / 256 / 512 / 2048."""
+    return (mxfp4_row_bytes(dim) + 15) & ~15
+
+
+def mxfp4_dim_of_stride(stride: int) -> int:
+    """The dim whose fused rows are `stride` bytes wide (17 bytes per block, rounded up to 16: no two dims share a stride)."""
+    blocks = stride // 17
+    if blocks < 1 or mxfp4_row_stride(32 * blocks) != stride:
+        raise ValueError(f"{stride} bytes is not the row stride of any MXFP4 dim (EMB_MXFP4_ROW_STRIDE)")
+    return 32 * blocks
+
+
+def _mxfp4_check_dim(dim: int) -> None:
+    if dim <= 0 or dim % 32:
+        raise ValueError(f"MXFP4 rows are blocks of 32 elements: dim {dim} is no positive multiple of 32")
+
+
+def mxfp4_split(rows, dim: int):
+    """Fused rows uint8 [rows, stride] -> (elements uint8 [rows, dim/2], scales uint8 [rows, dim/32]), copies."""
+    _mxfp4_check_dim(dim)
+    r = np.asarray(rows, dtype=np.uint8)
+    if r.ndim != 2 or r.shape[1] < mxfp4_row_bytes(dim):
+        raise ValueError(f"fused MXFP4 rows of dim {dim} are [rows, >= {mxfp4_row_bytes(dim)}] uint8, got {r.shape}")
+    return r[:, :dim // 2].copy(), r[:, dim // 2:mxfp4_row_bytes(dim)].copy()
+
+
+def mxfp4_join(elements, scales) -> np.ndarray:
+    """(elements uint8 [rows, dim/2], scales uint8 [rows, dim/32]) -> fused rows uint8 [rows, stride], zero padded."""
+    el, sc = np.asarray(elements, dtype=np.uint8), np.asarray(scales, dtype=np.uint8)
+    if el.ndim != 2 or sc.ndim != 2 or el.shape[0] != sc.shape[0] or el.shape[1] != 16 * sc.shape[1] or sc.shape[1] == 0:
+        raise ValueError(f"MXFP4 pair: elements [rows, dim/2] and scales [rows, dim/32], got {el.shape} and {sc.shape}")
+    dim = 2 * el.shape[1]
+    out = np.zeros((el.shape[0], mxfp4_row_stride(dim)), dtype=np.uint8)
+    out[:, :dim // 2] = el
+    out[:, dim // 2:mxfp4_row_bytes(dim)] = sc
+    return out
+
+
+def from_mxfp4(rows_u8, dim: int) -> np.ndarray:
+    """Fused MXFP4 rows -> float32 [rows, dim]: e2m1 * 2^(s - 127) as fp32 arithmetic gives it -- exact, fp32 denormals included,
+    but for the few products beyond the largest fp32 (scale bytes 253 / 254 under the largest magnitudes), which are +-inf; a block
+    whose scale byte is 0xFF is NaN."""
+    el, sc = mxfp4_split(rows_u8, dim)
+    nib = np.empty((el.shape[0], dim), dtype=np.uint8)
+    nib[:, 0::2] = el & 0xF
+    nib[:, 1::2] = el >> 4
+    val = np.where(nib & 8, -1.0, 1.0) * _E2M1[nib & 7]                         # (-0.0 for nibble 0x8)
+    s = np.repeat(sc.astype(np.int32), 32, axis=1)
+    with np.errstate(over="ignore"):
+        out = np.ldexp(val, s - 127).astype(np.float32)                         # float64 product of two exact values: exact
+    out[s == 255] = np.nan
+    return out
+
+
+def to_mxfp4(x_f32) -> np.ndarray:
+    """[rows, dim] real array (dim a multiple of 32) -> fused MXFP4 rows uint8 [rows, stride], by the OCP MX v1.0 rule: per block
+    X = 2^(floor(log2(max|v|)) - 2), its scale byte clamped to [0, 254]; elements v / X rounded to nearest, ties to the even
+    code, saturating at +-6.  A block that quantises to all zeros (an all-zero block; a block too small for scale byte 0) gets
+    scale byte 127 and keeps its signs, so the function is idempotent on its own output.  Non-finite input raises ValueError.
+    (Wider than fp32 on purpose: a float64 array can reach the upper clamp, which no finite fp32 does.)"""
+    x = np.asarray(x_f32, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("to_mxfp4 takes a 2-D [rows, dim] array")
+    _mxfp4_check_dim(x.shape[1])
+    if not np.isfinite(x).all():
+        raise ValueError("to_mxfp4: non-finite input (MXFP4 elements have no inf and no NaN)")
+    rows, dim = x.shape
+    blk = x.reshape(rows, dim // 32, 32)
+    amax = np.abs(blk).max(axis=2)
+    _, ex = np.frexp(amax)                                                      # amax = m * 2^ex, m in [0.5, 1): floor(log2) = ex - 1
+    s = np.clip(ex.astype(np.int64) - 1 - 2 + 127, 0, 254)
+    a = np.abs(np.ldexp(blk, (127 - s)[:, :, None]))                            # |v / X|, exact in float64
+    code = np.zeros(a.shape, dtype=np.uint8)
+    for k, mid in enumerate(_E2M1_MIDS):                                        # a tie goes to the even one of codes k, k + 1
+        code += (a >= mid) if k % 2 else (a > mid)
+    s = np.where((code == 0).all(axis=2), 127, s)
+    nib = (code | (np.signbit(blk).astype(np.uint8) << 3)).reshape(rows, dim)
+    return mxfp4_join(nib[:, 0::2] | (nib[:, 1::2] << 4), s.astype(np.uint8))
+
+
 class CriteoKaggleNpz:
     """Categorical side of a processed Criteo-Kaggle file as embedding-lookup batches."""
 

@@ -12,6 +12,7 @@ EMB_OK = 0
 EMB_ERR_INVALID, EMB_ERR_NOMEM, EMB_ERR_DEVICE, EMB_ERR_UNSUPPORTED, EMB_ERR_RANGE = -1, -2, -3, -4, -5
 EMB_F32, EMB_F16, EMB_FIXED32, EMB_BF16 = 0, 1, 2, 3
 EMB_F8_E4M3, EMB_F8_E5M2 = 8, 9     # OCP fp8 tables (#defines outside the enum in pimemb.h; 4-7 stay invalid)
+EMB_MXFP4 = 10                      # OCP MXFP4 tables: fused rows of E2M1 blocks and E8M0 scales (pimemb.h, formats.to_mxfp4)
 EMB_IDX_U32, EMB_IDX_I64 = 0, 1
 EMB_MEM_HOST, EMB_MEM_DEVICE = 0, 1
 EMB_FLAG_STAGE_TIMING, EMB_FLAG_CHECK_INPUTS, EMB_FLAG_DEFER_CHECK = 1, 2, 4

@@ -21,6 +21,9 @@ with an fp16 / bf16 weight return the weight's dtype, as nn.EmbeddingBag does: t
 engine's out_dtype="table", EMB_POOL_OUT_TABLE_DTYPE).  The fused modules follow their bags unless told otherwise.
 Weights may also be torch.float8_e4m3fn / torch.float8_e5m2 (dtype=, or a float8 `_weight`): 1-byte rows, `weight` and
 `state_dict()` return them as float8; their output is always fp32 (out_dtype="weight" is refused).
+dtype="mxfp4": an MXFP4 table (OCP Microscaling, 4.25 bits per element; embedding_dim a multiple of 32 up to 2048).  An fp32
+`_weight` is quantised once (formats.to_mxfp4), prepacked fused rows -- uint8 [num_embeddings, EMB_MXFP4_ROW_STRIDE(dim)] -- are
+taken as they are; `weight` and `state_dict()` hold the fused rows, which load back unchanged.  Output fp32 only.
 
 Input checking.  The C ABI is as unchecked as the reference (an out-of-range index is a wild read there,
 emb_dpu_lookup.c:113); these modules are what user tensors reach first, so by default every forward goes through
@@ -73,10 +76,24 @@ def _engine_out_dtype(out_dtype, table_dtype):
     """A module's out_dtype (None: fp32 rows; "weight": the weight's dtype) -> the engine's (None | "table")."""
     if out_dtype not in (None, "weight"):
         raise ValueError(f'out_dtype has to be None or "weight", got {out_dtype!r}')
+    if out_dtype == "weight" and table_dtype == "mxfp4":
+        raise ValueError('out_dtype="weight" needs an fp16 or bf16 weight: an MXFP4 table returns fp32 rows only')
     if out_dtype == "weight" and table_dtype in (torch.float8_e4m3fn, torch.float8_e5m2):
         raise ValueError('out_dtype="weight" needs an fp16 or bf16 weight: a float8 weight returns fp32 rows only (an fp8 output would '
                          "round the pooled value lossily)")
     return "table" if out_dtype == "weight" and table_dtype in (torch.float16, torch.bfloat16) else None
+
+
+def _mxfp4_rows(w, num_embeddings: int, embedding_dim: int, device):
+    """A module's MXFP4 weight -> (fused rows as a uint8 tensor on `device`, None) or (None, the shape error): prepacked fused
+    rows as they are, an fp32 [num_embeddings, embedding_dim] weight quantised once."""
+    from .formats import mxfp4_row_stride, to_mxfp4
+    if w.dtype == torch.uint8 and tuple(w.shape) == (num_embeddings, mxfp4_row_stride(embedding_dim)):
+        return w.detach().to(device).contiguous(), None
+    if w.dtype == torch.uint8 or tuple(w.shape) != (num_embeddings, embedding_dim):
+        return None, (f"an MXFP4 weight is fp32 ({num_embeddings}, {embedding_dim}) or fused uint8 rows ({num_embeddings}, "
+                      f"{mxfp4_row_stride(embedding_dim)}), got {w.dtype} {tuple(w.shape)}")
+    return torch.from_numpy(to_mxfp4(w.detach().float().cpu().numpy())).to(device), None
 
 
 def _bags_from(input, offsets, include_last_offset: bool):
@@ -121,6 +138,12 @@ class EmbeddingBag(torch.nn.Module):
         if _weight is None:      # nn.EmbeddingBag's default init is N(0, 1)
             _weight = torch.randn((self.num_embeddings, self.embedding_dim), device=dev)
         w = torch.as_tensor(_weight)
+        if dtype == "mxfp4":
+            rows, err = _mxfp4_rows(w, self.num_embeddings, self.embedding_dim, dev)
+            if err:
+                raise ValueError(err)
+            self.engine.load_table(self.table_id, rows, dtype=_l.EMB_MXFP4)
+            return
         if tuple(w.shape) != (self.num_embeddings, self.embedding_dim):
             raise ValueError(f"weight shape {tuple(w.shape)} != ({self.num_embeddings}, {self.embedding_dim})")
         self.engine.load_table(self.table_id, w.detach().to(dtype).contiguous())
@@ -163,6 +186,13 @@ class EmbeddingBag(torch.nn.Module):
                 missing_keys.append(key)
             return
         w = state_dict[key]
+        if self._table_dtype == "mxfp4":        # the fused rows a state_dict() of this module holds, or an fp32 weight to quantise
+            rows, err = _mxfp4_rows(w, self.num_embeddings, self.embedding_dim, torch.device("cuda", self.device_index))
+            if err:
+                error_msgs.append(f"size mismatch for {key}: {err}")
+            else:
+                self.engine.load_table(self.table_id, rows, dtype=_l.EMB_MXFP4)
+            return
         if tuple(w.shape) != (self.num_embeddings, self.embedding_dim):
             error_msgs.append(f"size mismatch for {key}: copying a param with shape {tuple(w.shape)} from checkpoint, "
                               f"the shape in current model is ({self.num_embeddings}, {self.embedding_dim}).")
