@@ -362,6 +362,47 @@ int emb_lookup_pooled(emb_engine *e, const emb_lookup_desc *descs, const emb_poo
 int emb_plan_create_pooled(emb_engine *e, const emb_lookup_desc *descs, const emb_pool_spec *pools, uint32_t n_descs,
                            emb_index_type itype, emb_plan **out);
 
+/* ---- strided pooled output: lookups that write straight into one [B, T * dim] buffer ------------------------------------
+ * emb_lookup_pooled / emb_plan_create_pooled over DEVICE buffers, with a row stride per descriptor: out_stride[i] is the
+ * number of FLOATS from one bag's pooled row of descriptor i to the next bag's, and descs[i].pooled is the address of bag 0's
+ * row (the caller has added the column offset).  Bag b's row goes to pooled + b * out_stride[i], exactly dim floats; not one
+ * byte between rows is touched.  That is the layout DLRM's interaction layer reads -- one row per sample, the tables' pooled
+ * rows side by side, the dense features in front if the caller likes -- without a torch.cat over T dense blocks afterwards.
+ * pools (may be NULL) and check (0 / 1 / 2) mean what they mean for emb_lookup_pooled; results are the same bits as the dense
+ * call's.  A refused call, and a checked call that found a bad index, leave the whole buffer untouched.
+ *   - Dense stays dense: out_stride == NULL, or an entry of 0 or of the table's dim, is a dense descriptor, and a call whose
+ *     descriptors are all dense IS emb_lookup_pooled / emb_plan_create_pooled (same launches, emb_plan_signature,
+ *     emb_plan_describe text and kernels).  Descriptors of one call may mix dense and strided outputs; launches are grouped
+ *     by (dtype, dim, pooling kind, output width, strided).
+ *   - A strided descriptor (stride != dim) needs stride >= dim, stride % 4 == 0, stride <= 0xffffffff and a 16-byte aligned
+ *     `pooled`: EMB_ERR_INVALID otherwise, emb_last_error names the descriptor.  Rows of different descriptors that overlap
+ *     are the caller's business and are not checked.
+ *   - Deliberately out of scope, EMB_ERR_UNSUPPORTED each: tables on the any-dim kernels (rows that are not 16-byte multiples
+ *     up to 1 KiB), EMB_FIXED32 tables, and EMB_POOL_OUT_TABLE_DTYPE together with a stride.
+ *   - A strided launch runs the twin (bag_strided_*) of the kernel a dense launch of the same shape runs -- wave-batch,
+ *     two-batch wave-batch, lane-group, or the pooled wave-batch / lane-group; MXFP4 always lane-group -- which reads the row
+ *     stride from its descriptor; never the hot-row kernel, for the same reason pooled launches never do.
+ *   - emb_plan_describe adds strided=1 to a strided launch's record (and only to those), emb_plan_signature differs from the
+ *     dense plan's, emb_plan_bytes is unchanged (the same bytes move), emb_stats counts the launches under their existing kind.
+ * HOST-pointer calls, the request queue, the ranged / counted / typed lookups and the sharded step stay dense.
+ * Rows of neighbouring tables share cache lines in the concatenated layout (dim 16 fp32: two 64-byte rows per 128-byte line)
+ * and may be stored by workgroups on different XCDs: the stores are disjoint 16-byte pieces, which is what the sharded direct
+ * path already relies on.
+ * Measured on MI355X (tools/strided_out_probe.py, profiles/strided/README.md), us per step, (a) the dense launch, (b) the dense
+ * launch + torch.cat of its outputs into [B, T * dim], (c) the strided launch writing that buffer:
+ *   26 Kaggle tables, dim 16, B = 39 292, one index per bag   fp32 (a) 19.40 (b) 52.61 (c) 23.73    bf16 (a) 20.99 (b) 43.70 (c) 20.18
+ *   8 tables, dim 128, B = 4096, 32 indices per bag           fp32 (a) 25.05 (b) 35.53 (c) 24.85    bf16 (a) 17.90 (b) 28.52 (c) 19.22
+ * (c) takes 0.45 - 0.70 of (b) at every point: for a caller that needs the concatenated layout the strided call wins.  Against
+ * the dense launch ALONE it LOSES at the dim-16 fp32 point, 1.22x (a), and at the pooled bf16 point, 1.07x; it is level (0.96 -
+ * 0.99) at the other two.  The cause of the fp32 loss is NOT established: two tables' 64-byte rows per 128-byte line, stored from
+ * different XCDs, is a supposition no counter run has tested, and the bf16 launch stores the same rows without paying.  So the
+ * strided output stays opt-in: a caller that consumes the T blocks one by one should keep the dense call. */
+int emb_lookup_strided(emb_engine *e, const emb_lookup_desc *descs, const emb_pool_spec *pools /* may be NULL */,
+                       const uint64_t *out_stride, uint32_t n_descs, emb_index_type itype, void *stream,
+                       uint32_t check, uint64_t *n_bad);
+int emb_plan_create_strided(emb_engine *e, const emb_lookup_desc *descs, const emb_pool_spec *pools,
+                            const uint64_t *out_stride, uint32_t n_descs, emb_index_type itype, emb_plan **out);
+
 /* Debug-only input check (the reference never checks: an out-of-range index is a wild MRAM read,
  * emb_dpu_lookup.c:113).  Counts indices >= nr_rows and non-monotone / out-of-range offsets over
  * DEVICE or HOST buffers; returns EMB_ERR_RANGE if *n_bad > 0.  (*n_bad, here and below, counts up to 16 777 215 and stays there.) */

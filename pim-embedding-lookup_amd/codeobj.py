@@ -67,27 +67,39 @@ class _Elf:
         return self.b[start:start + size]
 
 
-def device_code_object(lib_path: str, arch: str = "gfx950") -> bytes:
-    """The code object for `arch` out of the library's .hip_fatbin section."""
+def device_code_objects(lib_path: str, arch: str = "gfx950") -> list[bytes]:
+    """The code objects for `arch` out of the library's .hip_fatbin section, in link order: one offload bundle per translation
+    unit that holds kernels -- pimemb_kernels.hip first, then pimemb_strided_kernels.hip (csrc/Makefile: OBJS)."""
     with open(lib_path, "rb") as f:
         host = _Elf(f.read())
     fat = host.section(".hip_fatbin")
     if fat is None:
         raise ValueError(f"{lib_path}: no .hip_fatbin section (not a HIP library?)")
-    blob = host.data(fat)
-    at = blob.find(BUNDLE_MAGIC)
+    section = host.data(fat)
+    at = section.find(BUNDLE_MAGIC)
     if at < 0:
         raise ValueError(f"{lib_path}: .hip_fatbin holds no uncompressed clang offload bundle")
-    blob = blob[at:]
-    (n,) = struct.unpack_from("<Q", blob, len(BUNDLE_MAGIC))
-    p = len(BUNDLE_MAGIC) + 8
-    for _ in range(n):
-        off, size, tlen = struct.unpack_from("<QQQ", blob, p)
-        triple = blob[p + 24:p + 24 + tlen].decode(errors="replace")
-        p += 24 + tlen
-        if triple.startswith("hip") and triple.rstrip("-").endswith(arch) and size:
-            return blob[off:off + size]
-    raise ValueError(f"{lib_path}: no {arch} code object in the offload bundle")
+    out = []
+    while at >= 0:
+        blob = section[at:]
+        (n,) = struct.unpack_from("<Q", blob, len(BUNDLE_MAGIC))
+        p, end = len(BUNDLE_MAGIC) + 8, len(BUNDLE_MAGIC) + 8
+        for _ in range(n):
+            off, size, tlen = struct.unpack_from("<QQQ", blob, p)
+            triple = blob[p + 24:p + 24 + tlen].decode(errors="replace")
+            p += 24 + tlen
+            end = max(end, p, off + size)
+            if triple.startswith("hip") and triple.rstrip("-").endswith(arch) and size:
+                out.append(blob[off:off + size])
+        at = section.find(BUNDLE_MAGIC, at + end)           # (the next unit's bundle starts behind this one's last entry)
+    if not out:
+        raise ValueError(f"{lib_path}: no {arch} code object in the offload bundle")
+    return out
+
+
+def device_code_object(lib_path: str, arch: str = "gfx950") -> bytes:
+    """The FIRST of them: the code object of pimemb_kernels.hip, every kernel but the strided twins."""
+    return device_code_objects(lib_path, arch)[0]
 
 
 def device_code_sha256(lib_path: str, arch: str = "gfx950") -> str:
@@ -96,22 +108,24 @@ def device_code_sha256(lib_path: str, arch: str = "gfx950") -> str:
 
 def kernel_hashes(lib_path: str, arch: str = "gfx950") -> dict[str, str]:
     """{mangled kernel name: sha256(machine code || 64-byte kernel descriptor)} for every kernel of the code object.  The
-    descriptor's code-entry offset is masked: it moves whenever ANY kernel of the library grows, the kernel's code does not."""
-    co = _Elf(device_code_object(lib_path, arch))
-    syms = co.symbols()
-    funcs = {s["name"]: s for s in syms if s["type"] == 2 and s["size"]}                 # STT_FUNC
-    kds = {s["name"][:-3]: s for s in syms if s["type"] == 1 and s["name"].endswith(".kd")}   # STT_OBJECT
+    descriptor's code-entry offset is masked: it moves whenever ANY kernel of the library grows, the kernel's code does not.
+    Over every code object of the library (a kernel lives in exactly one)."""
     out = {}
-    for name, kd in kds.items():
-        f = funcs.get(name)
-        if f is None:
-            continue
-        h = hashlib.sha256()
-        h.update(co.bytes_at(f["shndx"], f["value"], f["size"]))
-        desc = bytearray(co.bytes_at(kd["shndx"], kd["value"], kd["size"] or 64))
-        desc[16:24] = bytes(8)       # kernel_code_entry_byte_offset: WHERE the code sits relative to the descriptor -- layout, not code
-        h.update(bytes(desc))
-        out[name] = h.hexdigest()
+    for blob in device_code_objects(lib_path, arch):
+        co = _Elf(blob)
+        syms = co.symbols()
+        funcs = {s["name"]: s for s in syms if s["type"] == 2 and s["size"]}                 # STT_FUNC
+        kds = {s["name"][:-3]: s for s in syms if s["type"] == 1 and s["name"].endswith(".kd")}   # STT_OBJECT
+        for name, kd in kds.items():
+            f = funcs.get(name)
+            if f is None:
+                continue
+            h = hashlib.sha256()
+            h.update(co.bytes_at(f["shndx"], f["value"], f["size"]))
+            desc = bytearray(co.bytes_at(kd["shndx"], kd["value"], kd["size"] or 64))
+            desc[16:24] = bytes(8)       # kernel_code_entry_byte_offset: WHERE the code sits relative to the descriptor -- layout, not code
+            h.update(bytes(desc))
+            out[name] = h.hexdigest()
     return out
 
 
@@ -123,10 +137,25 @@ def symbol_fragments(launch: dict) -> list[str]:
     same under the name bag_bf16pool_*, for fp8 tables (dtype 8 / 9) under bag_f8pool_*.  A half-output launch (a record with out=1, EMB_POOL_OUT_TABLE_DTYPE) runs the twin of
     that kernel: a pooled one under the name bag_hpool_* (fp16 and bf16 tables alike), a sum one the same bag_sum_* template
     with the internal dtype value DT | 16 (pimemb_bag_kernels.h: kHalfOutDT).  MXFP4 tables (dtype 10) have two kernel
-    templates of their own, without a DT argument."""
+    templates of their own, without a DT argument.  A strided launch (a record with strided=1, emb_plan_create_strided) runs
+    the twin of its kernel under a name that holds none of the fragments above: bag_strided_sum_<family>_kernel<IdxT, DT, LPR,
+    Cfg[, false]>, bag_strided_pool_<family>_kernel<IdxT, DT, LPR, Cfg> for every dtype alike, and for MXFP4
+    bag_strided_e2m1sum_group_kernel / bag_strided_e2m1pool_group_kernel<IdxT, LPR, Cfg>; the wave-batch, two-batch and
+    lane-group kinds only, never ranged or half-output."""
     idx = "j" if launch["itype"] == 0 else "l"
     kind, dt, lpr = launch["kind"], launch["dtype"], launch["lanes_per_row"]
     half = bool(launch.get("out"))
+    if launch.get("strided"):
+        pooled = "pool" in launch
+        if half or launch.get("ranged") or kind not in ((0, 1) if pooled else (0, 1, 2)) or (dt == 10 and kind != 1):
+            raise LookupError("no strided twin for this launch: %s" % (launch,))
+        if dt == 10:
+            return ["bag_strided_e2m1%s_group_kernelI%sLi%dENS_6BagCfgI" % ("pool" if pooled else "sum", idx, lpr)]
+        if pooled:
+            return ["bag_strided_pool_%s_kernelI%sLi%dELi%dENS_6BagCfgI" % ("group" if kind == 1 else "wavebatch", idx, dt, lpr)]
+        if kind == 1:
+            return ["bag_strided_sum_group_kernelI%sLi%dELi%dENS_6BagCfgI" % (idx, dt, lpr)]
+        return ["bag_strided_sum_wavebatch_kernelI%sLi%dELi%dENS_6BagCfgILi%dE" % (idx, dt, lpr, 128 if kind == 2 else 64)]
     if dt == 10:        # MXFP4: kernels of their own, lane-group only -- bag_mx4sum_group_kernel / bag_mx4pool_group_kernel<IdxT, LPR, Cfg>
         if kind != 1 or half or launch.get("ranged"):
             raise LookupError("an MXFP4 launch runs the lane-group kernels only: %s" % (launch,))
@@ -226,9 +255,15 @@ def _mp_arr(b, p, n):
 
 
 def kernel_resources(lib_path: str, arch: str = "gfx950") -> dict[str, dict]:
-    """{mangled kernel name: {vgpr, agpr, sgpr, vgpr_spill, sgpr_spill, lds, scratch, max_wg}} from the metadata note."""
-    co = _Elf(device_code_object(lib_path, arch))
+    """{mangled kernel name: {vgpr, agpr, sgpr, vgpr_spill, sgpr_spill, lds, scratch, max_wg}} from the metadata notes of the
+    library's code objects."""
     out = {}
+    for blob in device_code_objects(lib_path, arch):
+        _note_resources(_Elf(blob), out)
+    return out
+
+
+def _note_resources(co: _Elf, out: dict) -> None:
     for s in co.sections:
         if s["type"] != 7:                         # SHT_NOTE
             continue
@@ -247,7 +282,6 @@ def kernel_resources(lib_path: str, arch: str = "gfx950") -> dict[str, dict]:
                                            vgpr_spill=k.get(".vgpr_spill_count"), sgpr_spill=k.get(".sgpr_spill_count"),
                                            lds=k.get(".group_segment_fixed_size"), scratch=k.get(".private_segment_fixed_size"),
                                            max_wg=k.get(".max_flat_workgroup_size"))
-    return out
 
 
 def diff_kernels(hashes: dict, res: dict, other_hashes: dict, other_res: dict) -> list[str]:

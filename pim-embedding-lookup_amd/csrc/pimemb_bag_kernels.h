@@ -72,10 +72,16 @@ struct alignas(64) DevDesc {
         PoolView pool;
     };
 };
+// words[3], which neither view reaches: the row stride of a STRIDED descriptor's output, in floats (emb_lookup_strided; read by
+// the bag_strided_* twins only).  Zero in every other launch -- dense, ranged, hot-row, queue flush: `DevDesc d{}`.
+constexpr int kOutStrideWord = 3;
 static_assert(sizeof(DevDesc) == 128, "DevDesc is two 64-byte lines");
 static_assert(offsetof(DevDesc, words) == 88 && offsetof(DevDesc, ranged.row_lo) == 88 && offsetof(DevDesc, ranged.served) == 96 &&
-              offsetof(DevDesc, pool.weights) == 88 && offsetof(DevDesc, pool.padding_row) == 96 && offsetof(DevDesc, pool.op) == 104,
-              "the views overlay words[0..2]: engine, kernels, tuners and the host-side stub agree on these offsets");
+              offsetof(DevDesc, pool.weights) == 88 && offsetof(DevDesc, pool.padding_row) == 96 && offsetof(DevDesc, pool.op) == 104 &&
+              sizeof(RangedView) <= 8 * kOutStrideWord && sizeof(PoolView) <= 8 * kOutStrideWord &&
+              offsetof(DevDesc, words) + 8 * kOutStrideWord == 112,
+              "the views overlay words[0..2], the strided output's row stride is words[3] (byte 112): engine, kernels, tuners and "
+              "the host-side stub agree on these offsets");
 
 using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -686,51 +692,6 @@ __device__ __forceinline__ void bag_range(const IdxT *__restrict__ offsets, uint
     if (CLAMP && e > n_idx) e = n_idx;
 }
 
-// ---- v1: one lane group per bag, no cross-lane traffic (kept as the A/B baseline) -------------
-template <typename IdxT, int DT, int LPR, class Cfg>
-__global__ void __launch_bounds__(Cfg::kBlock)
-bag_sum_group_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg,
-                     const uint32_t *__restrict__ xmap) {
-    using Ops = RowOps<DT>;
-    constexpr uint32_t kWaves = Cfg::kBlock / 64;
-    constexpr uint32_t BPW = 64 / LPR;
-    constexpr uint32_t BAGS_PER_TILE = BPW * kWaves;
-
-    uint32_t desc_i, tile;
-    if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
-    const uint32_t chunks = chunks_arg & ~kXmapDirect;
-    const DescView<IdxT> t(descs + desc_i);
-
-    // (a LaneGeom here changes the code object of 30 of this kernel's 42 instantiations)
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
-    const uint32_t row_bytes = chunks * 16u;
-    const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
-    const char *__restrict__ wsub = t.weights + sub * 16u;
-
-    if (tile < t.n_tiles) {
-        const uint64_t bag = (uint64_t)tile * BAGS_PER_TILE + wave * BPW + grp;
-        const bool live = sub < chunks;
-        if (bag >= t.n_bags) return;                   // whole lane group leaves together
-        uint64_t p, e;
-        // (bag_range() spelled out: calling it changes the code object of 28 of the 42 instantiations, same registers, no spill)
-        if (t.offsets != nullptr) {
-            p = (uint64_t)load_meta<Cfg::kNtMeta>(t.offsets + bag);
-            e = (bag + 1 < t.n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(t.offsets + bag + 1) : t.n_idx;
-        } else {
-            p = bag * t.fixed_pooling;
-            e = p + t.fixed_pooling;
-        }
-        if (Cfg::kClamp && e > t.n_idx) e = t.n_idx;
-        typename Ops::Acc acc = Ops::zero();
-        walk_bag<IdxT, LPR, Cfg, Ops>(t.indices, p, e, sub, grp, live, acc, NoProbe{},
-                                      [&](uint64_t r, uint32_t) -> u32x4 {
-                                          return load_row<Cfg::kNtRow>(wsub + clamp_row<Cfg::kClamp, IdxT>(r, t.last_row) * row_bytes);
-                                      });
-        store_row<Ops, Cfg, LPR>(acc, t.out + bag * out_stride, sub, grp, chunks, live);
-    }
-}
-
 // ---- any row width: one thread per output element --------------------------------------------
 // Rows whose byte size is not a multiple of 16 (dim 2, 3, 10, 100 ... -- nn.EmbeddingBag takes any
 // dim, dlrm_s_pytorch.py's default sparse feature size is 2) or exceeds 1 KiB cannot use the 16-byte
@@ -900,202 +861,13 @@ constexpr uint32_t onehot_rounds_in_flight() {      // of the LPR rounds of a 64
     return ((uint32_t)LPR < depth) ? (uint32_t)LPR : depth;
 }
 
-// ---- v2: wave batches of 64 bags, coalesced bounds, shuffle-distributed, one-hot fast path -------
-// RANGED (the sharded lookup's direct path, pimemb_shard.cpp): one index per bag, and a descriptor serves only the bags
-// whose row falls into [row_lo, row_lo + nr_rows) (DevDesc::ranged.row_lo): out[b] = W[idx[b] - row_lo]; the other bags
-// are left untouched -- another shard of the table writes them, straight into the same output (DevDesc::ranged.served, if not null: a
-// uint32 counter in HBM the launch adds the number of bags it served to).  A shard scans the
-// requester's RAW index array (its own, or a peer's through its mapping): no router, no counts, no un-router.  A whole
-// table is the range [0, nr_rows), so replicated tables and shards share ONE launch of the tuned kernel.
-template <typename IdxT, int DT, int LPR, class Cfg, bool RANGED = false>
-__global__ void __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves)
-bag_sum_wavebatch_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg,
-                         const uint32_t *__restrict__ xmap) {
-    using Ops = RowOps<DT>;
-    constexpr uint32_t kWaves = Cfg::kBlock / 64;
-    constexpr uint32_t BPR = 64 / LPR;      // bags per round
-    constexpr uint32_t ROUNDS = LPR;        // rounds per 64-bag wave batch
-    constexpr uint32_t NB = Cfg::kBatches;  // wave batches per step
-    constexpr int U = Cfg::kUnroll;
-    constexpr uint32_t RU = onehot_rounds_in_flight<LPR, Cfg>();
-
-    uint32_t desc_i, tile;
-    if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
-    const uint32_t chunks = chunks_arg & ~kXmapDirect;
-    const DevDesc *dp = descs + desc_i;
-    const DescView<IdxT> t(dp);
-
-    const LaneGeom<LPR, Ops> ln(t.weights, chunks);
-    const bool lane_live = ln.sub < chunks;
-    uint64_t row_lo = 0;
-    bool open_end = false;               // RANGED: ids at or beyond the end of this range are this descriptor's to ZERO (EMB_RANGE_OPEN_END)
-    uint32_t *served_ctr = nullptr;      // RANGED: where this descriptor's launch adds the number of bags it served (or null)
-    if constexpr (RANGED) {
-        row_lo = dp->ranged.row_lo & ~kRangeOpenEnd;
-        open_end = (dp->ranged.row_lo & kRangeOpenEnd) != 0;
-        served_ctr = dp->ranged.served;
-    }
-
-    if (tile < t.n_tiles) {
-        const uint64_t step_base = ((uint64_t)tile * kWaves + ln.wave) * (64u * NB);
-        if (step_base >= t.n_bags) return;  // wave-uniform
-
-        // lane l of batch q holds the bounds of bag step_base + 64q + l (past-the-end = empty)
-        uint64_t st[NB];
-        uint32_t len[NB];
-        bool small = true;
-        // Speculation: in a one-hot batch with contiguous bags offsets[b] == b, so bag b's only index
-        // sits at indices[b].  Fetch it NOW, in the shadow of the bounds loads, and keep it only if
-        // the bounds agree -- one memory round trip less on the critical path of the Kaggle shape.
-        IdxT spec[NB];
-        if constexpr (Cfg::kSpeculate) {
-#pragma unroll
-            for (uint32_t q = 0; q < NB; q++) {
-                const uint64_t mb = step_base + 64u * q + ln.lane;
-                spec[q] = 0;
-                if (mb < t.n_idx) spec[q] = load_meta<Cfg::kNtMeta>(t.indices + mb);
-            }
-        }
-#pragma unroll
-        for (uint32_t q = 0; q < NB; q++) {
-            const uint64_t mb = step_base + 64u * q + ln.lane;
-            uint64_t en;    // (this block as a function shared with bag_pool_wavebatch_kernel: 18 instantiations here, 28 there change)
-            if (t.offsets != nullptr) {
-                st[q] = (mb < t.n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(t.offsets + mb) : t.n_idx;
-                en = (mb + 1 < t.n_bags) ? (uint64_t)load_meta<Cfg::kNtMeta>(t.offsets + mb + 1) : t.n_idx;
-            } else {
-                st[q] = (mb < t.n_bags ? mb : t.n_bags) * t.fixed_pooling;
-                en = (mb + 1 < t.n_bags ? mb + 1 : t.n_bags) * t.fixed_pooling;
-            }
-            if (Cfg::kClamp) {                       // malformed offsets: keep [st, en) inside [0, n_idx]
-                if (en > t.n_idx) en = t.n_idx;
-                if (st[q] > en) st[q] = en;
-            }
-            len[q] = (uint32_t)(en - st[q]);
-            small = small && (len[q] <= 1u);
-        }
-
-        if (__all(small)) {
-            // one-hot step: lane l fetches its bag's only index (coalesced), groups pull theirs and
-            // every gather of the step is issued before the first store.
-            IdxT my[NB];
-#pragma unroll
-            for (uint32_t q = 0; q < NB; q++) {
-                my[q] = 0;
-                if constexpr (Cfg::kSpeculate) {
-                    const uint64_t mb = step_base + 64u * q + ln.lane;
-                    if (len[q]) my[q] = (st[q] == mb) ? spec[q] : load_meta<Cfg::kNtMeta>(t.indices + st[q]);
-                } else {
-                    if (len[q]) my[q] = load_meta<Cfg::kNtMeta>(t.indices + st[q]);
-                }
-                if constexpr (RANGED) {     // row ids relative to this shard; a bag of another shard counts as empty
-                    const uint64_t id = (uint64_t)my[q];               // (a negative int64 id: huge, beyond every range)
-                    const uint64_t r = id - row_lo;                    // (wraps far out of range below row_lo)
-                    // len: 1 = served here; 2 = an id no range holds, and this descriptor answers for the open end: the bag's
-                    // pooled row is written as zeros (not served, not counted); 0 = some other shard's bag, left alone
-                    if (r > t.last_row) len[q] = (len[q] && open_end && id >= row_lo) ? 2u : 0u;
-                    my[q] = (IdxT)r;
-                }
-            }
-            if constexpr (RANGED) {
-                // Counted launch (a checked shard's direct path): the bags this wavefront serves, one atomic per wavefront,
-                // no return value.  The requester adds the counts of all shards up: a sum short of its bag count means an
-                // index no shard holds -- a bag left untouched (pimemb_shard.cpp: stage_unroute).
-                // A counter is EMB_SERVED_LANES words EMB_SERVED_STRIDE bytes apart, a workgroup adds to lane blockIdx % LANES:
-                // agent-scope atomics on ONE line retire one by one (~5.5 ns each: 8 000 wavefronts of the Kaggle launch on 26
-                // neighbouring words took 44 us against the lookup's 20), spread over lines they cost nothing measurable.
-                if (served_ctr != nullptr) {     // wave-uniform (a scalar load of the descriptor)
-                    uint32_t n = 0;
-#pragma unroll
-                    for (uint32_t q = 0; q < NB; q++) n += (uint32_t)__popcll(__ballot(len[q] == 1u));
-                    uint32_t *slot = served_ctr + (size_t)(blockIdx.x % EMB_SERVED_LANES) * (EMB_SERVED_STRIDE / 4u);
-                    if (ln.lane == 0 && n) (void)__hip_atomic_fetch_add(slot, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-#pragma unroll
-            for (uint32_t j0 = 0; j0 < ROUNDS; j0 += RU) {
-                u32x4 v[NB][RU];
-                bool has[NB][RU];
-                bool zero_it[NB][RU];      // (RANGED only: the open end's bags)
-#pragma unroll
-                for (uint32_t q = 0; q < NB; q++)
-#pragma unroll
-                    for (uint32_t jj = 0; jj < RU; jj++) {
-                        const uint32_t src = (j0 + jj) * BPR + ln.grp;
-                        const uint64_t r = clamp_row<Cfg::kClamp, IdxT>(shfl_index<IdxT>(my[q], src), t.last_row);
-                        const uint32_t l = shfl_u32(len[q], src);
-                        has[q][jj] = RANGED ? l == 1u : l != 0u;
-                        zero_it[q][jj] = RANGED && l == 2u;
-                        v[q][jj] = u32x4{0u, 0u, 0u, 0u};
-                        if (has[q][jj] && lane_live) v[q][jj] = load_row<Cfg::kNtRow>(ln.wsub + r * ln.row_bytes);
-                    }
-#pragma unroll
-                for (uint32_t q = 0; q < NB; q++)
-#pragma unroll
-                    for (uint32_t jj = 0; jj < RU; jj++) {
-                        const uint64_t bag = step_base + 64u * q + (j0 + jj) * BPR + ln.grp;
-                        // (RANGED: only the bags this shard holds the row of are written)
-                        const bool wr = RANGED ? (has[q][jj] || zero_it[q][jj]) : bag < t.n_bags;
-                        // (store_row alone, which covers both cases, changes the code object of 50 instantiations)
-                        if constexpr (!Ops::kGroupStore) {
-                            if (wr && lane_live) {
-                                typename Ops::Acc acc = Ops::zero();
-                                if (has[q][jj]) Ops::add(acc, v[q][jj]);
-                                Ops::template store<Cfg::kNtStore>(
-                                    acc, t.out + bag * ln.out_stride + ln.sub * Ops::kFloatsPerLane);
-                            }
-                        } else {   // all lanes take part in the group store's shuffles
-                            typename Ops::Acc acc = Ops::zero();
-                            // (fp8: a piece that was not gathered is all zero bytes, which widen to +0, and +0 + +0 = +0 --
-                            // added without the test, the eight conversions stay out of a branch per gathered row)
-                            if constexpr (kIsF8<DT>) Ops::add(acc, v[q][jj]);
-                            else if (has[q][jj] && lane_live) Ops::add(acc, v[q][jj]);
-                            store_row<Ops, Cfg, LPR>(acc, t.out + bag * ln.out_stride, ln.sub, ln.grp, chunks,
-                                                     wr && lane_live);
-                        }
-                    }
-            }
-            return;
-        }
-        if constexpr (RANGED) return;      // (the host hands a ranged launch fixed_pooling 1 only: every step is one-hot)
-
-        // general step: each round, a lane group walks its bag in index order (walk_bag's non-shuffle loop, spelled out: a call of
-        // walk_bag changes the code object of 46 instantiations)
-#pragma unroll 1
-        for (uint32_t q = 0; q < NB; q++) {
-#pragma unroll 1
-            for (uint32_t j = 0; j < ROUNDS; j++) {
-                const uint32_t src = j * BPR + ln.grp;
-                uint64_t p = shfl_u64(st[q], src);
-                const uint64_t e = p + shfl_u32(len[q], src);
-                const uint64_t bag = step_base + 64u * q + src;
-                // (no early `continue`: every lane must reach the next round's shuffles)
-                typename Ops::Acc acc = Ops::zero();
-                if (bag < t.n_bags && lane_live) {
-                    for (; p + U <= e; p += U) {
-                        uint64_t r[U];
-#pragma unroll
-                        for (int k = 0; k < U; k++) r[k] = (uint64_t)load_meta<Cfg::kNtMeta>(t.indices + p + k);
-                        u32x4 v[U];
-#pragma unroll
-                        for (int k = 0; k < U; k++)
-                            v[k] = load_row<Cfg::kNtRow>(ln.wsub + clamp_row<Cfg::kClamp, IdxT>(r[k], t.last_row) * ln.row_bytes);
-#pragma unroll
-                        for (int k = 0; k < U; k++) Ops::add(acc, v[k]);
-                    }
-                    for (; p < e; p++) {
-                        const uint64_t r = clamp_row<Cfg::kClamp, IdxT>((uint64_t)load_meta<Cfg::kNtMeta>(t.indices + p), t.last_row);
-                        Ops::add(acc, load_row<Cfg::kNtRow>(ln.wsub + r * ln.row_bytes));
-                    }
-                    if constexpr (!Ops::kGroupStore)
-                        Ops::template store<Cfg::kNtStore>(acc, t.out + bag * ln.out_stride + ln.sub * Ops::kFloatsPerLane);
-                }
-                if constexpr (Ops::kGroupStore)
-                    store_row<Ops, Cfg, LPR>(acc, t.out + bag * ln.out_stride, ln.sub, ln.grp, chunks, bag < t.n_bags && lane_live);
-            }
-        }
-    }
-}
+// The lane-group kernel (v1) and the wave-batch kernel (v2) themselves: pimemb_sum_kernels.inc, compiled under two sets of
+// names.  bag_sum_* here write dense pooled rows; the strided twins bag_strided_sum_* are at the end of this header.
+// PIMEMB_OUT_STRIDE(dp, dense): floats from one bag's pooled row to the next -- `dense` for every kernel but the strided twins.
+#define PIMEMB_OUT_STRIDE(dp, dense) (dense)
+#define PIMEMB_SUM_KERNEL(path) bag_sum_##path##_kernel
+#include "pimemb_sum_kernels.inc"
+#undef PIMEMB_SUM_KERNEL
 
 // ---- v3: lane-group kernel with the table's HOT ROWS staged in LDS -------------------------------
 // For skewed (Zipf-like) pooled workloads.  The engine keeps, per table, a compact copy of up to a
@@ -1342,41 +1114,6 @@ __host__ __device__ constexpr uint32_t mx4_row_stride(uint32_t chunks) { return 
 static_assert(mx4_row_stride(1) == EMB_MXFP4_ROW_STRIDE(32u) && mx4_row_stride(4) == EMB_MXFP4_ROW_STRIDE(128u) &&
               mx4_row_stride(64) == EMB_MXFP4_ROW_STRIDE(2048u), "the kernels' row stride is the header's");
 
-template <typename IdxT, int LPR, class Cfg>
-__global__ void __launch_bounds__(Cfg::kBlock)
-bag_mx4sum_group_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg, const uint32_t *__restrict__ xmap) {
-    using Ops = RowOps<kMXFP4>;
-    constexpr uint32_t kWaves = Cfg::kBlock / 64;
-    constexpr uint32_t BPW = 64 / LPR;
-    constexpr uint32_t BAGS_PER_TILE = BPW * kWaves;
-
-    uint32_t desc_i, tile;
-    if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
-    const uint32_t chunks = chunks_arg & ~kXmapDirect;
-    const DescView<IdxT> t(descs + desc_i);
-
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
-    const uint32_t row_stride = mx4_row_stride(chunks);
-    const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
-    const char *__restrict__ wsub = t.weights + sub * 16u;              // this lane's block of row 0 ...
-    const char *__restrict__ ssub = t.weights + chunks * 16u + sub;     // ... and that block's scale
-
-    if (tile < t.n_tiles) {
-        const uint64_t bag = (uint64_t)tile * BAGS_PER_TILE + wave * BPW + grp;
-        const bool live = sub < chunks;
-        if (bag >= t.n_bags) return;                   // whole lane group leaves together
-        uint64_t p, e;
-        bag_range<Cfg::kNtMeta, Cfg::kClamp>(t.offsets, t.n_bags, t.n_idx, t.fixed_pooling, bag, p, e);
-        typename Ops::Acc acc = Ops::zero();
-        walk_bag<IdxT, LPR, Cfg, Ops>(t.indices, p, e, sub, grp, live, acc, NoProbe{}, [&](uint64_t r, uint32_t) -> Mx4Piece {
-            const uint64_t at = clamp_row<Cfg::kClamp, IdxT>(r, t.last_row) * row_stride;
-            return Mx4Piece{load_row<Cfg::kNtRow>(wsub + at), load_mx4_scale(ssub + at)};
-        });
-        store_row<Ops, Cfg, LPR>(acc, t.out + bag * out_stride, sub, grp, chunks, live);
-    }
-}
-
 // pool_walk for MXFP4 rows: kUnroll indices (and weights) loaded, padding entries dropped, the remaining blocks and scales
 // gathered together, then taken in order.
 template <typename IdxT, class Cfg>
@@ -1420,43 +1157,33 @@ __device__ __forceinline__ void mx4_pool_walk(const IdxT *__restrict__ indices, 
     }
 }
 
-template <typename IdxT, int LPR, class Cfg>
-__global__ void __launch_bounds__(Cfg::kBlock)
-bag_mx4pool_group_kernel(const DevDesc *__restrict__ descs, uint32_t chunks_arg, const uint32_t *__restrict__ xmap) {
-    using Ops = RowOps<kMXFP4>;
-    constexpr uint32_t kWaves = Cfg::kBlock / 64;
-    constexpr uint32_t BPW = 64 / LPR;
-    constexpr uint32_t BAGS_PER_TILE = BPW * kWaves;
+// The two kernels themselves: pimemb_mx4_kernels.inc, under the names tests/test_mxfp4_cpu.py pins (28 kernels with `mx4`).
+#define PIMEMB_MX4_KERNEL(op) bag_mx4##op##_group_kernel
+#include "pimemb_mx4_kernels.inc"
+#undef PIMEMB_MX4_KERNEL
+#undef PIMEMB_OUT_STRIDE
 
-    uint32_t desc_i, tile;
-    if (!decode_block(xmap, chunks_arg & kXmapDirect, &desc_i, &tile)) return;
-    const uint32_t chunks = chunks_arg & ~kXmapDirect;
-    const DevDesc *dp = descs + desc_i;
-    const DescView<IdxT> t(dp);
-    const PoolArgs a = pool_args(dp);
-
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
-    const uint32_t row_stride = mx4_row_stride(chunks);
-    const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
-    const char *__restrict__ wsub = t.weights + sub * 16u;
-    const char *__restrict__ ssub = t.weights + chunks * 16u + sub;
-
-    if (tile < t.n_tiles) {
-        const uint64_t bag = (uint64_t)tile * BAGS_PER_TILE + wave * BPW + grp;
-        const bool live = sub < chunks;
-        if (bag >= t.n_bags) return;                   // whole lane group leaves together
-        uint64_t p, e;
-        bag_range<Cfg::kNtMeta, Cfg::kClamp>(t.offsets, t.n_bags, t.n_idx, t.fixed_pooling, bag, p, e);
-        typename Ops::Acc acc = Ops::zero();
-        uint32_t cnt = 0;
-        if (live) mx4_pool_walk<IdxT, Cfg>(t.indices, a, p, e, wsub, ssub, row_stride, t.last_row, acc, cnt);
-        if (a.mean && cnt > 1u) {
-#pragma unroll
-            for (int c = 0; c < 32; c++) acc[c] = pool_finish1(acc[c], cnt, true);
-        }
-        store_row<Ops, Cfg, LPR>(acc, t.out + bag * out_stride, sub, grp, chunks, live);
-    }
-}
+// ---- strided pooled output (emb_lookup_strided / emb_plan_create_strided): the twins -----------------------------------------
+// A strided descriptor's pooled rows are DevDesc::words[kOutStrideWord] floats apart instead of back to back -- one table's columns of a
+// [B, T * dim] buffer.  Every store path above addresses a row as out + bag * out_stride and stores relative to it, so the twins
+// are the SAME text with the stride read from the descriptor (wave-uniform: a scalar load next to the other fields) instead of
+// computed from `chunks`.  New instantiations under names of their own, not a runtime branch: the kernels above keep their machine
+// code, and the names hold none of the fragments the tests pin kernel sets by (bag_sum_, bag_pool_, bag_bf16pool_, bag_f8pool_,
+// bag_hpool_, mx4).  One pooled set serves every dtype.  No ranged, hot-row, any-dim or half-output twin.
+#define PIMEMB_OUT_STRIDE(dp, dense) ((uint32_t)(dp)->words[kOutStrideWord])
+#define PIMEMB_SUM_KERNEL(path) bag_strided_sum_##path##_kernel
+#include "pimemb_sum_kernels.inc"
+#undef PIMEMB_SUM_KERNEL
+#define PIMEMB_POOL_KERNEL(path) bag_strided_pool_##path##_kernel
+#define PIMEMB_POOL_HALF_OUT 0
+#define PIMEMB_POOL_ROWOPS(DT) RowOps<DT>
+#include "pimemb_pool_kernels.inc"
+#undef PIMEMB_POOL_KERNEL
+#undef PIMEMB_POOL_HALF_OUT
+#undef PIMEMB_POOL_ROWOPS
+#define PIMEMB_MX4_KERNEL(op) bag_strided_e2m1##op##_group_kernel
+#include "pimemb_mx4_kernels.inc"
+#undef PIMEMB_MX4_KERNEL
+#undef PIMEMB_OUT_STRIDE
 
 }  // namespace pimemb

@@ -237,6 +237,7 @@ struct PlanGroup {
     uint32_t pool = 0;               // 0: plain sum (bag_sum_*); else 1 + EMB_POOL_* of a pooled launch (bag_pool_*)
     uint32_t n_weighted = 0, n_padding = 0;   // pooled launch: descriptors with per-sample weights / a padding_idx
     bool out_half = false;           // EMB_POOL_OUT_TABLE_DTYPE: pooled rows leave in the table's 2-byte dtype (half-output twins)
+    bool strided = false;            // emb_lookup_strided: every descriptor carries its output's row stride (the bag_strided_* twins)
     size_t desc_off = 0, xmap_off = 0;  // byte offsets of this group's pieces in the launch image
     std::vector<uint32_t> xmap_words;
 };
@@ -449,6 +450,8 @@ bool is_plain_sum_half_out(const emb_pool_spec &ps) {
 bool wants_half_out(const emb_pool_spec *pools, uint32_t i) { return pools && (pools[i].flags & EMB_POOL_OUT_TABLE_DTYPE) != 0; }
 // Bytes of descriptor u's pooled rows: fp32, or the table's 2-byte dtype for a half-output descriptor.
 size_t out_elem_size(const emb_pool_spec *pools, uint32_t i) { return wants_half_out(pools, i) ? 2 : 4; }
+// emb_lookup_strided: descriptor i's pooled rows lie out_stride[i] floats apart -- unless that says what a dense output says.
+bool is_strided(const uint64_t *out_stride, uint32_t i, uint32_t dim) { return out_stride && out_stride[i] != 0 && out_stride[i] != dim; }
 
 // st_indices / st_offsets / st_out: if non-null, per-descriptor device pointers that replace the
 // caller's (the staged copies of a host-pointer call).
@@ -457,14 +460,17 @@ size_t out_elem_size(const emb_pool_spec *pools, uint32_t i) { return wants_half
 // travels to the kernel as it is: ids beyond the end of the range pool to zero rows).
 // served (ranged launches only): if non-null, served[i] (may be null) is a uint32 counter in HBM that descriptor i's
 // launch adds the number of bags it served to.
+// out_stride (emb_lookup_strided; DEVICE calls without row_lo only): if non-null, out_stride[i] floats lie between two bags'
+// pooled rows of descriptor i; 0 or the table's dim is a dense descriptor like any other.
 int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_index_type itype,
             const std::vector<const void *> *st_indices, const std::vector<const void *> *st_offsets,
             const std::vector<float *> *st_out, Resolved *r, bool cache_maps = false, const uint64_t *row_lo = nullptr,
             uint32_t *const *served = nullptr, const emb_pool_spec *pools = nullptr,
-            const std::vector<const float *> *st_weights = nullptr) {
+            const std::vector<const float *> *st_weights = nullptr, const uint64_t *out_stride = nullptr) {
     if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "bad index type");
-    // (dtype, dim, pooling kind, output width): kind 0 = plain sum, width 0 = fp32, the key every call without pooling specs has
-    std::map<std::tuple<int, uint32_t, uint32_t, uint32_t>, std::vector<uint32_t>> by_shape;
+    // (dtype, dim, pooling kind, output width, strided): kind 0 = plain sum, width 0 = fp32, strided 0 = rows back to back, the
+    // key every call without pooling specs and strides has
+    std::map<std::tuple<int, uint32_t, uint32_t, uint32_t, uint32_t>, std::vector<uint32_t>> by_shape;
     for (uint32_t i = 0; i < n_descs; i++) {
         const emb_lookup_desc &u = descs[i];
         if (u.table_id >= e->tables.size() || e->tables[u.table_id].rows == nullptr)
@@ -508,7 +514,23 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
             if (row_lo) return fail(EMB_ERR_UNSUPPORTED, "ranged lookups pool by plain sum only");
             if (!is_plain_sum_half_out(ps)) pool_kind = 1u + ps.mode;      // (only the flag: the sum kernels' half-output twins)
         }
-        by_shape[{(int)t.dtype, t.dim, pool_kind, wants_half_out(pools, i) ? 1u : 0u}].push_back(i);
+        const bool strided = is_strided(out_stride, i, t.dim);
+        if (strided) {
+            const uint64_t st = out_stride[i];
+            if (t.geom.scalar_lanes)
+                return fail(EMB_ERR_UNSUPPORTED, "desc %u: strided output needs rows of 16-byte multiples up to 1 KiB (table %u, dim %u, runs the "
+                            "any-dim kernels, which have no strided twin)", i, u.table_id, t.dim);
+            if (t.dtype == EMB_FIXED32)
+                return fail(EMB_ERR_UNSUPPORTED, "desc %u: strided output: table %u is fixed-point, whose kernels have no strided twin", i, u.table_id);
+            if (wants_half_out(pools, i))
+                return fail(EMB_ERR_UNSUPPORTED, "desc %u: strided output is fp32 only: EMB_POOL_OUT_TABLE_DTYPE with a row stride has no kernel", i);
+            if (st < t.dim || st % 4 != 0 || st > 0xffffffffull)
+                return fail(EMB_ERR_INVALID, "desc %u: out_stride %llu: need dim (%u) <= stride <= 4294967295 and stride %% 4 == 0", i,
+                            (unsigned long long)st, t.dim);
+            if (((uintptr_t)u.pooled & 15u) != 0)
+                return fail(EMB_ERR_INVALID, "desc %u: strided output: pooled (%p) must be 16-byte aligned", i, (void *)u.pooled);
+        }
+        by_shape[{(int)t.dtype, t.dim, pool_kind, wants_half_out(pools, i) ? 1u : 0u, strided ? 1u : 0u}].push_back(i);
     }
     const size_t isz = index_size(itype);
     for (auto &kv : by_shape) {
@@ -516,6 +538,7 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
         g.dtype = std::get<0>(kv.first);
         g.pool = std::get<2>(kv.first);
         g.out_half = std::get<3>(kv.first) != 0;
+        g.strided = std::get<4>(kv.first) != 0;
         g.n = (uint32_t)kv.second.size();
         const Table &t0 = e->tables[descs[kv.second[0]].table_id];
         g.geom = t0.geom;
@@ -534,7 +557,7 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
         g.ranged = row_lo != nullptr;
         if (g.ranged && g.kind == pimemb::KERNEL_GROUP) g.kind = pimemb::KERNEL_WAVEBATCH;    // (small launches too: the predicate lives there)
         if (g.pool && g.kind == pimemb::KERNEL_WAVEBATCH2) g.kind = pimemb::KERNEL_WAVEBATCH;  // (the pooled family has one wave-batch geometry)
-        if (g.kind == pimemb::KERNEL_GROUP && !g.pool && !g.out_half) {   // (a pooled or half-output launch never takes the hot-row kernel)   // pooled launch over tables with a hot-row set: LDS-staged kernel
+        if (g.kind == pimemb::KERNEL_GROUP && !g.pool && !g.out_half && !g.strided) {   // (a pooled, half-output or strided launch never takes the hot-row kernel)   // pooled launch over tables with a hot-row set: LDS-staged kernel
             for (uint32_t i : kv.second) {
                 const Table &t = e->tables[descs[i].table_id];
                 if (t.n_hot && t.hot_lds > g.hot_lds) g.hot_lds = (uint32_t)t.hot_lds;
@@ -561,6 +584,7 @@ int resolve(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_i
             d.n_tiles = (uint32_t)tiles;
             if (row_lo) d.ranged.row_lo = row_lo[i];
             if (row_lo && served) d.ranged.served = served[i];
+            if (g.strided) d.words[pimemb::kOutStrideWord] = out_stride[i];      // (zero in every other descriptor: `DevDesc d{}`)
             if (g.pool) {           // the pooling spec rides in DevDesc::pool (pimemb_bag_kernels.h: pool_args)
                 const emb_pool_spec &ps = pools[i];
                 const bool weighted = ps.per_sample_weights != nullptr, padded = (ps.flags & EMB_POOL_PADDING) != 0;
@@ -646,12 +670,12 @@ int launch_groups(emb_engine *e, const std::vector<PlanGroup> &groups, emb_index
     for (const PlanGroup &g : groups) {
         if (g.pool)
             HIP_TRY(pimemb::launch_bag_pool(g.d_descs, g.n, g.max_tiles, g.dtype, itype, g.geom, g.kind, g.d_xmap, g.xgrid,
-                                            g.xdirect, s, g.out_half));
+                                            g.xdirect, s, g.out_half, g.strided));
         else if (g.kind == pimemb::KERNEL_HOT)
             HIP_TRY(pimemb::launch_bag_sum_hot(g.d_descs, g.n, g.hot_wgs, g.hot_lds, g.dtype, itype, g.geom, s));
         else
             HIP_TRY(pimemb::launch_bag_sum(g.d_descs, g.n, g.max_tiles, g.dtype, itype, g.geom, g.kind, g.d_xmap,
-                                           g.xgrid, g.xdirect, s, g.ranged, g.out_half));
+                                           g.xgrid, g.xdirect, s, g.ranged, g.out_half, g.strided));
         e->n_kernel_launches.fetch_add(1, std::memory_order_relaxed);
         e->n_by_kind[g.kind].fetch_add(1, std::memory_order_relaxed);
     }
@@ -1417,7 +1441,7 @@ static int checked_launch(emb_engine *e, Resolved &r, emb_index_type itype, hipS
 
 static int lookup_batched_impl(emb_engine *e, const emb_lookup_desc *descs, uint32_t n_descs, emb_index_type itype,
                                emb_memspace space, void *stream, bool check, uint64_t *n_bad, bool defer = false,
-                               const emb_pool_spec *pools = nullptr) {
+                               const emb_pool_spec *pools = nullptr, const uint64_t *out_stride = nullptr) {
     if (n_bad) *n_bad = 0;
     if (!e) return fail(EMB_ERR_INVALID, "engine is NULL");
     if (n_descs == 0) return EMB_OK;
@@ -1435,7 +1459,7 @@ static int lookup_batched_impl(emb_engine *e, const emb_lookup_desc *descs, uint
     Resolved r;
     r.stream = s;
     const double p0 = g_prof.on ? now_us() : 0;
-    int rc = resolve(e, descs, n_descs, itype, nullptr, nullptr, nullptr, &r, /*cache_maps=*/true, nullptr, nullptr, pools);
+    int rc = resolve(e, descs, n_descs, itype, nullptr, nullptr, nullptr, &r, /*cache_maps=*/true, nullptr, nullptr, pools, nullptr, out_stride);
     if (rc) return rc;
     if (g_prof.on) g_prof.resolve += now_us() - p0;
     // checked: the descriptors are resolved ONCE; the validation kernel and the lookup kernels share one launch image and
@@ -1528,7 +1552,28 @@ int emb_lookup_ranged_typed(emb_engine *e, const emb_lookup_desc *descs, const u
 }
 
 static int plan_create(emb_engine *e, const emb_lookup_desc *descs, const uint64_t *row_lo, uint32_t *const *served,
-                       uint32_t n_descs, emb_index_type itype, emb_plan **out, const emb_pool_spec *pools = nullptr);
+                       uint32_t n_descs, emb_index_type itype, emb_plan **out, const emb_pool_spec *pools = nullptr,
+                       const uint64_t *out_stride = nullptr);
+
+// Strided pooled output: emb_lookup_pooled over DEVICE buffers with a row stride per descriptor (resolve: out_stride).  Strides
+// that all say "dense" (0, or the table's dim) change nothing: the groups, and with them launches, signature and text, are the
+// dense call's.
+int emb_lookup_strided(emb_engine *e, const emb_lookup_desc *descs, const emb_pool_spec *pools, const uint64_t *out_stride,
+                       uint32_t n_descs, emb_index_type itype, void *stream, uint32_t check, uint64_t *n_bad) {
+    if (n_bad) *n_bad = 0;
+    if (!e) return fail(EMB_ERR_INVALID, "engine is NULL");
+    if (check > 2) return fail(EMB_ERR_INVALID, "emb_lookup_strided: check must be 0, 1 or 2 (got %u)", check);
+    if (n_descs && !descs) return fail(EMB_ERR_INVALID, "descs is NULL");
+    const emb_pool_spec *live = live_pools(pools, n_descs);
+    if (check == 0)
+        return lookup_batched_impl(e, descs, n_descs, itype, EMB_MEM_DEVICE, stream, e->check_inputs, nullptr, e->defer_check, live, out_stride);
+    return lookup_batched_impl(e, descs, n_descs, itype, EMB_MEM_DEVICE, stream, true, n_bad, check == 2, live, out_stride);
+}
+
+int emb_plan_create_strided(emb_engine *e, const emb_lookup_desc *descs, const emb_pool_spec *pools, const uint64_t *out_stride,
+                            uint32_t n_descs, emb_index_type itype, emb_plan **out) {
+    return plan_create(e, descs, nullptr, nullptr, n_descs, itype, out, live_pools(pools, n_descs), out_stride);
+}
 
 int emb_plan_create_ranged(emb_engine *e, const emb_lookup_desc *descs, const uint64_t *row_lo, uint32_t n_descs,
                            emb_plan **out) {
@@ -1559,13 +1604,13 @@ int emb_plan_create_pooled(emb_engine *e, const emb_lookup_desc *descs, const em
 }
 
 static int plan_create(emb_engine *e, const emb_lookup_desc *descs, const uint64_t *row_lo, uint32_t *const *served,
-                       uint32_t n_descs, emb_index_type itype, emb_plan **out, const emb_pool_spec *pools) {
+                       uint32_t n_descs, emb_index_type itype, emb_plan **out, const emb_pool_spec *pools, const uint64_t *out_stride) {
     if (!e || !out) return fail(EMB_ERR_INVALID, "engine or out is NULL");
     *out = nullptr;
     if (!descs || n_descs == 0) return fail(EMB_ERR_INVALID, "plan needs at least one descriptor");
     DeviceGuard g(e->device);
     Resolved r;
-    int rc = resolve(e, descs, n_descs, itype, nullptr, nullptr, nullptr, &r, false, row_lo, served, pools);
+    int rc = resolve(e, descs, n_descs, itype, nullptr, nullptr, nullptr, &r, false, row_lo, served, pools, nullptr, out_stride);
     if (rc) return rc;
     emb_plan *p = new (std::nothrow) emb_plan();
     if (!p) return fail(EMB_ERR_NOMEM, "out of host memory");
@@ -1581,10 +1626,12 @@ static int plan_create(emb_engine *e, const emb_lookup_desc *descs, const uint64
             mix(g.xgrid); mix(g.xdirect); mix(g.ranged); mix(g.hot_wgs); mix(g.hot_lds); mix(pimemb::bags_per_tile(g.kind, g.geom));
             if (g.pool) mix(0x706f6f6c00ull | g.pool);     // (plain-sum groups mix exactly what they always did)
             if (g.out_half) mix(0x6f757400ull | 1u);       // (... and so do fp32-out groups)
+            if (g.strided) mix(0x7374726400ull | 1u);      // (... and dense ones)
             for (uint32_t w : g.xmap_words) mix(w);
             for (uint32_t i = 0; i < g.n; i++, di++) {
                 const DevDesc &d = r.descs[di];
                 mix(d.n_tiles); mix(d.n_bags); mix(d.n_idx); mix(d.nr_rows); mix(d.fixed_pooling); mix(d.offsets != nullptr); mix(d.n_hot);
+                if (g.strided) mix(d.words[pimemb::kOutStrideWord]);       // (a layout, never an address)
                 if (g.pool) {           // the pooling spec: the weights' presence, never their address
                     mix(d.pool.weights != nullptr); mix(d.pool.padding_row); mix(d.pool.op);
                 } else {
@@ -1667,6 +1714,11 @@ int emb_plan_describe(const emb_plan *p, char *buf, size_t capacity) {
         }
         if (g.out_half) {
             const int m = snprintf(buf + at, capacity - at, " out=1");
+            if (m < 0 || (size_t)m >= capacity - at) return fail(EMB_ERR_INVALID, "emb_plan_describe: %zu bytes do not hold the text", capacity);
+            at += (size_t)m;
+        }
+        if (g.strided) {
+            const int m = snprintf(buf + at, capacity - at, " strided=1");
             if (m < 0 || (size_t)m >= capacity - at) return fail(EMB_ERR_INVALID, "emb_plan_describe: %zu bytes do not hold the text", capacity);
             at += (size_t)m;
         }

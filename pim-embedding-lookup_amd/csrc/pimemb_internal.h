@@ -56,16 +56,27 @@ KernelKind choose_kernel(uint64_t total_bags, uint64_t total_indices, const Laun
 hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles,
                           int dtype, emb_index_type itype, const LaunchGeom &g,
                           KernelKind kind, const uint32_t *d_xmap, uint32_t xgrid, bool xdirect,
-                          hipStream_t stream, bool ranged = false, bool out_half = false);
+                          hipStream_t stream, bool ranged = false, bool out_half = false, bool strided = false);
 // out_half (here and in launch_bag_pool; EMB_POOL_OUT_TABLE_DTYPE): DevDesc::out points to rows of the table's 2-byte dtype
 // (fp16 / bf16 tables only; never ranged) and the launch runs the half-output twin of the kernel.
+// strided (here and in launch_bag_pool; emb_lookup_strided): every descriptor carries the row stride of its output in
+// DevDesc::words[kOutStrideWord] and the launch runs the strided twin (bag_strided_*) of the kernel: the wave-batch kinds and the
+// lane-group kind only, never ranged, half-output, any-dim or fixed-point.
 
 // Pooled lookup (emb_lookup_pooled: mean / max, per-sample weights, padding_idx) over descriptors of one dtype (fp32 / fp16 / bf16)
 // and dim whose pooling spec sits in DevDesc::pool (pimemb_bag_kernels.h, bag_pool_*).  kind: KERNEL_WAVEBATCH,
 // KERNEL_GROUP or KERNEL_ANYDIM (no two-batch or hot-row variant).  Pure enqueue.
 hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, int dtype,
                            emb_index_type itype, const LaunchGeom &g, KernelKind kind, const uint32_t *d_xmap,
-                           uint32_t xgrid, bool xdirect, hipStream_t stream, bool out_half = false);
+                           uint32_t xgrid, bool xdirect, hipStream_t stream, bool out_half = false, bool strided = false);
+
+// The strided twins, sum (pooled = false) and pooled, MXFP4 included: what launch_bag_sum / launch_bag_pool hand a launch with
+// `strided` to, after their own checks, with the grid and the `chunks` kernel argument they worked out.  Defined in
+// pimemb_strided_kernels.hip, a translation unit of its own so that the twins compile NEXT TO the other kernels, not after them
+// (the build waits for pimemb_kernels.hip as it is).  A WEAK reference: a program linked from the library's other objects alone
+// -- the host-side checks under tests/cpp -- still links; there a strided launch is hipErrorInvalidValue.
+hipError_t launch_bag_strided(const DevDesc *d_descs, dim3 grid, uint32_t chunks_arg, int dtype, emb_index_type itype, const LaunchGeom &g,
+                              KernelKind kind, const uint32_t *d_xmap, hipStream_t stream, bool pooled) __attribute__((weak));
 
 // Pooled launch with hot rows in LDS: `wgs` persistent workgroups per descriptor, `lds_bytes` of dynamic LDS.
 hipError_t launch_bag_sum_hot(const DevDesc *d_descs, uint32_t n_descs, uint32_t wgs, uint32_t lds_bytes,

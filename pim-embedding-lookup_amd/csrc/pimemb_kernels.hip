@@ -139,6 +139,23 @@ struct MappedLaunch {
         : grid(xmap ? dim3(xgrid, 1, 1) : dim3(max_tiles, n, 1)), chunks(g.chunks | ((xmap && xdirect) ? kXmapDirect : 0u)) {}
 };
 
+// ---- pooled lookups (bag_pool_*): fp32 / fp16 / bf16 tables; one instantiation per (index type, dtype, row width, path) -- the
+// pooling mode, weights and padding are per-descriptor values the kernels branch on (scalar branches) ----------------------
+// The pooled wave-batch kernel under the fp32 64-VGPR cap: its general (multi-index) step also carries a weight per gather
+// in flight, and eight of them spill (21 dwords per lane); four, as Wave2Cfg's general step, do not.  One-hot steps keep all
+// eight rounds' gathers in flight either way.  fp16 and bf16 rows: the fp16 configuration as it is (4 waves per SIMD, no spill).
+using PoolWaveCfg = BagCfg<64, 4, true, false, 8, 8, 1, false, true, false, kClampInputs>;
+template <int DT> struct PoolWaveCfgOf { using One = PoolWaveCfg; };
+template <> struct PoolWaveCfgOf<EMB_F16> { using One = WaveCfgF16; };
+template <> struct PoolWaveCfgOf<EMB_BF16> { using One = WaveCfgBF16; };
+template <> struct PoolWaveCfgOf<kF8E4M3> { using One = WaveCfgF8; };
+template <> struct PoolWaveCfgOf<kF8E5M2> { using One = WaveCfgF8; };
+
+// Up to here: the configurations and the dispatch, which pimemb_strided_kernels.hip needs word for word -- a twin runs under its
+// dense kernel's configuration.  That unit includes THIS file with PIMEMB_CONFIGURATIONS_ONLY defined and stops here: the
+// aliases stay in this file, where tests/test_queue_cases_cpu.py reads them off the text.
+#ifndef PIMEMB_CONFIGURATIONS_ONLY
+
 template <typename IdxT, int DT, int L>
 void launch_sum(const DevDesc *d, const MappedLaunch &m, KernelKind kind, const uint32_t *xmap, bool ranged, hipStream_t s) {
     using One = typename WaveCfgOf<DT>::One;
@@ -163,17 +180,6 @@ void launch_sum(const DevDesc *d, const MappedLaunch &m, KernelKind kind, const 
         hipLaunchKernelGGL((bag_sum_group_kernel<IdxT, DT, L, GroupCfg>), m.grid, dim3(GroupCfg::kBlock), 0, s, d, m.chunks, xmap);
 }
 
-// ---- pooled lookups (bag_pool_*): fp32 / fp16 / bf16 tables; one instantiation per (index type, dtype, row width, path) -- the
-// pooling mode, weights and padding are per-descriptor values the kernels branch on (scalar branches) ----------------------
-// The pooled wave-batch kernel under the fp32 64-VGPR cap: its general (multi-index) step also carries a weight per gather
-// in flight, and eight of them spill (21 dwords per lane); four, as Wave2Cfg's general step, do not.  One-hot steps keep all
-// eight rounds' gathers in flight either way.  fp16 and bf16 rows: the fp16 configuration as it is (4 waves per SIMD, no spill).
-using PoolWaveCfg = BagCfg<64, 4, true, false, 8, 8, 1, false, true, false, kClampInputs>;
-template <int DT> struct PoolWaveCfgOf { using One = PoolWaveCfg; };
-template <> struct PoolWaveCfgOf<EMB_F16> { using One = WaveCfgF16; };
-template <> struct PoolWaveCfgOf<EMB_BF16> { using One = WaveCfgBF16; };
-template <> struct PoolWaveCfgOf<kF8E4M3> { using One = WaveCfgF8; };
-template <> struct PoolWaveCfgOf<kF8E5M2> { using One = WaveCfgF8; };
 
 // ---- column scatter for populate_mram-style uploads -----------------------------------------
 __global__ void __launch_bounds__(kBlock)
@@ -1196,14 +1202,19 @@ KernelKind choose_kernel(uint64_t total_bags, uint64_t total_indices, const Laun
 hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles,
                           int dtype, emb_index_type itype, const LaunchGeom &g,
                           KernelKind kind, const uint32_t *d_xmap, uint32_t xgrid, bool xdirect,
-                          hipStream_t stream, bool ranged, bool out_half) {
+                          hipStream_t stream, bool ranged, bool out_half, bool strided) {
     if (n_descs == 0 || max_tiles == 0) return hipSuccess;
     if (d_xmap == nullptr && n_descs > 65535u) return hipErrorInvalidValue;
     if (ranged && ((kind != KERNEL_WAVEBATCH && kind != KERNEL_WAVEBATCH2) || (kind == KERNEL_WAVEBATCH2 && g.lanes_per_row > 4)))
         return hipErrorInvalidValue;
     if (kind == KERNEL_ANYDIM && (g.scalar_lanes == 0 || d_xmap != nullptr)) return hipErrorInvalidValue;
     if (out_half && (ranged || kind == KERNEL_HOT)) return hipErrorInvalidValue;
+    if (strided && (ranged || out_half || g.scalar_lanes || (kind != KERNEL_WAVEBATCH && kind != KERNEL_WAVEBATCH2 && kind != KERNEL_GROUP)))
+        return hipErrorInvalidValue;
     const MappedLaunch m(n_descs, max_tiles, g, d_xmap, xgrid, xdirect);
+    if (strided)        // the twins live in a translation unit of their own (pimemb_internal.h: launch_bag_strided)
+        return launch_bag_strided ? launch_bag_strided(d_descs, m.grid, m.chunks, dtype, itype, g, kind, d_xmap, stream, /*pooled=*/false)
+                                  : hipErrorInvalidValue;
     if (dtype == kMXFP4) {      // the lane-group kernel only: no wave-batch, ranged, hot-row or half-output twin
         if (kind != KERNEL_GROUP || ranged || out_half || g.scalar_lanes) return hipErrorInvalidValue;
         return with_lanes_per_row(g.lanes_per_row, [&](auto l) {
@@ -1231,13 +1242,17 @@ hipError_t launch_bag_sum(const DevDesc *d_descs, uint32_t n_descs, uint32_t max
 
 hipError_t launch_bag_pool(const DevDesc *d_descs, uint32_t n_descs, uint32_t max_tiles, int dtype,
                            emb_index_type itype, const LaunchGeom &g, KernelKind kind, const uint32_t *d_xmap,
-                           uint32_t xgrid, bool xdirect, hipStream_t stream, bool out_half) {
+                           uint32_t xgrid, bool xdirect, hipStream_t stream, bool out_half, bool strided) {
     if (n_descs == 0 || max_tiles == 0) return hipSuccess;
     if (out_half && dtype != EMB_F16 && dtype != EMB_BF16) return hipErrorInvalidValue;
     if (d_xmap == nullptr && n_descs > 65535u) return hipErrorInvalidValue;
     if (kind == KERNEL_ANYDIM ? (g.scalar_lanes == 0 || d_xmap != nullptr) : (kind != KERNEL_WAVEBATCH && kind != KERNEL_GROUP))
         return hipErrorInvalidValue;
+    if (strided && (out_half || kind == KERNEL_ANYDIM)) return hipErrorInvalidValue;
     const MappedLaunch m(n_descs, max_tiles, g, d_xmap, xgrid, xdirect);
+    if (strided)
+        return launch_bag_strided ? launch_bag_strided(d_descs, m.grid, m.chunks, dtype, itype, g, kind, d_xmap, stream, /*pooled=*/true)
+                                  : hipErrorInvalidValue;
     if (dtype == kMXFP4) {      // the lane-group kernel only
         if (kind != KERNEL_GROUP || g.scalar_lanes) return hipErrorInvalidValue;
         return with_lanes_per_row(g.lanes_per_row, [&](auto l) {
@@ -1350,5 +1365,9 @@ hipError_t launch_validate(DevDesc *d_descs, uint32_t n_descs, emb_index_type it
         hipLaunchKernelGGL(validate_kernel<int64_t>, grid, block, 0, stream, d_descs, n_descs, ctl, result, seq, poison ? 1 : 0);
     return hipGetLastError();
 }
+
+#else
+}  // namespace
+#endif      // PIMEMB_CONFIGURATIONS_ONLY
 
 }  // namespace pimemb

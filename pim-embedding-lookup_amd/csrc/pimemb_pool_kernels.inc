@@ -1,9 +1,12 @@
 // pimemb_pool_kernels.inc -- the three kernels of the pooled family (mean / max pooling, per-sample weights, padding_idx).
 // Included by pimemb_bag_kernels.h, inside namespace pimemb, ONCE PER SET OF ENTRY-POINT NAMES: PIMEMB_POOL_KERNEL(path) names
 // the kernel of a path (group, wavebatch, anydim); PIMEMB_POOL_ROWOPS(DT) is the accumulate / store trait and
-// PIMEMB_POOL_HALF_OUT says whether the set stores fp32 rows (0) or rows of the table's 2-byte dtype (1).
-// The same text compiled under four sets of names -- bag_pool_* (fp32, fp16), bag_bf16pool_* (bf16), bag_f8pool_* (fp8),
-// bag_hpool_* (half-width output of fp16 and bf16 tables) -- so that the kernels of the first set keep their machine code to the byte (as bodies
+// PIMEMB_POOL_HALF_OUT says whether the set stores fp32 rows (0) or rows of the table's 2-byte dtype (1).  PIMEMB_OUT_STRIDE(dp,
+// dense) is the distance in floats between two bags' pooled rows: `dense` everywhere but in the strided set, which reads it from
+// the descriptor (DevDesc::words[3]; the group and wave-batch paths only: the set's any-dim kernel is never instantiated).
+// The same text compiled under five sets of names -- bag_pool_* (fp32, fp16), bag_bf16pool_* (bf16), bag_f8pool_* (fp8),
+// bag_hpool_* (half-width output of fp16 and bf16 tables), bag_strided_pool_* (strided fp32 output, every dtype) -- so that
+// the kernels of the first set keep their machine code to the byte (as bodies
 // shared by thin kernels they do not: inlined, 50 of the 64 fp32 / fp16 pooled kernels change, some by up to 4 VGPRs).
 
 // Lane-group path (ragged bags, rows of 16-byte multiples up to 1 KiB): one lane group per bag, as bag_sum_group_kernel.
@@ -26,7 +29,7 @@ PIMEMB_POOL_KERNEL(group)(const DevDesc *__restrict__ descs, uint32_t chunks_arg
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t sub = lane & (LPR - 1), grp = lane / LPR;
     const uint32_t row_bytes = chunks * 16u;
-    const uint32_t out_stride = chunks * Ops::kFloatsPerLane;
+    const uint32_t out_stride = PIMEMB_OUT_STRIDE(dp, chunks * Ops::kFloatsPerLane);
     const char *__restrict__ wsub = t.weights + sub * 16u;
 
     if (tile < t.n_tiles) {
@@ -70,6 +73,7 @@ PIMEMB_POOL_KERNEL(wavebatch)(const DevDesc *__restrict__ descs, uint32_t chunks
     const PoolArgs a = pool_args(dp);
     const LaneGeom<LPR, Ops> ln(weights, chunks);
     const bool lane_live = ln.sub < chunks;
+    const uint32_t out_stride = PIMEMB_OUT_STRIDE(dp, ln.out_stride);    // floats between two bags' pooled rows: read ONCE, with the descriptor's other fields
 
     if (tile >= n_tiles) return;
     const uint64_t step_base = ((uint64_t)tile * kWaves + ln.wave) * 64u;
@@ -126,7 +130,7 @@ PIMEMB_POOL_KERNEL(wavebatch)(const DevDesc *__restrict__ descs, uint32_t chunks
                 typename Ops::Acc acc = Ops::zero();
                 if (has[jj] && lane_live) pool_combine<DT>(acc, v[jj], w, a.op, true);
                 // (all lanes take part in a group store's shuffles)
-                store_row<Ops, Cfg, LPR>(acc, out + bag * ln.out_stride, ln.sub, ln.grp, chunks, bag < n_bags && lane_live);
+                store_row<Ops, Cfg, LPR>(acc, out + bag * out_stride, ln.sub, ln.grp, chunks, bag < n_bags && lane_live);
             }
         }
         return;
@@ -144,7 +148,7 @@ PIMEMB_POOL_KERNEL(wavebatch)(const DevDesc *__restrict__ descs, uint32_t chunks
         uint32_t cnt = 0;
         if (bag < n_bags && lane_live) pool_walk<IdxT, DT, Cfg>(indices, a, p, e, ln.wsub, ln.row_bytes, last_row, acc, cnt);
         pool_finish<DT>(acc, cnt, a.mean);
-        store_row<Ops, Cfg, LPR>(acc, out + bag * ln.out_stride, ln.sub, ln.grp, chunks, bag < n_bags && lane_live);
+        store_row<Ops, Cfg, LPR>(acc, out + bag * out_stride, ln.sub, ln.grp, chunks, bag < n_bags && lane_live);
     }
 }
 

@@ -91,22 +91,31 @@ class EmbeddingBagCollection:
         return cls([w.shape[0] for w in ws], ws[0].shape[1], device=device, weights=ws, weighted_pooling=weighted_pooling,
                    pooling_weights=vw)
 
-    def apply_emb(self, lS_o, lS_i):
+    def apply_emb(self, lS_o, lS_i, concat: bool = False, out=None, col: int = 0):
         """lS_o[k], lS_i[k]: offsets / indices of table k (torch CUDA tensors, int64 or int32, or
         numpy arrays -> host path).  Returns ly: list of [B_k, m] fp32, freshly allocated -- one fused
-        launch on torch's current stream, no plan and no state kept (every batch brings new tensors)."""
+        launch on torch's current stream, no plan and no state kept (every batch brings new tensors).
+        concat=True (torch CUDA tensors): ONE [B, T * m] fp32 tensor instead, equal to torch.cat(ly, dim=1) and written in place
+        by the lookup -- the row the interaction layer reads; out= / col=: a 2-D float32 CUDA buffer whose columns col ..
+        col + T * m receive it, e.g. behind the dense features (engine.lookup_concat)."""
         if len(lS_o) != len(self.ln_emb) or len(lS_i) != len(self.ln_emb):
             raise ValueError("need one (offsets, indices) pair per table")
         # validated and looked up in ONE engine call; nothing runs on bad input
         check = False if self.trusted_inputs else ("deferred" if self.deferred_check else True)
+        if not concat and (out is not None or col):
+            raise ValueError("out= / col= need concat=True")
+        if concat and self._out is not None:
+            raise ValueError('concat=True returns one fp32 tensor: it does not combine with out_dtype="weight"')
         if self.v_W_l is not None:
-            return self._apply_emb_weighted(lS_o, lS_i, check)
+            return self._apply_emb_weighted(lS_o, lS_i, check, concat, out, col)
+        if concat:
+            return self.engine.lookup_concat(self._ids, list(lS_i), list(lS_o), out=out, col=col, check=check)
         if self._out is None and hasattr(lS_i, "dim") and hasattr(lS_o, "dim") and lS_i.dim() == 2 and lS_o.dim() == 2 and lS_i.is_cuda:
             # DLRM stacks fixed-size batches into [T, N] / [T, B] tensors: one [T, B, m] result, unbound
             return list(self.engine.lookup_stacked(self._ids, lS_i, lS_o, check=check).unbind(0))
         return self.engine.lookup_batched(self._ids, list(lS_i), list(lS_o), check=check, out_dtype=self._out)
 
-    def _apply_emb_weighted(self, lS_o, lS_i, check):
+    def _apply_emb_weighted(self, lS_o, lS_i, check, concat=False, out=None, col=0):
         """--weighted-pooling: per-sample weights v_W_l[k][indices] (gathered by torch on the GPU), then ONE pooled call."""
         lS_i, lS_o = list(lS_i), list(lS_o)
         if not all(getattr(i, "is_cuda", False) for i in lS_i):
@@ -114,6 +123,8 @@ class EmbeddingBagCollection:
         if check:      # (a wild index must not reach torch's gather either)
             self.validate(lS_o, lS_i)
         ws = [v.gather(0, i.long()) for v, i in zip(self.v_W_l, lS_i)]
+        if concat:
+            return self.engine.lookup_concat(self._ids, lS_i, lS_o, out=out, col=col, modes="sum", per_sample_weights=ws, check=check)
         return self.engine.lookup_pooled(self._ids, lS_i, lS_o, "sum", per_sample_weights=ws, check=check, out_dtype=self._out)
 
     def validate(self, lS_o, lS_i) -> None:
@@ -270,6 +281,8 @@ def main(argv=None):
     ap.add_argument("--save-model", type=str, default="")
     ap.add_argument("--numpy-rand-seed", type=int, default=123)
     ap.add_argument("--weighted-pooling", type=str, default=None, choices=["fixed", "learned"])
+    ap.add_argument("--concat-output", action="store_true",
+                    help="apply_emb returns ONE [B, T * m] tensor, written in place by the lookup (the interaction layer's input)")
     args, ignored = ap.parse_known_args(argv)
     if ignored:   # MLP / training / logging flags of the reference command lines (README.md:6,10,14)
         print("ignored (outside the embedding path):", " ".join(ignored))
@@ -300,18 +313,19 @@ def main(argv=None):
         else:
             batches.append(random_batch(rng, ebc.ln_emb, B, args.num_indices_per_lookup,
                                         args.num_indices_per_lookup_fixed, dev))
+    cat = bool(args.concat_output)
     for o, i in batches:          # checked once here (IndexError on a bad index), unchecked in the timed loops
-        ebc.apply_emb(o, i)
+        ebc.apply_emb(o, i, concat=cat)
     ebc.trusted_inputs = True
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for b in range(args.num_batches):
         o, i = batches[b % len(batches)]
-        ly = ebc.apply_emb(o, i)
+        ly = ebc.apply_emb(o, i, concat=cat)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.num_batches
-    n_bags = sum(int(x.shape[0]) for x in ly)
-    print(f"apply_emb: {len(ebc.ln_emb)} tables, m={ebc.m}, batch {B}: {dt * 1e3:.4f} ms/batch, "
+    n_bags = int(ly.shape[0]) * len(ebc.ln_emb) if cat else sum(int(x.shape[0]) for x in ly)
+    print(f"apply_emb{' (one [B, T * m] tensor)' if cat else ''}: {len(ebc.ln_emb)} tables, m={ebc.m}, batch {B}: {dt * 1e3:.4f} ms/batch, "
           f"{n_bags / dt:.3e} pooled lookups/s")
     if ebc.v_W_l is not None:     # (prepared plans hold the sum path only)
         ebc.close()

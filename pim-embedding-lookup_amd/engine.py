@@ -196,7 +196,8 @@ class Plan:
 
     def describe(self) -> list[dict]:
         """One dict per kernel launch of the plan: kind, dtype, itype, lanes_per_row, chunks, scalar_lanes, anydim_vec, ranged,
-        descs, grid, bags_per_tile; pool, weighted, padding for a pooled launch; out=1 for a half-output one (emb_plan_describe)."""
+        descs, grid, bags_per_tile; pool, weighted, padding for a pooled launch; out=1 for a half-output one; strided=1 for one
+        that writes strided rows (plan_concat) (emb_plan_describe)."""
         buf = C.create_string_buffer(4096)
         _l.check(self.engine._L.emb_plan_describe(self._p, buf, len(buf)))
         return [{k: int(v) for k, v in (kv.split("=") for kv in rec.split())} for rec in buf.value.decode().split(";") if rec]
@@ -720,15 +721,15 @@ class EmbeddingEngine:
             self._remember_call(key, buf_ptr, n, itype)
         return list(outs)
 
-    def _remember_call(self, key, desc_ptr, n, itype, pools=None) -> None:
+    def _remember_call(self, key, desc_ptr, n, itype, pools=None, strides=None) -> None:
         """Second sighting of a call signature: build its plan.  The cache holds plan_cache_size plans; when it is full the
         least recently used one goes -- but at most once per 64 cacheable calls: destroying a plan waits for the device,
         and a caller whose signatures keep changing must not pay that on every call (its recurring signatures keep their
         plans meanwhile)."""
         with self._plan_lock:
-            self._remember_locked(key, desc_ptr, n, itype, pools)
+            self._remember_locked(key, desc_ptr, n, itype, pools, strides)
 
-    def _remember_locked(self, key, desc_ptr, n, itype, pools=None) -> None:
+    def _remember_locked(self, key, desc_ptr, n, itype, pools=None, strides=None) -> None:
         if key in self._plan_cache or self._check_inputs:
             return
         h = hash(key)                         # (admission bookkeeping only: a collision costs one early plan, nothing else)
@@ -745,7 +746,8 @@ class EmbeddingEngine:
             victim = min(self._plan_cache, key=lambda k: self._plan_cache[k][1])
             self._plan_cache.pop(victim)[0].destroy()
         p = C.c_void_p()
-        rc = (self._L.emb_plan_create(self._h, desc_ptr, n, itype, C.byref(p)) if pools is None else
+        rc = (self._L.emb_plan_create_strided(self._h, desc_ptr, pools, strides, n, itype, C.byref(p)) if strides is not None else
+              self._L.emb_plan_create(self._h, desc_ptr, n, itype, C.byref(p)) if pools is None else
               self._L.emb_plan_create_pooled(self._h, desc_ptr, pools, n, itype, C.byref(p)))
         if rc != _l.EMB_OK:
             return
@@ -952,6 +954,106 @@ class EmbeddingEngine:
         p = C.c_void_p()
         _l.check(self._L.emb_plan_create_pooled(self._h, arr, pools, n, itype, C.byref(p)))
         return Plan(self, p.value, results, keep + pkeep)
+
+    # ---- strided pooled output: every table's pooled rows side by side in ONE [B, col + sum(dim)] buffer (emb_lookup_strided) ----
+    def _concat_call(self, table_ids, indices, offsets, out, col, modes, per_sample_weights, padding_idx, fixed_pooling):
+        """The arguments of a concat call: (descriptors, n, itype, pooling specs or None, strides, out, buffers to keep).  `out`
+        is checked -- or allocated -- before any C call: ValueError for a view whose inner stride is not 1, whose row stride
+        (or col) is no multiple of 4 floats, that is too narrow, whose rows overlap or that has the wrong number of rows; TypeError for anything but a 2-D
+        float32 torch CUDA tensor."""
+        n = len(table_ids)
+        if n == 0:
+            raise ValueError("lookup_concat needs at least one table")
+        col = int(col)
+        if col < 0:
+            raise ValueError("col must be >= 0")
+        dims = []
+        for t in table_ids:
+            if t not in self._tables:
+                raise KeyError(f"table {t} is not loaded")
+            dims.append(self._tables[t][1])
+        width = col + sum(dims)
+        if out is not None:
+            if not _is_torch(out) or str(out.dtype) != "torch.float32":
+                raise TypeError(f"lookup_concat needs a float32 torch tensor as out, got {getattr(out, 'dtype', type(out).__name__)}")
+            if out.dim() != 2:
+                raise ValueError(f"out must be 2-D [B, >= {width}], got {tuple(out.shape)}")
+            if out.stride(1) != 1:
+                raise ValueError(f"out must have inner stride 1 (a row's floats back to back), got stride {tuple(out.stride())}")
+            if out.stride(0) % 4 != 0 or col % 4 != 0:
+                raise ValueError(f"out's row stride and col must each be a multiple of 4 floats (rows start on 16-byte boundaries), got row stride "
+                                 f"{out.stride(0)}, col {col}")
+            if out.shape[1] < width:
+                raise ValueError(f"out is too narrow: {out.shape[1]} columns, col {col} + dims {sum(dims)} need {width}")
+            if out.shape[0] > 1 and out.stride(0) < width:       # (an expanded view: rows on top of each other -- and the C call
+                raise ValueError(f"out's rows overlap: row stride {out.stride(0)} for {width} columns written per row")   # reads stride 0 as dense)
+        arr, n, itype, space, _res, keep = self._descs(table_ids, indices, offsets, None, fixed_pooling, want_outputs=False)
+        n_bags = arr[0].n_bags
+        if any(arr[i].n_bags != n_bags for i in range(n)):
+            raise ValueError("lookup_concat: every table must have the same number of bags (one output row per sample)")
+        if out is not None and out.shape[0] != n_bags:
+            raise ValueError(f"out has {out.shape[0]} rows for {n_bags} bags")
+        if space != _l.EMB_MEM_DEVICE or not _is_torch(indices[0]) or (out is not None and not out.is_cuda):
+            raise TypeError("lookup_concat needs torch CUDA tensors (strided output exists for device buffers only)")
+        if out is None:
+            import torch
+            out = torch.empty((n_bags, width), dtype=torch.float32, device=indices[0].device)
+        base, at = out.data_ptr(), col
+        for i in range(n):
+            arr[i].pooled = base + 4 * at
+            at += dims[i]
+        strides = (C.c_uint64 * n)(*([out.stride(0)] * n))      # (one table, no gap: stride == dim, which the C call takes as dense)
+        pools = None
+        if modes is not None or per_sample_weights is not None or padding_idx is not None:
+            pools, pkeep = self._pools(n, arr, "sum" if modes is None else modes, per_sample_weights, padding_idx, space)
+            keep = keep + pkeep
+        return arr, n, itype, pools, strides, out, keep + [out]
+
+    def lookup_concat(self, table_ids: Sequence[int], indices: Sequence, offsets: Sequence, out=None, col: int = 0, modes=None,
+                      per_sample_weights=None, padding_idx=None, fixed_pooling=0, stream: int | None = None,
+                      check: bool | str = False):
+        """lookup_batched / lookup_pooled that returns ONE 2-D float32 CUDA tensor instead of a list: table i's pooled rows sit
+        at columns col + sum(dim_j, j < i) of every sample's row -- torch.cat(<the list>, dim=1) without the second pass over
+        the rows (emb_lookup_strided: the kernels store straight into the strided rows).  `out`: any 2-D float32 CUDA tensor
+        or view with stride(1) == 1 that has B rows and at least col + sum(dims) columns, e.g. the buffer that already
+        holds the dense features in its first `col` columns; nothing but the tables' columns is written.  Allocated
+        [B, col + sum(dims)] when None.  Its rows must not overlap and must start at 16-byte multiples: a row stride of at
+        least col + sum(dims) floats, row stride and col multiples of 4 floats (ValueError otherwise), and a data_ptr() on a
+        16-byte boundary (the C call refuses otherwise).
+        modes / per_sample_weights / padding_idx as lookup_pooled's, check as lookup_batched's: a refused call leaves `out`
+        untouched.  Tables on the any-dim kernels, fixed-point tables and out_dtype="table" have no strided output (the C
+        call refuses them).  Per-call plans are cached under a key of their own, which holds the strides: a dense call never
+        replays a strided plan, nor the other way round."""
+        arr, n, itype, pools, strides, out, _keep = self._concat_call(table_ids, indices, offsets, out, col, modes, per_sample_weights,
+                                                                      padding_idx, fixed_pooling)
+        if stream is None:
+            stream = _current_stream_for(*indices)
+        c = 0 if not check else (2 if check == "deferred" else 1)
+        key = None
+        if c == 0 and self.plan_cache_size:
+            key = ("concat", bytes(arr), b"" if pools is None else bytes(pools), bytes(strides), itype)
+            if self._launch_cached(key, stream):
+                return out
+        bad = C.c_uint64()
+        rc = self._L.emb_lookup_strided(self._h, arr, pools, strides, n, itype, stream, c, C.byref(bad))
+        if rc == _l.EMB_ERR_RANGE:
+            text = self._L.emb_last_error().decode(errors="replace")
+            if c == 2 or "EARLIER" in text:
+                raise IndexError(text)
+            self._raise_range(bad.value)
+        _l.check(rc)
+        if key is not None:
+            self._remember_call(key, arr, n, itype, pools, strides)
+        return out
+
+    def plan_concat(self, table_ids, indices, offsets, out=None, col: int = 0, modes=None, per_sample_weights=None, padding_idx=None,
+                    fixed_pooling=0) -> Plan:
+        """plan() for lookup_concat's call (emb_plan_create_strided): Plan.outputs is the ONE [B, >= col + sum(dims)] tensor."""
+        arr, n, itype, pools, strides, out, keep = self._concat_call(table_ids, indices, offsets, out, col, modes, per_sample_weights,
+                                                                     padding_idx, fixed_pooling)
+        p = C.c_void_p()
+        _l.check(self._L.emb_plan_create_strided(self._h, arr, pools, strides, n, itype, C.byref(p)))
+        return Plan(self, p.value, out, keep)
 
     def validate(self, table_ids, indices, offsets, fixed_pooling=0) -> int:
         """Debug check: number of out-of-range indices / broken offsets (0 = clean)."""

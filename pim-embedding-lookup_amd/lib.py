@@ -148,6 +148,9 @@ SIGNATURES = {
     "emb_lookup_pooled": (C.c_int, [_vp, C.POINTER(EmbLookupDesc), C.POINTER(EmbPoolSpec), _u32, C.c_int, C.c_int, _vp, _u32,
                                     C.POINTER(_u64)]),
     "emb_plan_create_pooled": (C.c_int, [_vp, C.POINTER(EmbLookupDesc), C.POINTER(EmbPoolSpec), _u32, C.c_int, _pp]),
+    "emb_lookup_strided": (C.c_int, [_vp, C.POINTER(EmbLookupDesc), C.POINTER(EmbPoolSpec), C.POINTER(_u64), _u32, C.c_int, _vp, _u32,
+                                     C.POINTER(_u64)]),
+    "emb_plan_create_strided": (C.c_int, [_vp, C.POINTER(EmbLookupDesc), C.POINTER(EmbPoolSpec), C.POINTER(_u64), _u32, C.c_int, _pp]),
     "emb_plan_launch": (C.c_int, [_vp, _vp]),
     "emb_plan_destroy": (C.c_int, [_vp]),
     "emb_plan_bytes": (C.c_int, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),

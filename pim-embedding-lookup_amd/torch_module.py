@@ -204,11 +204,16 @@ class EmbeddingBag(torch.nn.Module):
 
 
 class FusedEmbeddingBags(torch.nn.Module):
-    """All tables of a model: forward(lS_o, lS_i) -> list of [B, m] with ONE fused launch (apply_emb)."""
+    """All tables of a model: forward(lS_o, lS_i) -> list of [B, m] with ONE fused launch (apply_emb).
+    concat=True: forward returns ONE [B, sum(m)] fp32 tensor instead, equal to torch.cat(<the list>, dim=1) -- what the
+    interaction layer reads -- written in place by the lookup (engine.lookup_concat), and takes out= / col=: a 2-D float32 CUDA
+    buffer (or view, inner stride 1) whose columns col .. col + sum(m) receive the rows, e.g. behind the dense features."""
 
-    def __init__(self, bags, trusted_inputs: bool | None = None, deferred_check: bool | None = None, out_dtype: str | None = None):
+    def __init__(self, bags, trusted_inputs: bool | None = None, deferred_check: bool | None = None, out_dtype: str | None = None,
+                 concat: bool = False):
         super().__init__()
         self.bags = torch.nn.ModuleList(bags)
+        self.concat = _concat_flag(concat, bags, out_dtype)
         # unchecked only if every table says so (or the caller does); the same for the deferred verdict
         self.trusted_inputs = all(b.trusted_inputs for b in bags) if trusted_inputs is None else bool(trusted_inputs)
         self.deferred_check = all(b.deferred_check for b in bags) if deferred_check is None else bool(deferred_check)
@@ -220,21 +225,32 @@ class FusedEmbeddingBags(torch.nn.Module):
         self._ids = [b.table_id for b in self.bags]
 
     @classmethod
-    def from_torch(cls, emb_l, **kw):
-        return cls([EmbeddingBag.from_torch(m, **kw) for m in emb_l])
+    def from_torch(cls, emb_l, concat: bool = False, **kw):
+        return cls([EmbeddingBag.from_torch(m, **kw) for m in emb_l], concat=concat)
 
-    def forward(self, lS_o, lS_i):
+    def forward(self, lS_o, lS_i, out=None, col: int = 0):
         check = False if self.trusted_inputs else ("deferred" if self.deferred_check else True)
-        if self._outs is None and hasattr(lS_i, "dim") and lS_i.dim() == 2 and hasattr(lS_o, "dim") and lS_o.dim() == 2 and lS_i.is_cuda:
+        if not self.concat and (out is not None or col):
+            raise ValueError("out= / col= need a module made with concat=True")
+        if not self.concat and self._outs is None and hasattr(lS_i, "dim") and lS_i.dim() == 2 and hasattr(lS_o, "dim") and lS_o.dim() == 2 and lS_i.is_cuda:
             return list(self.engine.lookup_stacked(self._ids, lS_i, lS_o, check=check).unbind(0))      # (one fp32 [T, B, dim] tensor)
         idx, off = [], []
         for b, i, o in zip(self.bags, lS_i, lS_o):
             i1, o1 = _bags_from(i, o, b.include_last_offset)
             idx.append(i1.contiguous())
             off.append(o1.contiguous())
+        if self.concat:
+            return self.engine.lookup_concat(self._ids, idx, off, out=out, col=col, check=check)
         return self.engine.lookup_batched(self._ids, idx, off, check=check, out_dtype=self._outs)
 
     apply_emb = forward
+
+
+def _concat_flag(concat, bags, out_dtype) -> bool:
+    """concat=True of a fused module: one fp32 [B, sum(dim)] tensor -- which half-width rows cannot share."""
+    if concat and _fused_out_dtypes(bags, out_dtype) is not None:
+        raise ValueError('concat=True returns one fp32 tensor: it does not combine with out_dtype="weight"')
+    return bool(concat)
 
 
 def _fused_out_dtypes(bags, out_dtype):
@@ -329,11 +345,14 @@ def _weights_for(per_sample_weights, mode, input):
 
 class FusedPoolingEmbeddingBags(torch.nn.Module):
     """All tables of a model, each with its own mode and padding_idx: forward(lS_o, lS_i, lS_w=None) -> list of [B, m] with
-    ONE engine call (lS_w: per-table per-sample weights or None, sum tables only)."""
+    ONE engine call (lS_w: per-table per-sample weights or None, sum tables only).  concat=True, out= / col=: as
+    FusedEmbeddingBags -- ONE [B, sum(m)] fp32 tensor, every mode, weights and padding included."""
 
-    def __init__(self, bags, trusted_inputs: bool | None = None, deferred_check: bool | None = None, out_dtype: str | None = None):
+    def __init__(self, bags, trusted_inputs: bool | None = None, deferred_check: bool | None = None, out_dtype: str | None = None,
+                 concat: bool = False):
         super().__init__()
         self.bags = torch.nn.ModuleList(bags)
+        self.concat = _concat_flag(concat, bags, out_dtype)
         self.trusted_inputs = all(b.trusted_inputs for b in bags) if trusted_inputs is None else bool(trusted_inputs)
         self.deferred_check = all(b.deferred_check for b in bags) if deferred_check is None else bool(deferred_check)
         self._outs = _fused_out_dtypes(bags, out_dtype)
@@ -345,17 +364,22 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         self._pads = [b.padding_idx for b in self.bags]
 
     @classmethod
-    def from_torch(cls, emb_l, **kw):
-        return cls([PoolingEmbeddingBag.from_torch(m, **kw) for m in emb_l])
+    def from_torch(cls, emb_l, concat: bool = False, **kw):
+        return cls([PoolingEmbeddingBag.from_torch(m, **kw) for m in emb_l], concat=concat)
 
-    def forward(self, lS_o, lS_i, lS_w=None):
+    def forward(self, lS_o, lS_i, lS_w=None, out=None, col: int = 0):
         check = False if self.trusted_inputs else ("deferred" if self.deferred_check else True)
+        if not self.concat and (out is not None or col):
+            raise ValueError("out= / col= need a module made with concat=True")
         idx, off, ws = [], [], []
         for k, (b, i, o) in enumerate(zip(self.bags, lS_i, lS_o)):
             i1, o1 = _bags_from(i, o, b.include_last_offset)
             idx.append(i1.contiguous())
             off.append(o1.contiguous())
             ws.append(_weights_for(None if lS_w is None else lS_w[k], b.mode, i))
+        if self.concat:
+            return self.engine.lookup_concat(self._ids, idx, off, out=out, col=col, modes=self._modes,
+                                             per_sample_weights=None if lS_w is None else ws, padding_idx=self._pads, check=check)
         return self.engine.lookup_pooled(self._ids, idx, off, self._modes,
                                          per_sample_weights=None if lS_w is None else ws, padding_idx=self._pads, check=check,
                                          out_dtype=self._outs)
