@@ -109,7 +109,20 @@ def device_code_sha256(lib_path: str, arch: str = "gfx950") -> str:
 def kernel_hashes(lib_path: str, arch: str = "gfx950") -> dict[str, str]:
     """{mangled kernel name: sha256(machine code || 64-byte kernel descriptor)} for every kernel of the code object.  The
     descriptor's code-entry offset is masked: it moves whenever ANY kernel of the library grows, the kernel's code does not.
-    Over every code object of the library (a kernel lives in exactly one)."""
+    Over every code object of the library (a kernel lives in exactly one).  The walk of one build of a file is done once per
+    process (keyed by path, size and modification time): kernel_of_launch() resolves a record per kernel of a test run."""
+    import os
+    st = os.stat(lib_path)
+    key = (os.path.abspath(lib_path), arch, st.st_size, st.st_mtime_ns)
+    if key not in _hashes:
+        _hashes[key] = _kernel_hashes(lib_path, arch)
+    return dict(_hashes[key])
+
+
+_hashes: dict = {}
+
+
+def _kernel_hashes(lib_path: str, arch: str) -> dict[str, str]:
     out = {}
     for blob in device_code_objects(lib_path, arch):
         co = _Elf(blob)
@@ -137,8 +150,10 @@ def symbol_fragments(launch: dict) -> list[str]:
     same under the name bag_bf16pool_*, for fp8 tables (dtype 8 / 9) under bag_f8pool_*.  A half-output launch (a record with out=1, EMB_POOL_OUT_TABLE_DTYPE) runs the twin of
     that kernel: a pooled one under the name bag_hpool_* (fp16 and bf16 tables alike), a sum one the same bag_sum_* template
     with the internal dtype value DT | 16 (pimemb_bag_kernels.h: kHalfOutDT).  MXFP4 tables (dtype 10) have two kernel
-    templates of their own, without a DT argument.  A strided launch (a record with strided=1, emb_plan_create_strided) runs
-    the twin of its kernel under a name that holds none of the fragments above: bag_strided_sum_<family>_kernel<IdxT, DT, LPR,
+    templates of their own, without a DT argument.
+    A hot-row launch (kind 4: a small plain-sum launch over a table with a set_hot_rows hint) runs bag_sum_hot_kernel<IdxT, DT,
+    LPR, HotCfg>: fp32 output only, never ranged, pooled, half-output or strided.  A strided launch (a record with strided=1,
+    emb_plan_create_strided) runs the twin of its kernel under a name that holds none of the fragments above: bag_strided_sum_<family>_kernel<IdxT, DT, LPR,
     Cfg[, false]>, bag_strided_pool_<family>_kernel<IdxT, DT, LPR, Cfg> for every dtype alike, and for MXFP4
     bag_strided_e2m1sum_group_kernel / bag_strided_e2m1pool_group_kernel<IdxT, LPR, Cfg>; the wave-batch, two-batch and
     lane-group kinds only, never ranged or half-output."""
