@@ -223,6 +223,11 @@ int emb_learn_hot_rows(emb_engine *e, uint32_t table_id, const void *indices, ui
 int emb_table_info(emb_engine *e, uint32_t table_id, void **device_rows, uint64_t *nr_rows,
                    uint32_t *dim, emb_dtype *dtype);
 
+/* Rows of the table's hot set as staged by emb_set_hot_rows / emb_learn_hot_rows (0: none).  The set is a COPY of those rows,
+ * so whoever writes rows in place -- the row writer of pimemb_rows.h, a caller storing through emb_table_info's pointer -- asks
+ * this first: with a set staged, pooled lookups would go on serving the old bytes.  Host-only: reads a counter. */
+int emb_table_hot_count(emb_engine *e, uint32_t table_id, uint32_t *n_rows);
+
 /* The north star's lookup(table_id, offsets, indices) -> pooled_rows, one table.
  * `stream` is a hipStream_t (NULL = the default stream).  With EMB_MEM_HOST the call copies in,
  * runs and copies out synchronously; with EMB_MEM_DEVICE it only enqueues work on `stream`. */

@@ -7,16 +7,18 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb.so")
+ROWS_LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb_rows.so")     # the row writer (include/pimemb_rows.h): a companion library
 MARSHAL_PATH = os.path.join(PKG_DIR, "lib", "_pimemb_marshal.so")
 SOURCES = ["pimemb_kernels.hip", "pimemb_strided_kernels.hip", "pimemb_engine.cpp", "pimemb_compat.cpp", "pimemb_comm.cpp", "pimemb_shard.cpp", "pimemb_peer.cpp", "pimemb_peer.h", "pimemb_internal.h", "pimemb_torch_marshal.cpp",
            "pimemb_bag_kernels.h", "pimemb_pool_kernels.inc", "pimemb_sum_kernels.inc", "pimemb_mx4_kernels.inc", "pimemb_xcd_map.h", "pimemb_hot_rows.h", "pimemb_hostcopy.h", "Makefile",
+           "pimemb_rows.hip", "pimemb_rows_encode.h", os.path.join("..", "..", "include", "pimemb_rows.h"),
            os.path.join("..", "..", "include", "pimemb.h")]
 
 
 def is_stale() -> bool:
-    if not os.path.exists(LIB_PATH):
+    if not os.path.exists(LIB_PATH) or not os.path.exists(ROWS_LIB_PATH):
         return True
-    built = os.path.getmtime(LIB_PATH)
+    built = min(os.path.getmtime(LIB_PATH), os.path.getmtime(ROWS_LIB_PATH))
     return any(os.path.getmtime(os.path.join(CSRC_DIR, s)) > built for s in SOURCES if s != "pimemb_torch_marshal.cpp")
 
 
@@ -47,8 +49,8 @@ def build_marshal(verbose: bool = False) -> str | None:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile the HIP kernels + C-ABI into pim-embedding-lookup_amd/lib/libpimemb.so (in-tree, so
-    the built library travels to the GPU box with the repo snapshot)."""
+    """Compile the HIP kernels + C-ABI into pim-embedding-lookup_amd/lib/libpimemb.so and the row writer into
+    lib/libpimemb_rows.so next to it (in-tree, so the built libraries travel to the GPU box with the repo snapshot)."""
     if force:
         subprocess.check_call(["make", "-C", CSRC_DIR, "clean"], stdout=subprocess.DEVNULL)
     if force or is_stale():
@@ -61,6 +63,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 raise RuntimeError("building libpimemb.so failed:\n" + res.stdout)
     if not os.path.exists(LIB_PATH):
         raise RuntimeError("libpimemb.so missing after build")
+    if not os.path.exists(ROWS_LIB_PATH):
+        raise RuntimeError("libpimemb_rows.so missing after build")
     build_marshal(verbose)          # optional: a failure is a warning, never an error
     return LIB_PATH
 
@@ -71,7 +75,7 @@ def build_clamped(out_dir: str) -> str:
     out = os.path.join(out_dir, "libpimemb_clamp.so")
     flags = "-O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -I../../include -I. -DPIMEMB_CLAMP_INPUTS=1"
     res = subprocess.run(["make", "-C", CSRC_DIR, "-j8", f"CXXFLAGS={flags}", f"OUT={out}",
-                          f"OBJDIR={os.path.join(out_dir, 'obj_clamp')}"],
+                          f"OBJDIR={os.path.join(out_dir, 'obj_clamp')}", out],
                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if res.returncode != 0 or not os.path.exists(out):
         raise RuntimeError("building the clamped flavour failed:\n" + res.stdout)

@@ -1422,6 +1422,14 @@ int emb_learn_hot_rows(emb_engine *e, uint32_t table_id, const void *indices, ui
     return rc;
 }
 
+int emb_table_hot_count(emb_engine *e, uint32_t table_id, uint32_t *n_rows) {
+    if (!e || !n_rows) return fail(EMB_ERR_INVALID, "engine or n_rows is NULL");
+    if (table_id >= e->tables.size() || !e->tables[table_id].rows)
+        return fail(EMB_ERR_INVALID, "table %u is not loaded", table_id);
+    *n_rows = e->tables[table_id].n_hot;
+    return EMB_OK;
+}
+
 int emb_table_info(emb_engine *e, uint32_t table_id, void **device_rows, uint64_t *nr_rows,
                    uint32_t *dim, emb_dtype *dtype) {
     if (!e) return fail(EMB_ERR_INVALID, "engine is NULL");

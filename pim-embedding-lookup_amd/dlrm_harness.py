@@ -26,9 +26,11 @@ class EmbeddingBagCollection:
 
     def __init__(self, ln_emb, m_spa: int, device: int = 0, weights=None, seed: int = 0, dtype="f32",
                  trusted_inputs: bool = False, deferred_check: bool = False, weighted_pooling: str | None = None,
-                 pooling_weights=None, out_dtype: str | None = None):
+                 pooling_weights=None, out_dtype: str | None = None, quantize_on_device: bool = False):
         import torch
         self.torch = torch
+        # quantize_on_device=True: fp32 weights are encoded into `dtype` ON THE GPU (engine.load_table_f32: the row writer,
+        # bit for bit what the host encoders below give) instead of on the host -- no encoded copy of a table in host memory
         # out_dtype="weight": f16 / bf16 tables return rows of their own dtype (the fp32 sum rounded once), as nn.EmbeddingBag
         # does; None: fp32 rows whatever the tables hold
         if out_dtype not in (None, "weight"):
@@ -53,6 +55,14 @@ class EmbeddingBagCollection:
             else:  # DLRM init: U(-sqrt(1/n), sqrt(1/n))
                 a = float(np.sqrt(1.0 / n))
                 w = torch.empty((n, self.m), dtype=torch.float32, device=self.device).uniform_(-a, a, generator=g)
+            if quantize_on_device:
+                from . import lib as _lib
+                codes = {"f32": _lib.EMB_F32, "f16": _lib.EMB_F16, "bf16": _lib.EMB_BF16, "fp8_e4m3": _lib.EMB_F8_E4M3,
+                         "fp8_e5m2": _lib.EMB_F8_E5M2, "mxfp4": _lib.EMB_MXFP4}
+                if dtype not in codes:
+                    raise ValueError("dtype must be 'f32', 'f16', 'bf16', 'fp8_e4m3', 'fp8_e5m2' or 'mxfp4'")
+                self.engine.load_table_f32(k, w, codes[dtype])
+                continue
             tdt = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16, "fp8_e4m3": torch.float8_e4m3fn,
                    "fp8_e5m2": torch.float8_e5m2}.get(dtype)
             if dtype == "mxfp4":       # fp32 checkpoints are quantised by the OCP MX rule (formats.to_mxfp4); m a multiple of 32
@@ -84,12 +94,13 @@ class EmbeddingBagCollection:
                     raise ValueError(f"table {k}: {v.numel()} pooling weights for {self.ln_emb[k]} rows")
 
     @classmethod
-    def from_checkpoint(cls, path: str, device: int = 0, weighted_pooling: str | None = None):
+    def from_checkpoint(cls, path: str, device: int = 0, weighted_pooling: str | None = None, dtype="f32",
+                        quantize_on_device: bool = False):
         from .formats import load_dlrm_embedding_weights, load_dlrm_pooling_weights
         ws = load_dlrm_embedding_weights(path)
         vw = load_dlrm_pooling_weights(path, len(ws)) if weighted_pooling == "learned" else None
         return cls([w.shape[0] for w in ws], ws[0].shape[1], device=device, weights=ws, weighted_pooling=weighted_pooling,
-                   pooling_weights=vw)
+                   pooling_weights=vw, dtype=dtype, quantize_on_device=quantize_on_device)
 
     def apply_emb(self, lS_o, lS_i, concat: bool = False, out=None, col: int = 0):
         """lS_o[k], lS_i[k]: offsets / indices of table k (torch CUDA tensors, int64 or int32, or
@@ -283,6 +294,9 @@ def main(argv=None):
     ap.add_argument("--weighted-pooling", type=str, default=None, choices=["fixed", "learned"])
     ap.add_argument("--concat-output", action="store_true",
                     help="apply_emb returns ONE [B, T * m] tensor, written in place by the lookup (the interaction layer's input)")
+    ap.add_argument("--quantize-on-device", action="store_true",
+                    help="fp32 weights (a checkpoint's, or the random init) reach the tables through the GPU row writer "
+                         "(engine.load_table_f32) instead of the host encoders")
     args, ignored = ap.parse_known_args(argv)
     if ignored:   # MLP / training / logging flags of the reference command lines (README.md:6,10,14)
         print("ignored (outside the embedding path):", " ".join(ignored))
@@ -299,11 +313,13 @@ def main(argv=None):
     else:
         ln_emb = [int(x) for x in args.arch_embedding_size.split("-")]
     if args.load_model:
-        ebc = EmbeddingBagCollection.from_checkpoint(args.load_model, weighted_pooling=args.weighted_pooling)
+        ebc = EmbeddingBagCollection.from_checkpoint(args.load_model, weighted_pooling=args.weighted_pooling,
+                                                     quantize_on_device=args.quantize_on_device)
     else:
         if args.weighted_pooling == "learned":
             raise SystemExit("--weighted-pooling learned needs --load-model (the per-row weights v_W_l come from it)")
-        ebc = EmbeddingBagCollection(ln_emb, args.arch_sparse_feature_size, weighted_pooling=args.weighted_pooling)
+        ebc = EmbeddingBagCollection(ln_emb, args.arch_sparse_feature_size, weighted_pooling=args.weighted_pooling,
+                                     quantize_on_device=args.quantize_on_device)
     B = args.mini_batch_size
     batches = []
     for b in range(min(args.num_batches, 16)):

@@ -306,6 +306,77 @@ class NativeExchange:
             self._h = None
 
 
+class RowWriter:
+    """In-place row updates of an engine's tables (libpimemb_rows.so, include/pimemb_rows.h): fp32 rows in, the table's own
+    bytes out, encoded on the GPU bit for bit as formats.py's host encoders write them.  EmbeddingEngine.row_writer makes one.
+    One writer, one thread, one stream at a time: its scratch is shared by its calls."""
+
+    def __init__(self, engine: "EmbeddingEngine", max_rows: int):
+        if engine._L is not _l.load():
+            raise ValueError("the row writer works with the default libpimemb.so (the one libpimemb_rows.so links against), not with a lib_path engine")
+        self.engine = engine
+        self.max_rows = int(max_rows)
+        self._R = _l.load_rows()
+        h = C.c_void_p()
+        _l.check_rows(self._R.emb_rows_create(engine._h, self.max_rows, C.byref(h)))
+        self._h = h.value
+        engine._writers.append(self)
+
+    def update(self, table_id: int, ids, rows, *, src: str = "f32", unique: bool = False, stream: int | None = None) -> int:
+        """W[ids[p]] = rows[p] for p = 0, 1, ...: the last occurrence of an id wins.  ids: uint32 / int32 bits or int64; rows:
+        src="f32" float32 [n, dim], src="table" [n, ...] rows of the table's own row stride in bytes (any dtype of that width).
+        Both numpy arrays (or CPU tensors): the synchronous host path, any n; returns the number of rows skipped (an id outside
+        the table; an inf / NaN in an MXFP4 source row).  Both torch CUDA tensors / DeviceBuffers: enqueued on `stream` (torch's
+        current one by default), n <= max_rows; returns 0, skipped rows are counted for report().
+        unique=True is the promise that no id occurs twice (EMB_ROWS_UNIQUE_IDS: no duplicate pre-pass)."""
+        if src not in ("f32", "table"):
+            raise ValueError('src must be "f32" or "table"')
+        i, r = _Arg(ids), _Arg(rows)
+        if i.space != r.space:
+            raise ValueError("ids and rows must both be host arrays or both live on the device")
+        itype = _index_type_of(i.dtype)
+        if src == "f32" and str(r.dtype).replace("torch.", "") != "float32":
+            raise TypeError(f'src="f32" rows must be float32, got {r.dtype}')
+        if r.n != i.n:
+            raise ValueError(f"{i.n} ids for {r.n} rows")
+        nr_rows, dim, dt = self.engine._tables[table_id] if table_id in self.engine._tables else self.engine.table_info(table_id)[1:]
+        k = r.keep
+        row_bytes = (k.nbytes if hasattr(k, "nbytes") else k.numel() * k.element_size()) // max(r.n, 1)
+        from .formats import mxfp4_row_stride
+        want = dim * 4 if src == "f32" else mxfp4_row_stride(dim) if dt == _l.EMB_MXFP4 else \
+            dim * {_l.EMB_F32: 4, _l.EMB_FIXED32: 4, _l.EMB_F16: 2, _l.EMB_BF16: 2}.get(dt, 1)
+        if r.n and row_bytes != want:
+            raise ValueError(f"table {table_id}: a source row is {want} bytes, got {row_bytes}")
+        if stream is None and i.space == _l.EMB_MEM_DEVICE:
+            stream = _current_stream_for(ids, rows)
+        bad = C.c_uint64()
+        rc = self._R.emb_rows_update(self._h, table_id, i.ptr, itype, i.n, r.ptr, _l.EMB_ROWS_SRC_F32 if src == "f32" else _l.EMB_ROWS_SRC_TABLE_DTYPE,
+                                     i.space, _l.EMB_ROWS_UNIQUE_IDS if unique else 0, stream, C.byref(bad))
+        if rc == _l.EMB_ERR_RANGE and i.space == _l.EMB_MEM_HOST:
+            return bad.value
+        _l.check_rows(rc)
+        return 0
+
+    def report(self) -> int:
+        """Rows skipped by device-pointer updates since the last report (waits for the device; resets the count)."""
+        bad = C.c_uint64()
+        _l.check_rows(self._R.emb_rows_report(self._h, C.byref(bad)))
+        return bad.value
+
+    def close(self) -> None:
+        if self._h:
+            self._R.emb_rows_destroy(self._h)
+            self._h = None
+            if self in self.engine._writers:
+                self.engine._writers.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class EmbeddingEngine:
     """One engine per GPU: tables resident in HBM, lookups as fused HIP launches."""
 
@@ -324,6 +395,7 @@ class EmbeddingEngine:
         _l.check(self._L.emb_create(C.byref(cfg), C.byref(h)))
         self._h = h.value
         self._tables: dict[int, tuple[int, int, int]] = {}  # id -> (nr_rows, dim, dtype)
+        self._writers: list = []                            # live RowWriters (closed with the engine)
         # Scratch descriptor arrays are PER THREAD: the C call that reads them releases the GIL, so another thread packing
         # its own call into a shared array would be read half-way (lookups may be issued from several threads, pimemb.h).
         self._tls = threading.local()                       # .bufs: n descriptors -> (buffer, typed pointer, address)
@@ -409,6 +481,40 @@ class EmbeddingEngine:
         _l.check(self._L.emb_alloc_table(self._h, table_id, nr_rows, dim, dtype))
         self._tables[table_id] = (nr_rows, dim, dtype)
         self._same_dim.clear()
+
+    def row_writer(self, max_rows: int = 65536) -> RowWriter:
+        """A writer for in-place row updates of this engine's tables, for device-pointer calls of up to max_rows rows
+        (host-pointer calls of any size are chunked): see RowWriter.update.  Closed with the engine at the latest."""
+        return RowWriter(self, max_rows)
+
+    def load_table_f32(self, table_id: int, rows_f32, dtype: int, chunk_rows: int = 65536) -> None:
+        """Allocate table `table_id` as `dtype` (any but EMB_FIXED32) and fill it from float32 rows [nr_rows, dim], encoded ON
+        THE GPU chunk by chunk -- the bytes are those of load_table(to_*(rows)) with formats.py's host encoders.  A numpy array
+        (or CPU tensor) goes through the writer's pinned buffer: host memory beyond the source itself is one chunk.  A torch
+        CUDA tensor is read in place; nothing touches the host.  MXFP4: a row with an inf or a NaN raises ValueError, as
+        formats.to_mxfp4 does (the rows before it have been written)."""
+        cuda = _is_torch(rows_f32) and rows_f32.is_cuda
+        if _is_torch(rows_f32) and not cuda:
+            rows_f32 = rows_f32.detach().numpy()
+        if len(rows_f32.shape) != 2:
+            raise ValueError("table must be 2-D [nr_rows, dim]")
+        n, dim = int(rows_f32.shape[0]), int(rows_f32.shape[1])
+        self.alloc_table(table_id, n, dim, dtype)
+        with self.row_writer(min(int(chunk_rows), max(n, 1))) as w:
+            for at in range(0, n, int(chunk_rows)):
+                m = min(int(chunk_rows), n - at)
+                if cuda:
+                    import torch
+                    ids = torch.arange(at, at + m, dtype=torch.int64, device=rows_f32.device)
+                    w.update(table_id, ids, rows_f32[at:at + m].float().contiguous(), unique=True)
+                    bad = 0
+                else:
+                    bad = w.update(table_id, np.arange(at, at + m, dtype=np.int64), np.ascontiguousarray(rows_f32[at:at + m], dtype=np.float32),
+                                   unique=True)
+                if bad:
+                    raise ValueError(f"load_table_f32: table {table_id}: {bad} rows of rows [{at}, {at + m}) hold a non-finite value, which {('MXFP4' if dtype == _l.EMB_MXFP4 else 'this dtype')} cannot encode")
+            if cuda and w.report():
+                raise ValueError(f"load_table_f32: table {table_id}: rows with a non-finite value, which MXFP4 cannot encode, were skipped")
 
     def load_table_column(self, table_id: int, col: int, column: np.ndarray) -> None:
         column = np.ascontiguousarray(column, dtype=np.int32)
@@ -1151,6 +1257,8 @@ class EmbeddingEngine:
     def close(self) -> None:
         if self._h:
             self._drop_plans()                       # the plan cache's own plans
+            for w in list(self._writers):
+                w.close()
             pending = None
             try:
                 self.check_report()                  # a deferred verdict nobody met is raised here, after the engine is gone

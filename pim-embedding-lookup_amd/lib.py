@@ -130,6 +130,7 @@ SIGNATURES = {
     "emb_shard_sent_counts": (C.c_int, [_vp, _u64, C.POINTER(_u32), _u32]),
     "emb_shard_destroy": (C.c_int, [_vp]),
     "emb_table_info": (C.c_int, [_vp, _u32, _pp, C.POINTER(_u64), C.POINTER(_u32), C.POINTER(C.c_int)]),
+    "emb_table_hot_count": (C.c_int, [_vp, _u32, C.POINTER(_u32)]),
     "emb_lookup": (C.c_int, [_vp, _u32, _vp, _u64, _vp, _u64, _vp, C.c_int, C.c_int, _vp]),
     "emb_lookup_batched": (C.c_int, [_vp, C.POINTER(EmbLookupDesc), _u32, C.c_int, C.c_int, _vp]),
     "emb_queue_create": (C.c_int, [_vp, C.c_int, C.c_int, _pp]),
@@ -195,7 +196,22 @@ SIGNATURES = {
     "emb_compat_reset": (C.c_int, []),
 }
 
+# name -> (restype, argtypes); every function declared in include/pimemb_rows.h (libpimemb_rows.so, the row writer: a companion
+# library with its own code object, loaded next to libpimemb.so)
+EMB_ROWS_SRC_F32, EMB_ROWS_SRC_TABLE_DTYPE = 0, 1
+EMB_ROWS_UNIQUE_IDS = 1
+ROWS_SIGNATURES = {
+    "emb_rows_last_error": (C.c_char_p, []),
+    "emb_rows_scratch_bytes": (_u64, [_u64]),
+    "emb_rows_stage_bytes": (_u64, [_u64]),
+    "emb_rows_create": (C.c_int, [_vp, _u64, _pp]),
+    "emb_rows_destroy": (C.c_int, [_vp]),
+    "emb_rows_update": (C.c_int, [_vp, _u32, _vp, C.c_int, _u64, _vp, C.c_int, C.c_int, _u32, _vp, C.POINTER(_u64)]),
+    "emb_rows_report": (C.c_int, [_vp, C.POINTER(_u64)]),
+}
+
 _lib = None
+_rows_lib = None
 
 
 class PimembError(RuntimeError):
@@ -228,9 +244,38 @@ def load(path: str | None = None) -> C.CDLL:
         fn.argtypes = args
     if path is None:
         _lib = L
+        load_rows()                    # the companion library is part of the build: missing or incomplete is an error here too
     return L
+
+
+def load_rows() -> C.CDLL:
+    """Load libpimemb_rows.so (the row writer, include/pimemb_rows.h) next to the default libpimemb.so, which it links against
+    and which is mapped first, so that both share one engine library and one HIP runtime.  No fallback either."""
+    global _rows_lib
+    if _rows_lib is not None:
+        return _rows_lib
+    load()
+    if _rows_lib is not None:          # (load() came here itself)
+        return _rows_lib
+    from .build import ROWS_LIB_PATH
+    if not os.path.exists(ROWS_LIB_PATH):
+        raise FileNotFoundError(
+            f"{ROWS_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no fallback path.")
+    R = C.CDLL(ROWS_LIB_PATH)
+    for name, (res, args) in ROWS_SIGNATURES.items():
+        fn = getattr(R, name)  # AttributeError if the symbol is not exported
+        fn.restype = res
+        fn.argtypes = args
+    _rows_lib = R
+    return R
 
 
 def check(rc: int) -> None:
     if rc != EMB_OK:
         raise PimembError(rc, load().emb_last_error().decode(errors="replace"))
+
+
+def check_rows(rc: int) -> None:
+    if rc != EMB_OK:
+        raise PimembError(rc, load_rows().emb_rows_last_error().decode(errors="replace"))

@@ -320,6 +320,13 @@ class PoolingEmbeddingBag(torch.nn.Module):
                                          per_sample_weights=None if w is None else [w], padding_idx=self.padding_idx,
                                          check=self._check(), out_dtype=self._engine_out)[0]
 
+    def update_rows_(self, ids, rows):
+        """weight[ids[p]] = rows[p] (float32 [n, embedding_dim], encoded into the weight's dtype on the GPU), in place and in
+        stream order with forward(): lookups issued afterwards -- and state_dict() -- see the new rows.  The last occurrence of
+        a repeated id wins.  Returns self."""
+        _update_rows(self.engine, self.table_id, ids, rows)
+        return self
+
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         self._table._save_to_state_dict(destination, prefix, keep_vars)
 
@@ -329,6 +336,31 @@ class PoolingEmbeddingBag(torch.nn.Module):
     def extra_repr(self) -> str:
         return (f"{self.num_embeddings}, {self.embedding_dim}, mode={self.mode!r}, padding_idx={self.padding_idx}, "
                 f"table_id={self.table_id}, engine=MI355X")
+
+
+_UPDATE_ROWS = 65536      # rows per device-pointer call of the modules' shared row writer
+
+
+def _update_rows(engine: EmbeddingEngine, table_id: int, ids, rows) -> None:
+    """weight[ids[p]] = rows[p] in place on the GPU (engine.row_writer; the last occurrence of an id wins), enqueued on torch's
+    current stream, rows encoded into the table's dtype there.  IndexError -- after the other rows were written -- for ids
+    outside the table (and MXFP4 rows holding an inf or a NaN): the module asks the writer for its count of skipped rows, a
+    host wait as the modules' checked lookups have one."""
+    dev = torch.device("cuda", engine.device)
+    ids = torch.as_tensor(ids).to(dev).reshape(-1).contiguous()
+    if ids.dtype not in (torch.int64, torch.int32):
+        ids = ids.to(torch.int64)
+    rows = torch.as_tensor(rows).to(device=dev, dtype=torch.float32).contiguous()
+    if rows.dim() != 2 or rows.shape[0] != ids.shape[0]:
+        raise ValueError(f"update_rows_: rows must be [len(ids), dim], got {tuple(rows.shape)} for {ids.shape[0]} ids")
+    w = getattr(engine, "_module_writer", None)
+    if w is None or not w._h:
+        w = engine._module_writer = engine.row_writer(_UPDATE_ROWS)
+    for at in range(0, ids.shape[0], _UPDATE_ROWS):
+        w.update(table_id, ids[at:at + _UPDATE_ROWS], rows[at:at + _UPDATE_ROWS])
+    bad = w.report()
+    if bad:
+        raise IndexError(f"update_rows_: {bad} rows were skipped (an id outside the table, or a non-finite value for an MXFP4 table); the others were written")
 
 
 def _weights_for(per_sample_weights, mode, input):
@@ -385,6 +417,11 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
                                          out_dtype=self._outs)
 
     apply_emb = forward
+
+    def update_rows_(self, table: int, ids, rows):
+        """PoolingEmbeddingBag.update_rows_ on table number `table` of the model (its position in the module list)."""
+        self.bags[table].update_rows_(ids, rows)
+        return self
 
 
 __all__ = ["EmbeddingBag", "FusedEmbeddingBags", "PoolingEmbeddingBag", "FusedPoolingEmbeddingBags", "default_engine"]
