@@ -1,0 +1,139 @@
+/*
+ * pimemb_grad.h -- C ABI of the backward pass (libpimemb_grad.so): from the gradient of a pooled lookup's output to the
+ * sparse gradient of the table, or straight to new table rows by a fused SGD step -- on the GPU, in stream order with the
+ * lookups and the row writer, every sum in a fixed order: results are the same bits on every run.
+ *
+ * A companion library like libpimemb_rows.so, not part of libpimemb.so: it carries its own gfx950 code object and reaches tables
+ * only through the public ABI of pimemb.h (emb_table_info, emb_table_hot_count, emb_device_of, emb_device_alloc, ...), so
+ * libpimemb.so's and libpimemb_rows.so's code objects are the same with or without it.  Link with -lpimemb_grad -lpimemb.  All
+ * functions are `extern "C"`; plain pointers and sizes only.
+ *
+ * THE DEFINITION (tests/grad_ref.py restates it as a loop; the kernels are compared with that, bit for bit).
+ * One table of nr_rows x dim and a batch as the forward takes it (emb_lookup_desc's conventions): indices[n] (uint32 or int64),
+ * offsets[B] (the last bag ends at n; offsets == NULL with fixed_pooling = L means offsets[b] = b * L), the forward's
+ * emb_pool_spec, and G, the gradient of the pooled output: fp32 [B, dim] with a row stride of grad_ld >= dim floats (the
+ * [B, T*dim] buffer of a strided lookup is read in place: grad = buffer + column, grad_ld = T*dim).
+ *   Position to bag.  Position p belongs to bag(p), the LAST b with offsets[b] <= p; positions before offsets[0] belong to no
+ *     bag and are skipped.  Offsets are trusted to be the ones the forward accepted (non-decreasing, <= n); whatever they
+ *     hold, no access leaves [0, n), [0, B) or the table.
+ *   Good positions.  A position is good if it has a bag, its id -- compared at full width, never truncated -- lies in
+ *     [0, nr_rows), and (EMB_POOL_PADDING) its id is not padding_idx.  A position that has a bag and an id outside the table
+ *     is BAD: skipped and counted (emb_grad_report).  Padding positions are skipped and not counted.
+ *   Contribution c_p of a good position, dim fp32 values, every operation rounded on its own, never contracted into an FMA:
+ *       sum, no weights          c_p = G[bag(p)]
+ *       sum, per_sample_weights  c_p = w[p] * G[bag(p)]                    one fp32 multiply
+ *       mean                     c_p = G[bag(p)] / (float)cnt(bag(p))      an IEEE fp32 division; cnt = the number of non-padding
+ *                                positions of the bag, good or bad: what the forward divided by.  (A bag with cnt 0 has no good
+ *                                position and contributes nothing.)
+ *   Row gradient.  For a row r with good positions p1 < p2 < ... < pk:  g[r] = (((+0.0f + c_p1) + c_p2) + ...) + c_pk, fp32
+ *     additions IN POSITION ORDER.  That order is the point: float atomics would give sums that depend on scheduling.
+ *   Unique list U: the rows with at least one good position, ascending.
+ * Two results:
+ *   emb_grad_sparse   rows_out[|U|] (int64, ascending), grads_out[|U|, dim] (fp32) and |U| -- what nn.EmbeddingBag(sparse=True)
+ *                     leaves in weight.grad after .coalesce().  It depends on the table's SHAPE only: every table dtype but
+ *                     EMB_FIXED32 (EMB_ERR_UNSUPPORTED: a fixed-point table is not a floating-point parameter).
+ *   emb_grad_sgd      for every r in U:  W[r] = enc(dec(W[r]) - (lr * g[r])), in place; every other row keeps its bytes.  dec is
+ *                     the exact widening to fp32, lr * g one fp32 multiply, the subtraction one fp32 subtract, enc the encoder
+ *                     of the row writer for the table's dtype (identity, fp16 nearest-even with overflow to inf, bf16
+ *                     nearest-even: csrc/pimemb_rows_encode.h; the one-element step is csrc/pimemb_grad_step.h).  g is never
+ *                     written to memory.  Tables: EMB_F32, EMB_F16, EMB_BF16.
+ * EMB_ERR_UNSUPPORTED for the step, on purpose:
+ *   EMB_F8_E4M3 / EMB_F8_E5M2 / EMB_MXFP4   an SGD step in the stored precision mostly rounds away (two or three mantissa bits,
+ *                     one for MXFP4), and an MXFP4 block shares one scale: a step on one element would re-quantise its 31
+ *                     neighbours.  Keep fp32 master rows, take emb_grad_sparse, and write rows with emb_rows_update.
+ *   EMB_FIXED32       not a floating-point parameter.
+ *   a hot set staged (emb_table_hot_count != 0)   as in the row writer: a hot set is a COPY of rows, lookups would go on serving
+ *                     the old bytes: clear the set, step, set it again.
+ *   EMB_POOL_MAX      needs the forward's per-element argmax, which no kernel records.
+ * Prepared plans stay valid over a stepped table and read the new rows when launched behind the step.
+ * Out of scope: the gradient with respect to per_sample_weights; max mode; optimizers other than SGD; fusing several tables
+ * into one launch (emb_grad_sgd over several descriptors launches per descriptor); the ranged / sharded paths; NaN ordering and
+ * payloads, as everywhere in this library.
+ *
+ * How it runs.  A pre-pass gives every position its bag (binary search in offsets), flags it good / bad / padding, counts cnt
+ * per bag for mean, and orders the positions by (row id, position): a stable LSD radix sort over the ceil(log2(nr_rows + 1)) id
+ * bits, 8 bits a pass (positions that are not good sort behind every row).  The heads of the runs of equal ids are the unique
+ * rows; for emb_grad_sparse a scan of the head flags compacts them.  Then ONE LANE GROUP PER UNIQUE ROW walks its run in position order:
+ * each lane owns 4 consecutive fp32 elements and loads 16 bytes of G per occurrence, eight occurrences in flight before the
+ * first add, the adds in order -- the forward's gather turned round.  emb_grad_sgd ends the same kernel with decode /
+ * multiply / subtract / encode and one vector store of the lane's piece of the table row (16 bytes fp32, 8 bytes fp16 / bf16).
+ * Lane-group path: dim % 4 == 0, dim <= 512, grad (and grads_out) 16-byte aligned, grad_ld % 4 == 0; anything else runs an
+ * element-wise kernel (one thread per element of a unique row).
+ *
+ * Speed, measured on MI355X (tools/grad_probe.py, profiles/grad/README.md; one emb_grad_sgd of 2048 bags x 32 indices, dim 128, 4 M
+ * rows, device pointers).  Uniform ids: 72 us per step on fp32 and bf16 tables, against 73 / 106 us for torch's sparse
+ * EmbeddingBag backward + SGD step: level, and 1.5x faster.  The Kaggle shape (dim 16, 39 292 one-index bags): 49 against 56 us.
+ * Zipf ids, one row occurring 9 035 times: 3.7 ms, 14x SLOWER than torch (260 us) -- that row's sum is one chain of 9 035 ordered
+ * additions walked by one lane group, eight loads in flight at a time; splitting it would change the bits.  A step is 12 - 18x
+ * the forward lookup of the same batch (3 - 6 us), and with short runs 63 - 87 % of it is the pre-pass: 13 small launches.
+ *
+ * Threading.  A context owns one scratch area: calls on one context must not overlap -- issue them from one thread and on one
+ * stream (or order the streams yourself).  Steps must not run concurrently with table management on the engine
+ * (emb_alloc_table / emb_load_* / emb_set_hot_rows).  emb_grad_last_error() is thread-local.
+ */
+#ifndef PIMEMB_GRAD_H
+#define PIMEMB_GRAD_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "pimemb.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct emb_grad emb_grad; /* opaque: a context = device scratch (sort buffers, bag of every position, counters) */
+
+/* One table's share of a backward call: an emb_lookup_desc without `pooled`, plus the gradient and the forward's pooling. */
+typedef struct emb_grad_desc {
+    uint32_t table_id;
+    uint32_t fixed_pooling; /* offsets == NULL: offsets[b] = b * fixed_pooling (> 0) */
+    const void *indices;    /* uint32[n_indices] or int64[n_indices] */
+    const void *offsets;    /* uint32[n_bags] or int64[n_bags] (same width as indices), or NULL */
+    uint64_t n_indices;
+    uint64_t n_bags;
+    const float *grad;      /* G: float, row b at grad + b * grad_ld */
+    uint64_t grad_ld;       /* >= dim, in floats */
+    emb_pool_spec pool;     /* the forward's: mode EMB_POOL_SUM / EMB_POOL_MEAN, per_sample_weights (SUM only) or NULL, flags 0 or
+                               EMB_POOL_PADDING with padding_idx in [0, nr_rows); other flag bits are EMB_ERR_INVALID */
+} emb_grad_desc;
+
+/* Thread-local text of the last error a function of this header returned on this thread ("" if none). */
+const char *emb_grad_last_error(void);
+
+/* Bytes of DEVICE memory emb_grad_create(e, max_indices, max_bags) allocates: per index two (key, position) pairs of the
+ * sort, its bag and its unique-row number (24 bytes), the sort's digit counts (256 per 1024 indices) and their partial sums, 4
+ * bytes per bag, 256 bytes of counters; every piece rounded up to 256 bytes.  A pure function, monotone in both arguments. */
+uint64_t emb_grad_scratch_bytes(uint64_t max_indices, uint64_t max_bags);
+
+/* A context for tables of engine `e`, for calls of up to max_indices indices (1 .. 2^30) and max_bags bags (1 .. 2^31 - 1).  All
+ * memory a call uses is allocated here, once. */
+int emb_grad_create(emb_engine *e, uint64_t max_indices, uint64_t max_bags, emb_grad **out);
+/* Waits for the device, then frees the context.  Destroy contexts before emb_destroy of their engine. */
+int emb_grad_destroy(emb_grad *g);
+
+/* The sparse gradient of desc->table_id.  DEVICE pointers only, all of them: indices, offsets, weights, grad, and
+ *   rows_out      int64[capacity]
+ *   grads_out     float[capacity][dim], no padding between rows
+ *   capacity      rows the two hold; less than desc->n_indices is EMB_ERR_INVALID (|U| <= n_indices always fits)
+ *   n_unique_dev  a DEVICE uint64_t that receives |U|
+ * A pure enqueue on `stream` (a hipStream_t, NULL = the default stream): no allocation, no copy to or from the host, no host
+ * wait.  n_indices above the context's max_indices, or n_bags above its max_bags, is EMB_ERR_INVALID; n_indices == 0 is EMB_OK
+ * with |U| = 0.  Rows and gradients beyond |U| are left as they were.  Tables of 2^32 - 1 rows or more are EMB_ERR_UNSUPPORTED. */
+int emb_grad_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype, int64_t *rows_out, float *grads_out,
+                    uint64_t capacity, uint64_t *n_unique_dev, void *stream);
+
+/* The fused SGD step, descriptor after descriptor (a table named twice is stepped twice, in order).  DEVICE pointers only; a
+ * pure enqueue like emb_grad_sparse.  Every descriptor is checked before anything is enqueued: a refused call leaves every
+ * table as it was. */
+int emb_grad_sgd(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream);
+
+/* The number of BAD positions (an id outside the table) skipped since the last report; resets the count.  Waits for the
+ * device first, so the count covers every call enqueued so far. */
+int emb_grad_report(emb_grad *g, uint64_t *n_bad);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* PIMEMB_GRAD_H */

@@ -1,0 +1,709 @@
+// pimemb_grad.hip -- libpimemb_grad.so: the EmbeddingBag backward pass over a served table (include/pimemb_grad.h).
+//
+// A companion of libpimemb.so with a code object of its own, like the row writer: the kernels below are linked into no other
+// library, and tables are reached through the public ABI of pimemb.h alone.
+//
+// The pre-pass:
+//   grad_classify       one thread per position: its bag (binary search in offsets), good / bad / padding, the sort key (the row
+//                       id of a good position, nr_rows for every other one: they sort behind every row), cnt per bag for mean
+//   grad_sort_count / grad_scan_chunks / grad_scan_sums / grad_sort_scatter
+//                       a stable LSD radix sort of (key, position) pairs, 8 bits a pass: digit counts per tile of 1024
+//                       positions, an exclusive scan over the [digit][tile] matrix in two levels, and a scatter that ranks
+//                       the positions of a tile in their order (wavefront ballots, then counts per 64-position slice)
+//   grad_scan_chunks<true>   the same scan over the run-head flags of the sorted keys: the number of every unique row
+// The hot kernels (one per result, SGD = false / true):
+//   grad_rows_group     one lane group per unique row, a lane owns 4 consecutive fp32 elements: walks the row's run in position
+//                       order, the 16-byte loads of eight occurrences issued before the first add, the adds in order
+//   grad_rows_elem      any other dim / alignment: one thread per element of a unique row
+// Every fp32 operation of the definition is a statement of its own under `fp contract(off)` (and the unit is compiled with
+// -ffp-contract=off): nothing is fused into an FMA.
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "pimemb_grad.h"
+#include "pimemb_grad_step.h"
+
+namespace {
+
+using namespace pimemb_grad;
+
+constexpr int kF32 = 0, kF16 = 1, kFixed32 = 2, kBF16 = 3;
+constexpr uint32_t kBlock = 256;
+constexpr uint32_t kTile = 1024;            // positions per workgroup of the sort, entries per workgroup of the scan
+constexpr uint32_t kSlices = kTile / 64;    // 64-position slices of a tile: (round, wavefront) pairs, in position order
+constexpr uint32_t kNoBag = 0xffffffffu;
+enum CoefMode : uint32_t { COEF_SUM = 0, COEF_WEIGHTED = 1, COEF_MEAN = 2 };
+
+struct u32x2 {
+    uint32_t x, y;
+} __attribute__((aligned(8)));
+
+// ---- pre-pass ---------------------------------------------------------------------------------------------------------------
+
+// The last b in [0, B) with offsets[b] <= p, or kNoBag.  A plain binary search: whatever the offsets hold, it reads inside [0, B).
+template <bool IDX64>
+__device__ inline uint32_t bag_of(const void *offsets, uint32_t fixed_pooling, uint32_t B, uint32_t p) {
+    if (B == 0) return kNoBag;
+    if (!offsets) {
+        const uint32_t b = p / fixed_pooling;
+        return b < B ? b : B - 1;
+    }
+    uint32_t lo = 0, hi = B;                 // the first b with offsets[b] > p lies in [lo, hi]
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        bool le;
+        if (IDX64) le = static_cast<const long long *>(offsets)[mid] <= (long long)p;
+        else le = static_cast<const uint32_t *>(offsets)[mid] <= p;
+        if (le) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo == 0 ? kNoBag : lo - 1;
+}
+
+template <bool IDX64>
+__global__ __launch_bounds__(kBlock) void grad_classify(const void *ids, const void *offsets, uint32_t fixed_pooling, uint32_t n,
+                                                        uint32_t B, uint32_t nr_rows, uint32_t pad_on, uint64_t pad_idx,
+                                                        uint32_t *keys, uint32_t *vals, uint32_t *bagof, uint32_t *cnt /* or NULL */,
+                                                        unsigned long long *bad) {
+    const uint64_t p64 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p64 >= n) return;
+    const uint32_t p = (uint32_t)p64;
+    uint64_t id;
+    bool in_table;
+    if (IDX64) {
+        const long long v = static_cast<const long long *>(ids)[p];
+        id = (uint64_t)v;
+        in_table = v >= 0 && id < nr_rows;      // compared at full width: 2^32 + 5 is not row 5
+    } else {
+        id = static_cast<const uint32_t *>(ids)[p];
+        in_table = id < nr_rows;
+    }
+    const uint32_t b = bag_of<IDX64>(offsets, fixed_pooling, B, p);
+    const bool padding = pad_on && id == pad_idx;
+    uint32_t key = nr_rows;                     // not good: behind every row
+    if (b != kNoBag && !padding) {
+        if (cnt) atomicAdd(&cnt[b], 1u);        // good or bad: what the forward's mean divided by (integer adds: any order)
+        if (in_table) key = (uint32_t)id;
+        else atomicAdd(bad, 1ull);
+    }
+    keys[p] = key;
+    vals[p] = p;
+    bagof[p] = b;
+}
+
+// Exclusive scan of one value per thread over the workgroup (256 threads); *total = the workgroup's sum.
+__device__ inline uint32_t block_scan(uint32_t v, uint32_t *total, uint32_t *wave_sums /* LDS, 4 */) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)inc, off);
+        if (lane >= off) inc += o;
+    }
+    if (lane == 63) wave_sums[wave] = inc;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kBlock / 64; w++) {
+        const uint32_t s = wave_sums[w];
+        if (w < wave) base += s;
+        tot += s;
+    }
+    __syncthreads();                            // (wave_sums may be written again by the caller's next round)
+    *total = tot;
+    return base + inc - v;
+}
+
+__device__ inline uint32_t head_flag(const uint32_t *keys, uint32_t i, uint32_t n, uint32_t nr_rows) {
+    if (i >= n) return 0;
+    const uint32_t k = keys[i];
+    return k < nr_rows && (i == 0 || keys[i - 1] != k);
+}
+
+// Level one of the scan: workgroup `blk` scans entries [1024 blk, 1024 blk + 1024) of `data` (HEADS: of the run-head flags of the
+// sorted `keys`) into out[], relative to the chunk's start, and leaves the chunk's sum in sums[blk].
+template <bool HEADS>
+__global__ __launch_bounds__(kBlock) void grad_scan_chunks(const uint32_t *data, uint32_t len, uint32_t nr_rows, uint32_t *out, uint32_t *sums) {
+    __shared__ uint32_t wave_sums[kBlock / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * kTile + threadIdx.x * 4u;
+    uint32_t a[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        const uint64_t i = i0 + j;
+        if (HEADS) a[j] = i < len ? head_flag(data, (uint32_t)i, len, nr_rows) : 0u;
+        else a[j] = i < len ? data[i] : 0u;
+    }
+    uint32_t total;
+    uint32_t run = block_scan(a[0] + a[1] + a[2] + a[3], &total, wave_sums);
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        if (i0 + j < len) out[i0 + j] = run;
+        run += a[j];
+    }
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// Level two: ONE workgroup scans the chunk sums in place; *total_out (may be NULL) = the sum of everything.
+__global__ __launch_bounds__(kBlock) void grad_scan_sums(uint32_t *sums, uint32_t n_chunks, unsigned long long *total_out) {
+    __shared__ uint32_t wave_sums[kBlock / 64];
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n_chunks; base += kTile) {      // (uniform trip count)
+        const uint32_t i0 = base + threadIdx.x * 4u;
+        uint32_t a[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) a[j] = i0 + j < n_chunks ? sums[i0 + j] : 0u;
+        uint32_t total;
+        uint32_t run = carry + block_scan(a[0] + a[1] + a[2] + a[3], &total, wave_sums);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            if (i0 + j < n_chunks) sums[i0 + j] = run;
+            run += a[j];
+        }
+        carry += total;
+    }
+    if (total_out && threadIdx.x == 0) *total_out = carry;
+}
+
+// Digit counts of tile `blk`, stored digit-major -- hist[digit * n_tiles + blk] -- so that one exclusive scan over the whole
+// matrix gives every (digit, tile) pair the place of its first position.
+__global__ __launch_bounds__(kBlock) void grad_sort_count(const uint32_t *keys, uint32_t n, uint32_t shift, uint32_t *hist, uint32_t n_tiles) {
+    __shared__ uint32_t counts[256];
+    counts[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * kTile;
+#pragma unroll
+    for (uint32_t r = 0; r < kTile / kBlock; r++) {
+        const uint64_t i = base + r * kBlock + threadIdx.x;
+        if (i < n) atomicAdd(&counts[(keys[i] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[(uint64_t)threadIdx.x * n_tiles + blockIdx.x] = counts[threadIdx.x];
+}
+
+// The stable scatter of one pass.  A tile is 16 slices of 64 consecutive positions (round r of wavefront w: slice 4 r + w).  Inside
+// a slice, the lanes that hold the same digit find each other with 8 ballots: a position's rank among them is the number of
+// such lanes below it, and the lowest of them records their count.  Thread d then turns digit d's 16 slice counts into
+// offsets, and a position goes to   (scanned hist of its digit and tile) + (its slice's offset) + (its rank in the slice).
+__global__ __launch_bounds__(kBlock) void grad_sort_scatter(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
+                                                            uint32_t *vals_out, uint32_t n, uint32_t shift, const uint32_t *hist,
+                                                            const uint32_t *sums, uint32_t n_tiles) {
+    __shared__ uint32_t slice_counts[kSlices][256];
+    __shared__ uint32_t digit_base[256];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t s = 0; s < kSlices; s++) slice_counts[s][threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * kTile;
+    uint32_t key[kTile / kBlock], val[kTile / kBlock], rank[kTile / kBlock];
+#pragma unroll
+    for (uint32_t r = 0; r < kTile / kBlock; r++) {
+        const uint64_t i = base + r * kBlock + threadIdx.x;
+        const bool live = i < n;
+        key[r] = live ? keys_in[i] : 0u;
+        val[r] = live ? vals_in[i] : 0u;
+        const uint32_t d = (key[r] >> shift) & 255u;
+        unsigned long long same = __ballot(live);
+#pragma unroll
+        for (uint32_t bit = 0; bit < 8; bit++) {
+            const bool one = (d >> bit) & 1u;
+            const unsigned long long m = __ballot(one);
+            same &= one ? m : ~m;
+        }
+        rank[r] = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
+        if (live && rank[r] == 0) slice_counts[r * (kBlock / 64) + wave][d] = (uint32_t)__popcll(same);
+    }
+    __syncthreads();
+    {
+        const uint32_t d = threadIdx.x;
+        uint32_t run = 0;
+#pragma unroll
+        for (uint32_t s = 0; s < kSlices; s++) {
+            const uint32_t c = slice_counts[s][d];
+            slice_counts[s][d] = run;
+            run += c;
+        }
+        const uint64_t at = (uint64_t)d * n_tiles + blockIdx.x;
+        digit_base[d] = hist[at] + sums[at / kTile];
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < kTile / kBlock; r++) {
+        const uint64_t i = base + r * kBlock + threadIdx.x;
+        if (i >= n) continue;
+        const uint32_t d = (key[r] >> shift) & 255u;
+        const uint32_t dst = digit_base[d] + slice_counts[r * (kBlock / 64) + wave][d] + rank[r];
+        if (dst < n) {                         // (always, the counts being those of these very keys: kept as the bound of the store)
+            keys_out[dst] = key[r];
+            vals_out[dst] = val[r];
+        }
+    }
+}
+
+// ---- the hot kernels --------------------------------------------------------------------------------------------------------
+
+struct RowArgs {
+    const uint32_t *keys;        // sorted: the row id of every good position, runs of equal ids in position order; then nr_rows
+    const uint32_t *vals;        // the position behind every key
+    const uint32_t *bagof;       // position -> bag
+    const uint32_t *cnt;         // bag -> cnt (mean)
+    const float *weights;        // position -> w (weighted sum)
+    const float *grad;           // G
+    uint64_t ld;                 // floats from one row of G to the next
+    uint32_t n;
+    uint32_t n_bags;
+    uint32_t nr_rows;
+    uint32_t dim;
+    uint32_t coef;               // CoefMode
+    // the sparse gradient
+    const uint32_t *uidx;        // sorted place -> number of its unique row, relative to its chunk of 1024 places
+    const uint32_t *usums;       // ... + this per chunk
+    long long *rows_out;
+    float *grads_out;
+    // the fused step
+    char *table;
+    uint32_t stride;             // bytes from one table row to the next
+    int dtype;
+    float lr;
+};
+
+// The scalar a position's G row is multiplied with (weighted) or divided by (mean); 0 for a plain sum.
+__device__ inline float coef_of(const RowArgs &a, uint32_t p, uint32_t b) {
+    if (a.coef == COEF_WEIGHTED) return a.weights[p];
+    if (a.coef == COEF_MEAN) return (float)a.cnt[b];
+    return 0.f;
+}
+
+__device__ inline float contribution(uint32_t coef, float g, float s) {
+#pragma clang fp contract(off)
+    if (coef == COEF_WEIGHTED) return s * g;
+    if (coef == COEF_MEAN) return __fdiv_rn(g, s);
+    return g;
+}
+
+__device__ inline float add_in_order(float acc, float c) {
+#pragma clang fp contract(off)
+    return acc + c;
+}
+
+constexpr uint32_t kAhead = 8;      // occurrences whose loads are in flight before the first add
+
+// One unique row per group of `lanes` lanes (a power of two up to 64); lane lg handles the row's 16-byte pieces lg, lg + lanes
+// (two only beyond dim 256).  Place i of the sorted order is worked on only where a run starts there.
+template <bool SGD>
+__global__ __launch_bounds__(kBlock) void grad_rows_group(RowArgs a, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= a.n || lg >= chunks) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;
+    for (uint32_t c = lg; c < chunks; c += lanes) {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        uint32_t j = i;
+        for (;;) {
+            bool live[kAhead];
+            float4 g[kAhead];
+            float s[kAhead];
+#pragma unroll
+            for (uint32_t k = 0; k < kAhead; k++) {      // the loads of up to kAhead occurrences (a dead slot re-reads the run's first)
+                live[k] = k == 0 || (live[k - 1] && j + k < a.n && a.keys[j + k] == row);
+                const uint32_t p = min(a.vals[live[k] ? j + k : j], a.n - 1u);      // (what the pre-pass wrote lies below these bounds:
+                const uint32_t b = min(a.bagof[p], a.n_bags - 1u);                  //  they are the bounds of the loads all the same)
+                s[k] = coef_of(a, p, b);
+                g[k] = *reinterpret_cast<const float4 *>(a.grad + (uint64_t)b * a.ld + 4u * c);
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < kAhead; k++) {      // the adds, in position order
+                if (live[k]) {
+                    acc.x = add_in_order(acc.x, contribution(a.coef, g[k].x, s[k]));
+                    acc.y = add_in_order(acc.y, contribution(a.coef, g[k].y, s[k]));
+                    acc.z = add_in_order(acc.z, contribution(a.coef, g[k].z, s[k]));
+                    acc.w = add_in_order(acc.w, contribution(a.coef, g[k].w, s[k]));
+                }
+            }
+            if (!live[kAhead - 1]) break;
+            j += kAhead;
+            if (j >= a.n || a.keys[j] != row) break;
+        }
+        if (!SGD) {
+            const uint32_t u = a.uidx[i] + a.usums[i / kTile];
+            if (c == 0) a.rows_out[u] = (long long)row;
+            *reinterpret_cast<float4 *>(a.grads_out + (uint64_t)u * a.dim + 4u * c) = acc;
+        } else if (a.dtype == kStepF32) {
+            float4 *w = reinterpret_cast<float4 *>(a.table + (uint64_t)row * a.stride) + c;
+            float4 v = *w;
+            v.x = step_f32(v.x, acc.x, a.lr);
+            v.y = step_f32(v.y, acc.y, a.lr);
+            v.z = step_f32(v.z, acc.z, a.lr);
+            v.w = step_f32(v.w, acc.w, a.lr);
+            *w = v;
+        } else {
+            u32x2 *w = reinterpret_cast<u32x2 *>(a.table + (uint64_t)row * a.stride) + c;
+            const u32x2 v = *w;
+            u32x2 o;
+            o.x = step(a.dtype, v.x & 0xffffu, acc.x, a.lr) | (step(a.dtype, v.x >> 16, acc.y, a.lr) << 16);
+            o.y = step(a.dtype, v.y & 0xffffu, acc.z, a.lr) | (step(a.dtype, v.y >> 16, acc.w, a.lr) << 16);
+            *w = o;
+        }
+    }
+}
+
+// One thread per (sorted place, element): works where a run starts.
+template <bool SGD>
+__global__ __launch_bounds__(kBlock) void grad_rows_elem(RowArgs a) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid / a.dim;
+    const uint32_t c = (uint32_t)(gid - i64 * a.dim);
+    if (i64 >= a.n) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;
+    float acc = 0.f;
+    for (uint32_t j = i; j < a.n && a.keys[j] == row; j++) {
+        const uint32_t p = min(a.vals[j], a.n - 1u);
+        const uint32_t b = min(a.bagof[p], a.n_bags - 1u);
+        acc = add_in_order(acc, contribution(a.coef, a.grad[(uint64_t)b * a.ld + c], coef_of(a, p, b)));
+    }
+    if (!SGD) {
+        const uint32_t u = a.uidx[i] + a.usums[i / kTile];
+        if (c == 0) a.rows_out[u] = (long long)row;
+        a.grads_out[(uint64_t)u * a.dim + c] = acc;
+    } else if (a.dtype == kStepF32) {
+        float *w = reinterpret_cast<float *>(a.table + (uint64_t)row * a.stride) + c;
+        *w = step_f32(*w, acc, a.lr);
+    } else {
+        uint16_t *w = reinterpret_cast<uint16_t *>(a.table + (uint64_t)row * a.stride) + c;
+        *w = (uint16_t)step(a.dtype, *w, acc, a.lr);
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+
+thread_local char t_err[512] = "";
+
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+int fail(int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(t_err, sizeof t_err, fmt, ap);
+    va_end(ap);
+    return code;
+}
+int fail_engine(int code, const char *what) { return fail(code, "%s: %s", what, emb_last_error()); }
+
+#define GRAD_HIP(expr)                                                                          \
+    do {                                                                                        \
+        hipError_t err_ = (expr);                                                               \
+        if (err_ != hipSuccess) return fail(EMB_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(err_)); \
+    } while (0)
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+        else prev = -1;
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+uint64_t pow2ceil(uint64_t v) {
+    uint64_t p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+uint32_t log2of(uint64_t pow2) {
+    uint32_t l = 0;
+    while ((1ull << l) < pow2) l++;
+    return l;
+}
+
+constexpr uint64_t kMaxIndices = 1ull << 30, kMaxBags = 0x7fffffffull, kCounterBytes = 256;
+uint64_t up256(uint64_t b) { return (b + 255) & ~255ull; }
+uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
+
+// The scratch area: offsets of its pieces for a context of N indices and B bags.
+struct Layout {
+    uint64_t keys[2], vals[2], bagof, uidx, hist, sums, cnt, counters, total;
+};
+Layout layout_of(uint64_t N, uint64_t B) {
+    if (N > kMaxIndices) N = kMaxIndices;
+    if (B > kMaxBags) B = kMaxBags;
+    if (N == 0) N = 1;
+    Layout l{};
+    uint64_t at = 0;
+    auto take = [&](uint64_t bytes) {
+        const uint64_t here = at;
+        at += up256(bytes);
+        return here;
+    };
+    l.keys[0] = take(N * 4);
+    l.keys[1] = take(N * 4);
+    l.vals[0] = take(N * 4);
+    l.vals[1] = take(N * 4);
+    l.bagof = take(N * 4);
+    l.uidx = take(N * 4);
+    const uint64_t hist_len = 256 * tiles_of(N);
+    l.hist = take(hist_len * 4);
+    l.sums = take((tiles_of(hist_len > N ? hist_len : N) + 1) * 4);
+    l.cnt = take((B ? B : 1) * 4);
+    l.counters = take(kCounterBytes);
+    l.total = at;
+    return l;
+}
+
+}  // namespace
+
+struct emb_grad {
+    emb_engine *e = nullptr;
+    int device = 0;
+    uint64_t max_indices = 0, max_bags = 0;
+    char *scratch = nullptr;
+    Layout lay{};
+    unsigned long long *counters = nullptr;      // [0] bad positions since the last report
+};
+
+extern "C" {
+
+const char *emb_grad_last_error(void) { return t_err; }
+
+uint64_t emb_grad_scratch_bytes(uint64_t max_indices, uint64_t max_bags) { return layout_of(max_indices, max_bags).total; }
+
+int emb_grad_create(emb_engine *e, uint64_t max_indices, uint64_t max_bags, emb_grad **out) {
+    if (!e || !out) return fail(EMB_ERR_INVALID, "emb_grad_create: engine or out is NULL");
+    if (max_indices == 0 || max_indices > kMaxIndices) return fail(EMB_ERR_INVALID, "emb_grad_create: max_indices must be 1 .. 2^30");
+    if (max_bags == 0 || max_bags > kMaxBags) return fail(EMB_ERR_INVALID, "emb_grad_create: max_bags must be 1 .. 2^31 - 1");
+    int32_t dev = 0;
+    if (int rc = emb_device_of(e, &dev)) return fail_engine(rc, "emb_grad_create");
+    emb_grad *g = new emb_grad;
+    g->e = e;
+    g->device = dev;
+    g->max_indices = max_indices;
+    g->max_bags = max_bags;
+    g->lay = layout_of(max_indices, max_bags);
+    DeviceGuard guard(dev);
+    void *p = nullptr;
+    if (int rc = emb_device_alloc(e, g->lay.total, &p)) {
+        delete g;
+        return fail_engine(rc, "emb_grad_create");
+    }
+    g->scratch = static_cast<char *>(p);
+    g->counters = reinterpret_cast<unsigned long long *>(g->scratch + g->lay.counters);
+    const hipError_t err = hipMemset(g->counters, 0, kCounterBytes);
+    if (err != hipSuccess) {
+        fail(EMB_ERR_DEVICE, "emb_grad_create: %s", hipGetErrorString(err));
+        (void)emb_grad_destroy(g);
+        return EMB_ERR_DEVICE;
+    }
+    *out = g;
+    return EMB_OK;
+}
+
+int emb_grad_destroy(emb_grad *g) {
+    if (!g) return EMB_OK;
+    DeviceGuard guard(g->device);
+    (void)hipDeviceSynchronize();
+    if (g->scratch) (void)emb_device_free(g->e, g->scratch);
+    delete g;
+    return EMB_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+struct TableShape {
+    char *rows;
+    uint64_t nr_rows;
+    uint32_t dim;
+    int dtype;
+    uint32_t stride;
+};
+
+// Everything that can be refused about one descriptor, before anything is enqueued.
+int check_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, bool sgd, const char *who, TableShape *t) {
+    void *rows = nullptr;
+    emb_dtype dt;
+    if (int rc = emb_table_info(g->e, d.table_id, &rows, &t->nr_rows, &t->dim, &dt)) return fail_engine(rc, who);
+    __builtin_memcpy(&t->dtype, &dt, sizeof(int));      // (the fp8 / MXFP4 values lie outside the enum's range: pimemb.h)
+    t->rows = static_cast<char *>(rows);
+    if (t->dtype == kFixed32) return fail(EMB_ERR_UNSUPPORTED, "%s: table %u is EMB_FIXED32: a fixed-point table has no gradient here", who, d.table_id);
+    if (d.pool.mode == EMB_POOL_MAX)
+        return fail(EMB_ERR_UNSUPPORTED, "%s: EMB_POOL_MAX needs the forward's per-element argmax, which no kernel records", who);
+    if (d.pool.mode != EMB_POOL_SUM && d.pool.mode != EMB_POOL_MEAN) return fail(EMB_ERR_INVALID, "%s: unknown pooling mode %u", who, d.pool.mode);
+    if (d.pool.flags & ~EMB_POOL_PADDING) return fail(EMB_ERR_INVALID, "%s: pooling flag bits 0x%x have no meaning here", who, d.pool.flags & ~EMB_POOL_PADDING);
+    if (d.pool.per_sample_weights && d.pool.mode != EMB_POOL_SUM) return fail(EMB_ERR_INVALID, "%s: per_sample_weights go with EMB_POOL_SUM only", who);
+    if ((d.pool.flags & EMB_POOL_PADDING) && (d.pool.padding_idx < 0 || (uint64_t)d.pool.padding_idx >= t->nr_rows))
+        return fail(EMB_ERR_INVALID, "%s: padding_idx %lld lies outside table %u", who, (long long)d.pool.padding_idx, d.table_id);
+    if (sgd) {
+        if (t->dtype != kF32 && t->dtype != kF16 && t->dtype != kBF16)
+            return fail(EMB_ERR_UNSUPPORTED,
+                        "%s: table %u is fp8 or MXFP4: an SGD step in the stored precision mostly rounds away (and an MXFP4 block shares "
+                        "its scale); keep fp32 master rows, take emb_grad_sparse and write rows with emb_rows_update", who, d.table_id);
+        uint32_t n_hot = 0;
+        if (int rc = emb_table_hot_count(g->e, d.table_id, &n_hot)) return fail_engine(rc, who);
+        if (n_hot)
+            return fail(EMB_ERR_UNSUPPORTED,
+                        "%s: table %u has a hot set of %u rows staged, a copy taken when it was set that lookups would go on serving: "
+                        "clear the set (emb_set_hot_rows with n_rows = 0), step, then set it again", who, d.table_id, n_hot);
+    }
+    t->stride = t->dim * (t->dtype == kF32 ? 4u : 2u);      // (used by the step only)
+    if (t->nr_rows >= 0xffffffffull) return fail(EMB_ERR_UNSUPPORTED, "%s: table %u has 2^32 - 1 rows or more", who, d.table_id);
+    if (d.n_indices > g->max_indices)
+        return fail(EMB_ERR_INVALID, "%s: %llu indices in one call, the context was created for %llu", who, (unsigned long long)d.n_indices,
+                    (unsigned long long)g->max_indices);
+    if (d.n_bags > g->max_bags)
+        return fail(EMB_ERR_INVALID, "%s: %llu bags in one call, the context was created for %llu", who, (unsigned long long)d.n_bags,
+                    (unsigned long long)g->max_bags);
+    if (d.n_indices == 0) return EMB_OK;
+    if (!d.indices || !d.grad) return fail(EMB_ERR_INVALID, "%s: indices or grad is NULL", who);
+    if (!d.offsets && d.fixed_pooling == 0) return fail(EMB_ERR_INVALID, "%s: offsets is NULL and fixed_pooling is 0", who);
+    if (d.grad_ld < t->dim) return fail(EMB_ERR_INVALID, "%s: grad_ld %llu is below the table's dim %u", who, (unsigned long long)d.grad_ld, t->dim);
+    const size_t isz = itype == EMB_IDX_I64 ? 8 : 4;
+    if ((uintptr_t)d.indices % isz || (uintptr_t)d.offsets % isz || (uintptr_t)d.grad % 4 || (uintptr_t)d.pool.per_sample_weights % 4)
+        return fail(EMB_ERR_INVALID, "%s: indices, offsets, grad and weights must be naturally aligned", who);
+    return EMB_OK;
+}
+
+// The pre-pass of one descriptor (n_indices > 0), then the hot kernel: enqueues only.
+int enqueue(emb_grad *g, const emb_grad_desc &d, const TableShape &t, bool idx64, bool sgd, float lr, long long *rows_out, float *grads_out,
+            unsigned long long *n_unique_dev, hipStream_t s) {
+    const uint32_t n = (uint32_t)d.n_indices, B = (uint32_t)d.n_bags, nr = (uint32_t)t.nr_rows;
+    const Layout &l = g->lay;
+    uint32_t *keys[2] = {reinterpret_cast<uint32_t *>(g->scratch + l.keys[0]), reinterpret_cast<uint32_t *>(g->scratch + l.keys[1])};
+    uint32_t *vals[2] = {reinterpret_cast<uint32_t *>(g->scratch + l.vals[0]), reinterpret_cast<uint32_t *>(g->scratch + l.vals[1])};
+    uint32_t *bagof = reinterpret_cast<uint32_t *>(g->scratch + l.bagof), *uidx = reinterpret_cast<uint32_t *>(g->scratch + l.uidx);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(g->scratch + l.hist), *sums = reinterpret_cast<uint32_t *>(g->scratch + l.sums);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(g->scratch + l.cnt);
+    const bool mean = d.pool.mode == EMB_POOL_MEAN;
+    const bool pad = (d.pool.flags & EMB_POOL_PADDING) != 0;
+    if (mean && B) GRAD_HIP(hipMemsetAsync(cnt, 0, (size_t)B * 4, s));
+    const uint32_t pos_blocks = (n + kBlock - 1) / kBlock;
+    const uint64_t pad_idx = pad ? (uint64_t)d.pool.padding_idx : 0ull;
+    uint32_t *cnt_arg = mean ? cnt : nullptr;
+    if (idx64)
+        grad_classify<true><<<dim3(pos_blocks), dim3(kBlock), 0, s>>>(d.indices, d.offsets, d.fixed_pooling, n, B, nr, pad ? 1u : 0u, pad_idx, keys[0], vals[0],
+                                                                    bagof, cnt_arg, &g->counters[0]);
+    else
+        grad_classify<false><<<dim3(pos_blocks), dim3(kBlock), 0, s>>>(d.indices, d.offsets, d.fixed_pooling, n, B, nr, pad ? 1u : 0u, pad_idx, keys[0], vals[0],
+                                                                     bagof, cnt_arg, &g->counters[0]);
+    GRAD_HIP(hipGetLastError());
+    // the sort: the keys run up to nr_rows itself
+    uint32_t bits = 0;
+    while (bits < 32 && ((uint64_t)nr >> bits) != 0) bits++;
+    const uint32_t tiles = (uint32_t)tiles_of(n), hist_len = 256u * tiles, hist_chunks = (uint32_t)tiles_of(hist_len);
+    int cur = 0;
+    for (uint32_t shift = 0; shift < bits; shift += 8, cur ^= 1) {
+        grad_sort_count<<<dim3(tiles), dim3(kBlock), 0, s>>>(keys[cur], n, shift, hist, tiles);
+        grad_scan_chunks<false><<<dim3(hist_chunks), dim3(kBlock), 0, s>>>(hist, hist_len, 0u, hist, sums);
+        grad_scan_sums<<<dim3(1), dim3(kBlock), 0, s>>>(sums, hist_chunks, (unsigned long long *)nullptr);
+        grad_sort_scatter<<<dim3(tiles), dim3(kBlock), 0, s>>>(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift, hist, sums, tiles);
+        GRAD_HIP(hipGetLastError());
+    }
+    RowArgs a{};
+    a.keys = keys[cur];
+    a.vals = vals[cur];
+    a.bagof = bagof;
+    a.cnt = cnt;
+    a.weights = d.pool.per_sample_weights;
+    a.grad = d.grad;
+    a.ld = d.grad_ld;
+    a.n = n;
+    a.n_bags = B;
+    a.nr_rows = nr;
+    a.dim = t.dim;
+    a.coef = mean ? COEF_MEAN : d.pool.per_sample_weights ? COEF_WEIGHTED : COEF_SUM;
+    if (sgd) {
+        a.table = t.rows;
+        a.stride = t.stride;
+        a.dtype = t.dtype;
+        a.lr = lr;
+    } else {
+        grad_scan_chunks<true><<<dim3(tiles), dim3(kBlock), 0, s>>>(keys[cur], n, nr, uidx, sums);
+        grad_scan_sums<<<dim3(1), dim3(kBlock), 0, s>>>(sums, tiles, n_unique_dev);
+        GRAD_HIP(hipGetLastError());
+        a.uidx = uidx;
+        a.usums = sums;
+        a.rows_out = rows_out;
+        a.grads_out = grads_out;
+    }
+    const bool group = t.dim % 4 == 0 && t.dim <= 512 && d.grad_ld % 4 == 0 && (uintptr_t)d.grad % 16 == 0 && (sgd || (uintptr_t)grads_out % 16 == 0);
+    if (group) {
+        const uint32_t chunks = t.dim / 4;
+        uint32_t lanes = (uint32_t)pow2ceil(chunks);
+        lanes = lanes > 64 ? 64 : lanes;
+        const uint64_t blocks = ((uint64_t)n * lanes + kBlock - 1) / kBlock;
+        if (sgd) grad_rows_group<true><<<dim3((uint32_t)blocks), dim3(kBlock), 0, s>>>(a, lanes, log2of(lanes), chunks);
+        else grad_rows_group<false><<<dim3((uint32_t)blocks), dim3(kBlock), 0, s>>>(a, lanes, log2of(lanes), chunks);
+    } else {
+        const uint64_t blocks = ((uint64_t)n * t.dim + kBlock - 1) / kBlock;
+        if (blocks > 0x7fffffffull)
+            return fail(EMB_ERR_UNSUPPORTED, "emb_grad: %u indices of dim %u are more elements than one launch of the element-wise kernel takes", n, t.dim);
+        if (sgd) grad_rows_elem<true><<<dim3((uint32_t)blocks), dim3(kBlock), 0, s>>>(a);
+        else grad_rows_elem<false><<<dim3((uint32_t)blocks), dim3(kBlock), 0, s>>>(a);
+    }
+    GRAD_HIP(hipGetLastError());
+    return EMB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int emb_grad_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype, int64_t *rows_out, float *grads_out, uint64_t capacity,
+                    uint64_t *n_unique_dev, void *stream) {
+    if (!g || !desc) return fail(EMB_ERR_INVALID, "emb_grad_sparse: context or descriptor is NULL");
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "emb_grad_sparse: bad index type");
+    if (!n_unique_dev || (uintptr_t)n_unique_dev % 8) return fail(EMB_ERR_INVALID, "emb_grad_sparse: n_unique_dev is NULL or not 8-byte aligned");
+    TableShape t{};
+    if (int rc = check_desc(g, *desc, itype, false, "emb_grad_sparse", &t)) return rc;
+    if (capacity < desc->n_indices)
+        return fail(EMB_ERR_INVALID, "emb_grad_sparse: room for %llu rows, %llu indices may name as many", (unsigned long long)capacity,
+                    (unsigned long long)desc->n_indices);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    if (desc->n_indices == 0) {
+        GRAD_HIP(hipMemsetAsync(n_unique_dev, 0, 8, s));
+        return EMB_OK;
+    }
+    if (!rows_out || !grads_out || (uintptr_t)rows_out % 8 || (uintptr_t)grads_out % 4)
+        return fail(EMB_ERR_INVALID, "emb_grad_sparse: rows_out or grads_out is NULL or not naturally aligned");
+    return enqueue(g, *desc, t, itype == EMB_IDX_I64, false, 0.f, reinterpret_cast<long long *>(rows_out), grads_out,
+                   reinterpret_cast<unsigned long long *>(n_unique_dev), s);
+}
+
+int emb_grad_sgd(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream) {
+    if (!g) return fail(EMB_ERR_INVALID, "emb_grad_sgd: context is NULL");
+    if (n_descs && !descs) return fail(EMB_ERR_INVALID, "emb_grad_sgd: descs is NULL");
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "emb_grad_sgd: bad index type");
+    TableShape t{};
+    for (uint32_t k = 0; k < n_descs; k++)
+        if (int rc = check_desc(g, descs[k], itype, true, "emb_grad_sgd", &t)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    for (uint32_t k = 0; k < n_descs; k++) {
+        if (descs[k].n_indices == 0) continue;
+        if (int rc = check_desc(g, descs[k], itype, true, "emb_grad_sgd", &t)) return rc;      // (again, for the shape: cheap)
+        if (int rc = enqueue(g, descs[k], t, itype == EMB_IDX_I64, true, lr, nullptr, nullptr, nullptr, s)) return rc;
+    }
+    return EMB_OK;
+}
+
+int emb_grad_report(emb_grad *g, uint64_t *n_bad) {
+    if (!g) return fail(EMB_ERR_INVALID, "emb_grad_report: context is NULL");
+    DeviceGuard guard(g->device);
+    unsigned long long bad = 0;
+    GRAD_HIP(hipDeviceSynchronize());
+    GRAD_HIP(hipMemcpy(&bad, &g->counters[0], 8, hipMemcpyDeviceToHost));
+    GRAD_HIP(hipMemset(&g->counters[0], 0, 8));
+    if (n_bad) *n_bad = bad;
+    return EMB_OK;
+}
+
+}  // extern "C"

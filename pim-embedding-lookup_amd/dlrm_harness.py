@@ -3,8 +3,10 @@
 Stands where `dlrm_s_pytorch.py::apply_emb` stands in the reference's stack [EXT: that file is an
 empty submodule here; flags from README.md:6,10,14 and upmem/run.sh:72-82,111-121]: a list of
 `nn.EmbeddingBag(n_k, m, mode="sum")` called per table with (indices_k, offsets_k), each returning
-[B, m].  Here all tables are served by ONE fused HIP launch.  No autograd (inference only, as the
-reference's `--inference-only` runs), no MLPs -- the rest of the model is out of scope.
+[B, m].  Here all tables are served by ONE fused HIP launch.  Inference by default (as the reference's
+`--inference-only` runs); `--fused-sgd LR` trains the tables: apply_emb's result is attached to the autograd graph and
+loss.backward() applies the fused SGD step of the backward pass (include/pimemb_grad.h) to the served tables.  No MLPs -- the
+rest of the model is out of scope.
 
     python -m pim_embedding_lookup_amd.dlrm_harness --arch-sparse-feature-size=16 \
         --arch-embedding-size=1460-583-10131227-… --mini-batch-size=39292 --inference-only
@@ -77,6 +79,7 @@ class EmbeddingBagCollection:
             self.engine.load_table(k, w)
         self._plans = {}
         self._ids = list(range(len(self.ln_emb)))
+        self._fused_lr = None
         # DLRM --weighted-pooling: v_W_l[k] is a weight per ROW of table k (ones for "fixed", the checkpoint's for "learned");
         # a bag entry is weighted by its row's weight, gathered with torch (dlrm_s_pytorch.py: v_W_l[k].gather(0, indices))
         if weighted_pooling not in (None, "fixed", "learned"):
@@ -117,6 +120,8 @@ class EmbeddingBagCollection:
             raise ValueError("out= / col= need concat=True")
         if concat and self._out is not None:
             raise ValueError('concat=True returns one fp32 tensor: it does not combine with out_dtype="weight"')
+        if self._fused_lr is not None:
+            return self._apply_emb_fused_sgd(lS_o, lS_i, check, concat, out, col)
         if self.v_W_l is not None:
             return self._apply_emb_weighted(lS_o, lS_i, check, concat, out, col)
         if concat:
@@ -137,6 +142,40 @@ class EmbeddingBagCollection:
         if concat:
             return self.engine.lookup_concat(self._ids, lS_i, lS_o, out=out, col=col, modes="sum", per_sample_weights=ws, check=check)
         return self.engine.lookup_pooled(self._ids, lS_i, lS_o, "sum", per_sample_weights=ws, check=check, out_dtype=self._out)
+
+    def enable_fused_sgd(self, lr):
+        """From now on apply_emb (lists of torch CUDA tensors; f32 / f16 / bf16 tables) returns tensors attached to the autograd
+        graph whose backward applies W -= lr * grad to the served tables (GradContext.sgd_step): loss.backward() is the tables'
+        whole training step.  lr=None switches it off.  The per-row pooling weights of --weighted-pooling are not trained."""
+        self._fused_lr = None if lr is None else float(lr)
+        return self
+
+    def _apply_emb_fused_sgd(self, lS_o, lS_i, check, concat, out, col):
+        from . import torch_module as tm
+        lS_i, lS_o = [i.contiguous() for i in lS_i], [o.contiguous() for o in lS_o]
+        if not all(getattr(i, "is_cuda", False) for i in lS_i):
+            raise TypeError("the fused SGD step takes lists of torch CUDA index tensors")
+        if self.v_W_l is not None and check:
+            self.validate(lS_o, lS_i)
+        ws = None if self.v_W_l is None else [v.gather(0, i.long()) for v, i in zip(self.v_W_l, lS_i)]
+        lr = self._fused_lr
+
+        def lookup():
+            if concat:
+                return self.engine.lookup_concat(self._ids, lS_i, lS_o, out=out, col=col, modes="sum", per_sample_weights=ws, check=check)
+            return self.engine.lookup_pooled(self._ids, lS_i, lS_o, "sum", per_sample_weights=ws, check=check, out_dtype=self._out)
+
+        def step(g):
+            if concat:
+                g = g if g.stride(1) == 1 and (g.shape[0] < 2 or g.stride(0) >= g.shape[1]) else g.contiguous()
+                grads = [g[:, col + k * self.m:col + (k + 1) * self.m] for k in range(len(self._ids))]
+            else:
+                grads = [None if x is None else tm._grad_view(x, self.m) for x in g]
+            live = [k for k, x in enumerate(grads) if x is not None]
+            ctx = tm._grad_context(self.engine, max(i.shape[0] for i in lS_i), max(o.shape[0] for o in lS_o))
+            ctx.sgd_step([self._ids[k] for k in live], [lS_i[k] for k in live], [lS_o[k] for k in live], [grads[k] for k in live], lr,
+                         per_sample_weights=[None if ws is None else ws[k] for k in live])
+        return tm._FusedSGD.apply(tm._anchor(self, self.device), lookup, step)
 
     def validate(self, lS_o, lS_i) -> None:
         """emb_validate_inputs over one batch: IndexError on an index >= table rows or broken offsets, as
@@ -297,11 +336,14 @@ def main(argv=None):
     ap.add_argument("--quantize-on-device", action="store_true",
                     help="fp32 weights (a checkpoint's, or the random init) reach the tables through the GPU row writer "
                          "(engine.load_table_f32) instead of the host encoders")
+    ap.add_argument("--fused-sgd", type=float, default=None, metavar="LR",
+                    help="train the tables: apply_emb's result joins the autograd graph, and the backward of a dummy loss (the sum of "
+                         "the pooled rows) applies W -= LR * grad to the served tables on the GPU (include/pimemb_grad.h)")
     args, ignored = ap.parse_known_args(argv)
     if ignored:   # MLP / training / logging flags of the reference command lines (README.md:6,10,14)
         print("ignored (outside the embedding path):", " ".join(ignored))
-    if not args.inference_only:
-        print("note: only the inference embedding path exists here; running it (--inference-only implied)")
+    if not args.inference_only and args.fused_sgd is None:
+        print("note: running the inference embedding path (--inference-only implied); --fused-sgd LR trains the tables")
     import torch
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(args.numpy_rand_seed)
@@ -343,6 +385,23 @@ def main(argv=None):
     n_bags = int(ly.shape[0]) * len(ebc.ln_emb) if cat else sum(int(x.shape[0]) for x in ly)
     print(f"apply_emb{' (one [B, T * m] tensor)' if cat else ''}: {len(ebc.ln_emb)} tables, m={ebc.m}, batch {B}: {dt * 1e3:.4f} ms/batch, "
           f"{n_bags / dt:.3e} pooled lookups/s")
+    if args.fused_sgd is not None:      # forward + dummy loss + backward = lookup + fused SGD step on every table
+        ebc.enable_fused_sgd(args.fused_sgd)
+
+        def train_step(o, i):
+            ly = ebc.apply_emb(o, i, concat=cat)
+            loss = ly.sum() if cat else sum(y.sum() for y in ly)
+            loss.backward()
+        train_step(*batches[0])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for b in range(args.num_batches):
+            train_step(*batches[b % len(batches)])
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / args.num_batches
+        print(f"apply_emb + loss.backward() with the fused SGD step (lr {args.fused_sgd}): {dt * 1e3:.4f} ms/batch")
+        ebc.close()
+        return 0
     if ebc.v_W_l is not None:     # (prepared plans hold the sum path only)
         ebc.close()
         return 0

@@ -377,6 +377,149 @@ class RowWriter:
         self.close()
 
 
+class GradContext:
+    """The backward pass over an engine's tables (libpimemb_grad.so, include/pimemb_grad.h): from the gradient of a pooled
+    lookup's output to the table's sparse gradient, or straight to stepped rows (fused SGD) -- every sum in position order, the
+    same bits on every run.  EmbeddingEngine.grad_context makes one.  One context, one thread, one stream at a time: its scratch
+    is shared by its calls."""
+
+    def __init__(self, engine: "EmbeddingEngine", max_indices: int, max_bags: int):
+        if engine._L is not _l.load():
+            raise ValueError("the backward pass works with the default libpimemb.so (the one libpimemb_grad.so links against), not with a lib_path engine")
+        self.engine = engine
+        self.max_indices, self.max_bags = int(max_indices), int(max_bags)
+        self._G = _l.load_grad()
+        h = C.c_void_p()
+        _l.check_grad(self._G.emb_grad_create(engine._h, self.max_indices, self.max_bags, C.byref(h)))
+        self._h = h.value
+        engine._writers.append(self)
+
+    def _desc(self, d, table_id, indices, offsets, grad, mode, weights, padding_idx, fixed_pooling, keep):
+        """Fill one emb_grad_desc.  Torch CUDA tensors are read in place (grad may be a 2-D view with inner stride 1: its row
+        stride becomes grad_ld); numpy arrays are copied into DeviceBuffers, which `keep` holds.  Returns (index type, whether the
+        buffers are the caller's device tensors)."""
+        if mode not in ("sum", "mean", "max"):
+            raise ValueError(f"mode has to be one of sum, mean or max, got {mode!r}")
+        dev = _is_torch(indices) and indices.is_cuda
+        if dev:
+            import torch
+            if not (_is_torch(grad) and grad.is_cuda) or grad.dtype != torch.float32 or grad.dim() != 2 or (grad.shape[1] > 1 and grad.stride(1) != 1):
+                raise TypeError("grad must be a float32 CUDA tensor [n_bags, dim] (or such a view of a wider buffer, inner stride 1)")
+            ld = int(grad.stride(0)) if grad.shape[0] > 1 else int(grad.shape[1])
+            if offsets is not None and offsets.dtype != indices.dtype:
+                offsets = offsets.to(indices.dtype)
+            idx = indices.contiguous()
+            off = None if offsets is None else offsets.contiguous()
+            w = None if weights is None else weights.to(device=indices.device, dtype=torch.float32).contiguous()
+            keep += [idx, off, w, grad]
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            n, B, itype = idx.shape[0], (grad.shape[0] if off is None else off.shape[0]), _index_type_of(idx.dtype)
+            d.indices, d.offsets, d.grad, d.pool.per_sample_weights = ptr(idx), ptr(off), grad.data_ptr(), ptr(w)
+        else:
+            idx = np.ascontiguousarray(indices)
+            itype = _index_type_of(idx.dtype)
+            g = np.ascontiguousarray(grad, dtype=np.float32)
+            if g.ndim != 2:
+                raise TypeError("grad must be float32 [n_bags, dim]")
+            ld = g.shape[1]
+            off = None if offsets is None else np.ascontiguousarray(offsets, dtype=idx.dtype)
+            w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+            bufs = [None if a is None or a.size == 0 else DeviceBuffer.from_numpy(self.engine, a) for a in (idx, off, w, g)]
+            keep += bufs
+            ptr = lambda b: None if b is None else b.ptr  # noqa: E731
+            n, B = idx.shape[0], (g.shape[0] if off is None else off.shape[0])
+            d.indices, d.offsets, d.grad, d.pool.per_sample_weights = ptr(bufs[0]), ptr(bufs[1]), ptr(bufs[3]), ptr(bufs[2])
+        d.table_id, d.fixed_pooling, d.n_indices, d.n_bags, d.grad_ld = table_id, int(fixed_pooling), n, int(B), ld
+        d.pool.mode = POOL_MODES[mode]
+        d.pool.flags = 0 if padding_idx is None else _l.EMB_POOL_PADDING
+        d.pool.padding_idx = 0 if padding_idx is None else int(padding_idx)
+        return itype, dev
+
+    def sparse_grad(self, table: int, indices, offsets, grad, mode: str = "sum", per_sample_weights=None, padding_idx=None,
+                    stream: int | None = None, fixed_pooling: int = 0):
+        """(rows, grads): the rows of `table` that the batch names at least once, ascending (int64), and their gradients
+        (float32 [len(rows), dim]) -- what nn.EmbeddingBag(sparse=True) leaves in weight.grad after .coalesce().  indices /
+        offsets / grad ([n_bags, dim]) / per_sample_weights as the forward took them: numpy arrays (copied to the device and back)
+        or torch CUDA tensors (read in place, on `stream` or torch's current one; tensors come back, after one wait for the
+        number of rows).  offsets None: bags of fixed_pooling indices.  Positions whose id lies outside the table are skipped
+        and counted for report()."""
+        d, keep = _l.EmbGradDesc(), []
+        itype, dev = self._desc(d, table, indices, offsets, grad, mode, per_sample_weights, padding_idx, fixed_pooling, keep)
+        n = int(d.n_indices)
+        dim = self.engine.table_info(table)[2]
+        if dev:
+            import torch
+            rows = torch.empty((n,), dtype=torch.int64, device=indices.device)
+            grads = torch.empty((n, dim), dtype=torch.float32, device=indices.device)
+            count = torch.zeros((1,), dtype=torch.int64, device=indices.device)
+            if stream is None:
+                stream = _current_stream_for(indices)
+            _l.check_grad(self._G.emb_grad_sparse(self._h, C.byref(d), itype, rows.data_ptr(), grads.data_ptr(), n, count.data_ptr(), stream))
+            u = int(count.item())
+            return rows[:u], grads[:u]
+        rows_b = DeviceBuffer(self.engine, max(n, 1) * 8, np.int64, (max(n, 1),))
+        grads_b = DeviceBuffer(self.engine, max(n * dim, 1) * 4, np.float32, (max(n, 1), dim))
+        count_b = DeviceBuffer(self.engine, 8, np.uint64, (1,))
+        try:
+            _l.check_grad(self._G.emb_grad_sparse(self._h, C.byref(d), itype, rows_b.ptr, grads_b.ptr, n, count_b.ptr, stream))
+            self.engine.synchronize(stream)
+            u = int(count_b.numpy()[0])
+            return rows_b.numpy()[:u].copy(), grads_b.numpy()[:u].copy()
+        finally:
+            for b in (rows_b, grads_b, count_b, *keep):
+                if isinstance(b, DeviceBuffer):
+                    b.free()
+
+    def sgd_step(self, table_ids, indices, offsets, grads, lr: float, modes="sum", per_sample_weights=None, padding_idx=None,
+                 stream: int | None = None, fixed_pooling: int = 0) -> None:
+        """W[r] = enc(dec(W[r]) - lr * g[r]) for every row r the batch of its table names, in place, table after table (fp32,
+        fp16 and bf16 tables).  table_ids / indices / offsets / grads: one entry per table; modes, per_sample_weights and
+        padding_idx one value for all or one per table.  Each gradient is [n_bags, dim], and may be a column view of a wider
+        buffer (the [B, T*dim] gradient of a concatenated output is read in place).  Torch CUDA tensors: a pure enqueue on
+        `stream` (torch's current one by default); numpy arrays: copied to the device, and the call waits."""
+        n = len(table_ids)
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n  # noqa: E731
+        modes, ws, pads = per(modes), per(per_sample_weights), per(padding_idx)
+        arr, keep, itypes, devs = (_l.EmbGradDesc * max(n, 1))(), [], set(), set()
+        for k in range(n):
+            it, dev = self._desc(arr[k], table_ids[k], indices[k], None if offsets is None else offsets[k], grads[k], modes[k], ws[k], pads[k],
+                                 fixed_pooling, keep)
+            itypes.add(it)
+            devs.add(dev)
+        if len(itypes) > 1 or len(devs) > 1:
+            raise TypeError("the tables of one call share one index width and one memory space")
+        dev = bool(devs and devs.pop())
+        if stream is None and dev:
+            stream = _current_stream_for(*indices)
+        try:
+            _l.check_grad(self._G.emb_grad_sgd(self._h, arr, n, itypes.pop() if itypes else _l.EMB_IDX_I64, float(lr), stream))
+            if not dev:
+                self.engine.synchronize(stream)
+        finally:
+            for b in keep:
+                if isinstance(b, DeviceBuffer):
+                    b.free()
+
+    def report(self) -> int:
+        """Positions skipped for an id outside the table since the last report (waits for the device; resets the count)."""
+        bad = C.c_uint64()
+        _l.check_grad(self._G.emb_grad_report(self._h, C.byref(bad)))
+        return bad.value
+
+    def close(self) -> None:
+        if self._h:
+            self._G.emb_grad_destroy(self._h)
+            self._h = None
+            if self in self.engine._writers:
+                self.engine._writers.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class EmbeddingEngine:
     """One engine per GPU: tables resident in HBM, lookups as fused HIP launches."""
 
@@ -395,7 +538,7 @@ class EmbeddingEngine:
         _l.check(self._L.emb_create(C.byref(cfg), C.byref(h)))
         self._h = h.value
         self._tables: dict[int, tuple[int, int, int]] = {}  # id -> (nr_rows, dim, dtype)
-        self._writers: list = []                            # live RowWriters (closed with the engine)
+        self._writers: list = []                            # live RowWriters and GradContexts (closed with the engine)
         # Scratch descriptor arrays are PER THREAD: the C call that reads them releases the GIL, so another thread packing
         # its own call into a shared array would be read half-way (lookups may be issued from several threads, pimemb.h).
         self._tls = threading.local()                       # .bufs: n descriptors -> (buffer, typed pointer, address)
@@ -486,6 +629,11 @@ class EmbeddingEngine:
         """A writer for in-place row updates of this engine's tables, for device-pointer calls of up to max_rows rows
         (host-pointer calls of any size are chunked): see RowWriter.update.  Closed with the engine at the latest."""
         return RowWriter(self, max_rows)
+
+    def grad_context(self, max_indices: int = 1 << 20, max_bags: int = 1 << 20) -> GradContext:
+        """A context for the backward pass over this engine's tables (sparse gradients, the fused SGD step), for calls of up
+        to max_indices indices and max_bags bags per table: see GradContext.  Closed with the engine at the latest."""
+        return GradContext(self, max_indices, max_bags)
 
     def load_table_f32(self, table_id: int, rows_f32, dtype: int, chunk_rows: int = 65536) -> None:
         """Allocate table `table_id` as `dtype` (any but EMB_FIXED32) and fill it from float32 rows [nr_rows, dim], encoded ON

@@ -210,8 +210,29 @@ ROWS_SIGNATURES = {
     "emb_rows_report": (C.c_int, [_vp, C.POINTER(_u64)]),
 }
 
+
+
+class EmbGradDesc(C.Structure):
+    _fields_ = [("table_id", C.c_uint32), ("fixed_pooling", C.c_uint32), ("indices", C.c_void_p), ("offsets", C.c_void_p),
+                ("n_indices", C.c_uint64), ("n_bags", C.c_uint64), ("grad", C.c_void_p), ("grad_ld", C.c_uint64),
+                ("pool", EmbPoolSpec)]
+
+
+# name -> (restype, argtypes); every function declared in include/pimemb_grad.h (libpimemb_grad.so, the backward pass: the third
+# library, with its own code object as well)
+GRAD_SIGNATURES = {
+    "emb_grad_last_error": (C.c_char_p, []),
+    "emb_grad_scratch_bytes": (_u64, [_u64, _u64]),
+    "emb_grad_create": (C.c_int, [_vp, _u64, _u64, _pp]),
+    "emb_grad_destroy": (C.c_int, [_vp]),
+    "emb_grad_sparse": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.c_int, _vp, _vp, _u64, _vp, _vp]),
+    "emb_grad_sgd": (C.c_int, [_vp, C.POINTER(EmbGradDesc), _u32, C.c_int, C.c_float, _vp]),
+    "emb_grad_report": (C.c_int, [_vp, C.POINTER(_u64)]),
+}
+
 _lib = None
 _rows_lib = None
+_grad_lib = None
 
 
 class PimembError(RuntimeError):
@@ -244,7 +265,8 @@ def load(path: str | None = None) -> C.CDLL:
         fn.argtypes = args
     if path is None:
         _lib = L
-        load_rows()                    # the companion library is part of the build: missing or incomplete is an error here too
+        load_rows()                    # the companion libraries are part of the build: missing or incomplete is an error here too
+        load_grad()
     return L
 
 
@@ -271,6 +293,28 @@ def load_rows() -> C.CDLL:
     return R
 
 
+def load_grad() -> C.CDLL:
+    """Load libpimemb_grad.so (the backward pass, include/pimemb_grad.h) next to the default libpimemb.so, as load_rows does."""
+    global _grad_lib
+    if _grad_lib is not None:
+        return _grad_lib
+    load()
+    if _grad_lib is not None:          # (load() came here itself)
+        return _grad_lib
+    from .build import GRAD_LIB_PATH
+    if not os.path.exists(GRAD_LIB_PATH):
+        raise FileNotFoundError(
+            f"{GRAD_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no fallback path.")
+    G = C.CDLL(GRAD_LIB_PATH)
+    for name, (res, args) in GRAD_SIGNATURES.items():
+        fn = getattr(G, name)  # AttributeError if the symbol is not exported
+        fn.restype = res
+        fn.argtypes = args
+    _grad_lib = G
+    return G
+
+
 def check(rc: int) -> None:
     if rc != EMB_OK:
         raise PimembError(rc, load().emb_last_error().decode(errors="replace"))
@@ -279,3 +323,8 @@ def check(rc: int) -> None:
 def check_rows(rc: int) -> None:
     if rc != EMB_OK:
         raise PimembError(rc, load_rows().emb_rows_last_error().decode(errors="replace"))
+
+
+def check_grad(rc: int) -> None:
+    if rc != EMB_OK:
+        raise PimembError(rc, load_grad().emb_grad_last_error().decode(errors="replace"))

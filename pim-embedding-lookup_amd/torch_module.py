@@ -14,7 +14,14 @@ Which class does what:
   PoolingEmbeddingBag / FusedPoolingEmbeddingBags     the rest of nn.EmbeddingBag's inference side: mode "sum" / "mean" /
                                                       "max", per_sample_weights (sum only, as in torch) and padding_idx,
                                                       equal to torch's CPU result bit for bit (emb_lookup_pooled).
-Inference only (the engine has no backward); max_norm is not supported by any of them.
+Training the tables: the Pooling modules have a backward pass on the GPU (libpimemb_grad.so, include/pimemb_grad.h), for mode
+"sum" (with per_sample_weights and padding_idx) and "mean", every sum in position order -- the same bits on every run:
+`sparse_grad(input, offsets, grad_output)` returns what nn.EmbeddingBag(sparse=True) leaves in weight.grad (coalesced),
+`sgd_step_(input, offsets, grad_output, lr)` applies weight -= lr * grad in place (fp32 / fp16 / bf16 weights), and after
+`enable_fused_sgd(lr)` forward() returns a tensor attached to the autograd graph whose backward runs that step, as fused-optimizer
+embedding modules do: loss.backward() updates the served table, there is no weight.grad and nothing for an optimizer to do.  Off
+by default: a module on which it was never called returns plain tensors, as before.  Not there: the gradient with respect to
+per_sample_weights, mode "max", optimizers other than SGD, fp8 / MXFP4 weights.  max_norm is not supported by any module.
 
 Output dtype.  By default every module returns fp32 rows, whatever the table holds.  `out_dtype="weight"` makes a module
 with an fp16 / bf16 weight return the weight's dtype, as nn.EmbeddingBag does: the fp32 pooled value rounded once (the
@@ -316,9 +323,53 @@ class PoolingEmbeddingBag(torch.nn.Module):
     def forward(self, input, offsets=None, per_sample_weights=None):
         idx, off = _bags_from(input, offsets, self.include_last_offset)
         w = _weights_for(per_sample_weights, self.mode, input)
-        return self.engine.lookup_pooled(self._id_list, [idx.contiguous()], [off.contiguous()], self.mode,
-                                         per_sample_weights=None if w is None else [w], padding_idx=self.padding_idx,
-                                         check=self._check(), out_dtype=self._engine_out)[0]
+        idx, off = idx.contiguous(), off.contiguous()
+
+        def lookup():
+            return self.engine.lookup_pooled(self._id_list, [idx], [off], self.mode, per_sample_weights=None if w is None else [w],
+                                             padding_idx=self.padding_idx, check=self._check(), out_dtype=self._engine_out)[0]
+        lr = getattr(self, "_fused_lr", None)
+        if lr is None:
+            return lookup()
+        return _FusedSGD.apply(_anchor(self, idx.device), lookup, lambda g: self._step(idx, off, g, lr, w))
+
+    def enable_fused_sgd(self, lr: float):
+        """From now on forward() returns a tensor attached to the autograd graph, and its backward applies weight -= lr * grad
+        to the served table (sgd_step_ with the inputs forward saw): loss.backward() is the whole training step of this table.
+        lr=None switches it off again.  Returns self."""
+        object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
+        return self
+
+    def _step(self, idx, off, grad_output, lr, w):
+        if grad_output is None:
+            return
+        g = _grad_view(grad_output, self.embedding_dim)
+        _grad_context(self.engine, idx.shape[0], off.shape[0]).sgd_step(self._id_list, [idx], [off], [g], lr, modes=self.mode,
+                                                                        per_sample_weights=w, padding_idx=self.padding_idx)
+
+    def _bags_on_device(self, input, offsets, per_sample_weights):
+        dev = torch.device("cuda", self.device_index)
+        idx, off = _bags_from(torch.as_tensor(input).to(dev), None if offsets is None else torch.as_tensor(offsets).to(dev), self.include_last_offset)
+        w = _weights_for(None if per_sample_weights is None else torch.as_tensor(per_sample_weights).to(dev), self.mode, input)
+        return idx.contiguous(), off.contiguous(), w
+
+    def sparse_grad(self, input, offsets, grad_output, per_sample_weights=None):
+        """The gradient of the weight for one batch: a coalesced torch.sparse_coo_tensor [num_embeddings, embedding_dim] (fp32, on the
+        GPU) -- rows ascending, each the sum of its contributions in position order -- as nn.EmbeddingBag(sparse=True) leaves it in
+        weight.grad after .coalesce(), without the all-zero rows torch lists for padding entries.  The weight is not changed."""
+        idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
+        g = _grad_view(torch.as_tensor(grad_output).to(idx.device), self.embedding_dim)
+        rows, grads = _grad_context(self.engine, idx.shape[0], off.shape[0]).sparse_grad(
+            self.table_id, idx, off, g, mode=self.mode, per_sample_weights=w, padding_idx=self.padding_idx)
+        return torch.sparse_coo_tensor(rows.unsqueeze(0), grads, size=(self.num_embeddings, self.embedding_dim), is_coalesced=True)
+
+    def sgd_step_(self, input, offsets, grad_output, lr: float, per_sample_weights=None):
+        """weight[r] -= lr * grad[r] for every row the batch names, in place and in stream order with forward(): one fp32
+        multiply and one fp32 subtract per element, rounded once into the weight's dtype (fp32 / fp16 / bf16).  Entries whose
+        index lies outside the table are skipped and counted (engine._module_grad.report()).  Returns self."""
+        idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
+        self._step(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), w)
+        return self
 
     def update_rows_(self, ids, rows):
         """weight[ids[p]] = rows[p] (float32 [n, embedding_dim], encoded into the weight's dtype on the GPU), in place and in
@@ -336,6 +387,55 @@ class PoolingEmbeddingBag(torch.nn.Module):
     def extra_repr(self) -> str:
         return (f"{self.num_embeddings}, {self.embedding_dim}, mode={self.mode!r}, padding_idx={self.padding_idx}, "
                 f"table_id={self.table_id}, engine=MI355X")
+
+
+
+_GRAD_INDICES = 65536     # indices per call of the modules' shared backward context (it grows when a batch is larger)
+
+
+def _grad_context(engine: EmbeddingEngine, n_indices: int, n_bags: int):
+    """The backward context the modules of one engine share; replaced by a larger one when a batch does not fit."""
+    g = getattr(engine, "_module_grad", None)
+    if g is None or not g._h or g.max_indices < n_indices or g.max_bags < n_bags:
+        if g is not None and g._h:
+            g.close()
+        g = engine._module_grad = engine.grad_context(max(_GRAD_INDICES, int(n_indices)), max(_GRAD_INDICES, int(n_bags)))
+    return g
+
+
+def _grad_view(grad_output, dim: int):
+    """A gradient the kernels can read in place: float32, [B, dim], inner stride 1, rows that do not overlap (the gradient of
+    out.sum() is an expanded scalar: stride 0 -- that one is materialised)."""
+    g = grad_output if grad_output.dtype == torch.float32 else grad_output.float()
+    if g.dim() != 2 or g.shape[1] != dim:
+        raise ValueError(f"grad_output must be [n_bags, {dim}], got {tuple(g.shape)}")
+    if g.stride(1) != 1 or (g.shape[0] > 1 and g.stride(0) < dim):
+        g = g.contiguous()
+    return g
+
+
+class _FusedSGD(torch.autograd.Function):
+    """forward runs the lookup, backward the fused SGD step on the inputs forward saw.  The graph is anchored on a zero-sized
+    dummy leaf (its gradient stays None): the served table itself is not an autograd leaf."""
+
+    @staticmethod
+    def forward(ctx, anchor, lookup, step):
+        out = lookup()
+        ctx.step, ctx.many = step, isinstance(out, (list, tuple))
+        return tuple(out) if ctx.many else out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        ctx.step(list(grads) if ctx.many else grads[0])
+        return None, None, None
+
+
+def _anchor(module, device):
+    a = getattr(module, "_sgd_anchor", None)
+    if a is None:      # (a plain attribute, not a Parameter: state_dict() keeps its keys)
+        a = torch.zeros(0, device=device, requires_grad=True)
+        object.__setattr__(module, "_sgd_anchor", a)
+    return a
 
 
 _UPDATE_ROWS = 65536      # rows per device-pointer call of the modules' shared row writer
@@ -409,14 +509,63 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             idx.append(i1.contiguous())
             off.append(o1.contiguous())
             ws.append(_weights_for(None if lS_w is None else lS_w[k], b.mode, i))
-        if self.concat:
-            return self.engine.lookup_concat(self._ids, idx, off, out=out, col=col, modes=self._modes,
-                                             per_sample_weights=None if lS_w is None else ws, padding_idx=self._pads, check=check)
-        return self.engine.lookup_pooled(self._ids, idx, off, self._modes,
-                                         per_sample_weights=None if lS_w is None else ws, padding_idx=self._pads, check=check,
-                                         out_dtype=self._outs)
+        wl = None if lS_w is None else ws
+
+        def lookup():
+            if self.concat:
+                return self.engine.lookup_concat(self._ids, idx, off, out=out, col=col, modes=self._modes, per_sample_weights=wl,
+                                                 padding_idx=self._pads, check=check)
+            return self.engine.lookup_pooled(self._ids, idx, off, self._modes, per_sample_weights=wl, padding_idx=self._pads, check=check,
+                                             out_dtype=self._outs)
+        lr = getattr(self, "_fused_lr", None)
+        if lr is None:
+            return lookup()
+        return _FusedSGD.apply(_anchor(self, idx[0].device), lookup, lambda g: self._step(idx, off, g, lr, wl, col))
 
     apply_emb = forward
+
+    def enable_fused_sgd(self, lr: float):
+        """As PoolingEmbeddingBag.enable_fused_sgd, for every table of the model: the backward of forward()'s result -- the list,
+        or the one [B, sum(m)] tensor of concat=True -- steps all of them.  Returns self."""
+        object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
+        return self
+
+    def _step(self, idx, off, grad_output, lr, ws, col=0):
+        dims = [b.embedding_dim for b in self.bags]
+        if isinstance(grad_output, (list, tuple)):
+            if len(grad_output) != len(dims):
+                raise ValueError(f"{len(grad_output)} gradients for {len(dims)} tables")
+            grads = [None if g is None else _grad_view(g, d) for g, d in zip(grad_output, dims)]
+        else:      # ONE [B, sum(m)] gradient (of a concat=True forward; of a wider buffer from column `col`): read in place, table by table
+            g = grad_output if grad_output.dtype == torch.float32 else grad_output.float()
+            if g.dim() != 2 or g.shape[1] < col + sum(dims):
+                raise ValueError(f"grad_output must be [n_bags, >= {col + sum(dims)}], got {tuple(g.shape)}")
+            if g.stride(1) != 1 or (g.shape[0] > 1 and g.stride(0) < g.shape[1]):
+                g = g.contiguous()
+            at = [col + sum(dims[:k]) for k in range(len(dims))]
+            grads = [g[:, a:a + d] for a, d in zip(at, dims)]
+        live = [k for k, g in enumerate(grads) if g is not None]
+        if not live:
+            return
+        ctx = _grad_context(self.engine, max(idx[k].shape[0] for k in live), max(off[k].shape[0] for k in live))
+        ctx.sgd_step([self._ids[k] for k in live], [idx[k] for k in live], [off[k] for k in live], [grads[k] for k in live], lr,
+                     modes=[self._modes[k] for k in live], per_sample_weights=[None if ws is None else ws[k] for k in live],
+                     padding_idx=[self._pads[k] for k in live])
+
+    def sgd_step_(self, lS_o, lS_i, grad_output, lr: float, lS_w=None):
+        """PoolingEmbeddingBag.sgd_step_ for all tables in one call.  grad_output: a list of [B, m_k] gradients, or the ONE
+        [B, sum(m)] gradient of a concat=True forward, which is read in place (each table's columns through the row stride)."""
+        dev = torch.device("cuda", self.engine.device)
+        idx, off, ws = [], [], []
+        for k, (b, i, o) in enumerate(zip(self.bags, lS_i, lS_o)):
+            i1, o1 = _bags_from(torch.as_tensor(i).to(dev), None if o is None else torch.as_tensor(o).to(dev), b.include_last_offset)
+            idx.append(i1.contiguous())
+            off.append(o1.contiguous())
+            ws.append(_weights_for(None if lS_w is None else torch.as_tensor(lS_w[k]).to(dev), b.mode, i))
+        if not isinstance(grad_output, (list, tuple)):
+            grad_output = torch.as_tensor(grad_output).to(dev)
+        self._step(idx, off, grad_output, float(lr), None if lS_w is None else ws)
+        return self
 
     def update_rows_(self, table: int, ids, rows):
         """PoolingEmbeddingBag.update_rows_ on table number `table` of the model (its position in the module list)."""
