@@ -1,7 +1,7 @@
 /*
  * pimemb_grad.h -- C ABI of the backward pass (libpimemb_grad.so): from the gradient of a pooled lookup's output to the
- * sparse gradient of the table, or straight to new table rows by a fused SGD step -- on the GPU, in stream order with the
- * lookups and the row writer, every sum in a fixed order: results are the same bits on every run.
+ * sparse gradient of the table, or straight to new table rows by a fused SGD, Adagrad or row-wise Adagrad step -- on the GPU,
+ * in stream order with the lookups and the row writer, every sum in a fixed order: results are the same bits on every run.
  *
  * A companion library like libpimemb_rows.so, not part of libpimemb.so: it carries its own gfx950 code object and reaches tables
  * only through the public ABI of pimemb.h (emb_table_info, emb_table_hot_count, emb_device_of, emb_device_alloc, ...), so
@@ -46,9 +46,12 @@
  *                     the old bytes: clear the set, step, set it again.
  *   EMB_POOL_MAX      needs the forward's per-element argmax, which no kernel records.
  * Prepared plans stay valid over a stepped table and read the new rows when launched behind the step.
- * Out of scope: the gradient with respect to per_sample_weights; max mode; optimizers other than SGD; fusing several tables
- * into one launch (emb_grad_sgd over several descriptors launches per descriptor); the ranged / sharded paths; NaN ordering and
- * payloads, as everywhere in this library.
+ * emb_grad_step (below) is the same step with an optimizer that keeps state: Adagrad, and row-wise Adagrad.
+ * Out of scope: the gradient with respect to per_sample_weights; max mode; optimizers other than SGD, Adagrad and row-wise
+ * Adagrad (no momentum, no Adam), weight decay and lr_decay, optimizer state in anything but fp32; row-wise Adagrad off the
+ * lane-group shape (the element-wise kernel has no row-wide view of g, and a second reduction is not built for it:
+ * EMB_ERR_UNSUPPORTED); fusing several tables into one launch (emb_grad_sgd / emb_grad_step over several descriptors launch
+ * per descriptor); the ranged / sharded paths; NaN ordering and payloads, as everywhere in this library.
  *
  * How it runs.  A pre-pass gives every position its bag (binary search in offsets), flags it good / bad / padding, counts cnt
  * per bag for mean, and orders the positions by (row id, position): a stable LSD radix sort over the ceil(log2(nr_rows + 1)) id
@@ -128,6 +131,62 @@ int emb_grad_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype
  * pure enqueue like emb_grad_sparse.  Every descriptor is checked before anything is enqueued: a refused call leaves every
  * table as it was. */
 int emb_grad_sgd(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream);
+
+/* THE ADAGRAD STEPS (tests/optim_ref.py restates them as loops; the kernels are compared with that, bit for bit).  g[r], U, good /
+ * bad / padding positions, dec and enc are the ones defined at the top.  Every fp32 operation below is rounded on its own and
+ * never contracted into an FMA; division and square root are the IEEE correctly rounded ones (csrc/pimemb_grad_optim.h: the
+ * one-element arithmetic, compiled by the kernels and by a host check alike).  The optimizer state S is fp32 whatever the table's
+ * dtype, lives in a buffer of the caller's, and is initialised by the caller (torch's initial_accumulator_value is a fill).
+ *
+ * EMB_OPT_ADAGRAD: torch.optim.Adagrad on sparse gradients with lr_decay = 0 and weight_decay = 0.  S is float[nr_rows][dim], no
+ * padding.  For every r in U and every element d:
+ *       q     = g[r][d] * g[r][d]
+ *       S'    = S[r][d] + q
+ *       den   = sqrt(S') + eps
+ *       x     = g[r][d] / den
+ *       W'[r][d] = enc(dec(W[r][d]) - (lr * x))          S[r][d] = S'
+ *
+ * EMB_OPT_ROWWISE_ADAGRAD: the FBGEMM / DLRM "exact row-wise" form, one accumulator per row.  S is float[nr_rows].  For every r in U:
+ *       sq[d] = g[r][d] * g[r][d]                         d < dim;  sq[d] = +0 for dim <= d < 4 * pieces
+ *       t[c]  = ((sq[4c] + sq[4c+1]) + sq[4c+2]) + sq[4c+3]     c < pieces = dim / 4
+ *       v     = t, padded with +0 to L = min(64, pow2ceil(pieces)) entries;
+ *               where pieces > 64:  v[l] = t[l] + t[l + 64]  for l + 64 < pieces
+ *       while len(v) > 1:  v = [v[0] + v[1], v[2] + v[3], ...]       (adjacent pairs, level by level)
+ *       m     = v[0] / (float)dim
+ *       S'    = S[r] + m
+ *       step  = lr / (sqrt(S') + eps)                     (one division per row)
+ *       W'[r][d] = enc(dec(W[r][d]) - (step * g[r][d]))   S[r] = S'
+ *   The tree is stated over dim alone.  It is the xor butterfly v[l] += v[l ^ h] for h = 1, 2, 4, ... over the lane group that
+ *   already owns the row, in which lane l holds pieces l and l + 64; IEEE addition commutes, so every lane ends with the same bits
+ *   and applies `step` to its own pieces.  S[r] is stored by one lane, with a plain vector store.
+ * Rows outside U keep their table bytes and their state bytes.  g is never written to memory.  NaN payloads are unspecified.
+ * How the row-wise tail runs: the lanes of a group that own no piece (dim 48: 12 pieces in 16 lanes) stay in the kernel, hold +0 and
+ * take part in every shuffle; the shuffles come after the run walk, where a group's lanes are together again, with xor distances
+ * below the group's size only; beyond dim 256 a lane keeps two accumulators (it walks the run once per piece and holds both sums:
+ * the ISA shows no scratch), since the whole row's g is needed before the first table store. */
+typedef enum { EMB_OPT_ADAGRAD = 1, EMB_OPT_ROWWISE_ADAGRAD = 2 } emb_opt_kind;
+typedef struct emb_opt_spec {
+    uint32_t kind;     /* an emb_opt_kind */
+    float lr;
+    float eps;         /* >= 0 */
+    uint32_t reserved; /* 0 */
+} emb_opt_spec;
+
+/* Floats of optimizer state a table of nr_rows x dim needs: nr_rows * dim (EMB_OPT_ADAGRAD), nr_rows (EMB_OPT_ROWWISE_ADAGRAD);
+ * 0 for an unknown kind.  A pure function. */
+uint64_t emb_opt_state_floats(uint32_t kind, uint64_t nr_rows, uint32_t dim);
+
+/* The fused Adagrad / row-wise Adagrad step, descriptor after descriptor, as emb_grad_sgd: DEVICE pointers only, a pure enqueue.
+ * states[k] is a caller-owned DEVICE buffer of emb_opt_state_floats(opt->kind, nr_rows, dim) floats for descs[k]'s table, read and
+ * written in place.  Every descriptor and every state is checked before anything is enqueued: a refused call leaves every table
+ * and every state as it was.  Refused as emb_grad_sgd refuses (fp8 / MXFP4 / fixed-point tables, a hot set staged, EMB_POOL_MAX,
+ * the context's limits), and EMB_ERR_INVALID for: a NULL or not 4-byte aligned state where n_indices > 0, an unknown kind,
+ * reserved != 0, eps negative or NaN.
+ * EMB_OPT_ROWWISE_ADAGRAD needs the lane-group shape -- dim % 4 == 0, dim <= 512, grad 16-byte aligned, grad_ld % 4 == 0 -- and is
+ * EMB_ERR_UNSUPPORTED otherwise.  EMB_OPT_ADAGRAD runs on both kernels: the lane-group one where that shape holds and the state
+ * is 16-byte aligned as well, the element-wise one otherwise, with the same bits. */
+int emb_grad_step(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype,
+                  const emb_opt_spec *opt, void *stream);
 
 /* The number of BAD positions (an id outside the table) skipped since the last report; resets the count.  Waits for the
  * device first, so the count covers every call enqueued so far. */

@@ -11,10 +11,12 @@
 //                       positions, an exclusive scan over the [digit][tile] matrix in two levels, and a scatter that ranks
 //                       the positions of a tile in their order (wavefront ballots, then counts per 64-position slice)
 //   grad_scan_chunks<true>   the same scan over the run-head flags of the sorted keys: the number of every unique row
-// The hot kernels (one per result, SGD = false / true):
+// The hot kernels (one instantiation per result: the sparse gradient, the SGD step, the Adagrad step, the row-wise Adagrad step):
 //   grad_rows_group     one lane group per unique row, a lane owns 4 consecutive fp32 elements: walks the row's run in position
 //                       order, the 16-byte loads of eight occurrences issued before the first add, the adds in order
-//   grad_rows_elem      any other dim / alignment: one thread per element of a unique row
+//   grad_rows_elem      any other dim / alignment: one thread per element of a unique row (no row-wise Adagrad)
+// The Adagrad tails (csrc/pimemb_grad_optim.h) end the same kernels; the row-wise one sums the row's squares over its lane group
+// with an xor butterfly -- a fixed tree, stated over dim alone in the header: the same bits on every run.
 // Every fp32 operation of the definition is a statement of its own under `fp contract(off)` (and the unit is compiled with
 // -ffp-contract=off): nothing is fused into an FMA.
 #include <hip/hip_runtime.h>
@@ -24,6 +26,7 @@
 #include <string.h>
 
 #include "pimemb_grad.h"
+#include "pimemb_grad_optim.h"
 #include "pimemb_grad_step.h"
 
 namespace {
@@ -267,6 +270,9 @@ struct RowArgs {
     uint32_t stride;             // bytes from one table row to the next
     int dtype;
     float lr;
+    // the Adagrad steps
+    float *state;                // S: float[nr_rows][dim] (element-wise) or float[nr_rows] (row-wise)
+    float eps;
 };
 
 // The scalar a position's G row is multiplied with (weighted) or divided by (mean); 0 for a plain sum.
@@ -290,71 +296,135 @@ __device__ inline float add_in_order(float acc, float c) {
 
 constexpr uint32_t kAhead = 8;      // occurrences whose loads are in flight before the first add
 
+// What a hot kernel does with g[r]: write it out, or step the row with it.
+enum ResultKind : int { RES_SPARSE = 0, RES_SGD = 1, RES_ADAGRAD = 2, RES_ROWWISE = 3 };
+
+// The run walk of one 16-byte piece: g[row][4c .. 4c + 3], the run that starts at sorted place i summed in position order.
+__device__ __forceinline__ float4 walk_piece(const RowArgs &a, uint32_t i, uint32_t row, uint32_t c) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint32_t j = i;
+    for (;;) {
+        bool live[kAhead];
+        float4 g[kAhead];
+        float s[kAhead];
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {      // the loads of up to kAhead occurrences (a dead slot re-reads the run's first)
+            live[k] = k == 0 || (live[k - 1] && j + k < a.n && a.keys[j + k] == row);
+            const uint32_t p = min(a.vals[live[k] ? j + k : j], a.n - 1u);      // (what the pre-pass wrote lies below these bounds:
+            const uint32_t b = min(a.bagof[p], a.n_bags - 1u);                  //  they are the bounds of the loads all the same)
+            s[k] = coef_of(a, p, b);
+            g[k] = *reinterpret_cast<const float4 *>(a.grad + (uint64_t)b * a.ld + 4u * c);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {      // the adds, in position order
+            if (live[k]) {
+                acc.x = add_in_order(acc.x, contribution(a.coef, g[k].x, s[k]));
+                acc.y = add_in_order(acc.y, contribution(a.coef, g[k].y, s[k]));
+                acc.z = add_in_order(acc.z, contribution(a.coef, g[k].z, s[k]));
+                acc.w = add_in_order(acc.w, contribution(a.coef, g[k].w, s[k]));
+            }
+        }
+        if (!live[kAhead - 1]) break;
+        j += kAhead;
+        if (j >= a.n || a.keys[j] != row) break;
+    }
+    return acc;
+}
+
+// The tail of a stepped row's piece c: decode / step / encode and ONE vector store (16 bytes fp32, 8 bytes fp16 / bf16).  `rate` is
+// lr (RES_SGD, RES_ADAGRAD) or the row's step size (RES_ROWWISE); RES_ADAGRAD reads, steps and stores the piece of the state too.
+template <int KIND>
+__device__ __forceinline__ void step_piece(const RowArgs &a, uint32_t row, uint32_t c, float4 acc, float rate) {
+    float4 *sp = nullptr;
+    float4 st = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (KIND == RES_ADAGRAD) {
+        sp = reinterpret_cast<float4 *>(a.state + (uint64_t)row * a.dim) + c;
+        st = *sp;
+    }
+    if (a.dtype == kStepF32) {
+        float4 *w = reinterpret_cast<float4 *>(a.table + (uint64_t)row * a.stride) + c;
+        float4 v = *w;
+        if (KIND == RES_ADAGRAD) {
+            v.x = bits_f32(adagrad_step(kStepF32, f32_bits(v.x), acc.x, &st.x, rate, a.eps));
+            v.y = bits_f32(adagrad_step(kStepF32, f32_bits(v.y), acc.y, &st.y, rate, a.eps));
+            v.z = bits_f32(adagrad_step(kStepF32, f32_bits(v.z), acc.z, &st.z, rate, a.eps));
+            v.w = bits_f32(adagrad_step(kStepF32, f32_bits(v.w), acc.w, &st.w, rate, a.eps));
+        } else {
+            v.x = step_f32(v.x, acc.x, rate);
+            v.y = step_f32(v.y, acc.y, rate);
+            v.z = step_f32(v.z, acc.z, rate);
+            v.w = step_f32(v.w, acc.w, rate);
+        }
+        *w = v;
+    } else {
+        u32x2 *w = reinterpret_cast<u32x2 *>(a.table + (uint64_t)row * a.stride) + c;
+        const u32x2 v = *w;
+        u32x2 o;
+        if (KIND == RES_ADAGRAD) {
+            o.x = adagrad_step(a.dtype, v.x & 0xffffu, acc.x, &st.x, rate, a.eps) | (adagrad_step(a.dtype, v.x >> 16, acc.y, &st.y, rate, a.eps) << 16);
+            o.y = adagrad_step(a.dtype, v.y & 0xffffu, acc.z, &st.z, rate, a.eps) | (adagrad_step(a.dtype, v.y >> 16, acc.w, &st.w, rate, a.eps) << 16);
+        } else {
+            o.x = step(a.dtype, v.x & 0xffffu, acc.x, rate) | (step(a.dtype, v.x >> 16, acc.y, rate) << 16);
+            o.y = step(a.dtype, v.y & 0xffffu, acc.z, rate) | (step(a.dtype, v.y >> 16, acc.w, rate) << 16);
+        }
+        *w = o;
+    }
+    if (KIND == RES_ADAGRAD) *sp = st;
+}
+
+// t[c] of the row-wise definition: ((sq0 + sq1) + sq2) + sq3 over a piece's squares.
+__device__ __forceinline__ float piece_squares(float4 g) {
+    return adagrad_add(adagrad_add(adagrad_add(adagrad_square(g.x), adagrad_square(g.y)), adagrad_square(g.z)), adagrad_square(g.w));
+}
+
 // One unique row per group of `lanes` lanes (a power of two up to 64); lane lg handles the row's 16-byte pieces lg, lg + lanes
 // (two only beyond dim 256).  Place i of the sorted order is worked on only where a run starts there.
-template <bool SGD>
+// RES_ROWWISE needs the whole row's g before the first table store: a lane walks the run for piece lg, then for piece lg + lanes,
+// and keeps both sums (two accumulators -- the second walk's loads reuse the first's registers: no scratch in the ISA); the
+// lanes of a group with no piece (dim 48: 12 pieces, 16 lanes) stay, hold +0 and take part in every shuffle.  The shuffles sit
+// behind the walk, where the lanes of a group have come together again -- the groups of one wavefront walk runs of different
+// lengths, and the groups that are no run head have left -- and reach across xor distances below `lanes` only: never into
+// another group, never into a lane that has returned.
+template <int KIND>
 __global__ __launch_bounds__(kBlock) void grad_rows_group(RowArgs a, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
     const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const uint64_t i64 = gid >> lanes_log2;
     const uint32_t lg = (uint32_t)gid & (lanes - 1);
-    if (i64 >= a.n || lg >= chunks) return;
+    if (i64 >= a.n || (KIND != RES_ROWWISE && lg >= chunks)) return;
     const uint32_t i = (uint32_t)i64;
     const uint32_t row = a.keys[i];
-    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;      // (uniform over the lane group)
+    if (KIND == RES_ROWWISE) {
+        const bool own0 = lg < chunks, own1 = lg + lanes < chunks;        // (own1: beyond dim 256 only, where lanes == 64)
+        float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
+        if (own0) acc0 = walk_piece(a, i, row, lg);
+        if (own1) acc1 = walk_piece(a, i, row, lg + lanes);
+        float v = piece_squares(acc0);                                    // (+0 in a lane without a piece)
+        if (own1) v = adagrad_add(v, piece_squares(acc1));
+        for (uint32_t h = 1; h < lanes; h <<= 1) v = adagrad_add(v, __shfl_xor(v, (int)h));      // the pair tree: the same bits in every lane
+        float s = a.state[row];
+        const float rate = rowwise_step_size(v, a.dim, &s, a.lr, a.eps);
+        if (lg == 0) a.state[row] = s;                                    // (every lane's load of S[r] feeds its own s: it is done before this store issues)
+        if (own0) step_piece<KIND>(a, row, lg, acc0, rate);
+        if (own1) step_piece<KIND>(a, row, lg + lanes, acc1, rate);
+        return;
+    }
     for (uint32_t c = lg; c < chunks; c += lanes) {
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        uint32_t j = i;
-        for (;;) {
-            bool live[kAhead];
-            float4 g[kAhead];
-            float s[kAhead];
-#pragma unroll
-            for (uint32_t k = 0; k < kAhead; k++) {      // the loads of up to kAhead occurrences (a dead slot re-reads the run's first)
-                live[k] = k == 0 || (live[k - 1] && j + k < a.n && a.keys[j + k] == row);
-                const uint32_t p = min(a.vals[live[k] ? j + k : j], a.n - 1u);      // (what the pre-pass wrote lies below these bounds:
-                const uint32_t b = min(a.bagof[p], a.n_bags - 1u);                  //  they are the bounds of the loads all the same)
-                s[k] = coef_of(a, p, b);
-                g[k] = *reinterpret_cast<const float4 *>(a.grad + (uint64_t)b * a.ld + 4u * c);
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < kAhead; k++) {      // the adds, in position order
-                if (live[k]) {
-                    acc.x = add_in_order(acc.x, contribution(a.coef, g[k].x, s[k]));
-                    acc.y = add_in_order(acc.y, contribution(a.coef, g[k].y, s[k]));
-                    acc.z = add_in_order(acc.z, contribution(a.coef, g[k].z, s[k]));
-                    acc.w = add_in_order(acc.w, contribution(a.coef, g[k].w, s[k]));
-                }
-            }
-            if (!live[kAhead - 1]) break;
-            j += kAhead;
-            if (j >= a.n || a.keys[j] != row) break;
-        }
-        if (!SGD) {
+        const float4 acc = walk_piece(a, i, row, c);
+        if (KIND == RES_SPARSE) {
             const uint32_t u = a.uidx[i] + a.usums[i / kTile];
             if (c == 0) a.rows_out[u] = (long long)row;
             *reinterpret_cast<float4 *>(a.grads_out + (uint64_t)u * a.dim + 4u * c) = acc;
-        } else if (a.dtype == kStepF32) {
-            float4 *w = reinterpret_cast<float4 *>(a.table + (uint64_t)row * a.stride) + c;
-            float4 v = *w;
-            v.x = step_f32(v.x, acc.x, a.lr);
-            v.y = step_f32(v.y, acc.y, a.lr);
-            v.z = step_f32(v.z, acc.z, a.lr);
-            v.w = step_f32(v.w, acc.w, a.lr);
-            *w = v;
         } else {
-            u32x2 *w = reinterpret_cast<u32x2 *>(a.table + (uint64_t)row * a.stride) + c;
-            const u32x2 v = *w;
-            u32x2 o;
-            o.x = step(a.dtype, v.x & 0xffffu, acc.x, a.lr) | (step(a.dtype, v.x >> 16, acc.y, a.lr) << 16);
-            o.y = step(a.dtype, v.y & 0xffffu, acc.z, a.lr) | (step(a.dtype, v.y >> 16, acc.w, a.lr) << 16);
-            *w = o;
+            step_piece<KIND>(a, row, c, acc, a.lr);
         }
     }
 }
 
-// One thread per (sorted place, element): works where a run starts.
-template <bool SGD>
+// One thread per (sorted place, element): works where a run starts.  (No RES_ROWWISE: no thread here sees a whole row of g.)
+template <int KIND>
 __global__ __launch_bounds__(kBlock) void grad_rows_elem(RowArgs a) {
+    static_assert(KIND != RES_ROWWISE, "the element-wise kernel has no row-wide view of g");
     const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const uint64_t i64 = gid / a.dim;
     const uint32_t c = (uint32_t)(gid - i64 * a.dim);
@@ -368,17 +438,24 @@ __global__ __launch_bounds__(kBlock) void grad_rows_elem(RowArgs a) {
         const uint32_t b = min(a.bagof[p], a.n_bags - 1u);
         acc = add_in_order(acc, contribution(a.coef, a.grad[(uint64_t)b * a.ld + c], coef_of(a, p, b)));
     }
-    if (!SGD) {
+    if (KIND == RES_SPARSE) {
         const uint32_t u = a.uidx[i] + a.usums[i / kTile];
         if (c == 0) a.rows_out[u] = (long long)row;
         a.grads_out[(uint64_t)u * a.dim + c] = acc;
-    } else if (a.dtype == kStepF32) {
+        return;
+    }
+    float *sp = KIND == RES_ADAGRAD ? a.state + (uint64_t)row * a.dim + c : nullptr;
+    float st = KIND == RES_ADAGRAD ? *sp : 0.f;
+    if (a.dtype == kStepF32) {
         float *w = reinterpret_cast<float *>(a.table + (uint64_t)row * a.stride) + c;
-        *w = step_f32(*w, acc, a.lr);
+        if (KIND == RES_ADAGRAD) *w = bits_f32(adagrad_step(kStepF32, f32_bits(*w), acc, &st, a.lr, a.eps));
+        else *w = step_f32(*w, acc, a.lr);
     } else {
         uint16_t *w = reinterpret_cast<uint16_t *>(a.table + (uint64_t)row * a.stride) + c;
-        *w = (uint16_t)step(a.dtype, *w, acc, a.lr);
+        if (KIND == RES_ADAGRAD) *w = (uint16_t)adagrad_step(a.dtype, *w, acc, &st, a.lr, a.eps);
+        else *w = (uint16_t)step(a.dtype, *w, acc, a.lr);
     }
+    if (KIND == RES_ADAGRAD) *sp = st;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
@@ -527,7 +604,7 @@ struct TableShape {
 };
 
 // Everything that can be refused about one descriptor, before anything is enqueued.
-int check_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, bool sgd, const char *who, TableShape *t) {
+int check_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, const char *step /* "an SGD", "an Adagrad"; NULL: no step */, const char *who, TableShape *t) {
     void *rows = nullptr;
     emb_dtype dt;
     if (int rc = emb_table_info(g->e, d.table_id, &rows, &t->nr_rows, &t->dim, &dt)) return fail_engine(rc, who);
@@ -541,11 +618,11 @@ int check_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, bool s
     if (d.pool.per_sample_weights && d.pool.mode != EMB_POOL_SUM) return fail(EMB_ERR_INVALID, "%s: per_sample_weights go with EMB_POOL_SUM only", who);
     if ((d.pool.flags & EMB_POOL_PADDING) && (d.pool.padding_idx < 0 || (uint64_t)d.pool.padding_idx >= t->nr_rows))
         return fail(EMB_ERR_INVALID, "%s: padding_idx %lld lies outside table %u", who, (long long)d.pool.padding_idx, d.table_id);
-    if (sgd) {
+    if (step) {
         if (t->dtype != kF32 && t->dtype != kF16 && t->dtype != kBF16)
             return fail(EMB_ERR_UNSUPPORTED,
-                        "%s: table %u is fp8 or MXFP4: an SGD step in the stored precision mostly rounds away (and an MXFP4 block shares "
-                        "its scale); keep fp32 master rows, take emb_grad_sparse and write rows with emb_rows_update", who, d.table_id);
+                        "%s: table %u is fp8 or MXFP4: %s step in the stored precision mostly rounds away (and an MXFP4 block shares "
+                        "its scale); keep fp32 master rows, take emb_grad_sparse and write rows with emb_rows_update", who, d.table_id, step);
         uint32_t n_hot = 0;
         if (int rc = emb_table_hot_count(g->e, d.table_id, &n_hot)) return fail_engine(rc, who);
         if (n_hot)
@@ -572,8 +649,20 @@ int check_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, bool s
 }
 
 // The pre-pass of one descriptor (n_indices > 0), then the hot kernel: enqueues only.
-int enqueue(emb_grad *g, const emb_grad_desc &d, const TableShape &t, bool idx64, bool sgd, float lr, long long *rows_out, float *grads_out,
+struct StepSpec {
+    int kind = RES_SPARSE;       // ResultKind
+    float lr = 0.f, eps = 0.f;
+    float *state = nullptr;
+};
+
+// Whether a descriptor runs on the lane-group kernel (and, for RES_ROWWISE, whether it runs at all).
+bool group_shape(const emb_grad_desc &d, const TableShape &t) {
+    return t.dim % 4 == 0 && t.dim <= 512 && d.grad_ld % 4 == 0 && (uintptr_t)d.grad % 16 == 0;
+}
+
+int enqueue(emb_grad *g, const emb_grad_desc &d, const TableShape &t, bool idx64, const StepSpec &st, long long *rows_out, float *grads_out,
             unsigned long long *n_unique_dev, hipStream_t s) {
+    const bool step = st.kind != RES_SPARSE;     // (a step of any kind: no unique numbering, no output arrays)
     const uint32_t n = (uint32_t)d.n_indices, B = (uint32_t)d.n_bags, nr = (uint32_t)t.nr_rows;
     const Layout &l = g->lay;
     uint32_t *keys[2] = {reinterpret_cast<uint32_t *>(g->scratch + l.keys[0]), reinterpret_cast<uint32_t *>(g->scratch + l.keys[1])};
@@ -619,11 +708,13 @@ int enqueue(emb_grad *g, const emb_grad_desc &d, const TableShape &t, bool idx64
     a.nr_rows = nr;
     a.dim = t.dim;
     a.coef = mean ? COEF_MEAN : d.pool.per_sample_weights ? COEF_WEIGHTED : COEF_SUM;
-    if (sgd) {
+    if (step) {
         a.table = t.rows;
         a.stride = t.stride;
         a.dtype = t.dtype;
-        a.lr = lr;
+        a.lr = st.lr;
+        a.eps = st.eps;
+        a.state = st.state;
     } else {
         grad_scan_chunks<true><<<dim3(tiles), dim3(kBlock), 0, s>>>(keys[cur], n, nr, uidx, sums);
         grad_scan_sums<<<dim3(1), dim3(kBlock), 0, s>>>(sums, tiles, n_unique_dev);
@@ -633,20 +724,27 @@ int enqueue(emb_grad *g, const emb_grad_desc &d, const TableShape &t, bool idx64
         a.rows_out = rows_out;
         a.grads_out = grads_out;
     }
-    const bool group = t.dim % 4 == 0 && t.dim <= 512 && d.grad_ld % 4 == 0 && (uintptr_t)d.grad % 16 == 0 && (sgd || (uintptr_t)grads_out % 16 == 0);
+    const bool group = group_shape(d, t) && (step || (uintptr_t)grads_out % 16 == 0) && (st.kind != RES_ADAGRAD || (uintptr_t)st.state % 16 == 0);
+    if (st.kind == RES_ROWWISE && !group) return fail(EMB_ERR_UNSUPPORTED, "emb_grad: row-wise Adagrad needs the lane-group shape");      // (checked by the caller)
     if (group) {
         const uint32_t chunks = t.dim / 4;
         uint32_t lanes = (uint32_t)pow2ceil(chunks);
         lanes = lanes > 64 ? 64 : lanes;
         const uint64_t blocks = ((uint64_t)n * lanes + kBlock - 1) / kBlock;
-        if (sgd) grad_rows_group<true><<<dim3((uint32_t)blocks), dim3(kBlock), 0, s>>>(a, lanes, log2of(lanes), chunks);
-        else grad_rows_group<false><<<dim3((uint32_t)blocks), dim3(kBlock), 0, s>>>(a, lanes, log2of(lanes), chunks);
+        const dim3 grid((uint32_t)blocks), block(kBlock);
+        const uint32_t ll = log2of(lanes);
+        if (st.kind == RES_SGD) grad_rows_group<RES_SGD><<<grid, block, 0, s>>>(a, lanes, ll, chunks);
+        else if (st.kind == RES_ADAGRAD) grad_rows_group<RES_ADAGRAD><<<grid, block, 0, s>>>(a, lanes, ll, chunks);
+        else if (st.kind == RES_ROWWISE) grad_rows_group<RES_ROWWISE><<<grid, block, 0, s>>>(a, lanes, ll, chunks);
+        else grad_rows_group<RES_SPARSE><<<grid, block, 0, s>>>(a, lanes, ll, chunks);
     } else {
         const uint64_t blocks = ((uint64_t)n * t.dim + kBlock - 1) / kBlock;
         if (blocks > 0x7fffffffull)
             return fail(EMB_ERR_UNSUPPORTED, "emb_grad: %u indices of dim %u are more elements than one launch of the element-wise kernel takes", n, t.dim);
-        if (sgd) grad_rows_elem<true><<<dim3((uint32_t)blocks), dim3(kBlock), 0, s>>>(a);
-        else grad_rows_elem<false><<<dim3((uint32_t)blocks), dim3(kBlock), 0, s>>>(a);
+        const dim3 grid((uint32_t)blocks), block(kBlock);
+        if (st.kind == RES_SGD) grad_rows_elem<RES_SGD><<<grid, block, 0, s>>>(a);
+        else if (st.kind == RES_ADAGRAD) grad_rows_elem<RES_ADAGRAD><<<grid, block, 0, s>>>(a);
+        else grad_rows_elem<RES_SPARSE><<<grid, block, 0, s>>>(a);
     }
     GRAD_HIP(hipGetLastError());
     return EMB_OK;
@@ -662,7 +760,7 @@ int emb_grad_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype
     if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "emb_grad_sparse: bad index type");
     if (!n_unique_dev || (uintptr_t)n_unique_dev % 8) return fail(EMB_ERR_INVALID, "emb_grad_sparse: n_unique_dev is NULL or not 8-byte aligned");
     TableShape t{};
-    if (int rc = check_desc(g, *desc, itype, false, "emb_grad_sparse", &t)) return rc;
+    if (int rc = check_desc(g, *desc, itype, nullptr, "emb_grad_sparse", &t)) return rc;
     if (capacity < desc->n_indices)
         return fail(EMB_ERR_INVALID, "emb_grad_sparse: room for %llu rows, %llu indices may name as many", (unsigned long long)capacity,
                     (unsigned long long)desc->n_indices);
@@ -674,7 +772,7 @@ int emb_grad_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype
     }
     if (!rows_out || !grads_out || (uintptr_t)rows_out % 8 || (uintptr_t)grads_out % 4)
         return fail(EMB_ERR_INVALID, "emb_grad_sparse: rows_out or grads_out is NULL or not naturally aligned");
-    return enqueue(g, *desc, t, itype == EMB_IDX_I64, false, 0.f, reinterpret_cast<long long *>(rows_out), grads_out,
+    return enqueue(g, *desc, t, itype == EMB_IDX_I64, StepSpec{}, reinterpret_cast<long long *>(rows_out), grads_out,
                    reinterpret_cast<unsigned long long *>(n_unique_dev), s);
 }
 
@@ -684,13 +782,60 @@ int emb_grad_sgd(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_
     if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "emb_grad_sgd: bad index type");
     TableShape t{};
     for (uint32_t k = 0; k < n_descs; k++)
-        if (int rc = check_desc(g, descs[k], itype, true, "emb_grad_sgd", &t)) return rc;
+        if (int rc = check_desc(g, descs[k], itype, "an SGD", "emb_grad_sgd", &t)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(g->device);
     for (uint32_t k = 0; k < n_descs; k++) {
         if (descs[k].n_indices == 0) continue;
-        if (int rc = check_desc(g, descs[k], itype, true, "emb_grad_sgd", &t)) return rc;      // (again, for the shape: cheap)
-        if (int rc = enqueue(g, descs[k], t, itype == EMB_IDX_I64, true, lr, nullptr, nullptr, nullptr, s)) return rc;
+        if (int rc = check_desc(g, descs[k], itype, "an SGD", "emb_grad_sgd", &t)) return rc;      // (again, for the shape: cheap)
+        StepSpec st;
+        st.kind = RES_SGD;
+        st.lr = lr;
+        if (int rc = enqueue(g, descs[k], t, itype == EMB_IDX_I64, st, nullptr, nullptr, nullptr, s)) return rc;
+    }
+    return EMB_OK;
+}
+
+uint64_t emb_opt_state_floats(uint32_t kind, uint64_t nr_rows, uint32_t dim) {
+    if (kind == EMB_OPT_ADAGRAD) return nr_rows * dim;
+    if (kind == EMB_OPT_ROWWISE_ADAGRAD) return nr_rows;
+    return 0;
+}
+
+int emb_grad_step(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype, const emb_opt_spec *opt,
+                  void *stream) {
+    const char *who = "emb_grad_step";
+    if (!opt) return fail(EMB_ERR_INVALID, "%s: the optimizer spec is NULL", who);
+    if (opt->kind != EMB_OPT_ADAGRAD && opt->kind != EMB_OPT_ROWWISE_ADAGRAD) return fail(EMB_ERR_INVALID, "%s: unknown optimizer kind %u", who, opt->kind);
+    if (opt->reserved != 0) return fail(EMB_ERR_INVALID, "%s: the spec's reserved field must be 0, got %u", who, opt->reserved);
+    if (!(opt->eps >= 0.f)) return fail(EMB_ERR_INVALID, "%s: eps must not be negative or NaN, got %g", who, (double)opt->eps);
+    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
+    if (n_descs && (!descs || !states)) return fail(EMB_ERR_INVALID, "%s: descs or states is NULL", who);
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    const bool rowwise = opt->kind == EMB_OPT_ROWWISE_ADAGRAD;
+    TableShape t{};
+    for (uint32_t k = 0; k < n_descs; k++) {
+        if (int rc = check_desc(g, descs[k], itype, "an Adagrad", who, &t)) return rc;
+        if (descs[k].n_indices == 0) continue;
+        if (!states[k] || (uintptr_t)states[k] % 4)
+            return fail(EMB_ERR_INVALID, "%s: the state of table %u is NULL or not 4-byte aligned", who, descs[k].table_id);
+        if (rowwise && !group_shape(descs[k], t))
+            return fail(EMB_ERR_UNSUPPORTED,
+                        "%s: row-wise Adagrad needs the lane-group shape (dim %% 4 == 0, dim <= 512, grad 16-byte aligned, grad_ld %% 4 == 0): table %u "
+                        "has dim %u, grad %p, grad_ld %llu -- the element-wise kernel has no row-wide view of g", who, descs[k].table_id, t.dim,
+                        (const void *)descs[k].grad, (unsigned long long)descs[k].grad_ld);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    for (uint32_t k = 0; k < n_descs; k++) {
+        if (descs[k].n_indices == 0) continue;
+        if (int rc = check_desc(g, descs[k], itype, "an Adagrad", who, &t)) return rc;      // (again, for the shape: cheap)
+        StepSpec st;
+        st.kind = rowwise ? RES_ROWWISE : RES_ADAGRAD;
+        st.lr = opt->lr;
+        st.eps = opt->eps;
+        st.state = states[k];
+        if (int rc = enqueue(g, descs[k], t, itype == EMB_IDX_I64, st, nullptr, nullptr, nullptr, s)) return rc;
     }
     return EMB_OK;
 }

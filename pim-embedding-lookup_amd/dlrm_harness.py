@@ -5,8 +5,9 @@ empty submodule here; flags from README.md:6,10,14 and upmem/run.sh:72-82,111-12
 `nn.EmbeddingBag(n_k, m, mode="sum")` called per table with (indices_k, offsets_k), each returning
 [B, m].  Here all tables are served by ONE fused HIP launch.  Inference by default (as the reference's
 `--inference-only` runs); `--fused-sgd LR` trains the tables: apply_emb's result is attached to the autograd graph and
-loss.backward() applies the fused SGD step of the backward pass (include/pimemb_grad.h) to the served tables.  No MLPs -- the
-rest of the model is out of scope.
+loss.backward() applies the fused SGD step of the backward pass (include/pimemb_grad.h) to the served tables;
+`--fused-adagrad LR` / `--fused-rowwise-adagrad LR` do the same with the fused Adagrad / row-wise Adagrad step (the three are
+mutually exclusive).  No MLPs -- the rest of the model is out of scope.
 
     python -m pim_embedding_lookup_amd.dlrm_harness --arch-sparse-feature-size=16 \
         --arch-embedding-size=1460-583-10131227-… --mini-batch-size=39292 --inference-only
@@ -80,6 +81,7 @@ class EmbeddingBagCollection:
         self._plans = {}
         self._ids = list(range(len(self.ln_emb)))
         self._fused_lr = None
+        self._fused_adagrad, self.adagrad_sum = None, None      # (lr, eps, rowwise) and the per-table fp32 states of enable_fused_adagrad
         # DLRM --weighted-pooling: v_W_l[k] is a weight per ROW of table k (ones for "fixed", the checkpoint's for "learned");
         # a bag entry is weighted by its row's weight, gathered with torch (dlrm_s_pytorch.py: v_W_l[k].gather(0, indices))
         if weighted_pooling not in (None, "fixed", "learned"):
@@ -120,7 +122,7 @@ class EmbeddingBagCollection:
             raise ValueError("out= / col= need concat=True")
         if concat and self._out is not None:
             raise ValueError('concat=True returns one fp32 tensor: it does not combine with out_dtype="weight"')
-        if self._fused_lr is not None:
+        if self._fused_lr is not None or self._fused_adagrad is not None:
             return self._apply_emb_fused_sgd(lS_o, lS_i, check, concat, out, col)
         if self.v_W_l is not None:
             return self._apply_emb_weighted(lS_o, lS_i, check, concat, out, col)
@@ -148,6 +150,21 @@ class EmbeddingBagCollection:
         graph whose backward applies W -= lr * grad to the served tables (GradContext.sgd_step): loss.backward() is the tables'
         whole training step.  lr=None switches it off.  The per-row pooling weights of --weighted-pooling are not trained."""
         self._fused_lr = None if lr is None else float(lr)
+        self._fused_adagrad = None
+        return self
+
+    def enable_fused_adagrad(self, lr, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0):
+        """As enable_fused_sgd, with the fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row;
+        GradContext.adagrad_step).  The fp32 states -- self.adagrad_sum, one tensor per table -- are allocated here, once per
+        flavour, filled with initial_accumulator_value.  lr=None switches it off.  Switches a fused SGD off."""
+        import torch
+        if lr is None:
+            self._fused_adagrad = None
+            return self
+        if self.adagrad_sum is None or (self.adagrad_sum[0].dim() == 1) != bool(rowwise):
+            shape = lambda n: (n,) if rowwise else (n, self.m)  # noqa: E731
+            self.adagrad_sum = [torch.full(shape(int(n)), float(initial_accumulator_value), dtype=torch.float32, device=self.device) for n in self.ln_emb]
+        self._fused_adagrad, self._fused_lr = (float(lr), float(eps), bool(rowwise)), None
         return self
 
     def _apply_emb_fused_sgd(self, lS_o, lS_i, check, concat, out, col):
@@ -158,7 +175,7 @@ class EmbeddingBagCollection:
         if self.v_W_l is not None and check:
             self.validate(lS_o, lS_i)
         ws = None if self.v_W_l is None else [v.gather(0, i.long()) for v, i in zip(self.v_W_l, lS_i)]
-        lr = self._fused_lr
+        lr, ada = self._fused_lr, self._fused_adagrad
 
         def lookup():
             if concat:
@@ -173,8 +190,12 @@ class EmbeddingBagCollection:
                 grads = [None if x is None else tm._grad_view(x, self.m) for x in g]
             live = [k for k, x in enumerate(grads) if x is not None]
             ctx = tm._grad_context(self.engine, max(i.shape[0] for i in lS_i), max(o.shape[0] for o in lS_o))
-            ctx.sgd_step([self._ids[k] for k in live], [lS_i[k] for k in live], [lS_o[k] for k in live], [grads[k] for k in live], lr,
-                         per_sample_weights=[None if ws is None else ws[k] for k in live])
+            args = ([self._ids[k] for k in live], [lS_i[k] for k in live], [lS_o[k] for k in live], [grads[k] for k in live])
+            w_live = [None if ws is None else ws[k] for k in live]
+            if ada is None:
+                ctx.sgd_step(*args, lr, per_sample_weights=w_live)
+            else:
+                ctx.adagrad_step(*args, [self.adagrad_sum[k] for k in live], ada[0], eps=ada[1], rowwise=ada[2], per_sample_weights=w_live)
         return tm._FusedSGD.apply(tm._anchor(self, self.device), lookup, step)
 
     def validate(self, lS_o, lS_i) -> None:
@@ -339,11 +360,20 @@ def main(argv=None):
     ap.add_argument("--fused-sgd", type=float, default=None, metavar="LR",
                     help="train the tables: apply_emb's result joins the autograd graph, and the backward of a dummy loss (the sum of "
                          "the pooled rows) applies W -= LR * grad to the served tables on the GPU (include/pimemb_grad.h)")
+    ap.add_argument("--fused-adagrad", type=float, default=None, metavar="LR",
+                    help="as --fused-sgd, with the fused Adagrad step (eps 1e-10, fp32 state of the tables' shape)")
+    ap.add_argument("--fused-rowwise-adagrad", type=float, default=None, metavar="LR",
+                    help="as --fused-sgd, with the fused row-wise Adagrad step (one fp32 accumulator per row; feature size a multiple of 4)")
     args, ignored = ap.parse_known_args(argv)
     if ignored:   # MLP / training / logging flags of the reference command lines (README.md:6,10,14)
         print("ignored (outside the embedding path):", " ".join(ignored))
-    if not args.inference_only and args.fused_sgd is None:
-        print("note: running the inference embedding path (--inference-only implied); --fused-sgd LR trains the tables")
+    fused = [(name, lr) for name, lr in (("SGD", args.fused_sgd), ("Adagrad", args.fused_adagrad), ("row-wise Adagrad", args.fused_rowwise_adagrad))
+             if lr is not None]
+    if len(fused) > 1:
+        raise SystemExit("--fused-sgd, --fused-adagrad and --fused-rowwise-adagrad are mutually exclusive")
+    if not args.inference_only and not fused:
+        print("note: running the inference embedding path (--inference-only implied); --fused-sgd LR / --fused-adagrad LR / "
+              "--fused-rowwise-adagrad LR train the tables")
     import torch
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(args.numpy_rand_seed)
@@ -385,8 +415,12 @@ def main(argv=None):
     n_bags = int(ly.shape[0]) * len(ebc.ln_emb) if cat else sum(int(x.shape[0]) for x in ly)
     print(f"apply_emb{' (one [B, T * m] tensor)' if cat else ''}: {len(ebc.ln_emb)} tables, m={ebc.m}, batch {B}: {dt * 1e3:.4f} ms/batch, "
           f"{n_bags / dt:.3e} pooled lookups/s")
-    if args.fused_sgd is not None:      # forward + dummy loss + backward = lookup + fused SGD step on every table
-        ebc.enable_fused_sgd(args.fused_sgd)
+    if fused:      # forward + dummy loss + backward = lookup + the fused step on every table
+        opt_name, opt_lr = fused[0]
+        if opt_name == "SGD":
+            ebc.enable_fused_sgd(opt_lr)
+        else:
+            ebc.enable_fused_adagrad(opt_lr, rowwise=opt_name != "Adagrad")
 
         def train_step(o, i):
             ly = ebc.apply_emb(o, i, concat=cat)
@@ -399,7 +433,7 @@ def main(argv=None):
             train_step(*batches[b % len(batches)])
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.num_batches
-        print(f"apply_emb + loss.backward() with the fused SGD step (lr {args.fused_sgd}): {dt * 1e3:.4f} ms/batch")
+        print(f"apply_emb + loss.backward() with the fused {opt_name} step (lr {opt_lr}): {dt * 1e3:.4f} ms/batch")
         ebc.close()
         return 0
     if ebc.v_W_l is not None:     # (prepared plans hold the sum path only)

@@ -500,6 +500,67 @@ class GradContext:
                 if isinstance(b, DeviceBuffer):
                     b.free()
 
+    def state_shape(self, table: int, rowwise: bool = False) -> tuple:
+        """The shape of the fp32 optimizer state adagrad_step keeps for `table`: (nr_rows, dim), or (nr_rows,) row-wise."""
+        _ptr, n, dim, _dt = self.engine.table_info(table)
+        shape = (n,) if rowwise else (n, dim)
+        want = self._G.emb_opt_state_floats(_l.EMB_OPT_ROWWISE_ADAGRAD if rowwise else _l.EMB_OPT_ADAGRAD, n, dim)
+        assert want == int(np.prod(shape, dtype=np.uint64)), (want, shape)
+        return shape
+
+    def adagrad_step(self, table_ids, indices, offsets, grads, states, lr: float, eps: float = 1e-10, rowwise: bool = False, modes="sum",
+                     per_sample_weights=None, padding_idx=None, stream: int | None = None, fixed_pooling: int = 0) -> None:
+        """The fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row) of include/pimemb_grad.h, table after
+        table: conventions as sgd_step.  states: one per table, state_shape(table, rowwise) float32 values, read and written in
+        place -- float32 CUDA tensors of that numel (any shape, contiguous) with torch inputs; numpy float32 arrays with numpy
+        inputs, copied to the device and back into the very arrays.  The caller initialises them (zeros, or torch's
+        initial_accumulator_value)."""
+        n = len(table_ids)
+        if len(states) != n:
+            raise ValueError(f"{len(states)} states for {n} tables")
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n  # noqa: E731
+        modes, ws, pads = per(modes), per(per_sample_weights), per(padding_idx)
+        arr, keep, itypes, devs = (_l.EmbGradDesc * max(n, 1))(), [], set(), set()
+        for k in range(n):
+            it, dev = self._desc(arr[k], table_ids[k], indices[k], None if offsets is None else offsets[k], grads[k], modes[k], ws[k], pads[k],
+                                 fixed_pooling, keep)
+            itypes.add(it)
+            devs.add(dev)
+        if len(itypes) > 1 or len(devs) > 1:
+            raise TypeError("the tables of one call share one index width and one memory space")
+        dev = bool(devs and devs.pop())
+        if stream is None and dev:
+            stream = _current_stream_for(*indices)
+        ptrs, back = (C.c_void_p * max(n, 1))(), []
+        try:
+            for k in range(n):
+                want = int(np.prod(self.state_shape(table_ids[k], rowwise)))
+                st = states[k]
+                if st is None:
+                    ptrs[k] = None
+                elif dev:
+                    import torch
+                    if not (_is_torch(st) and st.is_cuda) or st.dtype != torch.float32 or not st.is_contiguous() or st.numel() != want:
+                        raise TypeError(f"state {k} must be a contiguous float32 CUDA tensor of {want} values")
+                    ptrs[k] = st.data_ptr()
+                else:
+                    if not isinstance(st, np.ndarray) or st.dtype != np.float32 or st.size != want or not st.flags.c_contiguous or not st.flags.writeable:
+                        raise TypeError(f"state {k} must be a writeable C-contiguous float32 numpy array of {want} values")
+                    buf = DeviceBuffer.from_numpy(self.engine, st)
+                    keep.append(buf)
+                    back.append((st, buf))
+                    ptrs[k] = buf.ptr
+            spec = _l.EmbOptSpec(_l.EMB_OPT_ROWWISE_ADAGRAD if rowwise else _l.EMB_OPT_ADAGRAD, float(lr), float(eps), 0)
+            _l.check_grad(self._G.emb_grad_step(self._h, arr, ptrs, n, itypes.pop() if itypes else _l.EMB_IDX_I64, C.byref(spec), stream))
+            if not dev:
+                self.engine.synchronize(stream)
+                for st, buf in back:
+                    st[...] = buf.numpy().reshape(st.shape)
+        finally:
+            for b in keep:
+                if isinstance(b, DeviceBuffer):
+                    b.free()
+
     def report(self) -> int:
         """Positions skipped for an id outside the table since the last report (waits for the device; resets the count)."""
         bad = C.c_uint64()

@@ -218,6 +218,13 @@ class EmbGradDesc(C.Structure):
                 ("pool", EmbPoolSpec)]
 
 
+EMB_OPT_ADAGRAD, EMB_OPT_ROWWISE_ADAGRAD = 1, 2
+
+
+class EmbOptSpec(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("lr", C.c_float), ("eps", C.c_float), ("reserved", C.c_uint32)]
+
+
 # name -> (restype, argtypes); every function declared in include/pimemb_grad.h (libpimemb_grad.so, the backward pass: the third
 # library, with its own code object as well)
 GRAD_SIGNATURES = {
@@ -228,6 +235,8 @@ GRAD_SIGNATURES = {
     "emb_grad_sparse": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.c_int, _vp, _vp, _u64, _vp, _vp]),
     "emb_grad_sgd": (C.c_int, [_vp, C.POINTER(EmbGradDesc), _u32, C.c_int, C.c_float, _vp]),
     "emb_grad_report": (C.c_int, [_vp, C.POINTER(_u64)]),
+    "emb_opt_state_floats": (_u64, [_u32, _u64, _u32]),
+    "emb_grad_step": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbOptSpec), _vp]),
 }
 
 _lib = None

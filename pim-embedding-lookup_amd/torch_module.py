@@ -20,8 +20,10 @@ Training the tables: the Pooling modules have a backward pass on the GPU (libpim
 `sgd_step_(input, offsets, grad_output, lr)` applies weight -= lr * grad in place (fp32 / fp16 / bf16 weights), and after
 `enable_fused_sgd(lr)` forward() returns a tensor attached to the autograd graph whose backward runs that step, as fused-optimizer
 embedding modules do: loss.backward() updates the served table, there is no weight.grad and nothing for an optimizer to do.  Off
-by default: a module on which it was never called returns plain tensors, as before.  Not there: the gradient with respect to
-per_sample_weights, mode "max", optimizers other than SGD, fp8 / MXFP4 weights.  max_norm is not supported by any module.
+by default: a module on which it was never called returns plain tensors, as before.  `enable_fused_adagrad(lr, eps, rowwise,
+initial_accumulator_value)` / `adagrad_step_` are the same with the fused Adagrad or row-wise Adagrad step; the fp32 state is
+`module.adagrad_sum` and, once it exists, `<prefix>adagrad_sum` in state_dict().  Not there: the gradient with respect to
+per_sample_weights, mode "max", momentum / Adam, weight decay, fp8 / MXFP4 weights.  max_norm is not supported by any module.
 
 Output dtype.  By default every module returns fp32 rows, whatever the table holds.  `out_dtype="weight"` makes a module
 with an fp16 / bf16 weight return the weight's dtype, as nn.EmbeddingBag does: the fp32 pooled value rounded once (the
@@ -328,7 +330,9 @@ class PoolingEmbeddingBag(torch.nn.Module):
         def lookup():
             return self.engine.lookup_pooled(self._id_list, [idx], [off], self.mode, per_sample_weights=None if w is None else [w],
                                              padding_idx=self.padding_idx, check=self._check(), out_dtype=self._engine_out)[0]
-        lr = getattr(self, "_fused_lr", None)
+        lr, ada = getattr(self, "_fused_lr", None), getattr(self, "_fused_adagrad", None)
+        if ada is not None:
+            return _FusedSGD.apply(_anchor(self, idx.device), lookup, lambda g: self._adagrad(idx, off, g, ada[0], ada[1], w))
         if lr is None:
             return lookup()
         return _FusedSGD.apply(_anchor(self, idx.device), lookup, lambda g: self._step(idx, off, g, lr, w))
@@ -336,9 +340,29 @@ class PoolingEmbeddingBag(torch.nn.Module):
     def enable_fused_sgd(self, lr: float):
         """From now on forward() returns a tensor attached to the autograd graph, and its backward applies weight -= lr * grad
         to the served table (sgd_step_ with the inputs forward saw): loss.backward() is the whole training step of this table.
-        lr=None switches it off again.  Returns self."""
+        lr=None switches it off again.  Switches a fused Adagrad off (its state stays).  Returns self."""
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
+        object.__setattr__(self, "_fused_adagrad", None)
         return self
+
+    def enable_fused_adagrad(self, lr: float, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0):
+        """As enable_fused_sgd, with the fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row) of
+        include/pimemb_grad.h: torch.optim.Adagrad(lr, eps=eps, initial_accumulator_value=...) without lr_decay and weight_decay.
+        The fp32 state -- module.adagrad_sum, [num_embeddings, embedding_dim] or [num_embeddings] -- is allocated once, filled with
+        initial_accumulator_value, kept over later calls (a change of `rowwise` allocates it anew), and saved by state_dict() as
+        `<prefix>adagrad_sum`.  lr=None switches the step off (the state stays).  Switches a fused SGD off.  Returns self."""
+        if lr is None:
+            object.__setattr__(self, "_fused_adagrad", None)
+            return self
+        _adagrad_state(self, bool(rowwise), float(initial_accumulator_value))
+        object.__setattr__(self, "_fused_adagrad", (float(lr), float(eps)))
+        object.__setattr__(self, "_fused_lr", None)
+        return self
+
+    @property
+    def adagrad_sum(self):
+        """The Adagrad state (float32 CUDA tensor), or None before enable_fused_adagrad / adagrad_step_ made one."""
+        return getattr(self, "_adagrad_sum", None)
 
     def _step(self, idx, off, grad_output, lr, w):
         if grad_output is None:
@@ -346,6 +370,22 @@ class PoolingEmbeddingBag(torch.nn.Module):
         g = _grad_view(grad_output, self.embedding_dim)
         _grad_context(self.engine, idx.shape[0], off.shape[0]).sgd_step(self._id_list, [idx], [off], [g], lr, modes=self.mode,
                                                                         per_sample_weights=w, padding_idx=self.padding_idx)
+
+    def _adagrad(self, idx, off, grad_output, lr, eps, w):
+        if grad_output is None:
+            return
+        g = _grad_view(grad_output, self.embedding_dim)
+        state = _adagrad_state(self)
+        _grad_context(self.engine, idx.shape[0], off.shape[0]).adagrad_step(self._id_list, [idx], [off], [g], [state], lr, eps=eps,
+                                                                            rowwise=state.dim() == 1, modes=self.mode, per_sample_weights=w,
+                                                                            padding_idx=self.padding_idx)
+
+    def adagrad_step_(self, input, offsets, grad_output, lr: float, eps: float = 1e-10, per_sample_weights=None):
+        """One fused Adagrad step on the rows the batch names, in place and in stream order with forward(), on the module's state
+        (adagrad_sum; of the flavour enable_fused_adagrad chose, or element-wise zeros if there is none yet).  Returns self."""
+        idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
+        self._adagrad(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), float(eps), w)
+        return self
 
     def _bags_on_device(self, input, offsets, per_sample_weights):
         dev = torch.device("cuda", self.device_index)
@@ -380,9 +420,28 @@ class PoolingEmbeddingBag(torch.nn.Module):
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         self._table._save_to_state_dict(destination, prefix, keep_vars)
+        if self.adagrad_sum is not None:      # (only a module that has an Adagrad state gains the key)
+            destination[prefix + "adagrad_sum"] = self.adagrad_sum.detach().clone()
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         self._table._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        key = prefix + "adagrad_sum"
+        if key in state_dict:
+            s = state_dict[key]
+            shapes = ((self.num_embeddings, self.embedding_dim), (self.num_embeddings,))
+            if tuple(s.shape) not in shapes:
+                error_msgs.append(f"size mismatch for {key}: an Adagrad state is {shapes[0]} or, row-wise, {shapes[1]}, got {tuple(s.shape)}")
+                return
+            have = self.adagrad_sum
+            if have is not None and have.dim() != s.dim():      # (the state's shape IS the flavour: a silent switch of optimizer otherwise)
+                flavour = lambda t: "row-wise" if t.dim() == 1 else "element-wise"  # noqa: E731
+                error_msgs.append(f"{key}: the checkpoint holds a {flavour(s)} Adagrad state {tuple(s.shape)}, this module has a {flavour(have)} one "
+                                  f"{tuple(have.shape)}; call enable_fused_adagrad(..., rowwise={s.dim() == 1}) before loading")
+                return
+            dev = torch.device("cuda", self.device_index)
+            object.__setattr__(self, "_adagrad_sum", s.detach().to(device=dev, dtype=torch.float32).contiguous().clone())
+        elif self.adagrad_sum is not None and strict:
+            missing_keys.append(key)
 
     def extra_repr(self) -> str:
         return (f"{self.num_embeddings}, {self.embedding_dim}, mode={self.mode!r}, padding_idx={self.padding_idx}, "
@@ -401,6 +460,20 @@ def _grad_context(engine: EmbeddingEngine, n_indices: int, n_bags: int):
             g.close()
         g = engine._module_grad = engine.grad_context(max(_GRAD_INDICES, int(n_indices)), max(_GRAD_INDICES, int(n_bags)))
     return g
+
+
+def _adagrad_state(bag, rowwise=None, init: float = 0.0):
+    """A PoolingEmbeddingBag's Adagrad state, made on first use: float32 [num_embeddings, embedding_dim], or [num_embeddings]
+    row-wise, filled with `init`.  rowwise None: whatever is there (element-wise if nothing is).  A plain attribute, not a
+    buffer: state_dict() lists it through the module's own _save_to_state_dict, and only once it exists."""
+    s = getattr(bag, "_adagrad_sum", None)
+    if s is not None and (rowwise is None or (s.dim() == 1) == rowwise):
+        return s
+    ctx = _grad_context(bag.engine, 1, 1)
+    shape = ctx.state_shape(bag.table_id, bool(rowwise))
+    s = torch.full(shape, float(init), dtype=torch.float32, device=torch.device("cuda", bag.device_index))
+    object.__setattr__(bag, "_adagrad_sum", s)
+    return s
 
 
 def _grad_view(grad_output, dim: int):
@@ -517,7 +590,9 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
                                                  padding_idx=self._pads, check=check)
             return self.engine.lookup_pooled(self._ids, idx, off, self._modes, per_sample_weights=wl, padding_idx=self._pads, check=check,
                                              out_dtype=self._outs)
-        lr = getattr(self, "_fused_lr", None)
+        lr, ada = getattr(self, "_fused_lr", None), getattr(self, "_fused_adagrad", None)
+        if ada is not None:
+            return _FusedSGD.apply(_anchor(self, idx[0].device), lookup, lambda g: self._adagrad(idx, off, g, ada[0], ada[1], wl, col))
         if lr is None:
             return lookup()
         return _FusedSGD.apply(_anchor(self, idx[0].device), lookup, lambda g: self._step(idx, off, g, lr, wl, col))
@@ -528,9 +603,29 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         """As PoolingEmbeddingBag.enable_fused_sgd, for every table of the model: the backward of forward()'s result -- the list,
         or the one [B, sum(m)] tensor of concat=True -- steps all of them.  Returns self."""
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
+        object.__setattr__(self, "_fused_adagrad", None)
         return self
 
-    def _step(self, idx, off, grad_output, lr, ws, col=0):
+    def enable_fused_adagrad(self, lr: float, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0):
+        """As PoolingEmbeddingBag.enable_fused_adagrad, for every table of the model: each bag holds its own state
+        (bags[k].adagrad_sum, saved as `bags.<k>.adagrad_sum`), one call steps them all.  Returns self."""
+        if lr is None:
+            object.__setattr__(self, "_fused_adagrad", None)
+            return self
+        for b in self.bags:
+            _adagrad_state(b, bool(rowwise), float(initial_accumulator_value))
+        object.__setattr__(self, "_fused_adagrad", (float(lr), float(eps)))
+        object.__setattr__(self, "_fused_lr", None)
+        return self
+
+    @property
+    def adagrad_sum(self):
+        """The bags' Adagrad states, in table order (None where a bag has none)."""
+        return [b.adagrad_sum for b in self.bags]
+
+    def _live_grads(self, idx, off, grad_output, ws, col):
+        """What a step of either optimizer is called with: (the backward context, positional arguments, keyword arguments, the
+        tables' numbers in the module list) over the tables that have a gradient, or None when none has."""
         dims = [b.embedding_dim for b in self.bags]
         if isinstance(grad_output, (list, tuple)):
             if len(grad_output) != len(dims):
@@ -546,15 +641,33 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             grads = [g[:, a:a + d] for a, d in zip(at, dims)]
         live = [k for k, g in enumerate(grads) if g is not None]
         if not live:
-            return
+            return None
         ctx = _grad_context(self.engine, max(idx[k].shape[0] for k in live), max(off[k].shape[0] for k in live))
-        ctx.sgd_step([self._ids[k] for k in live], [idx[k] for k in live], [off[k] for k in live], [grads[k] for k in live], lr,
-                     modes=[self._modes[k] for k in live], per_sample_weights=[None if ws is None else ws[k] for k in live],
-                     padding_idx=[self._pads[k] for k in live])
+        args = ([self._ids[k] for k in live], [idx[k] for k in live], [off[k] for k in live], [grads[k] for k in live])
+        kw = dict(modes=[self._modes[k] for k in live], per_sample_weights=[None if ws is None else ws[k] for k in live],
+                  padding_idx=[self._pads[k] for k in live])
+        return ctx, args, kw, live
 
-    def sgd_step_(self, lS_o, lS_i, grad_output, lr: float, lS_w=None):
-        """PoolingEmbeddingBag.sgd_step_ for all tables in one call.  grad_output: a list of [B, m_k] gradients, or the ONE
-        [B, sum(m)] gradient of a concat=True forward, which is read in place (each table's columns through the row stride)."""
+    def _step(self, idx, off, grad_output, lr, ws, col=0):
+        call = self._live_grads(idx, off, grad_output, ws, col)
+        if call is not None:
+            ctx, args, kw, _live = call
+            ctx.sgd_step(*args, lr, **kw)
+
+    def _adagrad(self, idx, off, grad_output, lr, eps, ws, col=0):
+        call = self._live_grads(idx, off, grad_output, ws, col)
+        if call is None:
+            return
+        ctx, args, kw, live = call
+        states = [_adagrad_state(self.bags[k]) for k in live]
+        for rowwise in (False, True):      # (one call per flavour: the bags of a model usually share one)
+            sel = [j for j, s in enumerate(states) if (s.dim() == 1) == rowwise]
+            if sel:
+                pick = lambda v: [v[j] for j in sel]  # noqa: E731
+                ctx.adagrad_step(*[pick(a) for a in args], pick(states), lr, eps=eps, rowwise=rowwise, **{k: pick(v) for k, v in kw.items()})
+
+    def _inputs_on_device(self, lS_o, lS_i, grad_output, lS_w):
+        """The explicit steps' inputs as forward() would hold them: (indices, offsets, weights or None, gradient), on the GPU."""
         dev = torch.device("cuda", self.engine.device)
         idx, off, ws = [], [], []
         for k, (b, i, o) in enumerate(zip(self.bags, lS_i, lS_o)):
@@ -564,7 +677,20 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             ws.append(_weights_for(None if lS_w is None else torch.as_tensor(lS_w[k]).to(dev), b.mode, i))
         if not isinstance(grad_output, (list, tuple)):
             grad_output = torch.as_tensor(grad_output).to(dev)
-        self._step(idx, off, grad_output, float(lr), None if lS_w is None else ws)
+        return idx, off, None if lS_w is None else ws, grad_output
+
+    def sgd_step_(self, lS_o, lS_i, grad_output, lr: float, lS_w=None):
+        """PoolingEmbeddingBag.sgd_step_ for all tables in one call.  grad_output: a list of [B, m_k] gradients, or the ONE
+        [B, sum(m)] gradient of a concat=True forward, which is read in place (each table's columns through the row stride)."""
+        idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
+        self._step(idx, off, g, float(lr), ws)
+        return self
+
+    def adagrad_step_(self, lS_o, lS_i, grad_output, lr: float, eps: float = 1e-10, lS_w=None):
+        """PoolingEmbeddingBag.adagrad_step_ for all tables in one call, on the bags' states; grad_output as sgd_step_ takes it: the
+        ONE [B, sum(m)] gradient of a concat=True forward is read in place."""
+        idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
+        self._adagrad(idx, off, g, float(lr), float(eps), ws)
         return self
 
     def update_rows_(self, table: int, ids, rows):

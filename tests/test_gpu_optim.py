@@ -1,0 +1,527 @@
+"""GPU: the fused Adagrad and row-wise Adagrad steps of the backward pass (emb_grad_step, include/pimemb_grad.h), bit for bit.  The
+reference is tests/optim_ref.py -- the definition as a loop over tests/grad_ref.py's rows, pinned against torch.optim.Adagrad by
+tests/test_optim_cpu.py -- and the inputs are tests/grad_cases.py's batch of about 2 000 positions over 3001 rows (a run of 140,
+singletons, rows 0 and 3000, padding, empty bags, bad ids of both widths).  Every test compares the WHOLE table's bytes and the
+WHOLE state's bits: untouched rows are covered too.  No tolerance anywhere."""
+import ctypes as C
+import os
+import sys
+from importlib import import_module
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import grad_cases as gc  # noqa: E402
+import grad_ref as gr  # noqa: E402
+import optim_ref as orf  # noqa: E402
+import pool_ref  # noqa: E402
+import rows_cases as rc  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+N = gc.NR_ROWS
+F = np.float32
+LR, EPS = F(0.1), F(1e-10)
+CODE = {"f32": 0, "f16": 1, "bf16": 3, "e4m3": 8, "e5m2": 9, "mxfp4": 10}
+
+
+def to_dev(a):
+    a = np.ascontiguousarray(a) if a.flags.writeable else np.array(a)
+    return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(DEV)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=F).view(np.uint32)
+
+
+@pytest.fixture(scope="module")
+def eng(pel):
+    e = pel.EmbeddingEngine(device=0, max_tables=64)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def ctx(eng):
+    c = eng.grad_context(4096, 512)
+    yield c
+    c.close()
+
+
+def load_bytes(eng, t, kind, raw):
+    view = {"f32": np.float32, "f16": np.uint16, "bf16": np.uint16}.get(kind, np.uint8)
+    eng.load_table(t, np.ascontiguousarray(raw).view(view), dtype=CODE[kind])
+
+
+def table_bytes(eng, t):
+    ptr, n, dim, dt = eng.table_info(t)
+    kind = {v: k for k, v in CODE.items()}.get(dt, "fixed32")
+    stride = rc.formats.mxfp4_row_stride(dim) if kind == "mxfp4" else dim * {"f32": 4, "fixed32": 4, "f16": 2, "bf16": 2}.get(kind, 1)
+    out = np.empty((n, stride), dtype=np.uint8)
+    torch.cuda.synchronize()
+    assert eng._L.emb_copy_to_host(eng._h, out.ctypes.data, ptr, out.nbytes) == 0
+    return out
+
+
+def batch_on_device(width, mode_name):
+    mode, weighted, padded = gc.MODES[mode_name]
+    ids, offsets = gc.bad_ids(width)
+    arr = gc.ids_array(ids, width)
+    return to_dev(arr), to_dev(offsets.astype(arr.dtype)), to_dev(gc.weights()) if weighted else None, gc.PAD if padded else None, mode
+
+
+_states = {}
+
+
+def denormal_rows():
+    """The in-table, non-padding rows named by the positions of bags 7 and 8."""
+    ids, offsets, _bad = gc.batch()
+    at = [p for b in (7, 8) for p in range(int(offsets[b]), int(offsets[b + 1]))]
+    return sorted({ids[p] for p in at if 0 <= ids[p] < N and ids[p] not in (gc.PAD, gc.HOT, 3000)})
+
+
+def init_state(dim, rowwise):
+    """The state before a step: random and non-negative over many magnitudes, every fifth row 0, the run of 140 at 0, row 3000 at
+    1e30 -- and fp32 DENORMALS on the rows that occur in bags 7 and 8, whose gradients are denormals (grad_cases.grads): where such a
+    row occurs nowhere else, g * g is 0, S' stays a denormal, and the device takes the square root of a denormal and divides a
+    denormal by it (reference() asserts that this happens)."""
+    key = (dim, rowwise)
+    if key not in _states:
+        rng = np.random.default_rng(900 + dim + rowwise)
+        shape = (N,) if rowwise else (N, dim)
+        s = (np.abs(rng.standard_normal(shape)) * np.exp2(rng.integers(-12, 12, size=(N,) + (1,) * (len(shape) - 1)))).astype(F)
+        s[::5] = 0
+        s[gc.HOT] = 0
+        s[3000] = F(1e30)
+        s[denormal_rows()] = np.array([1, 0x00400000, 0x007FFFFF], np.uint32).view(F)[np.arange(len(denormal_rows())) % 3].reshape((-1,) + (1,) * (len(shape) - 1))
+        s.setflags(write=False)
+        _states[key] = s
+    return _states[key]
+
+
+_wants = {}
+
+
+def reference(kind, dim, mode_name, width, rowwise, overflow=False):
+    """(table bytes, state) after ONE step from gc.step_table / init_state, by optim_ref; once per case."""
+    key = (kind, dim, mode_name, width, rowwise, overflow)
+    if key not in _wants:
+        rows, grads, n_bad = gc.reference(width, mode_name, dim, overflow=overflow)
+        assert n_bad == 5
+        _wants[key] = orf.adagrad_step(kind, gc.step_table(kind, dim), init_state(dim, rowwise), rows, grads, LR, EPS, rowwise=rowwise) + (rows,)
+        after = _wants[key][1][[r for r in denormal_rows() if r in set(rows.tolist())]]
+        assert ((after != 0) & (np.abs(after) < np.finfo(F).tiny)).any(), key      # a stepped row whose new state is a denormal
+    return _wants[key]
+
+
+def check(eng, t, d_state, want_table, want_state, what, nan_at=None):
+    got, got_s = table_bytes(eng, t), d_state.cpu().numpy().reshape(want_state.shape)
+    if nan_at is not None:      # (row, column) whose table value must be NaN in both: compared with isnan, then masked
+        kind, (r, c) = what[0], nan_at
+        esz = want_table.shape[1] // (want_state.shape[1] if want_state.ndim == 2 else what[1])
+        g, w = gr.decode(kind, got[r][None, :])[0], gr.decode(kind, want_table[r][None, :])[0]
+        assert np.isnan(g[c]) and np.isnan(w[c]), (what, g[c], w[c])
+        got, want_table = got.copy(), want_table.copy()
+        got[r, c * esz:(c + 1) * esz] = want_table[r, c * esz:(c + 1) * esz] = 0
+    bad = np.flatnonzero((got != want_table).any(axis=1))
+    assert bad.size == 0, (what, "table", bad[:8], got[bad[0]][:16], want_table[bad[0]][:16])
+    bad = np.flatnonzero((bits(got_s) != bits(want_state)).reshape(N, -1).any(axis=1))
+    assert bad.size == 0, (what, "state", bad[:8], got_s[bad[0]], want_state[bad[0]])
+
+
+def run_case(eng, ctx, kind, dim, mode_name, width, rowwise):
+    idx, off, w, pad, mode = batch_on_device(width, mode_name)
+    want_table, want_state, rows = reference(kind, dim, mode_name, width, rowwise)
+    init, s0 = gc.step_table(kind, dim), init_state(dim, rowwise)
+    changed = np.flatnonzero((bits(want_state) != bits(s0)).reshape(N, -1).any(axis=1))
+    assert len(changed) > len(rows) // 2 and set(changed) <= set(rows.tolist())
+    assert (want_table != init).any() and gc.HOT in rows and 0 in rows and 3000 in rows
+    load_bytes(eng, 2, kind, init)
+    d_state = to_dev(s0)
+    ctx.adagrad_step([2], [idx], [off], [to_dev(gc.grads(dim, overflow=False))], [d_state], LR, eps=EPS, rowwise=rowwise, modes=mode,
+                     per_sample_weights=w, padding_idx=pad)
+    check(eng, 2, d_state, want_table, want_state, (kind, dim, mode_name, width, rowwise))
+    assert ctx.report() == 5
+
+
+# ---- element-wise Adagrad ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("width", ["u32", "i64"])
+@pytest.mark.parametrize("mode_name", ["sum", "weighted+pad", "mean+pad"])
+@pytest.mark.parametrize("dim", [8, 48, 6])            # two lanes; 12 pieces in 16 lanes; the element-wise kernel
+@pytest.mark.parametrize("kind", ["f32", "f16", "bf16"])
+def test_adagrad_equals_the_definition_over_the_whole_table_and_state(eng, ctx, kind, dim, mode_name, width):
+    run_case(eng, ctx, kind, dim, mode_name, width, rowwise=False)
+
+
+# ---- row-wise Adagrad -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode_name", ["sum", "mean+pad"])
+@pytest.mark.parametrize("dim", [4, 8, 48, 256, 320, 512])      # one lane; two; 12 pieces in 16 lanes; a full wavefront; 16 lanes hold two pieces; all do
+@pytest.mark.parametrize("kind", ["f32", "bf16"])
+def test_rowwise_adagrad_equals_the_definition_over_the_whole_table_and_state(eng, ctx, kind, dim, mode_name):
+    run_case(eng, ctx, kind, dim, mode_name, "i64", rowwise=True)
+
+
+# ---- strided and misaligned inputs ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rowwise", [False, True])
+def test_gradient_is_read_in_place_out_of_a_wider_buffer(eng, ctx, rowwise):
+    dim = 8
+    idx, off, w, pad, mode = batch_on_device("i64", "mean+pad")
+    buf = np.full((gc.N_BAGS, 3 * dim), np.nan, dtype=F)                          # a neighbour's column read as gradient would show
+    buf[:, dim:2 * dim] = gc.grads(dim, overflow=False)
+    want_table, want_state, _ = reference("bf16", dim, "mean+pad", "i64", rowwise)
+    load_bytes(eng, 2, "bf16", gc.step_table("bf16", dim))
+    d_state = to_dev(init_state(dim, rowwise))
+    ctx.adagrad_step([2], [idx], [off], [to_dev(buf)[:, dim:2 * dim]], [d_state], LR, eps=EPS, rowwise=rowwise, modes=mode, padding_idx=pad)
+    check(eng, 2, d_state, want_table, want_state, ("bf16", dim, "strided", rowwise))
+    ctx.report()
+
+
+@pytest.mark.parametrize("what", ["grad", "state"])
+@pytest.mark.parametrize("kind", ["f32", "f16"])
+def test_misaligned_grad_or_state_takes_the_elementwise_kernel_with_the_same_bits(eng, ctx, kind, what):
+    """A gradient at column 1 of a [B, 3 * dim + 1] buffer, or a state that starts one float into its allocation: no 16-byte
+    alignment, so Adagrad runs on the element-wise kernel -- and gives what the lane-group kernel gives."""
+    dim = 8
+    idx, off, w, pad, mode = batch_on_device("u32", "weighted+pad")
+    want_table, want_state, _ = reference(kind, dim, "weighted+pad", "u32", False)
+    load_bytes(eng, 2, kind, gc.step_table(kind, dim))
+    G, s0 = gc.grads(dim, overflow=False), init_state(dim, False)
+    if what == "grad":
+        buf = np.full((gc.N_BAGS, 3 * dim + 1), np.nan, dtype=F)
+        buf[:, 1:1 + dim] = G
+        d_G, d_state = to_dev(buf)[:, 1:1 + dim], to_dev(s0)
+        assert d_G.data_ptr() % 16 == 4
+    else:
+        room = torch.full((s0.size + 8,), float("nan"), device=DEV)
+        d_G, d_state = to_dev(G), room[1:1 + s0.size]
+        d_state.copy_(to_dev(s0).reshape(-1))
+        assert d_state.data_ptr() % 16 == 4 and d_state.is_contiguous()
+    ctx.adagrad_step([2], [idx], [off], [d_G], [d_state], LR, eps=EPS, modes=mode, per_sample_weights=w, padding_idx=pad)
+    check(eng, 2, d_state, want_table, want_state, (kind, dim, what))
+    if what == "state":
+        assert torch.isnan(room[0]) and torch.isnan(room[1 + s0.size:]).all()     # nothing written around the state
+    ctx.report()
+
+
+# ---- state persistence ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind,dim,rowwise", [("f32", 48, False), ("bf16", 6, False), ("f32", 320, True), ("bf16", 8, True)])
+def test_two_steps_in_a_row_without_a_host_wait_carry_the_state(eng, ctx, kind, dim, rowwise):
+    idx, off, w, pad, mode = batch_on_device("i64", "sum")
+    t1, s1, _ = reference(kind, dim, "sum", "i64", rowwise)
+    rows2, grads2, _ = gc.reference("i64", "mean+pad", dim, overflow=False)
+    want_table, want_state = orf.adagrad_step(kind, t1, s1, rows2, grads2, LR, EPS, rowwise=rowwise)
+    load_bytes(eng, 2, kind, gc.step_table(kind, dim))
+    d_state, G = to_dev(init_state(dim, rowwise)), to_dev(gc.grads(dim, overflow=False))
+    ctx.adagrad_step([2], [idx], [off], [G], [d_state], LR, eps=EPS, rowwise=rowwise)       # the second reuses the scratch of the first
+    ctx.adagrad_step([2], [idx], [off], [G], [d_state], LR, eps=EPS, rowwise=rowwise, modes="mean", padding_idx=gc.PAD)
+    check(eng, 2, d_state, want_table, want_state, (kind, dim, rowwise, "two steps"))
+    assert ctx.report() == 10
+
+
+@pytest.mark.parametrize("rowwise", [False, True])
+def test_a_lookup_behind_the_step_reads_the_stepped_rows(eng, ctx, rowwise):
+    kind, dim = "bf16", 48
+    idx, off, w, pad, mode = batch_on_device("i64", "sum")
+    init = gc.step_table(kind, dim)
+    new, want_state, rows = reference(kind, dim, "sum", "i64", rowwise)
+    rng = np.random.default_rng(5)
+    lidx = np.concatenate([rows[:300], rng.integers(0, N, size=724)]).astype(np.int64)
+    loff = np.arange(0, len(lidx), 4, dtype=np.int64)
+    want_old = pool_ref.embedding_bag(gr.decode(kind, init), lidx, loff, "sum")
+    want_new = pool_ref.embedding_bag(gr.decode(kind, new), lidx, loff, "sum")
+    assert np.isfinite(want_new).all() and not np.array_equal(bits(want_old), bits(want_new))
+    load_bytes(eng, 2, kind, init)
+    d_lidx, d_loff, G, d_state = to_dev(lidx), to_dev(loff), to_dev(gc.grads(dim, overflow=False)), to_dev(init_state(dim, rowwise))
+    torch.cuda.synchronize()
+    cache, eng.plan_cache_size = eng.plan_cache_size, 0
+    try:
+        first = eng.lookup_pooled([2], [d_lidx], [d_loff], "sum")[0]
+        ctx.adagrad_step([2], [idx], [off], [G], [d_state], LR, eps=EPS, rowwise=rowwise)
+        second = eng.lookup_pooled([2], [d_lidx], [d_loff], "sum")[0]
+    finally:
+        eng.plan_cache_size = cache
+    torch.cuda.synchronize()                                                     # the first host wait
+    assert np.array_equal(bits(first.cpu().numpy()), bits(want_old))
+    assert np.array_equal(bits(second.cpu().numpy()), bits(want_new))
+    check(eng, 2, d_state, new, want_state, (kind, dim, rowwise, "lookup behind"))
+    ctx.report()
+
+
+# ---- overflow ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind,dim,rowwise", [("f32", 8, False), ("bf16", 6, False), ("f32", 8, True), ("bf16", 320, True)])
+def test_a_gradient_that_overflows_gives_nan_in_one_element_and_an_infinite_state(eng, ctx, kind, dim, rowwise):
+    """grads(overflow=True): row 5's g[0] is +inf.  Element-wise: S' = +inf, x = inf / inf = NaN.  Row-wise: the row's S' = +inf,
+    step = 0, and 0 * inf = NaN in column 0 alone (the other columns subtract a zero).  NaN payloads are unspecified: column 0 of
+    row 5 is compared with isnan, everything else bit for bit."""
+    idx, off, w, pad, mode = batch_on_device("i64", "sum")
+    want_table, want_state, rows = reference(kind, dim, "sum", "i64", rowwise, overflow=True)
+    assert np.isposinf(want_state[5] if rowwise else want_state[5, 0])
+    load_bytes(eng, 2, kind, gc.step_table(kind, dim))
+    d_state = to_dev(init_state(dim, rowwise))
+    ctx.adagrad_step([2], [idx], [off], [to_dev(gc.grads(dim, overflow=True))], [d_state], LR, eps=EPS, rowwise=rowwise)
+    got_s = d_state.cpu().numpy()
+    assert np.isposinf(got_s[5] if rowwise else got_s[5, 0])
+    check(eng, 2, d_state, want_table, want_state, (kind, dim, rowwise), nan_at=(5, 0))
+    ctx.report()
+
+
+# ---- refusals: the documented code, and the table and the state unchanged ------------------------------------------------------------
+def test_refusals_leave_the_table_and_the_state_alone(eng, ctx, pel):
+    UNS, INV = pel.lib.EMB_ERR_UNSUPPORTED, pel.lib.EMB_ERR_INVALID
+    idx, off, *_ = batch_on_device("i64", "sum")
+
+    def refused(t, dim, code, text, rowwise=False, grad=None, state="ok", **kw):
+        before = table_bytes(eng, t)
+        s0 = np.abs(np.random.default_rng(t).standard_normal((N,) if rowwise else (N, dim))).astype(F)
+        d_state = to_dev(s0)
+        G = to_dev(gc.grads(dim)) if grad is None else grad
+        with pytest.raises(pel.PimembError) as ei:
+            ctx.adagrad_step([t], [idx], [off], [G], [None if state is None else d_state], LR, rowwise=rowwise, **kw)
+        assert ei.value.code == code and text in str(ei.value), str(ei.value)
+        assert np.array_equal(table_bytes(eng, t), before) and np.array_equal(bits(d_state.cpu().numpy()), bits(s0))
+
+    load_bytes(eng, 6, "f32", gc.step_table("f32", 16))
+    for rowwise in (False, True):
+        eng.set_hot_rows(6, [1, 2, 3])
+        refused(6, 16, UNS, "clear the set", rowwise=rowwise)
+        eng.set_hot_rows(6, [])
+        refused(6, 16, UNS, "EMB_POOL_MAX", rowwise=rowwise, modes="max")
+        refused(6, 16, INV, "state of table 6 is NULL", rowwise=rowwise, state=None)
+        refused(6, 16, INV, "eps must not be negative", rowwise=rowwise, eps=-1e-10)
+        for kind, dim in (("e4m3", 16), ("e5m2", 16), ("mxfp4", 32)):
+            load_bytes(eng, 7, kind, rc.host_encode(kind, np.random.default_rng(2).standard_normal((N, dim)).astype(F)))
+            refused(7, dim, UNS, "fp8 or MXFP4", rowwise=rowwise)
+        eng.load_table(7, np.ones((N, 8), dtype=np.int32))
+        refused(7, 8, UNS, "EMB_FIXED32", rowwise=rowwise)
+    # row-wise Adagrad off the lane-group shape
+    load_bytes(eng, 7, "f32", gc.step_table("f32", 6))
+    refused(7, 6, UNS, "lane-group shape", rowwise=True)
+    buf = torch.zeros((gc.N_BAGS, 33), device=DEV)
+    refused(6, 16, UNS, "lane-group shape", rowwise=True, grad=buf[:, 1:17])      # grad not 16-byte aligned, grad_ld % 4 != 0
+    # an unknown kind and a reserved field, through the raw ABI
+    d, keep = pel.lib.EmbGradDesc(), []
+    G, d_state = to_dev(gc.grads(16)), torch.ones((N, 16), device=DEV)
+    ctx._desc(d, 6, idx, off, G, "sum", None, None, 0, keep)
+    ptrs = (C.c_void_p * 1)(d_state.data_ptr())
+    before = table_bytes(eng, 6)
+    for spec, text in ((pel.lib.EmbOptSpec(7, 0.1, 1e-10, 0), b"unknown optimizer kind 7"), (pel.lib.EmbOptSpec(1, 0.1, 1e-10, 5), b"reserved")):
+        assert ctx._G.emb_grad_step(ctx._h, C.byref(d), ptrs, 1, 1, C.byref(spec), None) == INV and text in ctx._G.emb_grad_last_error()
+    ptrs[0] = d_state.data_ptr() + 2                                              # not 4-byte aligned
+    assert ctx._G.emb_grad_step(ctx._h, C.byref(d), ptrs, 1, 1, C.byref(pel.lib.EmbOptSpec(1, 0.1, 1e-10, 0)), None) == INV
+    # a refused second table keeps the first one unstepped
+    s6, s7 = torch.ones(N, device=DEV), torch.ones(N, device=DEV)
+    with pytest.raises(pel.PimembError) as ei:
+        ctx.adagrad_step([6, 7], [idx, idx], [off, off], [G, to_dev(gc.grads(6))], [s6, s7], LR, rowwise=True)
+    assert ei.value.code == UNS
+    assert np.array_equal(table_bytes(eng, 6), before) and bool((s6 == 1).all()) and bool((s7 == 1).all()) and bool((d_state == 1).all())
+    # ... and the same call on table 6 alone runs
+    s0 = init_state(16, True)
+    d_state = to_dev(s0)
+    ctx.adagrad_step([6], [idx], [off], [G], [d_state], LR, eps=EPS, rowwise=True)
+    rows, grads, _ = gc.reference("i64", "sum", 16)
+    want_table, want_state = orf.adagrad_step("f32", gc.step_table("f32", 16), s0, rows, grads, LR, EPS, rowwise=True)
+    check(eng, 6, d_state, want_table, want_state, ("f32", 16, "after refusals"), nan_at=(5, 0))
+    ctx.report()
+
+
+def test_numpy_states_are_copied_in_and_back(eng, ctx):
+    ids, offsets = gc.bad_ids("u32")
+    for rowwise in (False, True):
+        want_table, want_state, _ = reference("f16", 8, "sum", "u32", rowwise)
+        load_bytes(eng, 2, "f16", gc.step_table("f16", 8))
+        state = np.array(init_state(8, rowwise))
+        assert ctx.state_shape(2, rowwise) == state.shape
+        ctx.adagrad_step([2], [gc.ids_array(ids, "u32")], [offsets], [gc.grads(8, overflow=False)], [state], LR, eps=EPS, rowwise=rowwise)
+        assert np.array_equal(bits(state), bits(want_state)) and np.array_equal(table_bytes(eng, 2), want_table)
+    ctx.report()
+
+
+# ---- the torch surface ------------------------------------------------------------------------------------------------------------
+tm = import_module("pim-embedding-lookup_amd.torch_module")
+ALR = 2.0 ** -6      # a power of two: lr * x is exact, whatever torch fuses
+
+
+def torch_cpu_bag(mode_name, weight=None):
+    mode, weighted, padded = gc.MODES[mode_name]
+    ids, offsets, G, w = gc.exact_batch(padded)
+    weight = exact_weights() if weight is None else weight
+    bag = torch.nn.EmbeddingBag(gc.EXACT_ROWS, 8, mode=mode, sparse=True, padding_idx=gc.PAD if padded else None, _weight=torch.from_numpy(weight.copy()))
+    return bag, torch.from_numpy(ids), torch.from_numpy(offsets), torch.from_numpy(G), torch.from_numpy(w) if weighted else None
+
+
+def exact_weights():
+    """The weights of the module tests: grad_cases' exact table, as in tests/test_gpu_grad.py's module tests."""
+    return gc.exact_table().copy()
+
+
+def our_bag(eng, mode_name, table_id, dtype=torch.float32):
+    mode, _weighted, padded = gc.MODES[mode_name]
+    return tm.PoolingEmbeddingBag(gc.EXACT_ROWS, 8, mode=mode, padding_idx=gc.PAD if padded else None, _weight=torch.from_numpy(exact_weights()),
+                                  engine=eng, table_id=table_id, dtype=dtype)
+
+
+ROUND_SCALES = (3, 4, 12)      # 3^2 = 9, 9 + 4^2 = 5^2, 25 + 12^2 = 13^2
+
+
+@pytest.mark.parametrize("mode_name", ["sum", "weighted", "mean", "sum+pad", "weighted+pad", "mean+pad"])
+def test_three_backward_rounds_equal_torchs_adagrad(eng, mode_name):
+    """W and adagrad_sum after three loss.backward() rounds equal torch.optim.Adagrad's on the CPU (and optim_ref's), bit for bit.
+    The rounds use the exact batch's G scaled by 3, 4 and 12, so that the state after each round is a perfect square -- 9 g^2,
+    25 g^2, 169 g^2, all exact in fp32 (g: small integers over 1, 2, 4 or 8) -- and its square root, 3|g|, 5|g|, 13|g|, is exact.
+    Why: a comparison with torch must not hang on how torch's CPU sqrt rounds an inexact root.  That is not the same on every
+    host: one torch 2.10 build returns 0x1.c0ffb6p+5 for sqrt(3150.0f) on an AMD EPYC 9575F and 0x1.c0ffb8p+5 -- the correctly
+    rounded value (exact: 0x1.c0ffb705...p+5), which numpy and this library's kernels give -- on another CPU.  A square root
+    whose error stays below one ulp returns an exactly representable root exactly, so here every host's torch computes
+    x = g / (k|g| + eps) = +-3/3, +-4/5, +-12/13 by one IEEE division, as the definition does.  How inexact roots round is
+    checked where the reference is correctly rounded by construction: the kernels against optim_ref, over whole tables, above."""
+    ref, ids, offsets, G, w = torch_cpu_bag(mode_name)
+    mode, weighted, padded = gc.MODES[mode_name]
+    want_w, want_s = exact_weights().view(np.uint8).reshape(gc.EXACT_ROWS, -1), np.zeros((gc.EXACT_ROWS, 8), F)
+    opt = torch.optim.Adagrad(ref.parameters(), lr=ALR, eps=1e-10)
+    bag = our_bag(eng, mode_name, 11)
+    assert bag.adagrad_sum is None and list(bag.state_dict()) == ["weight"]
+    assert bag.enable_fused_adagrad(ALR) is bag and tuple(bag.adagrad_sum.shape) == (gc.EXACT_ROWS, 8) and not bag.adagrad_sum.any()
+    d_ids, d_off, d_w = ids.to(DEV), offsets.to(DEV), None if w is None else w.to(DEV)
+    for scale, root in zip(ROUND_SCALES, (3, 5, 13)):
+        opt.zero_grad()
+        (ref(ids, offsets, w) * (G * scale)).sum().backward()
+        opt.step()
+        out = bag(d_ids, d_off, d_w)
+        assert out.requires_grad and tuple(out.shape) == (gc.EXACT_BAGS, 8)
+        (out * (G * scale).to(DEV)).sum().backward()                             # steps the served table and its state
+        rows, grads, _ = gr.sparse_grad(gc.EXACT_ROWS, ids.numpy(), offsets.numpy(), (G * scale).numpy(), mode, None if w is None else w.numpy(),
+                                        gc.PAD if padded else None)
+        want_w, want_s = orf.adagrad_step("f32", want_w, want_s, rows, grads, ALR, EPS)
+        g1 = grads.astype(np.float64) / scale                                    # the premise: the state is (root * g)^2, exactly
+        assert np.array_equal(want_s[rows].astype(np.float64), (root * g1) ** 2) and np.array_equal(np.sqrt(want_s[rows]).astype(np.float64), root * np.abs(g1))
+    ours_w, ours_s, t_w, t_s = bag.weight.cpu().numpy(), bag.adagrad_sum.cpu().numpy(), ref.weight.detach().numpy(), opt.state[ref.weight]["sum"].numpy()
+    print(mode_name, "elements that differ -- from optim_ref: W", int((bits(ours_w) != want_w.view(np.uint32)).sum()), "S", int((bits(ours_s) != bits(want_s)).sum()),
+          "-- from torch: W", int((bits(ours_w) != bits(t_w)).sum()), "S", int((bits(ours_s) != bits(t_s)).sum()))
+    assert np.array_equal(bits(ours_w), want_w.view(np.uint32)) and np.array_equal(bits(ours_s), bits(want_s))
+    assert np.array_equal(bits(ours_w), bits(t_w))
+    assert np.array_equal(bits(ours_s), bits(t_s))
+    assert not np.array_equal(bits(ours_w), bits(exact_weights())) and ours_s.any()
+    assert eng._module_grad.report() == 0
+
+
+def test_initial_accumulator_value_and_the_explicit_step(eng):
+    """One explicit step from initial_accumulator_value = 0.5: W and the state equal optim_ref's, and the state -- 0.5 + g^2, exact --
+    equals torch.optim.Adagrad's on the CPU.  (W is not compared with torch here: sqrt(0.5 + g^2) is inexact, and how torch's CPU
+    sqrt rounds an inexact root depends on the host; see the test above, which compares W with torch on exact roots.)"""
+    ref, ids, offsets, G, _w = torch_cpu_bag("mean")
+    rows, grads, _ = gr.sparse_grad(gc.EXACT_ROWS, ids.numpy(), offsets.numpy(), G.numpy(), "mean")
+    want_w, want_s = orf.adagrad_step("f32", exact_weights().view(np.uint8).reshape(gc.EXACT_ROWS, -1), np.full((gc.EXACT_ROWS, 8), 0.5, F), rows, grads, ALR, EPS)
+    opt = torch.optim.Adagrad(ref.parameters(), lr=ALR, eps=1e-10, initial_accumulator_value=0.5)
+    (ref(ids, offsets) * G).sum().backward()
+    opt.step()
+    bag = our_bag(eng, "mean", 11).enable_fused_adagrad(ALR, initial_accumulator_value=0.5).enable_fused_adagrad(None)
+    assert bag(ids.to(DEV), offsets.to(DEV)).requires_grad is False               # switched off: the state stays
+    assert bool((bag.adagrad_sum == 0.5).all())
+    assert bag.adagrad_step_(ids, offsets, G, ALR) is bag
+    assert np.array_equal(bits(bag.weight.cpu().numpy()), want_w.view(np.uint32)) and np.array_equal(bits(bag.adagrad_sum.cpu().numpy()), bits(want_s))
+    assert np.array_equal(bits(bag.adagrad_sum.cpu().numpy()), bits(opt.state[ref.weight]["sum"].numpy()))
+
+
+def test_fused_module_steps_three_tables_from_one_concat_gradient(eng):
+    names = ["sum", "mean", "sum+pad"]
+    refs = [torch_cpu_bag(m) for m in names]
+    for rowwise in (False, True):
+        fused = tm.FusedPoolingEmbeddingBags([our_bag(eng, m, 12 + k, dtype=torch.float32 if k != 1 else torch.bfloat16) for k, m in enumerate(names)],
+                                             concat=True)
+        lS_i, lS_o = [r[1].to(DEV) for r in refs], [r[2].to(DEV) for r in refs]
+        wide = torch.cat([refs[0][3], refs[1][3] * 2, -refs[2][3]], dim=1)        # ONE [B, 3 * dim] gradient
+        fused.enable_fused_adagrad(0.1, rowwise=rowwise, initial_accumulator_value=0.25)
+        assert [tuple(s.shape) for s in fused.adagrad_sum] == [(gc.EXACT_ROWS,) if rowwise else (gc.EXACT_ROWS, 8)] * 3
+        out = fused(lS_o, lS_i)
+        assert out.requires_grad and tuple(out.shape) == (gc.EXACT_BAGS, 24)
+        (out * wide.to(DEV)).sum().backward()
+        fused.adagrad_step_(lS_o, lS_i, wide.to(DEV), 0.05)                       # ... and the explicit call, on the same states
+        for k, (ref, ids, offsets, _G, _w) in enumerate(refs):
+            g = wide[:, 8 * k:8 * k + 8].numpy()
+            mode, _weighted, padded = gc.MODES[names[k]]
+            rows, grads, _ = gr.sparse_grad(gc.EXACT_ROWS, ids.numpy(), offsets.numpy(), g, mode, None, gc.PAD if padded else None)
+            kind = "bf16" if k == 1 else "f32"
+            want, state = gr.encode(kind, exact_weights()), np.full((gc.EXACT_ROWS,) if rowwise else (gc.EXACT_ROWS, 8), 0.25, F)
+            for lr in (0.1, 0.05):
+                want, state = orf.adagrad_step(kind, want, state, rows, grads, F(lr), EPS, rowwise=rowwise)
+            assert np.array_equal(fused.bags[k].weight.cpu().contiguous().view(torch.uint8).numpy().reshape(gc.EXACT_ROWS, -1), want), (k, rowwise)
+            assert np.array_equal(bits(fused.bags[k].adagrad_sum.cpu().numpy()), bits(state)), (k, rowwise)
+
+
+def test_state_dict_round_trip_restores_adagrad_sum(eng):
+    _ref, ids, offsets, G, _w = torch_cpu_bag("sum")
+    plain = our_bag(eng, "sum", 15)
+    assert list(plain.state_dict()) == ["weight"]                                # never enabled: today's keys exactly
+    bag = our_bag(eng, "sum", 16).enable_fused_adagrad(ALR, rowwise=True)
+    (bag(ids.to(DEV), offsets.to(DEV)) * G.to(DEV)).sum().backward()
+    sd = bag.state_dict()
+    assert list(sd) == ["weight", "adagrad_sum"] and tuple(sd["adagrad_sum"].shape) == (gc.EXACT_ROWS,) and sd["adagrad_sum"].any()
+    sd = {k: v.cpu() for k, v in sd.items()}
+    other = our_bag(eng, "sum", 17).enable_fused_adagrad(ALR, rowwise=True)
+    assert not other.adagrad_sum.any()
+    other.load_state_dict(sd)
+    assert np.array_equal(bits(other.adagrad_sum.cpu().numpy()), bits(sd["adagrad_sum"].numpy()))
+    assert np.array_equal(bits(other.weight.cpu().numpy()), bits(sd["weight"].numpy()))
+    for b in (bag, other):                                                       # and both go on from the same state to the same bits
+        (b(ids.to(DEV), offsets.to(DEV)) * G.to(DEV)).sum().backward()
+    assert np.array_equal(bits(other.weight.cpu().numpy()), bits(bag.weight.cpu().numpy()))
+    assert np.array_equal(bits(other.adagrad_sum.cpu().numpy()), bits(bag.adagrad_sum.cpu().numpy()))
+    wrong = our_bag(eng, "sum", 17).enable_fused_adagrad(ALR)                    # element-wise: the row-wise checkpoint is another optimizer
+    with pytest.raises(RuntimeError, match="row-wise Adagrad state"):
+        wrong.load_state_dict(sd)
+    assert tuple(wrong.adagrad_sum.shape) == (gc.EXACT_ROWS, 8) and not wrong.adagrad_sum.any()
+    fused = tm.FusedPoolingEmbeddingBags([plain, bag])
+    assert list(fused.state_dict()) == ["bags.0.weight", "bags.1.weight", "bags.1.adagrad_sum"]
+    plain.load_state_dict({"weight": sd["weight"]})                              # a checkpoint without the key still loads into a module without a state
+
+
+def test_enabling_one_fused_optimizer_disables_the_other(eng):
+    _ref, ids, offsets, G, _w = torch_cpu_bag("sum")
+    d_ids, d_off, d_G = ids.to(DEV), offsets.to(DEV), G.to(DEV)
+    bag = our_bag(eng, "sum", 18).enable_fused_adagrad(ALR)
+    bag.enable_fused_sgd(0.5)
+    (bag(d_ids, d_off) * d_G).sum().backward()
+    rows, grads, _ = gr.sparse_grad(gc.EXACT_ROWS, ids.numpy(), offsets.numpy(), G.numpy())
+    want = gr.sgd_step("f32", exact_weights().view(np.uint8).reshape(gc.EXACT_ROWS, -1), rows, grads, F(0.5))
+    assert np.array_equal(bag.weight.cpu().contiguous().view(torch.uint8).numpy().reshape(gc.EXACT_ROWS, -1), want)      # the SGD step ran
+    assert not bag.adagrad_sum.any()                                             # ... and the Adagrad state was not touched
+    bag.enable_fused_adagrad(ALR)
+    (bag(d_ids, d_off) * d_G).sum().backward()
+    want, state = orf.adagrad_step("f32", want, np.zeros((gc.EXACT_ROWS, 8), F), rows, grads, F(ALR), EPS)
+    assert np.array_equal(bag.weight.cpu().contiguous().view(torch.uint8).numpy().reshape(gc.EXACT_ROWS, -1), want)
+    assert np.array_equal(bits(bag.adagrad_sum.cpu().numpy()), bits(state))
+    assert bag.enable_fused_adagrad(None)(d_ids, d_off).requires_grad is False
+
+
+@pytest.mark.parametrize("rowwise", [False, True])
+def test_harness_fused_adagrad_steps_its_tables(pel, rowwise):
+    h = import_module("pim-embedding-lookup_amd.dlrm_harness")
+    rng = np.random.default_rng(43)
+    ln_emb, m, B = [257, 583, N], 16, 64
+    weights = [rng.standard_normal((n, m)).astype(F) for n in ln_emb]
+    lS_i = [rng.integers(0, n, size=B * 4) for n in ln_emb]
+    lS_o = [np.arange(0, B * 4, 4) for _ in ln_emb]
+    ebc = h.EmbeddingBagCollection(ln_emb, m, weights=weights).enable_fused_adagrad(0.1, rowwise=rowwise)
+    ly = ebc.apply_emb([torch.from_numpy(o).to(DEV) for o in lS_o], [torch.from_numpy(i).to(DEV) for i in lS_i])
+    sum(y.sum() for y in ly).backward()                                          # the dummy loss: every gradient element is 1
+    for k, n in enumerate(ln_emb):
+        rows, grads, _ = gr.sparse_grad(n, lS_i[k], lS_o[k], np.ones((B, m), F))
+        want, state = orf.adagrad_step("f32", weights[k].view(np.uint8).reshape(n, -1), np.zeros((n,) if rowwise else (n, m), F), rows, grads, F(0.1), EPS,
+                                       rowwise=rowwise)
+        assert np.array_equal(table_bytes(ebc.engine, k), want), k
+        assert np.array_equal(bits(ebc.adagrad_sum[k].cpu().numpy()), bits(state)), k
+    ebc.engine.close()
+
+
+def test_harness_flags_run(pel, capsys):
+    h = import_module("pim-embedding-lookup_amd.dlrm_harness")
+    common = ["--arch-sparse-feature-size=16", "--arch-embedding-size=1000-2000-300", "--mini-batch-size=64", "--num-batches=2", "--num-indices-per-lookup=4"]
+    for flag, name in (("--fused-adagrad", "Adagrad"), ("--fused-rowwise-adagrad", "row-wise Adagrad")):
+        assert h.main(common + [flag, "0.05"]) == 0
+        assert f"with the fused {name} step (lr 0.05)" in capsys.readouterr().out
+    with pytest.raises(SystemExit) as ei:
+        h.main(common + ["--fused-adagrad", "0.05", "--fused-sgd", "0.1"])
+    assert "mutually exclusive" in str(ei.value)
