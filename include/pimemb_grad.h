@@ -50,8 +50,10 @@
  * Out of scope: the gradient with respect to per_sample_weights; max mode; optimizers other than SGD, Adagrad and row-wise
  * Adagrad (no momentum, no Adam), weight decay and lr_decay, optimizer state in anything but fp32; row-wise Adagrad off the
  * lane-group shape (the element-wise kernel has no row-wide view of g, and a second reduction is not built for it:
- * EMB_ERR_UNSUPPORTED); fusing several tables into one launch (emb_grad_sgd / emb_grad_step over several descriptors launch
- * per descriptor); the ranged / sharded paths; NaN ordering and payloads, as everywhere in this library.
+ * EMB_ERR_UNSUPPORTED); a multi-table emb_grad_sparse (it stays single; emb_grad_sgd_multi / emb_grad_step_multi below fuse the
+ * steps of several tables); fusing descriptors of different dim, or of the element-wise shape, into one launch (they run on
+ * their own, as before); splitting long runs (a row that occurs thousands of times is still one chain walked by one lane
+ * group, in the multi-table step as well); the ranged / sharded paths; NaN ordering and payloads, as everywhere in this library.
  *
  * How it runs.  A pre-pass gives every position its bag (binary search in offsets), flags it good / bad / padding, counts cnt
  * per bag for mean, and orders the positions by (row id, position): a stable LSD radix sort over the ceil(log2(nr_rows + 1)) id
@@ -62,6 +64,13 @@
  * multiply / subtract / encode and one vector store of the lane's piece of the table row (16 bytes fp32, 8 bytes fp16 / bf16).
  * Lane-group path: dim % 4 == 0, dim <= 512, grad (and grads_out) 16-byte aligned, grad_ld % 4 == 0; anything else runs an
  * element-wise kernel (one thread per element of a unique row).
+ * emb_grad_sgd and emb_grad_step run that chain once per descriptor.  emb_grad_sgd_multi and emb_grad_step_multi run it once per
+ * GROUP of up to 16 descriptors (the rules are at emb_grad_multi_groups): one classify launch over the concatenated positions
+ * of the group, ONE sort over the composite key (descriptor, row) = key_base[k] + id, key_base being the running sum of the
+ * group's nr_rows, and one launch of the hot kernel, in which a lane group finds its descriptor from the key of its run.  The
+ * sort is stable and the positions are concatenated in descriptor order, so every (descriptor, row) run is in position order
+ * and never merges with another table's: a row's sum is the one of the definition, and the tables and states end with the
+ * bytes the per-descriptor calls leave.  The descriptor records travel as kernel arguments: no copy, no allocation.
  *
  * Speed, measured on MI355X (tools/grad_probe.py, profiles/grad/README.md; one emb_grad_sgd of 2048 bags x 32 indices, dim 128, 4 M
  * rows, device pointers).  Uniform ids: 72 us per step on fp32 and bf16 tables, against 73 / 106 us for torch's sparse
@@ -187,6 +196,44 @@ uint64_t emb_opt_state_floats(uint32_t kind, uint64_t nr_rows, uint32_t dim);
  * is 16-byte aligned as well, the element-wise one otherwise, with the same bits. */
 int emb_grad_step(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype,
                   const emb_opt_spec *opt, void *stream);
+
+/* THE MULTI-TABLE STEPS: emb_grad_sgd / emb_grad_step with one pre-pass and one launch of the hot kernel per GROUP of descriptors
+ * instead of per descriptor.  Same arguments, checks, refusals and error texts; every descriptor and every state is checked before
+ * anything is enqueued; DEVICE pointers only; a pure enqueue on `stream` (no allocation, no copy to or from the host, no host
+ * wait: the records of a group are kernel arguments); the bad-position count is the same.  Every table and every state ends with
+ * exactly the bytes emb_grad_sgd / emb_grad_step leave over the same descriptors.
+ *
+ * Groups.  Descriptors are taken in order; a group is a maximal run of consecutive descriptors -- empty ones (n_indices == 0) are
+ * skipped and do not end a run -- for which all of this holds:
+ *   1. each has the lane-group shape (dim % 4 == 0, dim <= 512, grad 16-byte aligned, grad_ld % 4 == 0; for EMB_OPT_ADAGRAD the
+ *      state 16-byte aligned as well);
+ *   2. all have the same dim;
+ *   3. no table_id occurs twice (a table named twice is stepped twice, in order: the second naming opens a new group);
+ *   4. at most EMB_GRAD_MULTI_MAX descriptors;
+ *   5. the sum of n_indices <= the context's max_indices, the sum of n_bags <= its max_bags (the scratch area is the one
+ *      emb_grad_scratch_bytes states: a group is laid out in it like one descriptor of that many positions and bags);
+ *   6. the sum of nr_rows <= 2^32 - 2: the composite keys and the one key behind them fit in uint32.
+ * A group of one descriptor runs the single-table chain of emb_grad_sgd / emb_grad_step, the element-wise kernel included: a call
+ * that cannot be fused is exactly that call.  A descriptor that exceeds the context on its own is EMB_ERR_INVALID, as there. */
+#define EMB_GRAD_MULTI_MAX 16
+
+typedef struct emb_grad_multi_shape { /* what the grouping looks at: one descriptor and its table */
+    uint32_t table_id;
+    uint32_t dim;
+    uint32_t lane_group; /* 1: rule 1 holds, 0: it does not */
+    uint64_t nr_rows;    /* (8-byte aligned: four bytes of padding before it) */
+    uint64_t n_indices;
+    uint64_t n_bags;
+} emb_grad_multi_shape;
+
+/* How a multi-table call over `shapes` would be split in a context of max_indices / max_bags: group_of[k] (n entries, may be NULL)
+ * receives the number of descriptor k's group, counted from 0 in order, 0xffffffff for an empty descriptor; returns the number of
+ * groups.  A pure host function, no GPU -- and the very function the two calls below split by. */
+uint32_t emb_grad_multi_groups(const emb_grad_multi_shape *shapes, uint32_t n, uint64_t max_indices, uint64_t max_bags, uint32_t *group_of);
+
+int emb_grad_sgd_multi(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream);
+int emb_grad_step_multi(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype,
+                        const emb_opt_spec *opt, void *stream);
 
 /* The number of BAD positions (an id outside the table) skipped since the last report; resets the count.  Waits for the
  * device first, so the count covers every call enqueued so far. */

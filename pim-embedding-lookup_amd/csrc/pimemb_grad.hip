@@ -15,6 +15,11 @@
 //   grad_rows_group     one lane group per unique row, a lane owns 4 consecutive fp32 elements: walks the row's run in position
 //                       order, the 16-byte loads of eight occurrences issued before the first add, the adds in order
 //   grad_rows_elem      any other dim / alignment: one thread per element of a unique row (no row-wise Adagrad)
+// The multi-table step (emb_grad_sgd_multi / emb_grad_step_multi: one pre-pass and one hot launch per group of up to 16 tables):
+//   grad_multi_classify grad_classify over the concatenated positions of a group: a position finds its descriptor, then its bag,
+//                       its class and its key = key_base[descriptor] + row id in that descriptor's terms
+//   grad_multi_rows     grad_rows_group over the runs of the composite keys: a lane group finds its run's descriptor from the
+//                       key and walks the run with that descriptor's pointers -- the same device functions, the same bits
 // The Adagrad tails (csrc/pimemb_grad_optim.h) end the same kernels; the row-wise one sums the row's squares over its lane group
 // with an xor butterfly -- a fixed tree, stated over dim alone in the header: the same bits on every run.
 // Every fp32 operation of the definition is a statement of its own under `fp contract(off)` (and the unit is compiled with
@@ -421,6 +426,144 @@ __global__ __launch_bounds__(kBlock) void grad_rows_group(RowArgs a, uint32_t la
     }
 }
 
+// ---- the multi-table step: one classify and one hot launch for a group of descriptors -------------------------------------------
+
+constexpr uint32_t kMultiMax = EMB_GRAD_MULTI_MAX;
+
+// One descriptor of a group, as the two kernels below need it.  Positions, bags and keys of the group are the descriptors'
+// laid end to end: descriptor k owns positions [pos_base, pos_base + n), cnt[bag_base ...] and keys [key_base, key_base + nr_rows).
+struct MultiDesc {
+    const void *ids;
+    const void *offsets;
+    const float *weights;        // position (of this descriptor) -> w, or NULL
+    const float *grad;
+    uint64_t ld;
+    uint64_t pad_idx;
+    char *table;
+    float *state;
+    uint32_t pos_base, n;
+    uint32_t bag_base, n_bags;
+    uint32_t key_base, nr_rows;
+    uint32_t fixed_pooling;
+    uint32_t pad_on;
+    uint32_t coef;               // CoefMode
+    uint32_t stride;
+    int dtype;
+    uint32_t unused;
+};
+
+// The records of a group travel BY VALUE, as kernel arguments (16 x 112 bytes and a few words: well under the 4 KB a launch takes):
+// the call stays a pure enqueue, with nothing to copy and nothing that must outlive it.  The kernels read them straight from the
+// argument segment, with the descriptor's number as the index (the ISA shows plain loads, no scratch).
+struct MultiArgs {
+    MultiDesc d[kMultiMax];
+    uint32_t k;                  // descriptors in use: 2 .. 16
+    uint32_t n;                  // positions of the group
+    uint32_t key_end;            // the sum of nr_rows: the key of every position that is not good
+    uint32_t dim;
+};
+
+// The classify of a group: one thread per position of the concatenation.  It finds its descriptor among the <= 16 position bases
+// and then does what grad_classify does inside that descriptor: the bag in ITS offsets, good / bad / padding against ITS table,
+// cnt in ITS share of cnt[].  bagof[] holds the bag number inside the descriptor; vals[] the position in the group.
+template <bool IDX64>
+__global__ __launch_bounds__(kBlock) void grad_multi_classify(const MultiArgs m, uint32_t *keys, uint32_t *vals, uint32_t *bagof, uint32_t *cnt,
+                                                              unsigned long long *bad) {
+    const uint64_t p64 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p64 >= m.n) return;
+    const uint32_t pg = (uint32_t)p64;
+    uint32_t k = 0;
+    for (uint32_t j = 1; j < m.k; j++)           // (uniform trip count; the bases ascend)
+        if (m.d[j].pos_base <= pg) k = j;
+    const MultiDesc &d = m.d[k];
+    const uint32_t p = pg - d.pos_base;
+    uint64_t id;
+    bool in_table;
+    if (IDX64) {
+        const long long v = static_cast<const long long *>(d.ids)[p];
+        id = (uint64_t)v;
+        in_table = v >= 0 && id < d.nr_rows;    // compared at full width, against this descriptor's table
+    } else {
+        id = static_cast<const uint32_t *>(d.ids)[p];
+        in_table = id < d.nr_rows;
+    }
+    const uint32_t b = bag_of<IDX64>(d.offsets, d.fixed_pooling, d.n_bags, p);
+    const bool padding = d.pad_on && id == d.pad_idx;
+    uint32_t key = m.key_end;                   // not good: behind every row of every table
+    if (b != kNoBag && !padding) {
+        if (d.coef == COEF_MEAN) atomicAdd(&cnt[d.bag_base + b], 1u);
+        if (in_table) key = d.key_base + (uint32_t)id;
+        else atomicAdd(bad, 1ull);
+    }
+    keys[pg] = key;
+    vals[pg] = pg;
+    bagof[pg] = b;
+}
+
+// The row-wise tail between the run walk and the table stores, in grad_rows_group's order: the row's squares over the lane group
+// (the same pair tree), S[row] stepped and stored by lane 0, the row's step size in every lane.
+__device__ __forceinline__ float rowwise_rate(const RowArgs &a, uint32_t row, uint32_t lg, uint32_t lanes, float4 acc0, float4 acc1, bool own1) {
+    float v = piece_squares(acc0);                                        // (+0 in a lane without a piece)
+    if (own1) v = adagrad_add(v, piece_squares(acc1));
+    for (uint32_t h = 1; h < lanes; h <<= 1) v = adagrad_add(v, __shfl_xor(v, (int)h));
+    float s = a.state[row];
+    const float rate = rowwise_step_size(v, a.dim, &s, a.lr, a.eps);
+    if (lg == 0) a.state[row] = s;
+    return rate;
+}
+
+// The hot kernel of a group: grad_rows_group with the RowArgs of the run's descriptor, found once per run from its key.
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void grad_multi_rows(const MultiArgs m, const uint32_t *keys, const uint32_t *vals, const uint32_t *bagof,
+                                                          const uint32_t *cnt, float lr, float eps, uint32_t lanes, uint32_t lanes_log2,
+                                                          uint32_t chunks) {
+    static_assert(KIND != RES_SPARSE, "the multi-table path steps; emb_grad_sparse stays single");
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= m.n || (KIND != RES_ROWWISE && lg >= chunks)) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t key = keys[i];
+    if (key >= m.key_end || (i > 0 && keys[i - 1] == key)) return;        // (uniform over the lane group)
+    uint32_t k = 0;
+    for (uint32_t j = 1; j < m.k; j++)
+        if (m.d[j].key_base <= key) k = j;
+    const MultiDesc &d = m.d[k];
+    RowArgs a{};
+    a.keys = keys;
+    a.vals = vals;
+    a.bagof = bagof;
+    a.cnt = cnt + d.bag_base;
+    a.weights = d.weights ? d.weights - d.pos_base : nullptr;             // (vals[] hold positions of the group)
+    a.grad = d.grad;
+    a.ld = d.ld;
+    a.n = m.n;
+    a.n_bags = d.n_bags;
+    a.nr_rows = d.nr_rows;
+    a.dim = m.dim;
+    a.coef = d.coef;
+    a.table = d.table;
+    a.stride = d.stride;
+    a.dtype = d.dtype;
+    a.lr = lr;
+    a.state = d.state;
+    a.eps = eps;
+    // from here on grad_rows_group's steps, with the run's key and the row it names apart (that kernel keeps its own text: its
+    // machine code is the one its profile was taken on); every operation on values is in the device functions both call
+    const uint32_t row = key - d.key_base;
+    if (KIND == RES_ROWWISE) {
+        const bool own0 = lg < chunks, own1 = lg + lanes < chunks;
+        float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
+        if (own0) acc0 = walk_piece(a, i, key, lg);
+        if (own1) acc1 = walk_piece(a, i, key, lg + lanes);
+        const float rate = rowwise_rate(a, row, lg, lanes, acc0, acc1, own1);
+        if (own0) step_piece<KIND>(a, row, lg, acc0, rate);
+        if (own1) step_piece<KIND>(a, row, lg + lanes, acc1, rate);
+        return;
+    }
+    for (uint32_t c = lg; c < chunks; c += lanes) step_piece<KIND>(a, row, c, walk_piece(a, i, key, c), a.lr);
+}
+
 // One thread per (sorted place, element): works where a run starts.  (No RES_ROWWISE: no thread here sees a whole row of g.)
 template <int KIND>
 __global__ __launch_bounds__(kBlock) void grad_rows_elem(RowArgs a) {
@@ -750,9 +893,183 @@ int enqueue(emb_grad *g, const emb_grad_desc &d, const TableShape &t, bool idx64
     return EMB_OK;
 }
 
+// One group of 2 .. 16 descriptors (emb_grad_multi_groups made it: lane-group shape, one dim, the sums within the context and
+// below 2^32 - 1 keys): the records, then classify, ONE sort over the composite keys, one hot launch.  Enqueues only.
+int enqueue_group(emb_grad *g, const emb_grad_desc *descs, float *const *states, const TableShape *shapes, const uint32_t *members, uint32_t k,
+                  bool idx64, const StepSpec &st, hipStream_t s) {
+    MultiArgs m{};
+    uint64_t pos = 0, bags = 0, keys_end = 0;
+    bool mean = false;
+    for (uint32_t j = 0; j < k; j++) {
+        const emb_grad_desc &d = descs[members[j]];
+        const TableShape &t = shapes[members[j]];
+        MultiDesc &r = m.d[j];
+        const bool pad = (d.pool.flags & EMB_POOL_PADDING) != 0;
+        r.ids = d.indices;
+        r.offsets = d.offsets;
+        r.weights = d.pool.per_sample_weights;
+        r.grad = d.grad;
+        r.ld = d.grad_ld;
+        r.pad_idx = pad ? (uint64_t)d.pool.padding_idx : 0ull;
+        r.table = t.rows;
+        r.state = states ? states[members[j]] : nullptr;
+        r.pos_base = (uint32_t)pos;
+        r.n = (uint32_t)d.n_indices;
+        r.bag_base = (uint32_t)bags;
+        r.n_bags = (uint32_t)d.n_bags;
+        r.key_base = (uint32_t)keys_end;
+        r.nr_rows = (uint32_t)t.nr_rows;
+        r.fixed_pooling = d.fixed_pooling;
+        r.pad_on = pad ? 1u : 0u;
+        r.coef = d.pool.mode == EMB_POOL_MEAN ? COEF_MEAN : d.pool.per_sample_weights ? COEF_WEIGHTED : COEF_SUM;
+        r.stride = t.stride;
+        r.dtype = t.dtype;
+        mean = mean || r.coef == COEF_MEAN;
+        pos += d.n_indices;
+        bags += d.n_bags;
+        keys_end += t.nr_rows;
+    }
+    if (k < 2 || k > kMultiMax || pos > g->max_indices || bags > g->max_bags || keys_end > 0xfffffffeull)
+        return fail(EMB_ERR_INVALID, "emb_grad: a group of %u descriptors, %llu indices, %llu bags and %llu rows does not fit", k, (unsigned long long)pos,
+                    (unsigned long long)bags, (unsigned long long)keys_end);      // (emb_grad_multi_groups keeps these)
+    m.k = k;
+    m.n = (uint32_t)pos;
+    m.key_end = (uint32_t)keys_end;
+    m.dim = shapes[members[0]].dim;
+    const uint32_t n = m.n;
+    const Layout &l = g->lay;
+    uint32_t *keys[2] = {reinterpret_cast<uint32_t *>(g->scratch + l.keys[0]), reinterpret_cast<uint32_t *>(g->scratch + l.keys[1])};
+    uint32_t *vals[2] = {reinterpret_cast<uint32_t *>(g->scratch + l.vals[0]), reinterpret_cast<uint32_t *>(g->scratch + l.vals[1])};
+    uint32_t *bagof = reinterpret_cast<uint32_t *>(g->scratch + l.bagof);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(g->scratch + l.hist), *sums = reinterpret_cast<uint32_t *>(g->scratch + l.sums);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(g->scratch + l.cnt);
+    if (mean && bags) GRAD_HIP(hipMemsetAsync(cnt, 0, (size_t)bags * 4, s));
+    const uint32_t pos_blocks = (n + kBlock - 1) / kBlock;
+    if (idx64) grad_multi_classify<true><<<dim3(pos_blocks), dim3(kBlock), 0, s>>>(m, keys[0], vals[0], bagof, cnt, &g->counters[0]);
+    else grad_multi_classify<false><<<dim3(pos_blocks), dim3(kBlock), 0, s>>>(m, keys[0], vals[0], bagof, cnt, &g->counters[0]);
+    GRAD_HIP(hipGetLastError());
+    uint32_t bits = 0;                           // the keys run up to key_end itself
+    while (bits < 32 && (keys_end >> bits) != 0) bits++;
+    const uint32_t tiles = (uint32_t)tiles_of(n), hist_len = 256u * tiles, hist_chunks = (uint32_t)tiles_of(hist_len);
+    int cur = 0;
+    for (uint32_t shift = 0; shift < bits; shift += 8, cur ^= 1) {
+        grad_sort_count<<<dim3(tiles), dim3(kBlock), 0, s>>>(keys[cur], n, shift, hist, tiles);
+        grad_scan_chunks<false><<<dim3(hist_chunks), dim3(kBlock), 0, s>>>(hist, hist_len, 0u, hist, sums);
+        grad_scan_sums<<<dim3(1), dim3(kBlock), 0, s>>>(sums, hist_chunks, (unsigned long long *)nullptr);
+        grad_sort_scatter<<<dim3(tiles), dim3(kBlock), 0, s>>>(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift, hist, sums, tiles);
+        GRAD_HIP(hipGetLastError());
+    }
+    const uint32_t chunks = m.dim / 4;
+    uint32_t lanes = (uint32_t)pow2ceil(chunks);
+    lanes = lanes > 64 ? 64 : lanes;
+    const uint64_t blocks = ((uint64_t)n * lanes + kBlock - 1) / kBlock;
+    const dim3 grid((uint32_t)blocks), block(kBlock);
+    const uint32_t ll = log2of(lanes);
+    if (st.kind == RES_SGD) grad_multi_rows<RES_SGD><<<grid, block, 0, s>>>(m, keys[cur], vals[cur], bagof, cnt, st.lr, st.eps, lanes, ll, chunks);
+    else if (st.kind == RES_ADAGRAD) grad_multi_rows<RES_ADAGRAD><<<grid, block, 0, s>>>(m, keys[cur], vals[cur], bagof, cnt, st.lr, st.eps, lanes, ll, chunks);
+    else grad_multi_rows<RES_ROWWISE><<<grid, block, 0, s>>>(m, keys[cur], vals[cur], bagof, cnt, st.lr, st.eps, lanes, ll, chunks);
+    GRAD_HIP(hipGetLastError());
+    return EMB_OK;
+}
+
+// What emb_grad_sgd(_multi) and emb_grad_step(_multi) share once their arguments are checked: every descriptor (and state) is
+// checked, then everything is enqueued -- descriptor after descriptor, or group after group (multi).
+int step_call(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype, const StepSpec &spec,
+              const char *step, const char *who, bool multi, void *stream) {
+    const bool rowwise = spec.kind == RES_ROWWISE;
+    TableShape *shapes = n_descs ? new TableShape[n_descs]() : nullptr;
+    struct Free {
+        TableShape *p;
+        ~Free() { delete[] p; }
+    } free_shapes{shapes};
+    for (uint32_t k = 0; k < n_descs; k++) {
+        if (int rc = check_desc(g, descs[k], itype, step, who, &shapes[k])) return rc;
+        if (descs[k].n_indices == 0 || spec.kind == RES_SGD) continue;
+        if (!states[k] || (uintptr_t)states[k] % 4)
+            return fail(EMB_ERR_INVALID, "%s: the state of table %u is NULL or not 4-byte aligned", who, descs[k].table_id);
+        if (rowwise && !group_shape(descs[k], shapes[k]))
+            return fail(EMB_ERR_UNSUPPORTED,
+                        "%s: row-wise Adagrad needs the lane-group shape (dim %% 4 == 0, dim <= 512, grad 16-byte aligned, grad_ld %% 4 == 0): table %u "
+                        "has dim %u, grad %p, grad_ld %llu -- the element-wise kernel has no row-wide view of g", who, descs[k].table_id, shapes[k].dim,
+                        (const void *)descs[k].grad, (unsigned long long)descs[k].grad_ld);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    const bool idx64 = itype == EMB_IDX_I64;
+    auto single = [&](uint32_t k) {
+        StepSpec st = spec;
+        st.state = states ? states[k] : nullptr;
+        return enqueue(g, descs[k], shapes[k], idx64, st, nullptr, nullptr, nullptr, s);
+    };
+    if (!multi) {
+        for (uint32_t k = 0; k < n_descs; k++) {
+            if (descs[k].n_indices == 0) continue;
+            if (int rc = single(k)) return rc;
+        }
+        return EMB_OK;
+    }
+    emb_grad_multi_shape *ms = n_descs ? new emb_grad_multi_shape[n_descs]() : nullptr;
+    uint32_t *group_of = n_descs ? new uint32_t[n_descs]() : nullptr;
+    struct Free2 {
+        emb_grad_multi_shape *a;
+        uint32_t *b;
+        ~Free2() {
+            delete[] a;
+            delete[] b;
+        }
+    } free_groups{ms, group_of};
+    for (uint32_t k = 0; k < n_descs; k++) {
+        const bool lane = group_shape(descs[k], shapes[k]) && (spec.kind != RES_ADAGRAD || (uintptr_t)states[k] % 16 == 0);
+        ms[k] = emb_grad_multi_shape{descs[k].table_id, shapes[k].dim, lane ? 1u : 0u, shapes[k].nr_rows, descs[k].n_indices, descs[k].n_bags};
+    }
+    const uint32_t n_groups = emb_grad_multi_groups(ms, n_descs, g->max_indices, g->max_bags, group_of);
+    uint32_t at = 0;
+    for (uint32_t grp = 0; grp < n_groups; grp++) {
+        uint32_t members[kMultiMax], k = 0;
+        for (; at < n_descs && (group_of[at] == grp || group_of[at] == 0xffffffffu); at++)
+            if (group_of[at] == grp && k < kMultiMax) members[k++] = at;
+        if (k == 1) {
+            if (int rc = single(members[0])) return rc;
+        } else if (int rc = enqueue_group(g, descs, states, shapes, members, k, idx64, spec, s)) {
+            return rc;
+        }
+    }
+    return EMB_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+uint32_t emb_grad_multi_groups(const emb_grad_multi_shape *shapes, uint32_t n, uint64_t max_indices, uint64_t max_bags, uint32_t *group_of) {
+    uint32_t groups = 0, first = 0, members = 0;      // the open group: its number is groups - 1, it began at `first`
+    uint64_t idx = 0, bags = 0, rows = 0;
+    bool open_fusable = false;
+    for (uint32_t k = 0; shapes && k < n; k++) {
+        const emb_grad_multi_shape &c = shapes[k];
+        if (c.n_indices == 0) {
+            if (group_of) group_of[k] = 0xffffffffu;
+            continue;
+        }
+        bool join = members > 0 && open_fusable && c.lane_group && c.dim == shapes[first].dim && members < EMB_GRAD_MULTI_MAX &&
+                    idx + c.n_indices <= max_indices && bags + c.n_bags <= max_bags && rows + c.nr_rows <= 0xfffffffeull;
+        for (uint32_t j = first; join && j < k; j++)
+            if (shapes[j].n_indices != 0 && shapes[j].table_id == c.table_id) join = false;
+        if (!join) {
+            groups++;
+            first = k;
+            members = 0;
+            idx = bags = rows = 0;
+            open_fusable = c.lane_group != 0;
+        }
+        members++;
+        idx += c.n_indices;
+        bags += c.n_bags;
+        rows += c.nr_rows;
+        if (group_of) group_of[k] = groups - 1;
+    }
+    return groups;
+}
 
 int emb_grad_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype, int64_t *rows_out, float *grads_out, uint64_t capacity,
                     uint64_t *n_unique_dev, void *stream) {
@@ -776,24 +1093,48 @@ int emb_grad_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype
                    reinterpret_cast<unsigned long long *>(n_unique_dev), s);
 }
 
+}  // extern "C"
+
+namespace {
+
+int sgd_call(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream, bool multi) {
+    const char *who = multi ? "emb_grad_sgd_multi" : "emb_grad_sgd";
+    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
+    if (n_descs && !descs) return fail(EMB_ERR_INVALID, "%s: descs is NULL", who);
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    StepSpec st;
+    st.kind = RES_SGD;
+    st.lr = lr;
+    return step_call(g, descs, nullptr, n_descs, itype, st, "an SGD", who, multi, stream);
+}
+
+int opt_call(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype, const emb_opt_spec *opt,
+             void *stream, bool multi) {
+    const char *who = multi ? "emb_grad_step_multi" : "emb_grad_step";
+    if (!opt) return fail(EMB_ERR_INVALID, "%s: the optimizer spec is NULL", who);
+    if (opt->kind != EMB_OPT_ADAGRAD && opt->kind != EMB_OPT_ROWWISE_ADAGRAD) return fail(EMB_ERR_INVALID, "%s: unknown optimizer kind %u", who, opt->kind);
+    if (opt->reserved != 0) return fail(EMB_ERR_INVALID, "%s: the spec's reserved field must be 0, got %u", who, opt->reserved);
+    if (!(opt->eps >= 0.f)) return fail(EMB_ERR_INVALID, "%s: eps must not be negative or NaN, got %g", who, (double)opt->eps);
+    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
+    if (n_descs && (!descs || !states)) return fail(EMB_ERR_INVALID, "%s: descs or states is NULL", who);
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    StepSpec st;
+    st.kind = opt->kind == EMB_OPT_ROWWISE_ADAGRAD ? RES_ROWWISE : RES_ADAGRAD;
+    st.lr = opt->lr;
+    st.eps = opt->eps;
+    return step_call(g, descs, states, n_descs, itype, st, "an Adagrad", who, multi, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
 int emb_grad_sgd(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream) {
-    if (!g) return fail(EMB_ERR_INVALID, "emb_grad_sgd: context is NULL");
-    if (n_descs && !descs) return fail(EMB_ERR_INVALID, "emb_grad_sgd: descs is NULL");
-    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "emb_grad_sgd: bad index type");
-    TableShape t{};
-    for (uint32_t k = 0; k < n_descs; k++)
-        if (int rc = check_desc(g, descs[k], itype, "an SGD", "emb_grad_sgd", &t)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DeviceGuard guard(g->device);
-    for (uint32_t k = 0; k < n_descs; k++) {
-        if (descs[k].n_indices == 0) continue;
-        if (int rc = check_desc(g, descs[k], itype, "an SGD", "emb_grad_sgd", &t)) return rc;      // (again, for the shape: cheap)
-        StepSpec st;
-        st.kind = RES_SGD;
-        st.lr = lr;
-        if (int rc = enqueue(g, descs[k], t, itype == EMB_IDX_I64, st, nullptr, nullptr, nullptr, s)) return rc;
-    }
-    return EMB_OK;
+    return sgd_call(g, descs, n_descs, itype, lr, stream, false);
+}
+
+int emb_grad_sgd_multi(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream) {
+    return sgd_call(g, descs, n_descs, itype, lr, stream, true);
 }
 
 uint64_t emb_opt_state_floats(uint32_t kind, uint64_t nr_rows, uint32_t dim) {
@@ -804,40 +1145,12 @@ uint64_t emb_opt_state_floats(uint32_t kind, uint64_t nr_rows, uint32_t dim) {
 
 int emb_grad_step(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype, const emb_opt_spec *opt,
                   void *stream) {
-    const char *who = "emb_grad_step";
-    if (!opt) return fail(EMB_ERR_INVALID, "%s: the optimizer spec is NULL", who);
-    if (opt->kind != EMB_OPT_ADAGRAD && opt->kind != EMB_OPT_ROWWISE_ADAGRAD) return fail(EMB_ERR_INVALID, "%s: unknown optimizer kind %u", who, opt->kind);
-    if (opt->reserved != 0) return fail(EMB_ERR_INVALID, "%s: the spec's reserved field must be 0, got %u", who, opt->reserved);
-    if (!(opt->eps >= 0.f)) return fail(EMB_ERR_INVALID, "%s: eps must not be negative or NaN, got %g", who, (double)opt->eps);
-    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
-    if (n_descs && (!descs || !states)) return fail(EMB_ERR_INVALID, "%s: descs or states is NULL", who);
-    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
-    const bool rowwise = opt->kind == EMB_OPT_ROWWISE_ADAGRAD;
-    TableShape t{};
-    for (uint32_t k = 0; k < n_descs; k++) {
-        if (int rc = check_desc(g, descs[k], itype, "an Adagrad", who, &t)) return rc;
-        if (descs[k].n_indices == 0) continue;
-        if (!states[k] || (uintptr_t)states[k] % 4)
-            return fail(EMB_ERR_INVALID, "%s: the state of table %u is NULL or not 4-byte aligned", who, descs[k].table_id);
-        if (rowwise && !group_shape(descs[k], t))
-            return fail(EMB_ERR_UNSUPPORTED,
-                        "%s: row-wise Adagrad needs the lane-group shape (dim %% 4 == 0, dim <= 512, grad 16-byte aligned, grad_ld %% 4 == 0): table %u "
-                        "has dim %u, grad %p, grad_ld %llu -- the element-wise kernel has no row-wide view of g", who, descs[k].table_id, t.dim,
-                        (const void *)descs[k].grad, (unsigned long long)descs[k].grad_ld);
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DeviceGuard guard(g->device);
-    for (uint32_t k = 0; k < n_descs; k++) {
-        if (descs[k].n_indices == 0) continue;
-        if (int rc = check_desc(g, descs[k], itype, "an Adagrad", who, &t)) return rc;      // (again, for the shape: cheap)
-        StepSpec st;
-        st.kind = rowwise ? RES_ROWWISE : RES_ADAGRAD;
-        st.lr = opt->lr;
-        st.eps = opt->eps;
-        st.state = states[k];
-        if (int rc = enqueue(g, descs[k], t, itype == EMB_IDX_I64, st, nullptr, nullptr, nullptr, s)) return rc;
-    }
-    return EMB_OK;
+    return opt_call(g, descs, states, n_descs, itype, opt, stream, false);
+}
+
+int emb_grad_step_multi(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype,
+                        const emb_opt_spec *opt, void *stream) {
+    return opt_call(g, descs, states, n_descs, itype, opt, stream, true);
 }
 
 int emb_grad_report(emb_grad *g, uint64_t *n_bad) {

@@ -7,7 +7,7 @@ empty submodule here; flags from README.md:6,10,14 and upmem/run.sh:72-82,111-12
 `--inference-only` runs); `--fused-sgd LR` trains the tables: apply_emb's result is attached to the autograd graph and
 loss.backward() applies the fused SGD step of the backward pass (include/pimemb_grad.h) to the served tables;
 `--fused-adagrad LR` / `--fused-rowwise-adagrad LR` do the same with the fused Adagrad / row-wise Adagrad step (the three are
-mutually exclusive).  No MLPs -- the rest of the model is out of scope.
+mutually exclusive; `--multi-table-step` sends them through the multi-table entry points).  No MLPs -- the rest of the model is out of scope.
 
     python -m pim_embedding_lookup_amd.dlrm_harness --arch-sparse-feature-size=16 \
         --arch-embedding-size=1460-583-10131227-… --mini-batch-size=39292 --inference-only
@@ -81,6 +81,7 @@ class EmbeddingBagCollection:
         self._plans = {}
         self._ids = list(range(len(self.ln_emb)))
         self._fused_lr = None
+        self.multi_table_step = False                           # the fused steps go through the multi-table entry points (--multi-table-step)
         self._fused_adagrad, self.adagrad_sum = None, None      # (lr, eps, rowwise) and the per-table fp32 states of enable_fused_adagrad
         # DLRM --weighted-pooling: v_W_l[k] is a weight per ROW of table k (ones for "fixed", the checkpoint's for "learned");
         # a bag entry is weighted by its row's weight, gathered with torch (dlrm_s_pytorch.py: v_W_l[k].gather(0, indices))
@@ -189,13 +190,16 @@ class EmbeddingBagCollection:
             else:
                 grads = [None if x is None else tm._grad_view(x, self.m) for x in g]
             live = [k for k, x in enumerate(grads) if x is not None]
-            ctx = tm._grad_context(self.engine, max(i.shape[0] for i in lS_i), max(o.shape[0] for o in lS_o))
+            multi = bool(self.multi_table_step)      # (its context holds all tables' indices and bags at once)
+            size = sum if multi else max
+            ctx = tm._grad_context(self.engine, size(i.shape[0] for i in lS_i), size(o.shape[0] for o in lS_o))
             args = ([self._ids[k] for k in live], [lS_i[k] for k in live], [lS_o[k] for k in live], [grads[k] for k in live])
             w_live = [None if ws is None else ws[k] for k in live]
             if ada is None:
-                ctx.sgd_step(*args, lr, per_sample_weights=w_live)
+                ctx.sgd_step(*args, lr, per_sample_weights=w_live, multi=multi)
             else:
-                ctx.adagrad_step(*args, [self.adagrad_sum[k] for k in live], ada[0], eps=ada[1], rowwise=ada[2], per_sample_weights=w_live)
+                ctx.adagrad_step(*args, [self.adagrad_sum[k] for k in live], ada[0], eps=ada[1], rowwise=ada[2], per_sample_weights=w_live,
+                                 multi=multi)
         return tm._FusedSGD.apply(tm._anchor(self, self.device), lookup, step)
 
     def validate(self, lS_o, lS_i) -> None:
@@ -364,6 +368,9 @@ def main(argv=None):
                     help="as --fused-sgd, with the fused Adagrad step (eps 1e-10, fp32 state of the tables' shape)")
     ap.add_argument("--fused-rowwise-adagrad", type=float, default=None, metavar="LR",
                     help="as --fused-sgd, with the fused row-wise Adagrad step (one fp32 accumulator per row; feature size a multiple of 4)")
+    ap.add_argument("--multi-table-step", action="store_true",
+                    help="with one of the --fused-* flags: step the tables through the multi-table entry points (one pre-pass and one "
+                         "launch per group of up to 16 tables instead of per table; the same bytes)")
     args, ignored = ap.parse_known_args(argv)
     if ignored:   # MLP / training / logging flags of the reference command lines (README.md:6,10,14)
         print("ignored (outside the embedding path):", " ".join(ignored))
@@ -371,6 +378,8 @@ def main(argv=None):
              if lr is not None]
     if len(fused) > 1:
         raise SystemExit("--fused-sgd, --fused-adagrad and --fused-rowwise-adagrad are mutually exclusive")
+    if args.multi_table_step and not fused:
+        raise SystemExit("--multi-table-step goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
     if not args.inference_only and not fused:
         print("note: running the inference embedding path (--inference-only implied); --fused-sgd LR / --fused-adagrad LR / "
               "--fused-rowwise-adagrad LR train the tables")
@@ -417,6 +426,7 @@ def main(argv=None):
           f"{n_bags / dt:.3e} pooled lookups/s")
     if fused:      # forward + dummy loss + backward = lookup + the fused step on every table
         opt_name, opt_lr = fused[0]
+        ebc.multi_table_step = bool(args.multi_table_step)
         if opt_name == "SGD":
             ebc.enable_fused_sgd(opt_lr)
         else:
@@ -433,7 +443,8 @@ def main(argv=None):
             train_step(*batches[b % len(batches)])
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.num_batches
-        print(f"apply_emb + loss.backward() with the fused {opt_name} step (lr {opt_lr}): {dt * 1e3:.4f} ms/batch")
+        print(f"apply_emb + loss.backward() with the fused {opt_name} step (lr {opt_lr}){', multi-table' if args.multi_table_step else ''}: "
+              f"{dt * 1e3:.4f} ms/batch")
         ebc.close()
         return 0
     if ebc.v_W_l is not None:     # (prepared plans hold the sum path only)

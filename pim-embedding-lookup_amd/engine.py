@@ -471,12 +471,13 @@ class GradContext:
                     b.free()
 
     def sgd_step(self, table_ids, indices, offsets, grads, lr: float, modes="sum", per_sample_weights=None, padding_idx=None,
-                 stream: int | None = None, fixed_pooling: int = 0) -> None:
+                 stream: int | None = None, fixed_pooling: int = 0, multi: bool = False) -> None:
         """W[r] = enc(dec(W[r]) - lr * g[r]) for every row r the batch of its table names, in place, table after table (fp32,
         fp16 and bf16 tables).  table_ids / indices / offsets / grads: one entry per table; modes, per_sample_weights and
         padding_idx one value for all or one per table.  Each gradient is [n_bags, dim], and may be a column view of a wider
         buffer (the [B, T*dim] gradient of a concatenated output is read in place).  Torch CUDA tensors: a pure enqueue on
-        `stream` (torch's current one by default); numpy arrays: copied to the device, and the call waits."""
+        `stream` (torch's current one by default); numpy arrays: copied to the device, and the call waits.  multi=True: the
+        multi-table step (emb_grad_sgd_multi) -- one pre-pass and one launch per group of tables (multi_groups), the same bytes."""
         n = len(table_ids)
         per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n  # noqa: E731
         modes, ws, pads = per(modes), per(per_sample_weights), per(padding_idx)
@@ -492,13 +493,27 @@ class GradContext:
         if stream is None and dev:
             stream = _current_stream_for(*indices)
         try:
-            _l.check_grad(self._G.emb_grad_sgd(self._h, arr, n, itypes.pop() if itypes else _l.EMB_IDX_I64, float(lr), stream))
+            call = self._G.emb_grad_sgd_multi if multi else self._G.emb_grad_sgd
+            _l.check_grad(call(self._h, arr, n, itypes.pop() if itypes else _l.EMB_IDX_I64, float(lr), stream))
             if not dev:
                 self.engine.synchronize(stream)
         finally:
             for b in keep:
                 if isinstance(b, DeviceBuffer):
                     b.free()
+
+    def multi_groups(self, table_ids, n_indices, n_bags, lane_group=True) -> list:
+        """How a multi=True step over these tables would be split in this context (emb_grad_multi_groups): the group number of
+        every entry, None for an empty one.  n_indices / n_bags: one count per table; lane_group: one bool for all or one per
+        table -- whether its gradient (and Adagrad state) has the lane-group shape of include/pimemb_grad.h."""
+        n = len(table_ids)
+        lg = list(lane_group) if isinstance(lane_group, (list, tuple)) else [lane_group] * n
+        shapes, out = (_l.EmbGradMultiShape * max(n, 1))(), (C.c_uint32 * max(n, 1))()
+        for k in range(n):
+            _ptr, rows, dim, _dt = self.engine.table_info(table_ids[k])
+            shapes[k] = _l.EmbGradMultiShape(int(table_ids[k]), dim, int(bool(lg[k])), rows, int(n_indices[k]), int(n_bags[k]))
+        self._G.emb_grad_multi_groups(shapes, n, self.max_indices, self.max_bags, out)
+        return [None if out[k] == _l.EMB_GRAD_NO_GROUP else int(out[k]) for k in range(n)]
 
     def state_shape(self, table: int, rowwise: bool = False) -> tuple:
         """The shape of the fp32 optimizer state adagrad_step keeps for `table`: (nr_rows, dim), or (nr_rows,) row-wise."""
@@ -509,12 +524,12 @@ class GradContext:
         return shape
 
     def adagrad_step(self, table_ids, indices, offsets, grads, states, lr: float, eps: float = 1e-10, rowwise: bool = False, modes="sum",
-                     per_sample_weights=None, padding_idx=None, stream: int | None = None, fixed_pooling: int = 0) -> None:
+                     per_sample_weights=None, padding_idx=None, stream: int | None = None, fixed_pooling: int = 0, multi: bool = False) -> None:
         """The fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row) of include/pimemb_grad.h, table after
         table: conventions as sgd_step.  states: one per table, state_shape(table, rowwise) float32 values, read and written in
         place -- float32 CUDA tensors of that numel (any shape, contiguous) with torch inputs; numpy float32 arrays with numpy
         inputs, copied to the device and back into the very arrays.  The caller initialises them (zeros, or torch's
-        initial_accumulator_value)."""
+        initial_accumulator_value).  multi=True: the multi-table step (emb_grad_step_multi), the same bytes."""
         n = len(table_ids)
         if len(states) != n:
             raise ValueError(f"{len(states)} states for {n} tables")
@@ -551,7 +566,8 @@ class GradContext:
                     back.append((st, buf))
                     ptrs[k] = buf.ptr
             spec = _l.EmbOptSpec(_l.EMB_OPT_ROWWISE_ADAGRAD if rowwise else _l.EMB_OPT_ADAGRAD, float(lr), float(eps), 0)
-            _l.check_grad(self._G.emb_grad_step(self._h, arr, ptrs, n, itypes.pop() if itypes else _l.EMB_IDX_I64, C.byref(spec), stream))
+            call = self._G.emb_grad_step_multi if multi else self._G.emb_grad_step
+            _l.check_grad(call(self._h, arr, ptrs, n, itypes.pop() if itypes else _l.EMB_IDX_I64, C.byref(spec), stream))
             if not dev:
                 self.engine.synchronize(stream)
                 for st, buf in back:

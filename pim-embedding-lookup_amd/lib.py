@@ -225,6 +225,15 @@ class EmbOptSpec(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("lr", C.c_float), ("eps", C.c_float), ("reserved", C.c_uint32)]
 
 
+EMB_GRAD_MULTI_MAX = 16
+EMB_GRAD_NO_GROUP = 0xFFFFFFFF      # emb_grad_multi_groups: an empty descriptor
+
+
+class EmbGradMultiShape(C.Structure):
+    _fields_ = [("table_id", C.c_uint32), ("dim", C.c_uint32), ("lane_group", C.c_uint32), ("nr_rows", C.c_uint64),
+                ("n_indices", C.c_uint64), ("n_bags", C.c_uint64)]
+
+
 # name -> (restype, argtypes); every function declared in include/pimemb_grad.h (libpimemb_grad.so, the backward pass: the third
 # library, with its own code object as well)
 GRAD_SIGNATURES = {
@@ -237,6 +246,9 @@ GRAD_SIGNATURES = {
     "emb_grad_report": (C.c_int, [_vp, C.POINTER(_u64)]),
     "emb_opt_state_floats": (_u64, [_u32, _u64, _u32]),
     "emb_grad_step": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbOptSpec), _vp]),
+    "emb_grad_multi_groups": (_u32, [C.POINTER(EmbGradMultiShape), _u32, _u64, _u64, C.POINTER(_u32)]),
+    "emb_grad_sgd_multi": (C.c_int, [_vp, C.POINTER(EmbGradDesc), _u32, C.c_int, C.c_float, _vp]),
+    "emb_grad_step_multi": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbOptSpec), _vp]),
 }
 
 _lib = None

@@ -599,16 +599,21 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
 
     apply_emb = forward
 
-    def enable_fused_sgd(self, lr: float):
+    def enable_fused_sgd(self, lr: float, multi_table: bool = False):
         """As PoolingEmbeddingBag.enable_fused_sgd, for every table of the model: the backward of forward()'s result -- the list,
-        or the one [B, sum(m)] tensor of concat=True -- steps all of them.  Returns self."""
+        or the one [B, sum(m)] tensor of concat=True -- steps all of them.  multi_table=True: by the multi-table step (one
+        pre-pass and one launch per group of up to 16 tables instead of per table; the same bytes).  Returns self."""
+        object.__setattr__(self, "_fused_multi", bool(multi_table))
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
         object.__setattr__(self, "_fused_adagrad", None)
         return self
 
-    def enable_fused_adagrad(self, lr: float, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0):
+    def enable_fused_adagrad(self, lr: float, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0,
+                             multi_table: bool = False):
         """As PoolingEmbeddingBag.enable_fused_adagrad, for every table of the model: each bag holds its own state
-        (bags[k].adagrad_sum, saved as `bags.<k>.adagrad_sum`), one call steps them all.  Returns self."""
+        (bags[k].adagrad_sum, saved as `bags.<k>.adagrad_sum`), one call steps them all.  multi_table: as enable_fused_sgd.
+        Returns self."""
+        object.__setattr__(self, "_fused_multi", bool(multi_table))
         if lr is None:
             object.__setattr__(self, "_fused_adagrad", None)
             return self
@@ -623,9 +628,10 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         """The bags' Adagrad states, in table order (None where a bag has none)."""
         return [b.adagrad_sum for b in self.bags]
 
-    def _live_grads(self, idx, off, grad_output, ws, col):
+    def _live_grads(self, idx, off, grad_output, ws, col, multi=False):
         """What a step of either optimizer is called with: (the backward context, positional arguments, keyword arguments, the
-        tables' numbers in the module list) over the tables that have a gradient, or None when none has."""
+        tables' numbers in the module list) over the tables that have a gradient, or None when none has.  multi: the context
+        holds the live tables' indices and bags all at once (their sums), so that the multi-table step can fuse them."""
         dims = [b.embedding_dim for b in self.bags]
         if isinstance(grad_output, (list, tuple)):
             if len(grad_output) != len(dims):
@@ -642,20 +648,23 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         live = [k for k, g in enumerate(grads) if g is not None]
         if not live:
             return None
-        ctx = _grad_context(self.engine, max(idx[k].shape[0] for k in live), max(off[k].shape[0] for k in live))
+        size = sum if multi else max
+        ctx = _grad_context(self.engine, size(idx[k].shape[0] for k in live), size(off[k].shape[0] for k in live))
         args = ([self._ids[k] for k in live], [idx[k] for k in live], [off[k] for k in live], [grads[k] for k in live])
         kw = dict(modes=[self._modes[k] for k in live], per_sample_weights=[None if ws is None else ws[k] for k in live],
                   padding_idx=[self._pads[k] for k in live])
         return ctx, args, kw, live
 
-    def _step(self, idx, off, grad_output, lr, ws, col=0):
-        call = self._live_grads(idx, off, grad_output, ws, col)
+    def _step(self, idx, off, grad_output, lr, ws, col=0, multi=None):
+        multi = getattr(self, "_fused_multi", False) if multi is None else bool(multi)
+        call = self._live_grads(idx, off, grad_output, ws, col, multi)
         if call is not None:
             ctx, args, kw, _live = call
-            ctx.sgd_step(*args, lr, **kw)
+            ctx.sgd_step(*args, lr, multi=multi, **kw)
 
-    def _adagrad(self, idx, off, grad_output, lr, eps, ws, col=0):
-        call = self._live_grads(idx, off, grad_output, ws, col)
+    def _adagrad(self, idx, off, grad_output, lr, eps, ws, col=0, multi=None):
+        multi = getattr(self, "_fused_multi", False) if multi is None else bool(multi)
+        call = self._live_grads(idx, off, grad_output, ws, col, multi)
         if call is None:
             return
         ctx, args, kw, live = call
@@ -664,7 +673,8 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             sel = [j for j, s in enumerate(states) if (s.dim() == 1) == rowwise]
             if sel:
                 pick = lambda v: [v[j] for j in sel]  # noqa: E731
-                ctx.adagrad_step(*[pick(a) for a in args], pick(states), lr, eps=eps, rowwise=rowwise, **{k: pick(v) for k, v in kw.items()})
+                ctx.adagrad_step(*[pick(a) for a in args], pick(states), lr, eps=eps, rowwise=rowwise, multi=multi,
+                                 **{k: pick(v) for k, v in kw.items()})
 
     def _inputs_on_device(self, lS_o, lS_i, grad_output, lS_w):
         """The explicit steps' inputs as forward() would hold them: (indices, offsets, weights or None, gradient), on the GPU."""
@@ -679,18 +689,19 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             grad_output = torch.as_tensor(grad_output).to(dev)
         return idx, off, None if lS_w is None else ws, grad_output
 
-    def sgd_step_(self, lS_o, lS_i, grad_output, lr: float, lS_w=None):
+    def sgd_step_(self, lS_o, lS_i, grad_output, lr: float, lS_w=None, multi_table: bool = False):
         """PoolingEmbeddingBag.sgd_step_ for all tables in one call.  grad_output: a list of [B, m_k] gradients, or the ONE
-        [B, sum(m)] gradient of a concat=True forward, which is read in place (each table's columns through the row stride)."""
+        [B, sum(m)] gradient of a concat=True forward, which is read in place (each table's columns through the row stride).
+        multi_table: as enable_fused_sgd."""
         idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
-        self._step(idx, off, g, float(lr), ws)
+        self._step(idx, off, g, float(lr), ws, multi=multi_table)
         return self
 
-    def adagrad_step_(self, lS_o, lS_i, grad_output, lr: float, eps: float = 1e-10, lS_w=None):
+    def adagrad_step_(self, lS_o, lS_i, grad_output, lr: float, eps: float = 1e-10, lS_w=None, multi_table: bool = False):
         """PoolingEmbeddingBag.adagrad_step_ for all tables in one call, on the bags' states; grad_output as sgd_step_ takes it: the
-        ONE [B, sum(m)] gradient of a concat=True forward is read in place."""
+        ONE [B, sum(m)] gradient of a concat=True forward is read in place.  multi_table: as enable_fused_sgd."""
         idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
-        self._adagrad(idx, off, g, float(lr), float(eps), ws)
+        self._adagrad(idx, off, g, float(lr), float(eps), ws, multi=multi_table)
         return self
 
     def update_rows_(self, table: int, ids, rows):
