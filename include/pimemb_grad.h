@@ -138,7 +138,8 @@ int emb_grad_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype
 
 /* The fused SGD step, descriptor after descriptor (a table named twice is stepped twice, in order).  DEVICE pointers only; a
  * pure enqueue like emb_grad_sparse.  Every descriptor is checked before anything is enqueued: a refused call leaves every
- * table as it was. */
+ * table as it was.  That holds for the one refusal that depends on the batch's size too: more than 2^31 - 1 workgroups of the
+ * element-wise kernel (n_indices * dim / 256) is EMB_ERR_UNSUPPORTED, found after every descriptor has passed the other checks. */
 int emb_grad_sgd(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream);
 
 /* THE ADAGRAD STEPS (tests/optim_ref.py restates them as loops; the kernels are compared with that, bit for bit).  g[r], U, good /

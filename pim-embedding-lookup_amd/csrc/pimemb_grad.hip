@@ -24,11 +24,16 @@
 // with an xor butterfly -- a fixed tree, stated over dim alone in the header: the same bits on every run.
 // Every fp32 operation of the definition is a statement of its own under `fp contract(off)` (and the unit is compiled with
 // -ffp-contract=off): nothing is fused into an FMA.
+// The host side works in two phases.  The PLAN checks every descriptor of a call and lays out its launch chains (one per descriptor,
+// or per group), refusing whatever cannot run; the ENQUEUE then runs chain after chain through one function and can fail on a
+// HIP error only.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+
+#include <vector>
 
 #include "pimemb_grad.h"
 #include "pimemb_grad_optim.h"
@@ -633,17 +638,6 @@ struct DeviceGuard {
     }
 };
 
-uint64_t pow2ceil(uint64_t v) {
-    uint64_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-uint32_t log2of(uint64_t pow2) {
-    uint32_t l = 0;
-    while ((1ull << l) < pow2) l++;
-    return l;
-}
-
 constexpr uint64_t kMaxIndices = 1ull << 30, kMaxBags = 0x7fffffffull, kCounterBytes = 256;
 uint64_t up256(uint64_t b) { return (b + 255) & ~255ull; }
 uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
@@ -791,249 +785,261 @@ int check_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, const 
     return EMB_OK;
 }
 
-// The pre-pass of one descriptor (n_indices > 0), then the hot kernel: enqueues only.
 struct StepSpec {
     int kind = RES_SPARSE;       // ResultKind
     float lr = 0.f, eps = 0.f;
-    float *state = nullptr;
+};
+struct SparseOut {               // where emb_grad_sparse writes; all NULL for a step (no unique numbering, no output arrays)
+    long long *rows = nullptr;
+    float *grads = nullptr;
+    unsigned long long *n_unique = nullptr;
 };
 
-// Whether a descriptor runs on the lane-group kernel (and, for RES_ROWWISE, whether it runs at all).
-bool group_shape(const emb_grad_desc &d, const TableShape &t) {
-    return t.dim % 4 == 0 && t.dim <= 512 && d.grad_ld % 4 == 0 && (uintptr_t)d.grad % 16 == 0;
+// THE predicate for "this descriptor runs on the lane-group kernel" (for RES_ROWWISE: whether it runs at all).  Evaluated once per
+// descriptor, into Planned::lane: the row-wise refusal, emb_grad_multi_shape::lane_group and the chain's kernel all read that.
+bool lane_group_path(const emb_grad_desc &d, const TableShape &t, int kind, const float *state, const float *grads_out) {
+    return t.dim % 4 == 0 && t.dim <= 512 && d.grad_ld % 4 == 0 && (uintptr_t)d.grad % 16 == 0 &&
+           (kind != RES_SPARSE || (uintptr_t)grads_out % 16 == 0) && (kind != RES_ADAGRAD || (uintptr_t)state % 16 == 0);
 }
 
-int enqueue(emb_grad *g, const emb_grad_desc &d, const TableShape &t, bool idx64, const StepSpec &st, long long *rows_out, float *grads_out,
-            unsigned long long *n_unique_dev, hipStream_t s) {
-    const bool step = st.kind != RES_SPARSE;     // (a step of any kind: no unique numbering, no output arrays)
-    const uint32_t n = (uint32_t)d.n_indices, B = (uint32_t)d.n_bags, nr = (uint32_t)t.nr_rows;
-    const Layout &l = g->lay;
-    uint32_t *keys[2] = {reinterpret_cast<uint32_t *>(g->scratch + l.keys[0]), reinterpret_cast<uint32_t *>(g->scratch + l.keys[1])};
-    uint32_t *vals[2] = {reinterpret_cast<uint32_t *>(g->scratch + l.vals[0]), reinterpret_cast<uint32_t *>(g->scratch + l.vals[1])};
-    uint32_t *bagof = reinterpret_cast<uint32_t *>(g->scratch + l.bagof), *uidx = reinterpret_cast<uint32_t *>(g->scratch + l.uidx);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(g->scratch + l.hist), *sums = reinterpret_cast<uint32_t *>(g->scratch + l.sums);
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(g->scratch + l.cnt);
-    const bool mean = d.pool.mode == EMB_POOL_MEAN;
+// The lane-group kernels' launch: a lane per 16-byte piece of a row, in groups of a power of two up to 64.
+struct LaneGeom {
+    uint32_t chunks, lanes, lanes_log2, blocks;
+};
+LaneGeom lane_geom(uint32_t dim, uint32_t n) {
+    LaneGeom l{dim / 4, 1, 0, 0};
+    for (; l.lanes < l.chunks && l.lanes < 64; l.lanes <<= 1) l.lanes_log2++;
+    l.blocks = (uint32_t)(((uint64_t)n * l.lanes + kBlock - 1) / kBlock);      // (n <= 2^30, 64 lanes: below 2^28)
+    return l;
+}
+
+// What the kernels take of a descriptor's emb_pool_spec: grad_classify's arguments, RowArgs and MultiDesc are filled from this.
+struct PoolArgs {
+    uint32_t coef, pad_on;       // CoefMode; 1: padding_idx is in use
+    uint64_t pad_idx;
+};
+PoolArgs pool_args(const emb_grad_desc &d) {
     const bool pad = (d.pool.flags & EMB_POOL_PADDING) != 0;
-    if (mean && B) GRAD_HIP(hipMemsetAsync(cnt, 0, (size_t)B * 4, s));
-    const uint32_t pos_blocks = (n + kBlock - 1) / kBlock;
-    const uint64_t pad_idx = pad ? (uint64_t)d.pool.padding_idx : 0ull;
-    uint32_t *cnt_arg = mean ? cnt : nullptr;
-    if (idx64)
-        grad_classify<true><<<dim3(pos_blocks), dim3(kBlock), 0, s>>>(d.indices, d.offsets, d.fixed_pooling, n, B, nr, pad ? 1u : 0u, pad_idx, keys[0], vals[0],
-                                                                    bagof, cnt_arg, &g->counters[0]);
-    else
-        grad_classify<false><<<dim3(pos_blocks), dim3(kBlock), 0, s>>>(d.indices, d.offsets, d.fixed_pooling, n, B, nr, pad ? 1u : 0u, pad_idx, keys[0], vals[0],
-                                                                     bagof, cnt_arg, &g->counters[0]);
-    GRAD_HIP(hipGetLastError());
-    // the sort: the keys run up to nr_rows itself
-    uint32_t bits = 0;
-    while (bits < 32 && ((uint64_t)nr >> bits) != 0) bits++;
-    const uint32_t tiles = (uint32_t)tiles_of(n), hist_len = 256u * tiles, hist_chunks = (uint32_t)tiles_of(hist_len);
-    int cur = 0;
-    for (uint32_t shift = 0; shift < bits; shift += 8, cur ^= 1) {
-        grad_sort_count<<<dim3(tiles), dim3(kBlock), 0, s>>>(keys[cur], n, shift, hist, tiles);
-        grad_scan_chunks<false><<<dim3(hist_chunks), dim3(kBlock), 0, s>>>(hist, hist_len, 0u, hist, sums);
-        grad_scan_sums<<<dim3(1), dim3(kBlock), 0, s>>>(sums, hist_chunks, (unsigned long long *)nullptr);
-        grad_sort_scatter<<<dim3(tiles), dim3(kBlock), 0, s>>>(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift, hist, sums, tiles);
-        GRAD_HIP(hipGetLastError());
-    }
-    RowArgs a{};
-    a.keys = keys[cur];
-    a.vals = vals[cur];
-    a.bagof = bagof;
-    a.cnt = cnt;
-    a.weights = d.pool.per_sample_weights;
-    a.grad = d.grad;
-    a.ld = d.grad_ld;
-    a.n = n;
-    a.n_bags = B;
-    a.nr_rows = nr;
-    a.dim = t.dim;
-    a.coef = mean ? COEF_MEAN : d.pool.per_sample_weights ? COEF_WEIGHTED : COEF_SUM;
-    if (step) {
-        a.table = t.rows;
-        a.stride = t.stride;
-        a.dtype = t.dtype;
-        a.lr = st.lr;
-        a.eps = st.eps;
-        a.state = st.state;
-    } else {
-        grad_scan_chunks<true><<<dim3(tiles), dim3(kBlock), 0, s>>>(keys[cur], n, nr, uidx, sums);
-        grad_scan_sums<<<dim3(1), dim3(kBlock), 0, s>>>(sums, tiles, n_unique_dev);
-        GRAD_HIP(hipGetLastError());
-        a.uidx = uidx;
-        a.usums = sums;
-        a.rows_out = rows_out;
-        a.grads_out = grads_out;
-    }
-    const bool group = group_shape(d, t) && (step || (uintptr_t)grads_out % 16 == 0) && (st.kind != RES_ADAGRAD || (uintptr_t)st.state % 16 == 0);
-    if (st.kind == RES_ROWWISE && !group) return fail(EMB_ERR_UNSUPPORTED, "emb_grad: row-wise Adagrad needs the lane-group shape");      // (checked by the caller)
-    if (group) {
-        const uint32_t chunks = t.dim / 4;
-        uint32_t lanes = (uint32_t)pow2ceil(chunks);
-        lanes = lanes > 64 ? 64 : lanes;
-        const uint64_t blocks = ((uint64_t)n * lanes + kBlock - 1) / kBlock;
-        const dim3 grid((uint32_t)blocks), block(kBlock);
-        const uint32_t ll = log2of(lanes);
-        if (st.kind == RES_SGD) grad_rows_group<RES_SGD><<<grid, block, 0, s>>>(a, lanes, ll, chunks);
-        else if (st.kind == RES_ADAGRAD) grad_rows_group<RES_ADAGRAD><<<grid, block, 0, s>>>(a, lanes, ll, chunks);
-        else if (st.kind == RES_ROWWISE) grad_rows_group<RES_ROWWISE><<<grid, block, 0, s>>>(a, lanes, ll, chunks);
-        else grad_rows_group<RES_SPARSE><<<grid, block, 0, s>>>(a, lanes, ll, chunks);
-    } else {
-        const uint64_t blocks = ((uint64_t)n * t.dim + kBlock - 1) / kBlock;
-        if (blocks > 0x7fffffffull)
-            return fail(EMB_ERR_UNSUPPORTED, "emb_grad: %u indices of dim %u are more elements than one launch of the element-wise kernel takes", n, t.dim);
-        const dim3 grid((uint32_t)blocks), block(kBlock);
-        if (st.kind == RES_SGD) grad_rows_elem<RES_SGD><<<grid, block, 0, s>>>(a);
-        else if (st.kind == RES_ADAGRAD) grad_rows_elem<RES_ADAGRAD><<<grid, block, 0, s>>>(a);
-        else grad_rows_elem<RES_SPARSE><<<grid, block, 0, s>>>(a);
-    }
-    GRAD_HIP(hipGetLastError());
-    return EMB_OK;
+    const uint32_t coef = d.pool.mode == EMB_POOL_MEAN ? COEF_MEAN : d.pool.per_sample_weights ? COEF_WEIGHTED : COEF_SUM;
+    return PoolArgs{coef, pad ? 1u : 0u, pad ? (uint64_t)d.pool.padding_idx : 0ull};
 }
 
-// One group of 2 .. 16 descriptors (emb_grad_multi_groups made it: lane-group shape, one dim, the sums within the context and
-// below 2^32 - 1 keys): the records, then classify, ONE sort over the composite keys, one hot launch.  Enqueues only.
-int enqueue_group(emb_grad *g, const emb_grad_desc *descs, float *const *states, const TableShape *shapes, const uint32_t *members, uint32_t k,
-                  bool idx64, const StepSpec &st, hipStream_t s) {
-    MultiArgs m{};
+// ---- phase one, the plan: no device work, and everything that can refuse a call -------------------------------------------------
+
+// One descriptor of a call, and the launch chain that STARTS at it (k == 0: none does): the cnt memset, classify, the sort, the head
+// scan (sparse) and the hot launch over the k non-empty descriptors of [this one, end) -- one, or a group's 2 .. 16.
+struct Planned {
+    TableShape t;
+    bool lane;                   // lane_group_path of this descriptor, and so the chain's kernel (the members of a group all have it)
+    bool mean;                   // a member pools by mean: cnt[] is cleared and counted
+    uint32_t k, end;
+    uint32_t n, n_bags, key_end; // positions, bags and rows summed over the members; key_end is the key of a position that is not good
+    LaneGeom geo;                // lane: the hot launch
+    uint32_t elem_blocks;        // !lane: its workgroups
+};
+
+// Plans the chain of the non-empty descriptors of [first, end): one descriptor, or a group as emb_grad_multi_groups made it.
+int plan_chain(const emb_grad *g, const emb_grad_desc *descs, Planned *p, uint32_t first, uint32_t end) {
+    Planned &c = p[first];
     uint64_t pos = 0, bags = 0, keys_end = 0;
-    bool mean = false;
-    for (uint32_t j = 0; j < k; j++) {
-        const emb_grad_desc &d = descs[members[j]];
-        const TableShape &t = shapes[members[j]];
-        MultiDesc &r = m.d[j];
-        const bool pad = (d.pool.flags & EMB_POOL_PADDING) != 0;
-        r.ids = d.indices;
-        r.offsets = d.offsets;
-        r.weights = d.pool.per_sample_weights;
-        r.grad = d.grad;
-        r.ld = d.grad_ld;
-        r.pad_idx = pad ? (uint64_t)d.pool.padding_idx : 0ull;
-        r.table = t.rows;
-        r.state = states ? states[members[j]] : nullptr;
-        r.pos_base = (uint32_t)pos;
-        r.n = (uint32_t)d.n_indices;
-        r.bag_base = (uint32_t)bags;
-        r.n_bags = (uint32_t)d.n_bags;
-        r.key_base = (uint32_t)keys_end;
-        r.nr_rows = (uint32_t)t.nr_rows;
-        r.fixed_pooling = d.fixed_pooling;
-        r.pad_on = pad ? 1u : 0u;
-        r.coef = d.pool.mode == EMB_POOL_MEAN ? COEF_MEAN : d.pool.per_sample_weights ? COEF_WEIGHTED : COEF_SUM;
-        r.stride = t.stride;
-        r.dtype = t.dtype;
-        mean = mean || r.coef == COEF_MEAN;
-        pos += d.n_indices;
-        bags += d.n_bags;
-        keys_end += t.nr_rows;
+    bool fusable = true;
+    for (uint32_t j = first; j < end; j++) {
+        if (descs[j].n_indices == 0) continue;
+        c.k++;
+        pos += descs[j].n_indices;
+        bags += descs[j].n_bags;
+        keys_end += p[j].t.nr_rows;
+        fusable = fusable && p[j].lane && p[j].t.dim == c.t.dim;
+        c.mean = c.mean || pool_args(descs[j]).coef == COEF_MEAN;
     }
-    if (k < 2 || k > kMultiMax || pos > g->max_indices || bags > g->max_bags || keys_end > 0xfffffffeull)
-        return fail(EMB_ERR_INVALID, "emb_grad: a group of %u descriptors, %llu indices, %llu bags and %llu rows does not fit", k, (unsigned long long)pos,
-                    (unsigned long long)bags, (unsigned long long)keys_end);      // (emb_grad_multi_groups keeps these)
-    m.k = k;
-    m.n = (uint32_t)pos;
-    m.key_end = (uint32_t)keys_end;
-    m.dim = shapes[members[0]].dim;
-    const uint32_t n = m.n;
-    const Layout &l = g->lay;
-    uint32_t *keys[2] = {reinterpret_cast<uint32_t *>(g->scratch + l.keys[0]), reinterpret_cast<uint32_t *>(g->scratch + l.keys[1])};
-    uint32_t *vals[2] = {reinterpret_cast<uint32_t *>(g->scratch + l.vals[0]), reinterpret_cast<uint32_t *>(g->scratch + l.vals[1])};
-    uint32_t *bagof = reinterpret_cast<uint32_t *>(g->scratch + l.bagof);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(g->scratch + l.hist), *sums = reinterpret_cast<uint32_t *>(g->scratch + l.sums);
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(g->scratch + l.cnt);
-    if (mean && bags) GRAD_HIP(hipMemsetAsync(cnt, 0, (size_t)bags * 4, s));
-    const uint32_t pos_blocks = (n + kBlock - 1) / kBlock;
-    if (idx64) grad_multi_classify<true><<<dim3(pos_blocks), dim3(kBlock), 0, s>>>(m, keys[0], vals[0], bagof, cnt, &g->counters[0]);
-    else grad_multi_classify<false><<<dim3(pos_blocks), dim3(kBlock), 0, s>>>(m, keys[0], vals[0], bagof, cnt, &g->counters[0]);
-    GRAD_HIP(hipGetLastError());
-    uint32_t bits = 0;                           // the keys run up to key_end itself
-    while (bits < 32 && (keys_end >> bits) != 0) bits++;
-    const uint32_t tiles = (uint32_t)tiles_of(n), hist_len = 256u * tiles, hist_chunks = (uint32_t)tiles_of(hist_len);
-    int cur = 0;
-    for (uint32_t shift = 0; shift < bits; shift += 8, cur ^= 1) {
-        grad_sort_count<<<dim3(tiles), dim3(kBlock), 0, s>>>(keys[cur], n, shift, hist, tiles);
-        grad_scan_chunks<false><<<dim3(hist_chunks), dim3(kBlock), 0, s>>>(hist, hist_len, 0u, hist, sums);
-        grad_scan_sums<<<dim3(1), dim3(kBlock), 0, s>>>(sums, hist_chunks, (unsigned long long *)nullptr);
-        grad_sort_scatter<<<dim3(tiles), dim3(kBlock), 0, s>>>(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift, hist, sums, tiles);
-        GRAD_HIP(hipGetLastError());
-    }
-    const uint32_t chunks = m.dim / 4;
-    uint32_t lanes = (uint32_t)pow2ceil(chunks);
-    lanes = lanes > 64 ? 64 : lanes;
-    const uint64_t blocks = ((uint64_t)n * lanes + kBlock - 1) / kBlock;
-    const dim3 grid((uint32_t)blocks), block(kBlock);
-    const uint32_t ll = log2of(lanes);
-    if (st.kind == RES_SGD) grad_multi_rows<RES_SGD><<<grid, block, 0, s>>>(m, keys[cur], vals[cur], bagof, cnt, st.lr, st.eps, lanes, ll, chunks);
-    else if (st.kind == RES_ADAGRAD) grad_multi_rows<RES_ADAGRAD><<<grid, block, 0, s>>>(m, keys[cur], vals[cur], bagof, cnt, st.lr, st.eps, lanes, ll, chunks);
-    else grad_multi_rows<RES_ROWWISE><<<grid, block, 0, s>>>(m, keys[cur], vals[cur], bagof, cnt, st.lr, st.eps, lanes, ll, chunks);
-    GRAD_HIP(hipGetLastError());
-    return EMB_OK;
-}
-
-// What emb_grad_sgd(_multi) and emb_grad_step(_multi) share once their arguments are checked: every descriptor (and state) is
-// checked, then everything is enqueued -- descriptor after descriptor, or group after group (multi).
-int step_call(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype, const StepSpec &spec,
-              const char *step, const char *who, bool multi, void *stream) {
-    const bool rowwise = spec.kind == RES_ROWWISE;
-    TableShape *shapes = n_descs ? new TableShape[n_descs]() : nullptr;
-    struct Free {
-        TableShape *p;
-        ~Free() { delete[] p; }
-    } free_shapes{shapes};
-    for (uint32_t k = 0; k < n_descs; k++) {
-        if (int rc = check_desc(g, descs[k], itype, step, who, &shapes[k])) return rc;
-        if (descs[k].n_indices == 0 || spec.kind == RES_SGD) continue;
-        if (!states[k] || (uintptr_t)states[k] % 4)
-            return fail(EMB_ERR_INVALID, "%s: the state of table %u is NULL or not 4-byte aligned", who, descs[k].table_id);
-        if (rowwise && !group_shape(descs[k], shapes[k]))
-            return fail(EMB_ERR_UNSUPPORTED,
-                        "%s: row-wise Adagrad needs the lane-group shape (dim %% 4 == 0, dim <= 512, grad 16-byte aligned, grad_ld %% 4 == 0): table %u "
-                        "has dim %u, grad %p, grad_ld %llu -- the element-wise kernel has no row-wide view of g", who, descs[k].table_id, shapes[k].dim,
-                        (const void *)descs[k].grad, (unsigned long long)descs[k].grad_ld);
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DeviceGuard guard(g->device);
-    const bool idx64 = itype == EMB_IDX_I64;
-    auto single = [&](uint32_t k) {
-        StepSpec st = spec;
-        st.state = states ? states[k] : nullptr;
-        return enqueue(g, descs[k], shapes[k], idx64, st, nullptr, nullptr, nullptr, s);
-    };
-    if (!multi) {
-        for (uint32_t k = 0; k < n_descs; k++) {
-            if (descs[k].n_indices == 0) continue;
-            if (int rc = single(k)) return rc;
-        }
+    if (c.k > 1 && (c.k > kMultiMax || !fusable || pos > g->max_indices || bags > g->max_bags || keys_end > 0xfffffffeull))
+        return fail(EMB_ERR_INVALID, "emb_grad: a group of %u descriptors, %llu indices, %llu bags and %llu rows does not fit", c.k, (unsigned long long)pos,
+                    (unsigned long long)bags, (unsigned long long)keys_end);      // (emb_grad_multi_groups makes no such group)
+    c.end = end;
+    c.n = (uint32_t)pos;         // (one descriptor: check_desc kept these within the context, and nr_rows below 2^32 - 1)
+    c.n_bags = (uint32_t)bags;
+    c.key_end = (uint32_t)keys_end;
+    if (c.lane) {
+        c.geo = lane_geom(c.t.dim, c.n);
         return EMB_OK;
     }
-    emb_grad_multi_shape *ms = n_descs ? new emb_grad_multi_shape[n_descs]() : nullptr;
-    uint32_t *group_of = n_descs ? new uint32_t[n_descs]() : nullptr;
-    struct Free2 {
-        emb_grad_multi_shape *a;
-        uint32_t *b;
-        ~Free2() {
-            delete[] a;
-            delete[] b;
-        }
-    } free_groups{ms, group_of};
+    const uint64_t blocks = ((uint64_t)c.n * c.t.dim + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffull)
+        return fail(EMB_ERR_UNSUPPORTED, "emb_grad: %u indices of dim %u are more elements than one launch of the element-wise kernel takes", c.n, c.t.dim);
+    c.elem_blocks = (uint32_t)blocks;
+    return EMB_OK;
+}
+
+// The plan of a step call: every descriptor and state checked, in order; then the chains -- one per non-empty descriptor, or one per
+// group (ms != NULL: the multi calls; ms and group_of have n_descs entries like `plan`).
+int plan_step(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype, const StepSpec &spec, const char *step,
+              const char *who, Planned *plan, emb_grad_multi_shape *ms, uint32_t *group_of) {
     for (uint32_t k = 0; k < n_descs; k++) {
-        const bool lane = group_shape(descs[k], shapes[k]) && (spec.kind != RES_ADAGRAD || (uintptr_t)states[k] % 16 == 0);
-        ms[k] = emb_grad_multi_shape{descs[k].table_id, shapes[k].dim, lane ? 1u : 0u, shapes[k].nr_rows, descs[k].n_indices, descs[k].n_bags};
+        const emb_grad_desc &d = descs[k];
+        Planned &p = plan[k];
+        if (int rc = check_desc(g, d, itype, step, who, &p.t)) return rc;
+        float *state = d.n_indices && states ? states[k] : nullptr;
+        if (d.n_indices && spec.kind != RES_SGD && (!state || (uintptr_t)state % 4))
+            return fail(EMB_ERR_INVALID, "%s: the state of table %u is NULL or not 4-byte aligned", who, d.table_id);
+        p.lane = lane_group_path(d, p.t, spec.kind, state, nullptr);
+        if (d.n_indices && spec.kind == RES_ROWWISE && !p.lane)
+            return fail(EMB_ERR_UNSUPPORTED,
+                        "%s: row-wise Adagrad needs the lane-group shape (dim %% 4 == 0, dim <= 512, grad 16-byte aligned, grad_ld %% 4 == 0): table %u "
+                        "has dim %u, grad %p, grad_ld %llu -- the element-wise kernel has no row-wide view of g", who, d.table_id, p.t.dim,
+                        (const void *)d.grad, (unsigned long long)d.grad_ld);
+        if (ms) ms[k] = emb_grad_multi_shape{d.table_id, p.t.dim, p.lane ? 1u : 0u, p.t.nr_rows, d.n_indices, d.n_bags};
     }
-    const uint32_t n_groups = emb_grad_multi_groups(ms, n_descs, g->max_indices, g->max_bags, group_of);
-    uint32_t at = 0;
-    for (uint32_t grp = 0; grp < n_groups; grp++) {
-        uint32_t members[kMultiMax], k = 0;
-        for (; at < n_descs && (group_of[at] == grp || group_of[at] == 0xffffffffu); at++)
-            if (group_of[at] == grp && k < kMultiMax) members[k++] = at;
-        if (k == 1) {
-            if (int rc = single(members[0])) return rc;
-        } else if (int rc = enqueue_group(g, descs, states, shapes, members, k, idx64, spec, s)) {
-            return rc;
-        }
+    if (ms) emb_grad_multi_groups(ms, n_descs, g->max_indices, g->max_bags, group_of);
+    for (uint32_t k = 0, end; k < n_descs; k = end) {
+        end = k + 1;             // (a group's members are consecutive but for the empty descriptors among them)
+        if (descs[k].n_indices == 0) continue;
+        while (ms && end < n_descs && (group_of[end] == group_of[k] || descs[end].n_indices == 0)) end++;
+        if (int rc = plan_chain(g, descs, plan, k, end)) return rc;
     }
+    return EMB_OK;
+}
+
+// ---- phase two, the enqueue: from the first launch on, the only possible failure is a HIP error ---------------------------------
+
+struct Scratch {                 // the scratch area as the kernels take it
+    uint32_t *keys[2], *vals[2], *bagof, *uidx, *hist, *sums, *cnt;
+};
+Scratch scratch_of(const emb_grad *g) {
+    const Layout &l = g->lay;
+    auto at = [g](uint64_t off) { return reinterpret_cast<uint32_t *>(g->scratch + off); };
+    return Scratch{{at(l.keys[0]), at(l.keys[1])}, {at(l.vals[0]), at(l.vals[1])}, at(l.bagof), at(l.uidx), at(l.hist), at(l.sums), at(l.cnt)};
+}
+
+// The stable sort of the n (key, position) pairs in keys[0] / vals[0], the keys running up to key_end itself: four launches per 8
+// bits of key_end.  *cur = which of the two buffers holds the result.
+int sort_pairs(const Scratch &sc, uint32_t n, uint32_t key_end, hipStream_t s, int *cur) {
+    uint32_t bits = 0;
+    while (bits < 32 && ((uint64_t)key_end >> bits) != 0) bits++;
+    const uint32_t tiles = (uint32_t)tiles_of(n), hist_len = 256u * tiles, hist_chunks = (uint32_t)tiles_of(hist_len);
+    int c = 0;
+    for (uint32_t shift = 0; shift < bits; shift += 8, c ^= 1) {
+        grad_sort_count<<<dim3(tiles), dim3(kBlock), 0, s>>>(sc.keys[c], n, shift, sc.hist, tiles);
+        grad_scan_chunks<false><<<dim3(hist_chunks), dim3(kBlock), 0, s>>>(sc.hist, hist_len, 0u, sc.hist, sc.sums);
+        grad_scan_sums<<<dim3(1), dim3(kBlock), 0, s>>>(sc.sums, hist_chunks, (unsigned long long *)nullptr);
+        grad_sort_scatter<<<dim3(tiles), dim3(kBlock), 0, s>>>(sc.keys[c], sc.vals[c], sc.keys[c ^ 1], sc.vals[c ^ 1], n, shift, sc.hist, sc.sums, tiles);
+        GRAD_HIP(hipGetLastError());
+    }
+    *cur = c;
+    return EMB_OK;
+}
+
+// The records of the group planned at descriptor `first`: positions, bags and keys of its members laid end to end.
+void fill_multi(MultiArgs &m, const emb_grad_desc *descs, float *const *states, const Planned *p, uint32_t first) {
+    const Planned &c = p[first];
+    m = MultiArgs{};
+    m.k = c.k, m.n = c.n, m.key_end = c.key_end, m.dim = c.t.dim;
+    uint32_t pos = 0, bags = 0, key = 0, j = 0;
+    for (uint32_t at = first; at < c.end; at++) {
+        const emb_grad_desc &d = descs[at];
+        if (d.n_indices == 0) continue;
+        const TableShape &t = p[at].t;
+        const PoolArgs pa = pool_args(d);
+        MultiDesc &r = m.d[j++];
+        r.ids = d.indices, r.offsets = d.offsets, r.fixed_pooling = d.fixed_pooling;
+        r.weights = d.pool.per_sample_weights, r.coef = pa.coef, r.pad_on = pa.pad_on, r.pad_idx = pa.pad_idx;
+        r.grad = d.grad, r.ld = d.grad_ld;
+        r.table = t.rows, r.stride = t.stride, r.dtype = t.dtype;
+        r.state = states ? states[at] : nullptr;
+        r.pos_base = pos, r.n = (uint32_t)d.n_indices;
+        r.bag_base = bags, r.n_bags = (uint32_t)d.n_bags;
+        r.key_base = key, r.nr_rows = (uint32_t)t.nr_rows;
+        pos += r.n, bags += r.n_bags, key += r.nr_rows;
+    }
+}
+
+// Runs the chain planned at descriptor `first`, for a chain of one and for a group alike.
+int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, const Planned *p, uint32_t first, bool idx64, const StepSpec &spec,
+              const SparseOut &out, hipStream_t s) {
+    const Planned &c = p[first];
+    const emb_grad_desc &d = descs[first];       // (a chain of one: its descriptor)
+    const PoolArgs pa = pool_args(d);
+    const Scratch sc = scratch_of(g);
+    const LaneGeom &l = c.geo;
+    const bool group = c.k > 1;
+    const uint32_t n = c.n;
+    const dim3 block(kBlock), pos_grid((n + kBlock - 1) / kBlock);
+    unsigned long long *bad = &g->counters[0];
+    MultiArgs m;                                 // (filled for a group only)
+    if (c.mean && c.n_bags) GRAD_HIP(hipMemsetAsync(sc.cnt, 0, (size_t)c.n_bags * 4, s));
+    if (group) {
+        fill_multi(m, descs, states, p, first);
+        if (idx64) grad_multi_classify<true><<<pos_grid, block, 0, s>>>(m, sc.keys[0], sc.vals[0], sc.bagof, sc.cnt, bad);
+        else grad_multi_classify<false><<<pos_grid, block, 0, s>>>(m, sc.keys[0], sc.vals[0], sc.bagof, sc.cnt, bad);
+    } else {
+        uint32_t *cnt = c.mean ? sc.cnt : nullptr;
+        if (idx64)
+            grad_classify<true><<<pos_grid, block, 0, s>>>(d.indices, d.offsets, d.fixed_pooling, n, c.n_bags, c.key_end, pa.pad_on, pa.pad_idx, sc.keys[0],
+                                                          sc.vals[0], sc.bagof, cnt, bad);
+        else
+            grad_classify<false><<<pos_grid, block, 0, s>>>(d.indices, d.offsets, d.fixed_pooling, n, c.n_bags, c.key_end, pa.pad_on, pa.pad_idx, sc.keys[0],
+                                                           sc.vals[0], sc.bagof, cnt, bad);
+    }
+    GRAD_HIP(hipGetLastError());
+    int cur = 0;
+    if (int rc = sort_pairs(sc, n, c.key_end, s, &cur)) return rc;
+    const uint32_t *keys = sc.keys[cur], *vals = sc.vals[cur];
+    if (group) {
+        const dim3 grid(l.blocks);
+        if (spec.kind == RES_SGD) grad_multi_rows<RES_SGD><<<grid, block, 0, s>>>(m, keys, vals, sc.bagof, sc.cnt, spec.lr, spec.eps, l.lanes, l.lanes_log2, l.chunks);
+        else if (spec.kind == RES_ADAGRAD)
+            grad_multi_rows<RES_ADAGRAD><<<grid, block, 0, s>>>(m, keys, vals, sc.bagof, sc.cnt, spec.lr, spec.eps, l.lanes, l.lanes_log2, l.chunks);
+        else grad_multi_rows<RES_ROWWISE><<<grid, block, 0, s>>>(m, keys, vals, sc.bagof, sc.cnt, spec.lr, spec.eps, l.lanes, l.lanes_log2, l.chunks);
+        GRAD_HIP(hipGetLastError());
+        return EMB_OK;
+    }
+    RowArgs a{};
+    a.keys = keys, a.vals = vals, a.bagof = sc.bagof, a.cnt = sc.cnt;
+    a.weights = d.pool.per_sample_weights, a.coef = pa.coef;
+    a.grad = d.grad, a.ld = d.grad_ld;
+    a.n = n, a.n_bags = c.n_bags, a.nr_rows = c.key_end, a.dim = c.t.dim;
+    if (spec.kind != RES_SPARSE) {
+        a.table = c.t.rows, a.stride = c.t.stride, a.dtype = c.t.dtype;
+        a.lr = spec.lr, a.eps = spec.eps, a.state = states ? states[first] : nullptr;
+    } else {
+        const uint32_t tiles = (uint32_t)tiles_of(n);
+        grad_scan_chunks<true><<<dim3(tiles), block, 0, s>>>(keys, n, c.key_end, sc.uidx, sc.sums);
+        grad_scan_sums<<<dim3(1), block, 0, s>>>(sc.sums, tiles, out.n_unique);
+        GRAD_HIP(hipGetLastError());
+        a.uidx = sc.uidx, a.usums = sc.sums, a.rows_out = out.rows, a.grads_out = out.grads;
+    }
+    if (c.lane) {
+        const dim3 grid(l.blocks);
+        if (spec.kind == RES_SGD) grad_rows_group<RES_SGD><<<grid, block, 0, s>>>(a, l.lanes, l.lanes_log2, l.chunks);
+        else if (spec.kind == RES_ADAGRAD) grad_rows_group<RES_ADAGRAD><<<grid, block, 0, s>>>(a, l.lanes, l.lanes_log2, l.chunks);
+        else if (spec.kind == RES_ROWWISE) grad_rows_group<RES_ROWWISE><<<grid, block, 0, s>>>(a, l.lanes, l.lanes_log2, l.chunks);
+        else grad_rows_group<RES_SPARSE><<<grid, block, 0, s>>>(a, l.lanes, l.lanes_log2, l.chunks);
+    } else {
+        const dim3 grid(c.elem_blocks);
+        if (spec.kind == RES_SGD) grad_rows_elem<RES_SGD><<<grid, block, 0, s>>>(a);
+        else if (spec.kind == RES_ADAGRAD) grad_rows_elem<RES_ADAGRAD><<<grid, block, 0, s>>>(a);
+        else grad_rows_elem<RES_SPARSE><<<grid, block, 0, s>>>(a);      // (RES_ROWWISE never gets here: the plan refused it)
+    }
+    GRAD_HIP(hipGetLastError());
+    return EMB_OK;
+}
+
+// What emb_grad_sgd(_multi) and emb_grad_step(_multi) share once their arguments are checked: the plan of the whole call, then chain
+// after chain enqueued.
+int step_call(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype, const StepSpec &spec,
+              const char *step, const char *who, bool multi, void *stream) {
+    const bool sgd = spec.kind == RES_SGD;       // (no states)
+    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
+    if (n_descs && (!descs || (!sgd && !states))) return fail(EMB_ERR_INVALID, "%s: %s is NULL", who, sgd ? "descs" : "descs or states");
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    std::vector<Planned> plan(n_descs);
+    std::vector<emb_grad_multi_shape> ms(multi ? n_descs : 0);
+    std::vector<uint32_t> group_of(multi ? n_descs : 0);
+    if (int rc = plan_step(g, descs, states, n_descs, itype, spec, step, who, plan.data(), multi ? ms.data() : nullptr, group_of.data())) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    for (uint32_t k = 0; k < n_descs; k++)
+        if (plan[k].k)
+            if (int rc = run_chain(g, descs, states, plan.data(), k, itype == EMB_IDX_I64, spec, SparseOut{}, s)) return rc;
     return EMB_OK;
 }
 
@@ -1076,37 +1082,29 @@ int emb_grad_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype
     if (!g || !desc) return fail(EMB_ERR_INVALID, "emb_grad_sparse: context or descriptor is NULL");
     if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "emb_grad_sparse: bad index type");
     if (!n_unique_dev || (uintptr_t)n_unique_dev % 8) return fail(EMB_ERR_INVALID, "emb_grad_sparse: n_unique_dev is NULL or not 8-byte aligned");
-    TableShape t{};
-    if (int rc = check_desc(g, *desc, itype, nullptr, "emb_grad_sparse", &t)) return rc;
+    Planned p{};                                 // the plan: a chain of one, with the unique numbering switched on
+    if (int rc = check_desc(g, *desc, itype, nullptr, "emb_grad_sparse", &p.t)) return rc;
     if (capacity < desc->n_indices)
         return fail(EMB_ERR_INVALID, "emb_grad_sparse: room for %llu rows, %llu indices may name as many", (unsigned long long)capacity,
                     (unsigned long long)desc->n_indices);
+    if (desc->n_indices && (!rows_out || !grads_out || (uintptr_t)rows_out % 8 || (uintptr_t)grads_out % 4))
+        return fail(EMB_ERR_INVALID, "emb_grad_sparse: rows_out or grads_out is NULL or not naturally aligned");
+    p.lane = lane_group_path(*desc, p.t, RES_SPARSE, nullptr, grads_out);
+    if (desc->n_indices)
+        if (int rc = plan_chain(g, desc, &p, 0, 1)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(g->device);
     if (desc->n_indices == 0) {
         GRAD_HIP(hipMemsetAsync(n_unique_dev, 0, 8, s));
         return EMB_OK;
     }
-    if (!rows_out || !grads_out || (uintptr_t)rows_out % 8 || (uintptr_t)grads_out % 4)
-        return fail(EMB_ERR_INVALID, "emb_grad_sparse: rows_out or grads_out is NULL or not naturally aligned");
-    return enqueue(g, *desc, t, itype == EMB_IDX_I64, StepSpec{}, reinterpret_cast<long long *>(rows_out), grads_out,
-                   reinterpret_cast<unsigned long long *>(n_unique_dev), s);
+    const SparseOut out{reinterpret_cast<long long *>(rows_out), grads_out, reinterpret_cast<unsigned long long *>(n_unique_dev)};
+    return run_chain(g, desc, nullptr, &p, 0, itype == EMB_IDX_I64, StepSpec{}, out, s);
 }
 
 }  // extern "C"
 
 namespace {
-
-int sgd_call(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream, bool multi) {
-    const char *who = multi ? "emb_grad_sgd_multi" : "emb_grad_sgd";
-    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
-    if (n_descs && !descs) return fail(EMB_ERR_INVALID, "%s: descs is NULL", who);
-    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
-    StepSpec st;
-    st.kind = RES_SGD;
-    st.lr = lr;
-    return step_call(g, descs, nullptr, n_descs, itype, st, "an SGD", who, multi, stream);
-}
 
 int opt_call(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype, const emb_opt_spec *opt,
              void *stream, bool multi) {
@@ -1115,13 +1113,7 @@ int opt_call(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint
     if (opt->kind != EMB_OPT_ADAGRAD && opt->kind != EMB_OPT_ROWWISE_ADAGRAD) return fail(EMB_ERR_INVALID, "%s: unknown optimizer kind %u", who, opt->kind);
     if (opt->reserved != 0) return fail(EMB_ERR_INVALID, "%s: the spec's reserved field must be 0, got %u", who, opt->reserved);
     if (!(opt->eps >= 0.f)) return fail(EMB_ERR_INVALID, "%s: eps must not be negative or NaN, got %g", who, (double)opt->eps);
-    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
-    if (n_descs && (!descs || !states)) return fail(EMB_ERR_INVALID, "%s: descs or states is NULL", who);
-    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
-    StepSpec st;
-    st.kind = opt->kind == EMB_OPT_ROWWISE_ADAGRAD ? RES_ROWWISE : RES_ADAGRAD;
-    st.lr = opt->lr;
-    st.eps = opt->eps;
+    const StepSpec st{opt->kind == EMB_OPT_ROWWISE_ADAGRAD ? RES_ROWWISE : RES_ADAGRAD, opt->lr, opt->eps};
     return step_call(g, descs, states, n_descs, itype, st, "an Adagrad", who, multi, stream);
 }
 
@@ -1130,11 +1122,11 @@ int opt_call(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint
 extern "C" {
 
 int emb_grad_sgd(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream) {
-    return sgd_call(g, descs, n_descs, itype, lr, stream, false);
+    return step_call(g, descs, nullptr, n_descs, itype, StepSpec{RES_SGD, lr, 0.f}, "an SGD", "emb_grad_sgd", false, stream);
 }
 
 int emb_grad_sgd_multi(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream) {
-    return sgd_call(g, descs, n_descs, itype, lr, stream, true);
+    return step_call(g, descs, nullptr, n_descs, itype, StepSpec{RES_SGD, lr, 0.f}, "an SGD", "emb_grad_sgd_multi", true, stream);
 }
 
 uint64_t emb_opt_state_floats(uint32_t kind, uint64_t nr_rows, uint32_t dim) {

@@ -435,6 +435,32 @@ class GradContext:
         d.pool.padding_idx = 0 if padding_idx is None else int(padding_idx)
         return itype, dev
 
+    def _step_descs(self, table_ids, indices, offsets, grads, modes, per_sample_weights, padding_idx, fixed_pooling, stream, keep):
+        """What sgd_step and adagrad_step share: (the emb_grad_desc array, its length, the index type, whether the inputs are the
+        caller's device tensors, the stream).  modes, per_sample_weights and padding_idx: one value for all tables or one per table;
+        `keep` receives what must outlive the call (_free releases its DeviceBuffers)."""
+        n = len(table_ids)
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n  # noqa: E731
+        modes, ws, pads = per(modes), per(per_sample_weights), per(padding_idx)
+        arr, itypes, devs = (_l.EmbGradDesc * max(n, 1))(), set(), set()
+        for k in range(n):
+            it, dev = self._desc(arr[k], table_ids[k], indices[k], None if offsets is None else offsets[k], grads[k], modes[k], ws[k], pads[k],
+                                 fixed_pooling, keep)
+            itypes.add(it)
+            devs.add(dev)
+        if len(itypes) > 1 or len(devs) > 1:
+            raise TypeError("the tables of one call share one index width and one memory space")
+        dev = bool(devs and devs.pop())
+        if stream is None and dev:
+            stream = _current_stream_for(*indices)
+        return arr, n, itypes.pop() if itypes else _l.EMB_IDX_I64, dev, stream
+
+    @staticmethod
+    def _free(keep) -> None:
+        for b in keep:
+            if isinstance(b, DeviceBuffer):
+                b.free()
+
     def sparse_grad(self, table: int, indices, offsets, grad, mode: str = "sum", per_sample_weights=None, padding_idx=None,
                     stream: int | None = None, fixed_pooling: int = 0):
         """(rows, grads): the rows of `table` that the batch names at least once, ascending (int64), and their gradients
@@ -466,9 +492,7 @@ class GradContext:
             u = int(count_b.numpy()[0])
             return rows_b.numpy()[:u].copy(), grads_b.numpy()[:u].copy()
         finally:
-            for b in (rows_b, grads_b, count_b, *keep):
-                if isinstance(b, DeviceBuffer):
-                    b.free()
+            self._free((rows_b, grads_b, count_b, *keep))
 
     def sgd_step(self, table_ids, indices, offsets, grads, lr: float, modes="sum", per_sample_weights=None, padding_idx=None,
                  stream: int | None = None, fixed_pooling: int = 0, multi: bool = False) -> None:
@@ -478,29 +502,16 @@ class GradContext:
         buffer (the [B, T*dim] gradient of a concatenated output is read in place).  Torch CUDA tensors: a pure enqueue on
         `stream` (torch's current one by default); numpy arrays: copied to the device, and the call waits.  multi=True: the
         multi-table step (emb_grad_sgd_multi) -- one pre-pass and one launch per group of tables (multi_groups), the same bytes."""
-        n = len(table_ids)
-        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n  # noqa: E731
-        modes, ws, pads = per(modes), per(per_sample_weights), per(padding_idx)
-        arr, keep, itypes, devs = (_l.EmbGradDesc * max(n, 1))(), [], set(), set()
-        for k in range(n):
-            it, dev = self._desc(arr[k], table_ids[k], indices[k], None if offsets is None else offsets[k], grads[k], modes[k], ws[k], pads[k],
-                                 fixed_pooling, keep)
-            itypes.add(it)
-            devs.add(dev)
-        if len(itypes) > 1 or len(devs) > 1:
-            raise TypeError("the tables of one call share one index width and one memory space")
-        dev = bool(devs and devs.pop())
-        if stream is None and dev:
-            stream = _current_stream_for(*indices)
+        keep = []
         try:
+            arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, grads, modes, per_sample_weights, padding_idx, fixed_pooling,
+                                                          stream, keep)
             call = self._G.emb_grad_sgd_multi if multi else self._G.emb_grad_sgd
-            _l.check_grad(call(self._h, arr, n, itypes.pop() if itypes else _l.EMB_IDX_I64, float(lr), stream))
+            _l.check_grad(call(self._h, arr, n, itype, float(lr), stream))
             if not dev:
                 self.engine.synchronize(stream)
         finally:
-            for b in keep:
-                if isinstance(b, DeviceBuffer):
-                    b.free()
+            self._free(keep)
 
     def multi_groups(self, table_ids, n_indices, n_bags, lane_group=True) -> list:
         """How a multi=True step over these tables would be split in this context (emb_grad_multi_groups): the group number of
@@ -530,24 +541,13 @@ class GradContext:
         place -- float32 CUDA tensors of that numel (any shape, contiguous) with torch inputs; numpy float32 arrays with numpy
         inputs, copied to the device and back into the very arrays.  The caller initialises them (zeros, or torch's
         initial_accumulator_value).  multi=True: the multi-table step (emb_grad_step_multi), the same bytes."""
-        n = len(table_ids)
-        if len(states) != n:
-            raise ValueError(f"{len(states)} states for {n} tables")
-        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n  # noqa: E731
-        modes, ws, pads = per(modes), per(per_sample_weights), per(padding_idx)
-        arr, keep, itypes, devs = (_l.EmbGradDesc * max(n, 1))(), [], set(), set()
-        for k in range(n):
-            it, dev = self._desc(arr[k], table_ids[k], indices[k], None if offsets is None else offsets[k], grads[k], modes[k], ws[k], pads[k],
-                                 fixed_pooling, keep)
-            itypes.add(it)
-            devs.add(dev)
-        if len(itypes) > 1 or len(devs) > 1:
-            raise TypeError("the tables of one call share one index width and one memory space")
-        dev = bool(devs and devs.pop())
-        if stream is None and dev:
-            stream = _current_stream_for(*indices)
-        ptrs, back = (C.c_void_p * max(n, 1))(), []
+        if len(states) != len(table_ids):
+            raise ValueError(f"{len(states)} states for {len(table_ids)} tables")
+        keep, back = [], []
         try:
+            arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, grads, modes, per_sample_weights, padding_idx, fixed_pooling,
+                                                          stream, keep)
+            ptrs = (C.c_void_p * max(n, 1))()
             for k in range(n):
                 want = int(np.prod(self.state_shape(table_ids[k], rowwise)))
                 st = states[k]
@@ -567,15 +567,13 @@ class GradContext:
                     ptrs[k] = buf.ptr
             spec = _l.EmbOptSpec(_l.EMB_OPT_ROWWISE_ADAGRAD if rowwise else _l.EMB_OPT_ADAGRAD, float(lr), float(eps), 0)
             call = self._G.emb_grad_step_multi if multi else self._G.emb_grad_step
-            _l.check_grad(call(self._h, arr, ptrs, n, itypes.pop() if itypes else _l.EMB_IDX_I64, C.byref(spec), stream))
+            _l.check_grad(call(self._h, arr, ptrs, n, itype, C.byref(spec), stream))
             if not dev:
                 self.engine.synchronize(stream)
                 for st, buf in back:
                     st[...] = buf.numpy().reshape(st.shape)
         finally:
-            for b in keep:
-                if isinstance(b, DeviceBuffer):
-                    b.free()
+            self._free(keep)
 
     def report(self) -> int:
         """Positions skipped for an id outside the table since the last report (waits for the device; resets the count)."""

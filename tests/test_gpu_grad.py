@@ -13,26 +13,16 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import grad_cases as gc  # noqa: E402
 import grad_ref as gr  # noqa: E402
+import optim_ref as orf  # noqa: E402
 import pool_ref  # noqa: E402
 import rows_cases as rc  # noqa: E402
+from grad_gpu import DEV, bits, load_bytes, table_bytes, to_dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 N = gc.NR_ROWS
 WIDTHS = ["u32", "i64"]
 GROUP_DIMS, ELEM_DIMS = [4, 12, 128, 256, 512], [5, 17]
-CODE = {"f32": 0, "f16": 1, "bf16": 3, "e4m3": 8, "e5m2": 9, "mxfp4": 10}
-
-
-def to_dev(a):
-    """numpy -> CUDA tensor (uint32 bits travel as int32)."""
-    a = np.ascontiguousarray(a) if a.flags.writeable else np.array(a)      # (the shared case arrays are read-only: torch wants its own)
-    return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(DEV)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -59,22 +49,6 @@ def shape_table(eng, dim):
         eng.load_table(t, np.zeros((N, dim), dtype=np.float32))
         _shape_tables[dim] = t
     return _shape_tables[dim]
-
-
-def load_bytes(eng, t, kind, raw):
-    view = {"f32": np.float32, "f16": np.uint16, "bf16": np.uint16}.get(kind, np.uint8)
-    eng.load_table(t, np.ascontiguousarray(raw).view(view), dtype=CODE[kind])
-
-
-def table_bytes(eng, t):
-    """The whole table as it lies in HBM, through emb_copy_to_host."""
-    ptr, n, dim, dt = eng.table_info(t)
-    kind = {v: k for k, v in CODE.items()}.get(dt, "fixed32")
-    stride = rc.formats.mxfp4_row_stride(dim) if kind == "mxfp4" else dim * {"f32": 4, "fixed32": 4, "f16": 2, "bf16": 2}.get(kind, 1)
-    out = np.empty((n, stride), dtype=np.uint8)
-    torch.cuda.synchronize()
-    assert eng._L.emb_copy_to_host(eng._h, out.ctypes.data, ptr, out.nbytes) == 0
-    return out
 
 
 def batch_on_device(width, mode_name, lead=False):
@@ -375,6 +349,47 @@ def test_step_refusals_leave_the_table_alone(eng, ctx, pel):
     rows, grads, _ = gc.reference("i64", "sum", 16)
     assert np.array_equal(table_bytes(eng, 6), gr.sgd_step("f32", gc.step_table("f32", 16), rows, grads, gc.LR))
     ctx.report()
+
+
+def test_a_refusal_by_launch_size_leaves_the_earlier_table_alone(eng, pel):
+    """Descriptor 1 is more than one launch of the element-wise kernel takes: its dim, 524 289, is odd, and 2^20 indices of it are
+    2^20 * 524 289 / 256 = 2 147 487 744 workgroups, above 2^31 - 1.  That is found in the plan of the call, before anything is
+    enqueued: descriptor 0's table and state keep every byte, no bad position is counted, and a step issued right afterwards on
+    the same context gives the reference's bytes -- nothing of the refused call was left on the stream."""
+    wide, big_n, eps = 524289, 1 << 20, np.float32(1e-10)
+    assert (big_n * wide + 255) // 256 == 2147487744 > 2 ** 31 - 1
+    idx, off, *_ = batch_on_device("u32", "sum")
+    G = to_dev(gc.grads(8, overflow=False))
+    rows, grads, n_bad = gc.reference("u32", "sum", 8, overflow=False)
+    init = gc.step_table("f32", 8)
+    s0 = np.abs(np.random.default_rng(3).standard_normal((N, 8))).astype(np.float32)
+    eng.alloc_table(9, 1, wide, pel.lib.EMB_F32)
+    idx1, off1 = to_dev(np.zeros(big_n, np.uint32)), to_dev(np.zeros(1, np.uint32))      # 2^20 times row 0, in one bag
+    G1, st1 = (torch.zeros((1, wide), dtype=torch.float32, device=DEV) for _ in range(2))
+    with eng.grad_context(big_n, 512) as big:
+        def step(which, tables, idxs, offs, Gs, states):
+            if which == "adagrad":
+                big.adagrad_step(tables, idxs, offs, Gs, states, gc.LR, eps=eps)
+            else:
+                big.sgd_step(tables, idxs, offs, Gs, gc.LR, multi=which == "sgd_multi")
+        for which in ("sgd", "sgd_multi", "adagrad"):
+            load_bytes(eng, 8, "f32", init)
+            st0 = to_dev(s0)
+            with pytest.raises(pel.PimembError) as ei:
+                step(which, [8, 9], [idx, idx1], [off, off1], [G, G1], [st0, st1])
+            assert ei.value.code == pel.lib.EMB_ERR_UNSUPPORTED, which
+            assert "more elements than one launch of the element-wise kernel takes" in str(ei.value), str(ei.value)
+            assert np.array_equal(table_bytes(eng, 8), init), which
+            assert np.array_equal(bits(st0.cpu().numpy()), bits(s0)), which
+            assert big.report() == 0, which
+            step(which, [8], [idx], [off], [G], [st0])
+            if which == "adagrad":
+                want, want_state = orf.adagrad_step("f32", init, s0, rows, grads, gc.LR, eps, rowwise=False)
+            else:
+                want, want_state = gr.sgd_step("f32", init, rows, grads, gc.LR), s0
+            assert np.array_equal(table_bytes(eng, 8), want), which
+            assert np.array_equal(bits(st0.cpu().numpy()), bits(want_state)), which
+            assert big.report() == n_bad == 5, which
 
 
 # ---- the torch surface ----------------------------------------------------------------------------------------------------------

@@ -16,22 +16,15 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import grad_order_cases as oc  # noqa: E402
 import grad_ref as gr  # noqa: E402
 import optim_ref as orf  # noqa: E402
+from grad_gpu import DEV, F, load_bytes, table_bytes, to_dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-F = np.float32
 LR, EPS = oc.LR, F(1e-10)
-CODE = {"f32": 0, "f16": 1, "bf16": 3}
 MAX_N = 4097
 # (coefficient path, index width, offsets None with fixed_pooling = 1)
 VARIANTS = [(p, w, f) for p in oc.PATHS for w in ("u32", "i64") for f in (False, True)]
 ROW_SENTINEL, GRAD_SENTINEL = -7, 12345.0
-
-
-def to_dev(a):
-    a = np.ascontiguousarray(a) if a.flags.writeable else np.array(a)
-    return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(DEV)
 
 
 def host(x):
@@ -69,18 +62,6 @@ def shape_table(eng, pel, nr_rows, dim):
         eng.alloc_table(t, nr_rows, dim, pel.lib.EMB_F16)
         _shape_tables[key] = t
     return _shape_tables[key]
-
-
-def load_bytes(eng, t, kind, raw):
-    eng.load_table(t, np.ascontiguousarray(raw).view({"f32": np.float32}.get(kind, np.uint16)), dtype=CODE[kind])
-
-
-def table_bytes(eng, t):
-    ptr, n, dim, dt = eng.table_info(t)
-    out = np.empty((n, dim * (4 if dt == CODE["f32"] else 2)), dtype=np.uint8)
-    torch.cuda.synchronize()
-    assert eng._L.emb_copy_to_host(eng._h, out.ctypes.data, ptr, out.nbytes) == 0
-    return out
 
 
 def device_batch(case, dim, path, width, fixed, narrow=False):

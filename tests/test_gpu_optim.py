@@ -18,23 +18,12 @@ import grad_ref as gr  # noqa: E402
 import optim_ref as orf  # noqa: E402
 import pool_ref  # noqa: E402
 import rows_cases as rc  # noqa: E402
+from grad_gpu import DEV, F, bits, load_bytes, table_bytes, to_dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 N = gc.NR_ROWS
-F = np.float32
 LR, EPS = F(0.1), F(1e-10)
-CODE = {"f32": 0, "f16": 1, "bf16": 3, "e4m3": 8, "e5m2": 9, "mxfp4": 10}
-
-
-def to_dev(a):
-    a = np.ascontiguousarray(a) if a.flags.writeable else np.array(a)
-    return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(DEV)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=F).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -49,21 +38,6 @@ def ctx(eng):
     c = eng.grad_context(4096, 512)
     yield c
     c.close()
-
-
-def load_bytes(eng, t, kind, raw):
-    view = {"f32": np.float32, "f16": np.uint16, "bf16": np.uint16}.get(kind, np.uint8)
-    eng.load_table(t, np.ascontiguousarray(raw).view(view), dtype=CODE[kind])
-
-
-def table_bytes(eng, t):
-    ptr, n, dim, dt = eng.table_info(t)
-    kind = {v: k for k, v in CODE.items()}.get(dt, "fixed32")
-    stride = rc.formats.mxfp4_row_stride(dim) if kind == "mxfp4" else dim * {"f32": 4, "fixed32": 4, "f16": 2, "bf16": 2}.get(kind, 1)
-    out = np.empty((n, stride), dtype=np.uint8)
-    torch.cuda.synchronize()
-    assert eng._L.emb_copy_to_host(eng._h, out.ctypes.data, ptr, out.nbytes) == 0
-    return out
 
 
 def batch_on_device(width, mode_name):

@@ -19,14 +19,19 @@ The per-kernel split and the launches per step are a kernel-trace matter, in a r
 Without --step every shape runs as a child process of its own under its own time limit, and the probe stops at the first one
 that fails or runs out of time.
 
-    python tools/grad_multi_probe.py --out grad_multi_probe.json [--parent-grad-lib PATH]
+    python tools/grad_multi_probe.py --out grad_multi_probe.json [--parent-grad-lib PATH [--repeats R]]
+
+--repeats R (with a parent build) adds, per shape, R rounds of both builds' emb_grad_sgd and emb_grad_sgd_multi through the C ABI:
+the check of a change to the host side, whose effect must lie within the spread of the parent's own repeats.
 """
 import argparse
 import ctypes as C
 import json
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -45,6 +50,46 @@ def shape_of(name, pel):
     if name == "uniform8":
         return [4 << 20] * 8, 128, 32, 2048
     raise SystemExit(f"unknown shape {name}")
+
+
+def repeats_against_parent(pel, eng, ctx, args, timed, tabs, idx, off, G, max_indices, max_bags):
+    """--repeats R: emb_grad_sgd and emb_grad_sgd_multi of this build and of the parent's, straight through the C ABI over ONE
+    descriptor array (no Python marshalling in the figure), and of a second load of each build as the control, all timed in turn,
+    R rounds: {name: [us per call, ...]}.  The spread between the parent's own figures -- over the rounds and over its two loads --
+    is the yardstick for a change that leaves the kernels alone."""
+    import torch
+    T = len(tabs)
+    arr, keep = (pel.lib.EmbGradDesc * T)(), []
+    itype = {ctx._desc(arr[t], t, idx[t], off[t], G[t], "sum", None, None, 0, keep)[0] for t in range(T)}.pop()
+    stream = torch.cuda.current_stream().cuda_stream
+    # each build twice: the second from a copy of the file, so it is a library of its own with its own code object and context --
+    # what differs between the two is what differs between ANY two loads of the same code (the control)
+    tmp, parent = tempfile.mkdtemp(), os.path.abspath(args.parent_grad_lib)
+    libs = {"": (ctx._G, ctx._h)}
+    for name, path in (("again_", shutil.copy(ctx._G._name, os.path.join(tmp, "this_again.so"))), ("parent_", parent),
+                       ("parent_again_", shutil.copy(parent, os.path.join(tmp, "parent_again.so")))):
+        P = C.CDLL(path)
+        for fn in ("emb_grad_create", "emb_grad_destroy", "emb_grad_sgd", "emb_grad_sgd_multi"):
+            getattr(P, fn).restype, getattr(P, fn).argtypes = pel.lib.GRAD_SIGNATURES[fn]
+        h = C.c_void_p()
+        assert P.emb_grad_create(eng._h, max_indices, max_bags, C.byref(h)) == 0
+        libs[name] = (P, h)
+
+    def call(lib, handle, fn):
+        def run():
+            assert getattr(lib, fn)(handle, arr, T, itype, 0.01, stream) == 0
+        return run
+    runs = {name + what: call(lib, h, fn) for what, fn in (("multi", "emb_grad_sgd_multi"), ("single", "emb_grad_sgd")) for name, (lib, h) in libs.items()}
+    out = {k: [] for k in runs}
+    for _ in range(args.repeats):
+        for k, run in runs.items():
+            out[k].append(timed(run))
+    torch.cuda.synchronize()
+    for name, (P, h) in libs.items():
+        if name:
+            P.emb_grad_destroy(h)
+    shutil.rmtree(tmp)
+    return out
 
 
 def run_step(name, args):
@@ -88,6 +133,8 @@ def run_step(name, args):
     if args.what in ("all", "single"):
         rec["single_us"] = timed(lambda: ctx.sgd_step(tabs, idx, off, G, 0.01))
     assert ctx.report() == 0
+    if args.what == "all" and args.parent_grad_lib and args.repeats > 1:
+        rec["repeats"] = repeats_against_parent(pel, eng, ctx, args, timed, tabs, idx, off, G, T * n, T * B)
     if args.what == "all" and args.parent_grad_lib:
         # the parent commit's libpimemb_grad.so, over the same engine (libpimemb.so is already mapped under its soname) and the very
         # descriptors GradContext fills: its own context, its own kernels
@@ -146,6 +193,7 @@ def main():
     ap.add_argument("--parent-grad-lib", default="", help="a libpimemb_grad.so built from the parent commit: the baseline")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=1, help="with --parent-grad-lib: time both builds' two calls through the C ABI this often, in turn")
     ap.add_argument("--steps", default=",".join(STEPS))
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -154,7 +202,7 @@ def main():
         return 0
     results = []
     for name in args.steps.split(","):
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", name, "--iters", str(args.iters), "--warmup", str(args.warmup)]
+        cmd = [sys.executable, os.path.abspath(__file__), "--step", name, "--iters", str(args.iters), "--warmup", str(args.warmup), "--repeats", str(args.repeats)]
         if args.parent_grad_lib:
             cmd += ["--parent-grad-lib", args.parent_grad_lib]
         try:
@@ -170,6 +218,8 @@ def main():
         print(f"{name:9s} groups {rec['groups']} longest run {rec['longest_run']}  multi {rec['multi_us']:8.1f} us   {rec['baseline']} {rec.get('parent_single_us', rec['single_us']):8.1f} us "
               f"({rec['multi_over_baseline']:.2f}x, {rec['verdict_vs_baseline']})   this build single {rec['single_us']:8.1f} us   torch bwd+sgd "
               f"{rec['torch_bwd_sgd_us']:8.1f} us ({rec['multi_over_torch']:.2f}x, {rec['verdict_vs_torch']})   forward {rec['forward_us']:7.1f} us", flush=True)
+        for k, v in rec.get("repeats", {}).items():
+            print(f"    C ABI, {len(v)} rounds: {k:13s} min {min(v):9.1f}  max {max(v):9.1f} us   " + " ".join(f"{x:.1f}" for x in v), flush=True)
         if args.out:
             with open(args.out, "w") as f:
                 json.dump(results, f, indent=1)
