@@ -52,8 +52,10 @@
  * lane-group shape (the element-wise kernel has no row-wide view of g, and a second reduction is not built for it:
  * EMB_ERR_UNSUPPORTED); a multi-table emb_grad_sparse (it stays single; emb_grad_sgd_multi / emb_grad_step_multi below fuse the
  * steps of several tables); fusing descriptors of different dim, or of the element-wise shape, into one launch (they run on
- * their own, as before); splitting long runs (a row that occurs thousands of times is still one chain walked by one lane
- * group, in the multi-table step as well); the ranged / sharded paths; NaN ordering and payloads, as everywhere in this library.
+ * their own, as before); splitting long runs IN THE POSITION ORDER (there a row that occurs thousands of times is one chain walked
+ * by one lane group, in the multi-table step as well: a context of EMB_GRAD_ORDER_SEGMENTED, below, sums such a row in parallel, in
+ * a second order that is as fixed as this one -- it is opt-in per context and nothing chooses it for the caller); a third level
+ * of that order; the ranged / sharded paths; NaN ordering and payloads, as everywhere in this library.
  *
  * How it runs.  A pre-pass gives every position its bag (binary search in offsets), flags it good / bad / padding, counts cnt
  * per bag for mean, and orders the positions by (row id, position): a stable LSD radix sort over the ceil(log2(nr_rows + 1)) id
@@ -78,6 +80,10 @@
  * Zipf ids, one row occurring 9 035 times: 3.7 ms, 14x SLOWER than torch (260 us) -- that row's sum is one chain of 9 035 ordered
  * additions walked by one lane group, eight loads in flight at a time; splitting it would change the bits.  A step is 12 - 18x
  * the forward lookup of the same batch (3 - 6 us), and with short runs 63 - 87 % of it is the pre-pass: 13 small launches.
+ * A context of EMB_GRAD_ORDER_SEGMENTED (below; profiles/grad_segmented/README.md, medians of five alternating rounds) takes that
+ * Zipf step in 134 us at S = 64: 28x faster than the position order, 1.9x faster than torch; the 26 Criteo-Kaggle tables (runs of
+ * 13 114) by the multi-table step in 0.50 ms against 13.9 ms, 2.2x faster than torch.  Where no run is longer than S it pays for its
+ * extra launch: 83 against 72 us on the uniform shape (SLOWER than the position order by 15 %), 52 against 49 us on the Kaggle one.
  *
  * Threading.  A context owns one scratch area: calls on one context must not overlap -- issue them from one thread and on one
  * stream (or order the streams yourself).  Steps must not run concurrently with table management on the engine
@@ -120,8 +126,56 @@ const char *emb_grad_last_error(void);
 uint64_t emb_grad_scratch_bytes(uint64_t max_indices, uint64_t max_bags);
 
 /* A context for tables of engine `e`, for calls of up to max_indices indices (1 .. 2^30) and max_bags bags (1 .. 2^31 - 1).  All
- * memory a call uses is allocated here, once. */
+ * memory a call uses is allocated here, once.  Its sums follow the position order. */
 int emb_grad_create(emb_engine *e, uint64_t max_indices, uint64_t max_bags, emb_grad **out);
+
+/* THE SEGMENTED ORDER: a second, equally fixed order of additions, which long runs can be summed in in parallel.  It is a property
+ * of the context, chosen when it is created; the position order stays the default, and a context of one order never gives the
+ * other's bits.  tests/grad_seg_ref.py restates it as a loop; the kernels are compared with that, bit for bit.
+ *   EMB_GRAD_ORDER_SEGMENTED with segment length S, a power of two, 8 <= S <= 1024.  For a row r with good positions
+ *   p1 < p2 < ... < pk and the contributions c_p defined at the top, let m = ceil(k / S):
+ *       t_j  = (((+0.0f + c_p[jS+1]) + c_p[jS+2]) + ...) + c_p[min((j+1)S, k)]      j = 0 .. m-1: position order inside a segment
+ *       g[r] = ((t_0 + t_1) + t_2) + ... + t_(m-1)                                   segment order, starting FROM t_0
+ *   Every addition is rounded on its own; nothing is contracted into an FMA.
+ * Segments are counted by a position's ordinal within ITS OWN ROW'S run, never by its place in the sorted batch: g[r] depends on
+ * that row's occurrences alone -- not on the rest of the batch, and not on which tables share a group of a multi-table call, whose
+ * tables and states therefore still end with the bytes of the per-descriptor calls.
+ * For k <= S + 1 the result is bit-identical to the position order: t_0 is the old chain, and a last segment of one element adds
+ * that element itself (+0 + c differs from c for c = -0 only, and t_0 + (+0) = t_0 + (-0): a chain that starts from +0 is never
+ * -0).  Everything else is unchanged: U, good / bad / padding positions, dec, enc, the SGD, Adagrad and row-wise Adagrad steps, the
+ * row-wise pair tree, every refusal, the bad-position count.  Every call on a segmented context follows the order:
+ * emb_grad_sparse, emb_grad_sgd, emb_grad_step and the two _multi calls, on the lane-group kernels and on the element-wise one.
+ * How it runs.  Behind the sort one more launch, one lane group per sorted place, sums every segment of every run longer than S
+ * in position order -- the run walk bounded to S occurrences, live only where a segment starts -- and stores t_j in 16-byte pieces
+ * into the context's partial buffer; the hot kernels' segmented twins then read t_0, t_1, ... of such a run, eight independent
+ * loads in flight, and add them in segment order.  A run of up to S occurrences is walked as before.  A segment's slot in the
+ * buffer follows from its first sorted place alone (csrc/pimemb_grad_segments.h: at most two segments of long runs start in any
+ * S-aligned block of places, and then the second is a run head: 2 * ceil(n / S) slots, no scan).  The element-wise kernel folds
+ * the segments of a run in one thread, a nested loop: the same bits, no buffer, and no gain in speed.
+ * Out of scope: a third level (a row with k occurrences still ends in one chain of ceil(k / S) partials: 2^20 occurrences at S = 64
+ * are 16 384 dependent additions); choosing the order or S from the batch. */
+typedef enum { EMB_GRAD_ORDER_POSITION = 0, EMB_GRAD_ORDER_SEGMENTED = 1 } emb_grad_order;
+typedef struct emb_grad_config {
+    uint32_t order;    /* an emb_grad_order */
+    uint32_t segment;  /* SEGMENTED: S, a power of two in 8 .. 1024; POSITION: 0 */
+    uint32_t max_dim;  /* SEGMENTED: the largest dim of a table a call may name, 1 or more (the engine sets no upper limit on a
+                          table's dim, so none is set here); POSITION: 0 */
+    uint32_t reserved; /* 0 */
+} emb_grad_config;
+
+/* Bytes of DEVICE memory emb_grad_create_ex allocates.  EMB_GRAD_ORDER_POSITION: emb_grad_scratch_bytes(max_indices, max_bags).
+ * EMB_GRAD_ORDER_SEGMENTED adds the partial buffer: 2 * ceil(max_indices / S) slots of ceil(min(max_dim, 512) / 4) pieces of 16
+ * bytes (512: the widest row of the lane-group kernels; wider tables run element-wise and use no buffer), rounded up to 256 bytes.
+ * A pure function, monotone in max_indices, max_bags and max_dim; 0 for a config emb_grad_create_ex refuses. */
+uint64_t emb_grad_scratch_bytes_ex(uint64_t max_indices, uint64_t max_bags, const emb_grad_config *cfg);
+
+/* emb_grad_create with the order of additions chosen; with EMB_GRAD_ORDER_POSITION it IS emb_grad_create.  EMB_ERR_INVALID for a
+ * NULL config, an unknown order, a segment that is no power of two in 8 .. 1024, max_dim 0, reserved != 0, and segment or max_dim
+ * other than 0 with EMB_GRAD_ORDER_POSITION -- checked before the engine is looked at.  On a segmented context a descriptor whose
+ * table has dim > max_dim is EMB_ERR_INVALID, found with the other checks, before anything is enqueued. */
+int emb_grad_create_ex(emb_engine *e, uint64_t max_indices, uint64_t max_bags, const emb_grad_config *cfg, emb_grad **out);
+/* The config the context was created with (emb_grad_create: EMB_GRAD_ORDER_POSITION, zeros). */
+int emb_grad_config_of(const emb_grad *g, emb_grad_config *out);
 /* Waits for the device, then frees the context.  Destroy contexts before emb_destroy of their engine. */
 int emb_grad_destroy(emb_grad *g);
 

@@ -20,6 +20,10 @@
 //                       its class and its key = key_base[descriptor] + row id in that descriptor's terms
 //   grad_multi_rows     grad_rows_group over the runs of the composite keys: a lane group finds its run's descriptor from the
 //                       key and walks the run with that descriptor's pointers -- the same device functions, the same bits
+// The segmented order (a context of EMB_GRAD_ORDER_SEGMENTED: a run longer than S is summed segment by segment, then over the segments):
+//   grad_seg_partials / grad_seg_multi_partials     one lane group per sorted place, working where a segment of a long run starts:
+//                       that segment's sum, stored into the context's partial buffer (csrc/pimemb_grad_segments.h numbers the slots)
+//   grad_seg_rows_group / grad_seg_multi_rows / grad_seg_rows_elem     the hot kernels' twins: a long run is the sum of its partials
 // The Adagrad tails (csrc/pimemb_grad_optim.h) end the same kernels; the row-wise one sums the row's squares over its lane group
 // with an xor butterfly -- a fixed tree, stated over dim alone in the header: the same bits on every run.
 // Every fp32 operation of the definition is a statement of its own under `fp contract(off)` (and the unit is compiled with
@@ -37,6 +41,7 @@
 
 #include "pimemb_grad.h"
 #include "pimemb_grad_optim.h"
+#include "pimemb_grad_segments.h"
 #include "pimemb_grad_step.h"
 
 namespace {
@@ -606,6 +611,273 @@ __global__ __launch_bounds__(kBlock) void grad_rows_elem(RowArgs a) {
     if (KIND == RES_ADAGRAD) *sp = st;
 }
 
+// ---- EMB_GRAD_ORDER_SEGMENTED: the same kernels over a second, equally fixed order of additions -----------------------------------
+// A run longer than S is summed in two levels: t_j, the sum of its j-th segment of S occurrences in position order from +0, and
+// g = ((t_0 + t_1) + t_2) + ...  The partials launch computes every t_j of every long run in parallel, one lane group per segment,
+// into the context's partial buffer (csrc/pimemb_grad_segments.h numbers the slots); the hot kernels' segmented twins read them
+// back in segment order.  A run of up to S occurrences is walked as before.  The kernels above keep their text and their machine
+// code: what is segmented lives in the kernels below, and their extra arguments travel in SegArgs, not in RowArgs / MultiArgs.
+
+struct SegArgs {
+    float4 *partials;            // [n_slots][chunks]: t_j of the segment in slot seg_slot(its first sorted place), piece by piece
+    uint32_t S, S_log2;
+    uint32_t n_slots;            // slots the buffer holds at this call's `chunks`: the bound of every slot number
+};
+
+// Whether sorted place i (key `key`, a good one) starts a segment of a long run: 0 no, 1 yes, 2 yes and it is the run's head.
+// A head starts one iff the run reaches S places further.  Any other place lies fewer than S places behind its head unless
+// keys[i - S] is the same key; only then is the head looked for, as the lower bound of `key` in the sorted keys [0, i - S].
+__device__ __forceinline__ int seg_start_kind(const uint32_t *keys, uint32_t n, uint32_t i, uint32_t key, uint32_t S) {
+    if (i == 0 || keys[i - 1] != key) return i + S < n && keys[i + S] == key ? 2 : 0;      // (i < n <= 2^30, S <= 1024)
+    if (i < S || keys[i - S] != key) return 0;
+    uint32_t lo = 0, hi = i - S;                 // keys[hi] == key: the head lies in [lo, hi]
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return ((i - lo) & (S - 1u)) == 0 ? 1 : 0;
+}
+
+// walk_piece bounded to one segment: t_j[4c .. 4c + 3] of the segment that starts at sorted place i, its up to S occurrences summed
+// in position order from +0, eight loads in flight (S is a multiple of eight: a full segment is whole rounds).
+__device__ __forceinline__ float4 walk_segment(const RowArgs &a, uint32_t i, uint32_t row, uint32_t c, uint32_t S) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint32_t end = min(i + S, a.n);
+    uint32_t j = i;
+    for (;;) {
+        bool live[kAhead];
+        float4 g[kAhead];
+        float s[kAhead];
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {      // (a dead slot re-reads the round's first occurrence)
+            live[k] = k == 0 || (live[k - 1] && j + k < end && a.keys[j + k] == row);
+            const uint32_t p = min(a.vals[live[k] ? j + k : j], a.n - 1u);
+            const uint32_t b = min(a.bagof[p], a.n_bags - 1u);
+            s[k] = coef_of(a, p, b);
+            g[k] = *reinterpret_cast<const float4 *>(a.grad + (uint64_t)b * a.ld + 4u * c);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {      // the adds, in position order
+            if (live[k]) {
+                acc.x = add_in_order(acc.x, contribution(a.coef, g[k].x, s[k]));
+                acc.y = add_in_order(acc.y, contribution(a.coef, g[k].y, s[k]));
+                acc.z = add_in_order(acc.z, contribution(a.coef, g[k].z, s[k]));
+                acc.w = add_in_order(acc.w, contribution(a.coef, g[k].w, s[k]));
+            }
+        }
+        if (!live[kAhead - 1]) break;
+        j += kAhead;
+        if (j >= end || a.keys[j] != row) break;
+    }
+    return acc;
+}
+
+// The run walk of one piece in the segmented order.  A run of up to S occurrences is walk_piece's; a longer one is the sum of its
+// partials, starting from t_0: the loads of eight of them (and of the keys that say whether their segments exist) are independent
+// of each other and in flight together, the adds in segment order.  The slot of a segment follows from its place alone.
+__device__ __forceinline__ float4 seg_walk_piece(const RowArgs &a, const SegArgs &sg, uint32_t i, uint32_t row, uint32_t c, uint32_t chunks) {
+    if (!(i + sg.S < a.n && a.keys[i + sg.S] == row)) return walk_piece(a, i, row, c);
+    float4 acc = sg.partials[(uint64_t)min(seg_slot(i, sg.S_log2, true), sg.n_slots - 1u) * chunks + c];      // t_0 itself: the sum starts from it
+    uint32_t j = i + sg.S;                       // where the round's first segment starts: t_1 exists, the run being long
+    for (;;) {
+        uint32_t live = 1;                       // segments of this round that exist: the first `live` of its eight
+        float4 t[kAhead];
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {      // (a dead slot re-reads the round's first partial)
+            const uint32_t at = j + k * sg.S;        // (j < n <= 2^30, k * S < 2^13)
+            if (k > 0 && live == k && at < a.n && a.keys[at] == row) live = k + 1;
+            const uint32_t slot = min(seg_slot(k < live ? at : j, sg.S_log2, false), sg.n_slots - 1u);
+            t[k] = sg.partials[(uint64_t)slot * chunks + c];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {      // the adds, in segment order
+            if (k < live) {
+                acc.x = add_in_order(acc.x, t[k].x);
+                acc.y = add_in_order(acc.y, t[k].y);
+                acc.z = add_in_order(acc.z, t[k].z);
+                acc.w = add_in_order(acc.w, t[k].w);
+            }
+        }
+        if (live < kAhead) break;
+        j += kAhead * sg.S;
+        if (j >= a.n || a.keys[j] != row) break;
+    }
+    return acc;
+}
+
+// The partials of the long runs' segments: a lane group that starts one sums it, lane lg the pieces lg, lg + lanes, and stores
+// them with plain vector stores.
+__device__ __forceinline__ void seg_partials_body(const RowArgs &a, const SegArgs &sg, uint32_t i, uint32_t key, int kind, uint32_t lg, uint32_t lanes,
+                                                  uint32_t chunks) {
+    const uint32_t slot = min(seg_slot(i, sg.S_log2, kind == 2), sg.n_slots - 1u);
+    for (uint32_t c = lg; c < chunks; c += lanes) sg.partials[(uint64_t)slot * chunks + c] = walk_segment(a, i, key, c, sg.S);
+}
+
+// One lane group per sorted place, as grad_rows_group is launched; it works where a segment of a long run starts.
+__global__ __launch_bounds__(kBlock) void grad_seg_partials(RowArgs a, SegArgs sg, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= a.n || lg >= chunks) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows) return;
+    const int kind = seg_start_kind(a.keys, a.n, i, row, sg.S);           // (uniform over the lane group)
+    if (kind) seg_partials_body(a, sg, i, row, kind, lg, lanes, chunks);
+}
+
+// What grad_rows_group does with a run, in the segmented order; `key` is what the run's places hold, `row` the table row it names.
+template <int KIND>
+__device__ __forceinline__ void seg_rows_body(const RowArgs &a, const SegArgs &sg, uint32_t i, uint32_t key, uint32_t row, uint32_t lg, uint32_t lanes,
+                                              uint32_t chunks) {
+    if (KIND == RES_ROWWISE) {
+        const bool own0 = lg < chunks, own1 = lg + lanes < chunks;
+        float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
+        if (own0) acc0 = seg_walk_piece(a, sg, i, key, lg, chunks);
+        if (own1) acc1 = seg_walk_piece(a, sg, i, key, lg + lanes, chunks);
+        const float rate = rowwise_rate(a, row, lg, lanes, acc0, acc1, own1);
+        if (own0) step_piece<KIND>(a, row, lg, acc0, rate);
+        if (own1) step_piece<KIND>(a, row, lg + lanes, acc1, rate);
+        return;
+    }
+    for (uint32_t c = lg; c < chunks; c += lanes) {
+        const float4 acc = seg_walk_piece(a, sg, i, key, c, chunks);
+        if (KIND == RES_SPARSE) {
+            const uint32_t u = a.uidx[i] + a.usums[i / kTile];
+            if (c == 0) a.rows_out[u] = (long long)row;
+            *reinterpret_cast<float4 *>(a.grads_out + (uint64_t)u * a.dim + 4u * c) = acc;
+        } else {
+            step_piece<KIND>(a, row, c, acc, a.lr);
+        }
+    }
+}
+
+// grad_rows_group in the segmented order (launched behind grad_seg_partials, with the same geometry).
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void grad_seg_rows_group(RowArgs a, SegArgs sg, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= a.n || (KIND != RES_ROWWISE && lg >= chunks)) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;      // (uniform over the lane group)
+    seg_rows_body<KIND>(a, sg, i, row, row, lg, lanes, chunks);
+}
+
+// The RowArgs of the descriptor a composite key belongs to, as grad_multi_rows fills them; *row = the table row the key names.
+__device__ __forceinline__ RowArgs multi_row_args(const MultiArgs &m, uint32_t key, const uint32_t *keys, const uint32_t *vals, const uint32_t *bagof,
+                                                  const uint32_t *cnt, float lr, float eps, uint32_t *row) {
+    uint32_t k = 0;
+    for (uint32_t j = 1; j < m.k; j++)
+        if (m.d[j].key_base <= key) k = j;
+    const MultiDesc &d = m.d[k];
+    RowArgs a{};
+    a.keys = keys;
+    a.vals = vals;
+    a.bagof = bagof;
+    a.cnt = cnt + d.bag_base;
+    a.weights = d.weights ? d.weights - d.pos_base : nullptr;             // (vals[] hold positions of the group)
+    a.grad = d.grad;
+    a.ld = d.ld;
+    a.n = m.n;
+    a.n_bags = d.n_bags;
+    a.nr_rows = d.nr_rows;
+    a.dim = m.dim;
+    a.coef = d.coef;
+    a.table = d.table;
+    a.stride = d.stride;
+    a.dtype = d.dtype;
+    a.lr = lr;
+    a.state = d.state;
+    a.eps = eps;
+    *row = key - d.key_base;
+    return a;
+}
+
+// grad_seg_partials over the runs of a group's composite keys: adjacent keys of two tables are two runs, as everywhere.
+__global__ __launch_bounds__(kBlock) void grad_seg_multi_partials(const MultiArgs m, const uint32_t *keys, const uint32_t *vals, const uint32_t *bagof,
+                                                                  const uint32_t *cnt, SegArgs sg, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= m.n || lg >= chunks) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t key = keys[i];
+    if (key >= m.key_end) return;
+    const int kind = seg_start_kind(keys, m.n, i, key, sg.S);
+    if (!kind) return;
+    uint32_t row;
+    const RowArgs a = multi_row_args(m, key, keys, vals, bagof, cnt, 0.f, 0.f, &row);
+    seg_partials_body(a, sg, i, key, kind, lg, lanes, chunks);
+}
+
+// grad_multi_rows in the segmented order.
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void grad_seg_multi_rows(const MultiArgs m, const uint32_t *keys, const uint32_t *vals, const uint32_t *bagof,
+                                                              const uint32_t *cnt, float lr, float eps, SegArgs sg, uint32_t lanes, uint32_t lanes_log2,
+                                                              uint32_t chunks) {
+    static_assert(KIND != RES_SPARSE, "the multi-table path steps; emb_grad_sparse stays single");
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= m.n || (KIND != RES_ROWWISE && lg >= chunks)) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t key = keys[i];
+    if (key >= m.key_end || (i > 0 && keys[i - 1] == key)) return;        // (uniform over the lane group)
+    uint32_t row;
+    const RowArgs a = multi_row_args(m, key, keys, vals, bagof, cnt, lr, eps, &row);
+    seg_rows_body<KIND>(a, sg, i, key, row, lg, lanes, chunks);
+}
+
+// grad_rows_elem in the segmented order: the thread of an element folds segment after segment itself, a nested loop in one
+// chain -- the same bits as the lane-group kernels, no partial buffer, and no gain in speed.
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void grad_seg_rows_elem(RowArgs a, uint32_t S) {
+    static_assert(KIND != RES_ROWWISE, "the element-wise kernel has no row-wide view of g");
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid / a.dim;
+    const uint32_t c = (uint32_t)(gid - i64 * a.dim);
+    if (i64 >= a.n) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;
+    float acc = 0.f, t = 0.f;
+    uint32_t in_seg = 0;
+    bool first = true;                           // t_0 is taken as it is: the sum of the partials starts from it
+    for (uint32_t j = i; j < a.n && a.keys[j] == row; j++) {
+        const uint32_t p = min(a.vals[j], a.n - 1u);
+        const uint32_t b = min(a.bagof[p], a.n_bags - 1u);
+        t = add_in_order(t, contribution(a.coef, a.grad[(uint64_t)b * a.ld + c], coef_of(a, p, b)));
+        if (++in_seg == S) {
+            acc = first ? t : add_in_order(acc, t);
+            first = false;
+            t = 0.f;
+            in_seg = 0;
+        }
+    }
+    if (in_seg) acc = first ? t : add_in_order(acc, t);
+    if (KIND == RES_SPARSE) {
+        const uint32_t u = a.uidx[i] + a.usums[i / kTile];
+        if (c == 0) a.rows_out[u] = (long long)row;
+        a.grads_out[(uint64_t)u * a.dim + c] = acc;
+        return;
+    }
+    float *sp = KIND == RES_ADAGRAD ? a.state + (uint64_t)row * a.dim + c : nullptr;
+    float st = KIND == RES_ADAGRAD ? *sp : 0.f;
+    if (a.dtype == kStepF32) {
+        float *w = reinterpret_cast<float *>(a.table + (uint64_t)row * a.stride) + c;
+        if (KIND == RES_ADAGRAD) *w = bits_f32(adagrad_step(kStepF32, f32_bits(*w), acc, &st, a.lr, a.eps));
+        else *w = step_f32(*w, acc, a.lr);
+    } else {
+        uint16_t *w = reinterpret_cast<uint16_t *>(a.table + (uint64_t)row * a.stride) + c;
+        if (KIND == RES_ADAGRAD) *w = (uint16_t)adagrad_step(a.dtype, *w, acc, &st, a.lr, a.eps);
+        else *w = (uint16_t)step(a.dtype, *w, acc, a.lr);
+    }
+    if (KIND == RES_ADAGRAD) *sp = st;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 
 thread_local char t_err[512] = "";
@@ -644,9 +916,10 @@ uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
 
 // The scratch area: offsets of its pieces for a context of N indices and B bags.
 struct Layout {
-    uint64_t keys[2], vals[2], bagof, uidx, hist, sums, cnt, counters, total;
+    uint64_t keys[2], vals[2], bagof, uidx, hist, sums, cnt, counters, partials, total;
 };
-Layout layout_of(uint64_t N, uint64_t B) {
+// (seg_S == 0: the position order, whose area is what it was; otherwise the partial buffer of the segmented order lies behind it)
+Layout layout_of(uint64_t N, uint64_t B, uint32_t seg_S = 0, uint32_t max_dim = 0) {
     if (N > kMaxIndices) N = kMaxIndices;
     if (B > kMaxBags) B = kMaxBags;
     if (N == 0) N = 1;
@@ -668,6 +941,8 @@ Layout layout_of(uint64_t N, uint64_t B) {
     l.sums = take((tiles_of(hist_len > N ? hist_len : N) + 1) * 4);
     l.cnt = take((B ? B : 1) * 4);
     l.counters = take(kCounterBytes);
+    l.partials = at;
+    if (seg_S) take(seg_buffer_bytes(N, seg_S, max_dim));
     l.total = at;
     return l;
 }
@@ -681,7 +956,25 @@ struct emb_grad {
     char *scratch = nullptr;
     Layout lay{};
     unsigned long long *counters = nullptr;      // [0] bad positions since the last report
+    emb_grad_config cfg{};                       // the order of additions of every call on this context
+    uint32_t seg_log2 = 0;                       // EMB_GRAD_ORDER_SEGMENTED: log2 of cfg.segment
+    bool segmented() const { return cfg.order == EMB_GRAD_ORDER_SEGMENTED; }
 };
+
+namespace {
+
+// Everything that can be refused about a config; NULL text: it is fine.
+const char *config_fault(const emb_grad_config *cfg) {
+    if (!cfg) return "the config is NULL";
+    if (cfg->reserved != 0) return "the config's reserved field must be 0";
+    if (cfg->order == EMB_GRAD_ORDER_POSITION) return cfg->segment || cfg->max_dim ? "segment and max_dim must be 0 with EMB_GRAD_ORDER_POSITION" : nullptr;
+    if (cfg->order != EMB_GRAD_ORDER_SEGMENTED) return "unknown order";
+    if (!seg_length_ok(cfg->segment)) return "segment must be a power of two in 8 .. 1024";
+    if (cfg->max_dim == 0) return "max_dim must be at least 1";
+    return nullptr;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -689,7 +982,26 @@ const char *emb_grad_last_error(void) { return t_err; }
 
 uint64_t emb_grad_scratch_bytes(uint64_t max_indices, uint64_t max_bags) { return layout_of(max_indices, max_bags).total; }
 
+uint64_t emb_grad_scratch_bytes_ex(uint64_t max_indices, uint64_t max_bags, const emb_grad_config *cfg) {
+    if (config_fault(cfg)) return 0;
+    return layout_of(max_indices, max_bags, cfg->order == EMB_GRAD_ORDER_SEGMENTED ? cfg->segment : 0u, cfg->max_dim).total;
+}
+
 int emb_grad_create(emb_engine *e, uint64_t max_indices, uint64_t max_bags, emb_grad **out) {
+    const emb_grad_config position{EMB_GRAD_ORDER_POSITION, 0, 0, 0};
+    return emb_grad_create_ex(e, max_indices, max_bags, &position, out);
+}
+
+int emb_grad_config_of(const emb_grad *g, emb_grad_config *out) {
+    if (!g || !out) return fail(EMB_ERR_INVALID, "emb_grad_config_of: context or out is NULL");
+    *out = g->cfg;
+    return EMB_OK;
+}
+
+int emb_grad_create_ex(emb_engine *e, uint64_t max_indices, uint64_t max_bags, const emb_grad_config *cfg, emb_grad **out) {
+    if (const char *fault = config_fault(cfg))
+        return fail(EMB_ERR_INVALID, "emb_grad_create: %s (order %u, segment %u, max_dim %u, reserved %u)", fault, cfg ? cfg->order : 0u, cfg ? cfg->segment : 0u,
+                    cfg ? cfg->max_dim : 0u, cfg ? cfg->reserved : 0u);
     if (!e || !out) return fail(EMB_ERR_INVALID, "emb_grad_create: engine or out is NULL");
     if (max_indices == 0 || max_indices > kMaxIndices) return fail(EMB_ERR_INVALID, "emb_grad_create: max_indices must be 1 .. 2^30");
     if (max_bags == 0 || max_bags > kMaxBags) return fail(EMB_ERR_INVALID, "emb_grad_create: max_bags must be 1 .. 2^31 - 1");
@@ -700,7 +1012,9 @@ int emb_grad_create(emb_engine *e, uint64_t max_indices, uint64_t max_bags, emb_
     g->device = dev;
     g->max_indices = max_indices;
     g->max_bags = max_bags;
-    g->lay = layout_of(max_indices, max_bags);
+    g->cfg = *cfg;
+    g->seg_log2 = g->segmented() ? seg_log2(cfg->segment) : 0u;
+    g->lay = layout_of(max_indices, max_bags, g->segmented() ? cfg->segment : 0u, cfg->max_dim);
     DeviceGuard guard(dev);
     void *p = nullptr;
     if (int rc = emb_device_alloc(e, g->lay.total, &p)) {
@@ -748,6 +1062,9 @@ int check_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, const 
     __builtin_memcpy(&t->dtype, &dt, sizeof(int));      // (the fp8 / MXFP4 values lie outside the enum's range: pimemb.h)
     t->rows = static_cast<char *>(rows);
     if (t->dtype == kFixed32) return fail(EMB_ERR_UNSUPPORTED, "%s: table %u is EMB_FIXED32: a fixed-point table has no gradient here", who, d.table_id);
+    if (g->segmented() && t->dim > g->cfg.max_dim)
+        return fail(EMB_ERR_INVALID, "%s: table %u has dim %u, the context's segmented order was created for a max_dim of %u", who, d.table_id, t->dim,
+                    g->cfg.max_dim);
     if (d.pool.mode == EMB_POOL_MAX)
         return fail(EMB_ERR_UNSUPPORTED, "%s: EMB_POOL_MAX needs the forward's per-element argmax, which no kernel records", who);
     if (d.pool.mode != EMB_POOL_SUM && d.pool.mode != EMB_POOL_MEAN) return fail(EMB_ERR_INVALID, "%s: unknown pooling mode %u", who, d.pool.mode);
@@ -983,6 +1300,24 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
     int cur = 0;
     if (int rc = sort_pairs(sc, n, c.key_end, s, &cur)) return rc;
     const uint32_t *keys = sc.keys[cur], *vals = sc.vals[cur];
+    const bool seg = g->segmented();
+    SegArgs sg{};                                // (filled for the lane-group kernels of a segmented context only)
+    if (seg && c.lane) {
+        sg.partials = reinterpret_cast<float4 *>(g->scratch + g->lay.partials);
+        sg.S = g->cfg.segment, sg.S_log2 = g->seg_log2;
+        sg.n_slots = (uint32_t)seg_slots(g->max_indices, sg.S);      // (l.chunks <= seg_pieces(max_dim): check_desc; max_indices <= 2^30)
+    }
+    if (group && seg) {
+        const dim3 grid(l.blocks);
+        grad_seg_multi_partials<<<grid, block, 0, s>>>(m, keys, vals, sc.bagof, sc.cnt, sg, l.lanes, l.lanes_log2, l.chunks);
+        if (spec.kind == RES_SGD)
+            grad_seg_multi_rows<RES_SGD><<<grid, block, 0, s>>>(m, keys, vals, sc.bagof, sc.cnt, spec.lr, spec.eps, sg, l.lanes, l.lanes_log2, l.chunks);
+        else if (spec.kind == RES_ADAGRAD)
+            grad_seg_multi_rows<RES_ADAGRAD><<<grid, block, 0, s>>>(m, keys, vals, sc.bagof, sc.cnt, spec.lr, spec.eps, sg, l.lanes, l.lanes_log2, l.chunks);
+        else grad_seg_multi_rows<RES_ROWWISE><<<grid, block, 0, s>>>(m, keys, vals, sc.bagof, sc.cnt, spec.lr, spec.eps, sg, l.lanes, l.lanes_log2, l.chunks);
+        GRAD_HIP(hipGetLastError());
+        return EMB_OK;
+    }
     if (group) {
         const dim3 grid(l.blocks);
         if (spec.kind == RES_SGD) grad_multi_rows<RES_SGD><<<grid, block, 0, s>>>(m, keys, vals, sc.bagof, sc.cnt, spec.lr, spec.eps, l.lanes, l.lanes_log2, l.chunks);
@@ -1007,7 +1342,19 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
         GRAD_HIP(hipGetLastError());
         a.uidx = sc.uidx, a.usums = sc.sums, a.rows_out = out.rows, a.grads_out = out.grads;
     }
-    if (c.lane) {
+    if (seg && c.lane) {
+        const dim3 grid(l.blocks);
+        grad_seg_partials<<<grid, block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
+        if (spec.kind == RES_SGD) grad_seg_rows_group<RES_SGD><<<grid, block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
+        else if (spec.kind == RES_ADAGRAD) grad_seg_rows_group<RES_ADAGRAD><<<grid, block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
+        else if (spec.kind == RES_ROWWISE) grad_seg_rows_group<RES_ROWWISE><<<grid, block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
+        else grad_seg_rows_group<RES_SPARSE><<<grid, block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
+    } else if (seg) {
+        const dim3 grid(c.elem_blocks);
+        if (spec.kind == RES_SGD) grad_seg_rows_elem<RES_SGD><<<grid, block, 0, s>>>(a, g->cfg.segment);
+        else if (spec.kind == RES_ADAGRAD) grad_seg_rows_elem<RES_ADAGRAD><<<grid, block, 0, s>>>(a, g->cfg.segment);
+        else grad_seg_rows_elem<RES_SPARSE><<<grid, block, 0, s>>>(a, g->cfg.segment);
+    } else if (c.lane) {
         const dim3 grid(l.blocks);
         if (spec.kind == RES_SGD) grad_rows_group<RES_SGD><<<grid, block, 0, s>>>(a, l.lanes, l.lanes_log2, l.chunks);
         else if (spec.kind == RES_ADAGRAD) grad_rows_group<RES_ADAGRAD><<<grid, block, 0, s>>>(a, l.lanes, l.lanes_log2, l.chunks);

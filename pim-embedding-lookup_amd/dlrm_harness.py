@@ -7,7 +7,8 @@ empty submodule here; flags from README.md:6,10,14 and upmem/run.sh:72-82,111-12
 `--inference-only` runs); `--fused-sgd LR` trains the tables: apply_emb's result is attached to the autograd graph and
 loss.backward() applies the fused SGD step of the backward pass (include/pimemb_grad.h) to the served tables;
 `--fused-adagrad LR` / `--fused-rowwise-adagrad LR` do the same with the fused Adagrad / row-wise Adagrad step (the three are
-mutually exclusive; `--multi-table-step` sends them through the multi-table entry points).  No MLPs -- the rest of the model is out of scope.
+mutually exclusive; `--multi-table-step` sends them through the multi-table entry points, `--segmented-sums [S]` makes them sum in the
+segmented order of additions).  No MLPs -- the rest of the model is out of scope.
 
     python -m pim_embedding_lookup_amd.dlrm_harness --arch-sparse-feature-size=16 \
         --arch-embedding-size=1460-583-10131227-… --mini-batch-size=39292 --inference-only
@@ -82,6 +83,7 @@ class EmbeddingBagCollection:
         self._ids = list(range(len(self.ln_emb)))
         self._fused_lr = None
         self.multi_table_step = False                           # the fused steps go through the multi-table entry points (--multi-table-step)
+        self.segmented_sums = None                              # the fused steps' segment length in the segmented order of additions; None: position order (--segmented-sums)
         self._fused_adagrad, self.adagrad_sum = None, None      # (lr, eps, rowwise) and the per-table fp32 states of enable_fused_adagrad
         # DLRM --weighted-pooling: v_W_l[k] is a weight per ROW of table k (ones for "fixed", the checkpoint's for "learned");
         # a bag entry is weighted by its row's weight, gathered with torch (dlrm_s_pytorch.py: v_W_l[k].gather(0, indices))
@@ -192,7 +194,8 @@ class EmbeddingBagCollection:
             live = [k for k, x in enumerate(grads) if x is not None]
             multi = bool(self.multi_table_step)      # (its context holds all tables' indices and bags at once)
             size = sum if multi else max
-            ctx = tm._grad_context(self.engine, size(i.shape[0] for i in lS_i), size(o.shape[0] for o in lS_o))
+            order = ("segmented", self.m, int(self.segmented_sums)) if self.segmented_sums else ("position",)
+            ctx = tm._grad_context(self.engine, size(i.shape[0] for i in lS_i), size(o.shape[0] for o in lS_o), *order)
             args = ([self._ids[k] for k in live], [lS_i[k] for k in live], [lS_o[k] for k in live], [grads[k] for k in live])
             w_live = [None if ws is None else ws[k] for k in live]
             if ada is None:
@@ -371,6 +374,10 @@ def main(argv=None):
     ap.add_argument("--multi-table-step", action="store_true",
                     help="with one of the --fused-* flags: step the tables through the multi-table entry points (one pre-pass and one "
                          "launch per group of up to 16 tables instead of per table; the same bytes)")
+    ap.add_argument("--segmented-sums", type=int, nargs="?", const=0, default=None, metavar="S",
+                    help="with one of the --fused-* flags: sum a row's occurrences in segments of S (a power of two, 8 .. 1024; "
+                         "default: GradContext's), the segmented order of include/pimemb_grad.h -- for skewed ids, where some rows "
+                         "occur thousands of times in a batch; as fixed as the position order, other bits")
     args, ignored = ap.parse_known_args(argv)
     if ignored:   # MLP / training / logging flags of the reference command lines (README.md:6,10,14)
         print("ignored (outside the embedding path):", " ".join(ignored))
@@ -380,6 +387,8 @@ def main(argv=None):
         raise SystemExit("--fused-sgd, --fused-adagrad and --fused-rowwise-adagrad are mutually exclusive")
     if args.multi_table_step and not fused:
         raise SystemExit("--multi-table-step goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
+    if args.segmented_sums is not None and not fused:
+        raise SystemExit("--segmented-sums goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
     if not args.inference_only and not fused:
         print("note: running the inference embedding path (--inference-only implied); --fused-sgd LR / --fused-adagrad LR / "
               "--fused-rowwise-adagrad LR train the tables")
@@ -427,6 +436,9 @@ def main(argv=None):
     if fused:      # forward + dummy loss + backward = lookup + the fused step on every table
         opt_name, opt_lr = fused[0]
         ebc.multi_table_step = bool(args.multi_table_step)
+        if args.segmented_sums is not None:
+            from .engine import GradContext
+            ebc.segmented_sums = args.segmented_sums or GradContext.DEFAULT_SEGMENT
         if opt_name == "SGD":
             ebc.enable_fused_sgd(opt_lr)
         else:
@@ -443,8 +455,8 @@ def main(argv=None):
             train_step(*batches[b % len(batches)])
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.num_batches
-        print(f"apply_emb + loss.backward() with the fused {opt_name} step (lr {opt_lr}){', multi-table' if args.multi_table_step else ''}: "
-              f"{dt * 1e3:.4f} ms/batch")
+        print(f"apply_emb + loss.backward() with the fused {opt_name} step (lr {opt_lr}){', multi-table' if args.multi_table_step else ''}"
+              f"{', segmented sums of %d' % ebc.segmented_sums if ebc.segmented_sums else ''}: {dt * 1e3:.4f} ms/batch")
         ebc.close()
         return 0
     if ebc.v_W_l is not None:     # (prepared plans hold the sum path only)

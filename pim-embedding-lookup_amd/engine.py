@@ -381,17 +381,38 @@ class GradContext:
     """The backward pass over an engine's tables (libpimemb_grad.so, include/pimemb_grad.h): from the gradient of a pooled
     lookup's output to the table's sparse gradient, or straight to stepped rows (fused SGD) -- every sum in position order, the
     same bits on every run.  EmbeddingEngine.grad_context makes one.  One context, one thread, one stream at a time: its scratch
-    is shared by its calls."""
+    is shared by its calls.
+    order="segmented": every call of the context sums a row's occurrences in segments of `segment` (a power of two, 8 .. 1024;
+    default DEFAULT_SEGMENT) whose sums are then added in segment order -- EMB_GRAD_ORDER_SEGMENTED of the header: as fixed as the
+    position order, other bits where a row occurs more than segment + 1 times, and long runs summed in parallel.  max_dim: the
+    widest table a call may name (default 512, the widest row of the lane-group kernels; the partial buffer grows with it up to
+    there).  .order, .segment and .max_dim say what the context was made with (None, None for the position order)."""
 
-    def __init__(self, engine: "EmbeddingEngine", max_indices: int, max_bags: int):
+    DEFAULT_SEGMENT = 64
+    DEFAULT_MAX_DIM = 512
+
+    def __init__(self, engine: "EmbeddingEngine", max_indices: int, max_bags: int, order: str = "position", segment: int | None = None,
+                 max_dim: int | None = None):
         if engine._L is not _l.load():
             raise ValueError("the backward pass works with the default libpimemb.so (the one libpimemb_grad.so links against), not with a lib_path engine")
+        if order not in _l.GRAD_ORDERS:
+            raise ValueError(f"order has to be one of {sorted(_l.GRAD_ORDERS)}, got {order!r}")
+        if order == "position" and (segment is not None or max_dim is not None):
+            raise ValueError("segment and max_dim go with order='segmented'")
         self.engine = engine
         self.max_indices, self.max_bags = int(max_indices), int(max_bags)
         self._G = _l.load_grad()
+        cfg = _l.EmbGradConfig(_l.GRAD_ORDERS[order], 0, 0, 0)
+        if order == "segmented":
+            cfg.segment = self.DEFAULT_SEGMENT if segment is None else int(segment)
+            cfg.max_dim = self.DEFAULT_MAX_DIM if max_dim is None else int(max_dim)
         h = C.c_void_p()
-        _l.check_grad(self._G.emb_grad_create(engine._h, self.max_indices, self.max_bags, C.byref(h)))
+        _l.check_grad(self._G.emb_grad_create_ex(engine._h, self.max_indices, self.max_bags, C.byref(cfg), C.byref(h)))
         self._h = h.value
+        made = _l.EmbGradConfig()
+        _l.check_grad(self._G.emb_grad_config_of(self._h, C.byref(made)))
+        self.order = {v: k for k, v in _l.GRAD_ORDERS.items()}[made.order]
+        self.segment, self.max_dim = (int(made.segment), int(made.max_dim)) if self.order == "segmented" else (None, None)
         engine._writers.append(self)
 
     def _desc(self, d, table_id, indices, offsets, grad, mode, weights, padding_idx, fixed_pooling, keep):
@@ -705,10 +726,12 @@ class EmbeddingEngine:
         (host-pointer calls of any size are chunked): see RowWriter.update.  Closed with the engine at the latest."""
         return RowWriter(self, max_rows)
 
-    def grad_context(self, max_indices: int = 1 << 20, max_bags: int = 1 << 20) -> GradContext:
+    def grad_context(self, max_indices: int = 1 << 20, max_bags: int = 1 << 20, order: str = "position", segment: int | None = None,
+                     max_dim: int | None = None) -> GradContext:
         """A context for the backward pass over this engine's tables (sparse gradients, the fused SGD step), for calls of up
-        to max_indices indices and max_bags bags per table: see GradContext.  Closed with the engine at the latest."""
-        return GradContext(self, max_indices, max_bags)
+        to max_indices indices and max_bags bags per table: see GradContext.  order="segmented" (with segment and max_dim): the
+        segmented order of additions, for batches in which rows occur thousands of times.  Closed with the engine at the latest."""
+        return GradContext(self, max_indices, max_bags, order, segment, max_dim)
 
     def load_table_f32(self, table_id: int, rows_f32, dtype: int, chunk_rows: int = 65536) -> None:
         """Allocate table `table_id` as `dtype` (any but EMB_FIXED32) and fill it from float32 rows [nr_rows, dim], encoded ON

@@ -234,6 +234,14 @@ class EmbGradMultiShape(C.Structure):
                 ("n_indices", C.c_uint64), ("n_bags", C.c_uint64)]
 
 
+EMB_GRAD_ORDER_POSITION, EMB_GRAD_ORDER_SEGMENTED = 0, 1
+GRAD_ORDERS = {"position": EMB_GRAD_ORDER_POSITION, "segmented": EMB_GRAD_ORDER_SEGMENTED}
+
+
+class EmbGradConfig(C.Structure):
+    _fields_ = [("order", C.c_uint32), ("segment", C.c_uint32), ("max_dim", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # name -> (restype, argtypes); every function declared in include/pimemb_grad.h (libpimemb_grad.so, the backward pass: the third
 # library, with its own code object as well)
 GRAD_SIGNATURES = {
@@ -241,6 +249,9 @@ GRAD_SIGNATURES = {
     "emb_grad_scratch_bytes": (_u64, [_u64, _u64]),
     "emb_grad_create": (C.c_int, [_vp, _u64, _u64, _pp]),
     "emb_grad_destroy": (C.c_int, [_vp]),
+    "emb_grad_scratch_bytes_ex": (_u64, [_u64, _u64, C.POINTER(EmbGradConfig)]),
+    "emb_grad_create_ex": (C.c_int, [_vp, _u64, _u64, C.POINTER(EmbGradConfig), _pp]),
+    "emb_grad_config_of": (C.c_int, [_vp, C.POINTER(EmbGradConfig)]),
     "emb_grad_sparse": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.c_int, _vp, _vp, _u64, _vp, _vp]),
     "emb_grad_sgd": (C.c_int, [_vp, C.POINTER(EmbGradDesc), _u32, C.c_int, C.c_float, _vp]),
     "emb_grad_report": (C.c_int, [_vp, C.POINTER(_u64)]),

@@ -337,20 +337,25 @@ class PoolingEmbeddingBag(torch.nn.Module):
             return lookup()
         return _FusedSGD.apply(_anchor(self, idx.device), lookup, lambda g: self._step(idx, off, g, lr, w))
 
-    def enable_fused_sgd(self, lr: float):
+    def enable_fused_sgd(self, lr: float, order: str = "position"):
         """From now on forward() returns a tensor attached to the autograd graph, and its backward applies weight -= lr * grad
         to the served table (sgd_step_ with the inputs forward saw): loss.backward() is the whole training step of this table.
-        lr=None switches it off again.  Switches a fused Adagrad off (its state stays).  Returns self."""
+        lr=None switches it off again.  Switches a fused Adagrad off (its state stays).  order="segmented": a row's occurrences
+        are summed in the segmented order of include/pimemb_grad.h (GradContext) -- for batches that name some rows thousands of
+        times; as fixed as the position order, other bits.  Returns self."""
+        object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
         object.__setattr__(self, "_fused_adagrad", None)
         return self
 
-    def enable_fused_adagrad(self, lr: float, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0):
-        """As enable_fused_sgd, with the fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row) of
+    def enable_fused_adagrad(self, lr: float, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0,
+                             order: str = "position"):
+        """As enable_fused_sgd (order= included), with the fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row) of
         include/pimemb_grad.h: torch.optim.Adagrad(lr, eps=eps, initial_accumulator_value=...) without lr_decay and weight_decay.
         The fp32 state -- module.adagrad_sum, [num_embeddings, embedding_dim] or [num_embeddings] -- is allocated once, filled with
         initial_accumulator_value, kept over later calls (a change of `rowwise` allocates it anew), and saved by state_dict() as
         `<prefix>adagrad_sum`.  lr=None switches the step off (the state stays).  Switches a fused SGD off.  Returns self."""
+        object.__setattr__(self, "_fused_order", _order(order))
         if lr is None:
             object.__setattr__(self, "_fused_adagrad", None)
             return self
@@ -364,27 +369,32 @@ class PoolingEmbeddingBag(torch.nn.Module):
         """The Adagrad state (float32 CUDA tensor), or None before enable_fused_adagrad / adagrad_step_ made one."""
         return getattr(self, "_adagrad_sum", None)
 
-    def _step(self, idx, off, grad_output, lr, w):
+    def _context(self, idx, off, order=None):
+        """The engine's backward context of `order` (None: the one enable_fused_* chose; the position order if none did)."""
+        order = getattr(self, "_fused_order", "position") if order is None else _order(order)
+        return _grad_context(self.engine, idx.shape[0], off.shape[0], order, self.embedding_dim)
+
+    def _step(self, idx, off, grad_output, lr, w, order=None):
         if grad_output is None:
             return
         g = _grad_view(grad_output, self.embedding_dim)
-        _grad_context(self.engine, idx.shape[0], off.shape[0]).sgd_step(self._id_list, [idx], [off], [g], lr, modes=self.mode,
-                                                                        per_sample_weights=w, padding_idx=self.padding_idx)
+        self._context(idx, off, order).sgd_step(self._id_list, [idx], [off], [g], lr, modes=self.mode, per_sample_weights=w,
+                                                padding_idx=self.padding_idx)
 
-    def _adagrad(self, idx, off, grad_output, lr, eps, w):
+    def _adagrad(self, idx, off, grad_output, lr, eps, w, order=None):
         if grad_output is None:
             return
         g = _grad_view(grad_output, self.embedding_dim)
         state = _adagrad_state(self)
-        _grad_context(self.engine, idx.shape[0], off.shape[0]).adagrad_step(self._id_list, [idx], [off], [g], [state], lr, eps=eps,
-                                                                            rowwise=state.dim() == 1, modes=self.mode, per_sample_weights=w,
-                                                                            padding_idx=self.padding_idx)
+        self._context(idx, off, order).adagrad_step(self._id_list, [idx], [off], [g], [state], lr, eps=eps, rowwise=state.dim() == 1,
+                                                    modes=self.mode, per_sample_weights=w, padding_idx=self.padding_idx)
 
-    def adagrad_step_(self, input, offsets, grad_output, lr: float, eps: float = 1e-10, per_sample_weights=None):
+    def adagrad_step_(self, input, offsets, grad_output, lr: float, eps: float = 1e-10, per_sample_weights=None, order: str = "position"):
         """One fused Adagrad step on the rows the batch names, in place and in stream order with forward(), on the module's state
-        (adagrad_sum; of the flavour enable_fused_adagrad chose, or element-wise zeros if there is none yet).  Returns self."""
+        (adagrad_sum; of the flavour enable_fused_adagrad chose, or element-wise zeros if there is none yet).  order: as
+        enable_fused_sgd.  Returns self."""
         idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
-        self._adagrad(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), float(eps), w)
+        self._adagrad(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), float(eps), w, order)
         return self
 
     def _bags_on_device(self, input, offsets, per_sample_weights):
@@ -393,22 +403,24 @@ class PoolingEmbeddingBag(torch.nn.Module):
         w = _weights_for(None if per_sample_weights is None else torch.as_tensor(per_sample_weights).to(dev), self.mode, input)
         return idx.contiguous(), off.contiguous(), w
 
-    def sparse_grad(self, input, offsets, grad_output, per_sample_weights=None):
+    def sparse_grad(self, input, offsets, grad_output, per_sample_weights=None, order: str = "position"):
         """The gradient of the weight for one batch: a coalesced torch.sparse_coo_tensor [num_embeddings, embedding_dim] (fp32, on the
-        GPU) -- rows ascending, each the sum of its contributions in position order -- as nn.EmbeddingBag(sparse=True) leaves it in
-        weight.grad after .coalesce(), without the all-zero rows torch lists for padding entries.  The weight is not changed."""
+        GPU) -- rows ascending, each the sum of its contributions in position order (order="segmented": in the segmented order) --
+        as nn.EmbeddingBag(sparse=True) leaves it in weight.grad after .coalesce(), without the all-zero rows torch lists for
+        padding entries.  The weight is not changed."""
         idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
         g = _grad_view(torch.as_tensor(grad_output).to(idx.device), self.embedding_dim)
-        rows, grads = _grad_context(self.engine, idx.shape[0], off.shape[0]).sparse_grad(
+        rows, grads = self._context(idx, off, order).sparse_grad(
             self.table_id, idx, off, g, mode=self.mode, per_sample_weights=w, padding_idx=self.padding_idx)
         return torch.sparse_coo_tensor(rows.unsqueeze(0), grads, size=(self.num_embeddings, self.embedding_dim), is_coalesced=True)
 
-    def sgd_step_(self, input, offsets, grad_output, lr: float, per_sample_weights=None):
+    def sgd_step_(self, input, offsets, grad_output, lr: float, per_sample_weights=None, order: str = "position"):
         """weight[r] -= lr * grad[r] for every row the batch names, in place and in stream order with forward(): one fp32
         multiply and one fp32 subtract per element, rounded once into the weight's dtype (fp32 / fp16 / bf16).  Entries whose
-        index lies outside the table are skipped and counted (engine._module_grad.report()).  Returns self."""
+        index lies outside the table are skipped and counted (engine._module_grad.report()).  order: as enable_fused_sgd.
+        Returns self."""
         idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
-        self._step(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), w)
+        self._step(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), w, order)
         return self
 
     def update_rows_(self, ids, rows):
@@ -452,13 +464,27 @@ class PoolingEmbeddingBag(torch.nn.Module):
 _GRAD_INDICES = 65536     # indices per call of the modules' shared backward context (it grows when a batch is larger)
 
 
-def _grad_context(engine: EmbeddingEngine, n_indices: int, n_bags: int):
-    """The backward context the modules of one engine share; replaced by a larger one when a batch does not fit."""
-    g = getattr(engine, "_module_grad", None)
-    if g is None or not g._h or g.max_indices < n_indices or g.max_bags < n_bags:
+def _order(order: str) -> str:
+    if order not in ("position", "segmented"):
+        raise ValueError(f"order has to be 'position' or 'segmented', got {order!r}")
+    return order
+
+
+def _grad_context(engine: EmbeddingEngine, n_indices: int, n_bags: int, order: str = "position", dim: int = 0, segment: int | None = None):
+    """The backward context of `order` the modules of one engine share -- one per order: engine._module_grad (the position order)
+    and engine._module_grad_segmented -- replaced by a larger one when a batch, or for the segmented order a table of `dim`, does
+    not fit.  segment: the segment length to use (None: the one in use, or GradContext's default)."""
+    attr = "_module_grad" if order == "position" else "_module_grad_segmented"
+    g = getattr(engine, attr, None)
+    seg = order == "segmented"
+    if g is None or not g._h or g.max_indices < n_indices or g.max_bags < n_bags or (seg and (g.max_dim < dim or segment not in (None, g.segment))):
+        wide = max(int(dim), g.max_dim if g is not None and g.max_dim else 0)
+        segment = g.segment if segment is None and g is not None else segment
         if g is not None and g._h:
             g.close()
-        g = engine._module_grad = engine.grad_context(max(_GRAD_INDICES, int(n_indices)), max(_GRAD_INDICES, int(n_bags)))
+        kw = dict(order="segmented", max_dim=max(wide, 1), segment=segment) if seg else {}
+        g = engine.grad_context(max(_GRAD_INDICES, int(n_indices)), max(_GRAD_INDICES, int(n_bags)), **kw)
+        setattr(engine, attr, g)
     return g
 
 
@@ -599,20 +625,23 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
 
     apply_emb = forward
 
-    def enable_fused_sgd(self, lr: float, multi_table: bool = False):
+    def enable_fused_sgd(self, lr: float, multi_table: bool = False, order: str = "position"):
         """As PoolingEmbeddingBag.enable_fused_sgd, for every table of the model: the backward of forward()'s result -- the list,
         or the one [B, sum(m)] tensor of concat=True -- steps all of them.  multi_table=True: by the multi-table step (one
-        pre-pass and one launch per group of up to 16 tables instead of per table; the same bytes).  Returns self."""
+        pre-pass and one launch per group of up to 16 tables instead of per table; the same bytes).  order: as there.
+        Returns self."""
+        object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_multi", bool(multi_table))
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
         object.__setattr__(self, "_fused_adagrad", None)
         return self
 
     def enable_fused_adagrad(self, lr: float, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0,
-                             multi_table: bool = False):
+                             multi_table: bool = False, order: str = "position"):
         """As PoolingEmbeddingBag.enable_fused_adagrad, for every table of the model: each bag holds its own state
-        (bags[k].adagrad_sum, saved as `bags.<k>.adagrad_sum`), one call steps them all.  multi_table: as enable_fused_sgd.
-        Returns self."""
+        (bags[k].adagrad_sum, saved as `bags.<k>.adagrad_sum`), one call steps them all.  multi_table and order: as
+        enable_fused_sgd.  Returns self."""
+        object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_multi", bool(multi_table))
         if lr is None:
             object.__setattr__(self, "_fused_adagrad", None)
@@ -628,7 +657,7 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         """The bags' Adagrad states, in table order (None where a bag has none)."""
         return [b.adagrad_sum for b in self.bags]
 
-    def _live_grads(self, idx, off, grad_output, ws, col, multi=False):
+    def _live_grads(self, idx, off, grad_output, ws, col, multi=False, order=None):
         """What a step of either optimizer is called with: (the backward context, positional arguments, keyword arguments, the
         tables' numbers in the module list) over the tables that have a gradient, or None when none has.  multi: the context
         holds the live tables' indices and bags all at once (their sums), so that the multi-table step can fuse them."""
@@ -649,22 +678,23 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         if not live:
             return None
         size = sum if multi else max
-        ctx = _grad_context(self.engine, size(idx[k].shape[0] for k in live), size(off[k].shape[0] for k in live))
+        order = getattr(self, "_fused_order", "position") if order is None else _order(order)
+        ctx = _grad_context(self.engine, size(idx[k].shape[0] for k in live), size(off[k].shape[0] for k in live), order, max(dims))
         args = ([self._ids[k] for k in live], [idx[k] for k in live], [off[k] for k in live], [grads[k] for k in live])
         kw = dict(modes=[self._modes[k] for k in live], per_sample_weights=[None if ws is None else ws[k] for k in live],
                   padding_idx=[self._pads[k] for k in live])
         return ctx, args, kw, live
 
-    def _step(self, idx, off, grad_output, lr, ws, col=0, multi=None):
+    def _step(self, idx, off, grad_output, lr, ws, col=0, multi=None, order=None):
         multi = getattr(self, "_fused_multi", False) if multi is None else bool(multi)
-        call = self._live_grads(idx, off, grad_output, ws, col, multi)
+        call = self._live_grads(idx, off, grad_output, ws, col, multi, order)
         if call is not None:
             ctx, args, kw, _live = call
             ctx.sgd_step(*args, lr, multi=multi, **kw)
 
-    def _adagrad(self, idx, off, grad_output, lr, eps, ws, col=0, multi=None):
+    def _adagrad(self, idx, off, grad_output, lr, eps, ws, col=0, multi=None, order=None):
         multi = getattr(self, "_fused_multi", False) if multi is None else bool(multi)
-        call = self._live_grads(idx, off, grad_output, ws, col, multi)
+        call = self._live_grads(idx, off, grad_output, ws, col, multi, order)
         if call is None:
             return
         ctx, args, kw, live = call
@@ -689,19 +719,20 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             grad_output = torch.as_tensor(grad_output).to(dev)
         return idx, off, None if lS_w is None else ws, grad_output
 
-    def sgd_step_(self, lS_o, lS_i, grad_output, lr: float, lS_w=None, multi_table: bool = False):
+    def sgd_step_(self, lS_o, lS_i, grad_output, lr: float, lS_w=None, multi_table: bool = False, order: str = "position"):
         """PoolingEmbeddingBag.sgd_step_ for all tables in one call.  grad_output: a list of [B, m_k] gradients, or the ONE
         [B, sum(m)] gradient of a concat=True forward, which is read in place (each table's columns through the row stride).
-        multi_table: as enable_fused_sgd."""
+        multi_table and order: as enable_fused_sgd."""
         idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
-        self._step(idx, off, g, float(lr), ws, multi=multi_table)
+        self._step(idx, off, g, float(lr), ws, multi=multi_table, order=order)
         return self
 
-    def adagrad_step_(self, lS_o, lS_i, grad_output, lr: float, eps: float = 1e-10, lS_w=None, multi_table: bool = False):
+    def adagrad_step_(self, lS_o, lS_i, grad_output, lr: float, eps: float = 1e-10, lS_w=None, multi_table: bool = False,
+                      order: str = "position"):
         """PoolingEmbeddingBag.adagrad_step_ for all tables in one call, on the bags' states; grad_output as sgd_step_ takes it: the
-        ONE [B, sum(m)] gradient of a concat=True forward is read in place.  multi_table: as enable_fused_sgd."""
+        ONE [B, sum(m)] gradient of a concat=True forward is read in place.  multi_table and order: as enable_fused_sgd."""
         idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
-        self._adagrad(idx, off, g, float(lr), float(eps), ws, multi=multi_table)
+        self._adagrad(idx, off, g, float(lr), float(eps), ws, multi=multi_table, order=order)
         return self
 
     def update_rows_(self, table: int, ids, rows):
