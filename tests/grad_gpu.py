@@ -1,5 +1,6 @@
 """What the GPU tests of the backward pass share (tests/test_gpu_grad.py, test_gpu_optim.py, test_gpu_grad_multi.py,
-test_gpu_grad_order.py): arrays to the device, tables in and out as bytes.  A plain module like tests/grad_cases.py; the engine
+test_gpu_grad_order.py, test_gpu_grad_segmented.py, test_gpu_grad_segmented_ragged.py, test_gpu_grad_graph.py): arrays to the device,
+tables in and out as bytes, the assertions on tables and states, the ragged batch on the device.  A plain module like tests/grad_cases.py; the engine
 and context fixtures stay in the test files, their contexts differ in size.  Nothing here runs the code under test."""
 import os
 import sys
@@ -25,6 +26,23 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=F).view(np.uint32)
 
 
+def host(x):
+    return x.cpu().numpy() if hasattr(x, "cpu") else x
+
+
+def check_table(got, want, what):
+    """The assertion of every table comparison: every byte of every row."""
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert bad.size == 0, (what, "table rows", bad[:8], got[bad[0]][:16], want[bad[0]][:16])
+
+
+def check_state(d_state, want, what):
+    """The assertion of every optimizer-state comparison: every bit of every row's state."""
+    got = host(d_state).reshape(want.shape)
+    bad = np.flatnonzero((bits(got) != bits(want)).reshape(want.shape[0], -1).any(axis=1))
+    assert bad.size == 0, (what, "state rows", bad[:8], got[bad[0]], want[bad[0]])
+
+
 def load_bytes(eng, t, kind, raw):
     view = {"f32": np.float32, "f16": np.uint16, "bf16": np.uint16}.get(kind, np.uint8)
     eng.load_table(t, np.ascontiguousarray(raw).view(view), dtype=CODE[kind])
@@ -39,3 +57,32 @@ def table_bytes(eng, t):
     torch.cuda.synchronize()
     assert eng._L.emb_copy_to_host(eng._h, out.ctypes.data, ptr, out.nbytes) == 0
     return out
+
+
+def in_place(G, ld, col):
+    """G as a view of a wider NaN buffer: columns col .. col + dim of ld."""
+    wide = torch.full((G.shape[0], ld), float("nan"), dtype=torch.float32, device=DEV)
+    wide[:, col:col + G.shape[1]] = G
+    return wide[:, col:col + G.shape[1]]
+
+
+class RaggedBatch:
+    """One variant of grad_seg_ref.ragged_case on the device, with what the calls take."""
+
+    def __init__(self, case, mode_name, width, dim, lead=False, narrow=False, bags=None, view=None):
+        ids, off, mode, w, pad = case.args(mode_name, width, lead, bags)
+        self.case, self.key, self.host_args = case, (mode_name, width, dim, lead, narrow, bags), (ids, off, mode, w, pad)
+        self.idx, self.off = to_dev(case.ids_array(width, bags)), to_dev(case.offsets_array(width, lead, bags))
+        self.G = to_dev(case.grads(dim, narrow)[:bags])
+        if view is not None:
+            self.G = in_place(self.G, *view)
+        self.mode, self.pad = mode, pad
+        self.w = None if w is None else to_dev(w)
+        self.n, self.B, self.n_bad = len(ids), len(off), case.n_bad(lead, bags)
+
+    def reference(self, S):
+        mode_name, width, dim, lead, narrow, bags = self.key
+        return self.case.reference(S, mode_name, width, dim, lead, narrow, bags)
+
+    def sparse(self, ctx, t):
+        return ctx.sparse_grad(t, self.idx, self.off, self.G, mode=self.mode, per_sample_weights=self.w, padding_idx=self.pad)

@@ -1,9 +1,11 @@
 """GPU: the segmented order of additions of the backward pass (EMB_GRAD_ORDER_SEGMENTED, include/pimemb_grad.h) on contexts of
-S = 8 and S = 16, bit for bit against tests/grad_seg_ref.py's loop.  The inputs are that module's: one-index bags whose gradient
+S = 8, 16 and 64 (GradContext's default) with every case, of S = 1024 (the maximum) and of S = 32, 128, 256 and 512 with a reduced
+set of runs, bit for bit against tests/grad_seg_ref.py's loop.  The inputs are that module's: one-index bags whose gradient
 columns 0 and 1 overflow as soon as two neighbours inside a segment are added in the wrong order, column 2 the position's number
 (exact sums), column 3 the absorb column -- exactly 1.0 in the position order, above it by an amount that depends on S in the
 segmented one, and on where the segments are cut -- and NaN wherever a position is not good.  tests/test_grad_segmented_cpu.py
-shows that the comparison used here rejects the wrong orders.  n <= 4097 throughout; report() is checked in every case."""
+shows that the comparison used here rejects the wrong orders.  n <= 4097 on the contexts of S = 8 and 16, up to 15 374 on the wider
+ones (where column 2 is no longer exact in any order: grad_seg_ref.reduced_case); report() is checked in every case."""
 import ctypes as C
 import os
 import sys
@@ -17,17 +19,15 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import grad_order_cases as oc  # noqa: E402
 import grad_ref as gr  # noqa: E402
 import grad_seg_ref as sr  # noqa: E402
-from grad_gpu import DEV, F, load_bytes, table_bytes, to_dev  # noqa: E402
+from grad_gpu import DEV, F, check_state, check_table, host, load_bytes, table_bytes, to_dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 LR, EPS = sr.LR, sr.EPS
 MAX_N, MAX_DIM = 4097, 320
+WIDE_N = 16384                       # the contexts of S >= 32: lengths_case(64) has 5523 positions, reduced_case(1024) 15 374
+FULL = sr.SEGMENTS + sr.WIDE_SEGMENTS[:1]      # the segment lengths that run every case
 tm = import_module("pim-embedding-lookup_amd.torch_module")
-
-
-def host(x):
-    return x.cpu().numpy() if hasattr(x, "cpu") else x
 
 
 @pytest.fixture(scope="module")
@@ -41,6 +41,7 @@ def eng(pel):
 def ctxs(eng):
     """{S: a segmented context}, and under "position" a position-order one."""
     c = {S: eng.grad_context(MAX_N, MAX_N, order="segmented", segment=S, max_dim=MAX_DIM) for S in sr.SEGMENTS}
+    c.update({S: eng.grad_context(WIDE_N, WIDE_N, order="segmented", segment=S, max_dim=MAX_DIM) for S in sr.WIDE_SEGMENTS + sr.MID_SEGMENTS})
     c["position"] = eng.grad_context(MAX_N, MAX_N)
     yield c
     for x in c.values():
@@ -103,17 +104,6 @@ def adagrad(ctx, t, batch, d_state, rowwise, pad=None):
                      padding_idx=pad, fixed_pooling=fp)
 
 
-def check_table(got, want, what):
-    bad = np.flatnonzero((got != want).any(axis=1))
-    assert bad.size == 0, (what, "table rows", bad[:8], got[bad[0]][:16], want[bad[0]][:16])
-
-
-def check_state(d_state, want, what):
-    got = host(d_state).reshape(want.shape)
-    bad = np.flatnonzero((oc.bits(got) != oc.bits(want)).reshape(want.shape[0], -1).any(axis=1))
-    assert bad.size == 0, (what, "state rows", bad[:8], got[bad[0]], want[bad[0]])
-
-
 def sgd_case(eng, ctx, case, kind, dim, path, width, fixed, t=2, misaligned=False):
     """One fused SGD step in the segmented order; the WHOLE table is compared."""
     init = oc.step_table(kind, case.nr_rows, dim)
@@ -148,7 +138,7 @@ SPARSE_DIMS = {4: ALL, 16: ALL[1::4], 48: ALL[2::4], 128: ALL[3::4], 320: ALL[0:
 
 
 @pytest.mark.parametrize("dim", list(SPARSE_DIMS))
-@pytest.mark.parametrize("S", sr.SEGMENTS)
+@pytest.mark.parametrize("S", FULL)
 def test_run_lengths_on_both_sides_of_the_segment_boundaries(eng, ctxs, pel, S, dim):
     """In one batch: runs of S-1, S, S+1, S+2, 2S-1, 2S, 2S+1, 3S+5, 8S+3 (nine partials) and 65S+1 (66: several rounds of partial
     loads); three bad ids and a padding id in between, whose NaN rows must never show.  dim 4: one lane; 16; 48: idle lanes in the
@@ -158,7 +148,7 @@ def test_run_lengths_on_both_sides_of_the_segment_boundaries(eng, ctxs, pel, S, 
     check_sparse(ctxs[S], shape_table(eng, pel, case.nr_rows, dim), case, dim, SPARSE_DIMS[dim])
 
 
-@pytest.mark.parametrize("S", sr.SEGMENTS)
+@pytest.mark.parametrize("S", FULL)
 def test_a_misaligned_gradient_runs_the_element_wise_kernel_in_the_same_order(eng, ctxs, pel, S):
     case = sr.lengths_case(S, True)
     check_sparse(ctxs[S], shape_table(eng, pel, case.nr_rows, 8), case, 8, ALL[::5], misaligned=True)
@@ -168,7 +158,7 @@ def test_a_misaligned_gradient_runs_the_element_wise_kernel_in_the_same_order(en
 # ---- run placement -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dim", [4, 16, 5])
 @pytest.mark.parametrize("tail", ["bad", "end"])
-@pytest.mark.parametrize("S", sr.SEGMENTS)
+@pytest.mark.parametrize("S", FULL)
 def test_long_runs_at_the_end_next_to_each_other_and_around_a_short_one(eng, ctxs, pel, S, tail, dim):
     """A long run that ends the good positions with the keys of the positions that are not good directly behind it ("bad"), or ends
     the array ("end"); a run of 2S + 3 directly followed by a run of 2S, so that two segment starts share one S-aligned block of
@@ -177,7 +167,7 @@ def test_long_runs_at_the_end_next_to_each_other_and_around_a_short_one(eng, ctx
     check_sparse(ctxs[S], shape_table(eng, pel, case.nr_rows, dim), case, dim, ALL[(dim + S) % 4::4])
 
 
-@pytest.mark.parametrize("S", sr.SEGMENTS)
+@pytest.mark.parametrize("S", FULL)
 def test_one_row_holds_every_position(eng, ctxs, pel, S):
     case = sr.one_row_case(S)
     assert len(case.seg_reference(S, 8)[0]) == 1
@@ -192,7 +182,7 @@ SGD_SHAPES = [("f32", 128, "sum", "i64", False), ("f16", 48, "weighted", "u32", 
 
 
 @pytest.mark.parametrize("kind,dim,path,width,fixed", SGD_SHAPES, ids=["-".join(map(str, s[:3])) for s in SGD_SHAPES])
-@pytest.mark.parametrize("S", sr.SEGMENTS)
+@pytest.mark.parametrize("S", FULL)
 def test_sgd_step_in_the_segmented_order(eng, ctxs, S, kind, dim, path, width, fixed):
     sgd_case(eng, ctxs[S], sr.lengths_case(S, True), kind, dim, path, width, fixed)
 
@@ -202,7 +192,7 @@ STEP_SHAPES = [("f16", 16, False, "sum", "u32", False), ("f32", 6, False, "mean"
 
 
 @pytest.mark.parametrize("kind,dim,rowwise,path,width,fixed", STEP_SHAPES, ids=["-".join(map(str, s[:3])) for s in STEP_SHAPES])
-@pytest.mark.parametrize("S", sr.SEGMENTS)
+@pytest.mark.parametrize("S", FULL)
 def test_adagrad_steps_in_the_segmented_order(eng, ctxs, S, kind, dim, rowwise, path, width, fixed):
     """Narrow gradients (the squares of +-FLT_MAX would overflow the state): the order rests on the absorb column and the randoms.
     Adagrad on the lane-group kernel and on the element-wise one (dim 6); row-wise Adagrad with idle lanes (dim 48), with two walks
@@ -210,11 +200,41 @@ def test_adagrad_steps_in_the_segmented_order(eng, ctxs, S, kind, dim, rowwise, 
     step_case(eng, ctxs[S], sr.lengths_case(S, True), kind, dim, rowwise, path, width, fixed)
 
 
-@pytest.mark.parametrize("S", sr.SEGMENTS)
+@pytest.mark.parametrize("S", FULL)
 def test_steps_on_the_placement_cases(eng, ctxs, S):
     sgd_case(eng, ctxs[S], sr.placement_case(S, "bad"), "f32", 16, "sum", "u32", False)
     step_case(eng, ctxs[S], sr.placement_case(S, "end"), "bf16", 16, True, "mean", "i64", True)
     step_case(eng, ctxs[S], sr.placement_case(S, "bad"), "f32", 5, False, "sum", "i64", False)
+
+
+# ---- the wider segment lengths on the reduced runs ---------------------------------------------------------------------------------------
+WIDE_DIMS = {4: ALL[0::4], 8: ALL[2::4], 5: ALL[1::4]}
+
+
+@pytest.mark.parametrize("dim", list(WIDE_DIMS))
+def test_segments_of_1024_on_both_sides_of_their_boundaries(eng, ctxs, pel, dim):
+    """The longest segment: 128 rounds of eight loads per segment, a look-ahead of up to 7168 sorted places, 15 374 positions (a
+    binary search over sixteen sort tiles).  Runs of S-1, S, S+1, S+2, 2S+1 and 9S+3 (ten partials: one full round and one more);
+    dims 4 and 8 on the lane-group kernel, 5 on the element-wise one."""
+    S = sr.WIDE_SEGMENTS[-1]
+    case = sr.reduced_case(S)
+    assert ctxs[S].segment == S == 1024 and case.n <= WIDE_N
+    check_sparse(ctxs[S], shape_table(eng, pel, case.nr_rows, dim), case, dim, WIDE_DIMS[dim])
+
+
+def test_steps_in_segments_of_1024(eng, ctxs):
+    S = sr.WIDE_SEGMENTS[-1]
+    case = sr.reduced_case(S)
+    sgd_case(eng, ctxs[S], case, "bf16", 8, "weighted", "u32", False)
+    sgd_case(eng, ctxs[S], case, "f32", 5, "sum", "i64", True)
+    step_case(eng, ctxs[S], case, "f32", 4, True, "mean", "i64", True)
+
+
+@pytest.mark.parametrize("S", sr.MID_SEGMENTS)
+def test_the_segment_lengths_in_between_on_the_reduced_runs(eng, ctxs, pel, S):
+    case = sr.reduced_case(S)
+    assert ctxs[S].segment == S
+    check_sparse(ctxs[S], shape_table(eng, pel, case.nr_rows, 4), case, 4, ALL[S.bit_length() % 4::4])
 
 
 # ---- the multi-table steps -----------------------------------------------------------------------------------------------------------------
@@ -226,7 +246,7 @@ def multi_batches(cases, paths, narrow):
     return ([b[0] for b in batches], [b[1] for b in batches], [b[2] for b in batches]), dict(modes=[b[3] for b in batches], per_sample_weights=[b[4] for b in batches])
 
 
-@pytest.mark.parametrize("S", sr.SEGMENTS)
+@pytest.mark.parametrize("S", FULL)
 def test_multi_table_steps_equal_the_per_table_calls_and_the_reference(eng, ctxs, S):
     """Three tables of one dim in one group; the last row of table k and row 0 of table k + 1 both carry long runs: adjacent
     composite keys, which must not merge.  SGD, Adagrad and row-wise Adagrad; the grouping is what it was."""
@@ -268,7 +288,7 @@ def test_multi_table_steps_equal_the_per_table_calls_and_the_reference(eng, ctxs
 
 
 # ---- compatibility with the position order ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("S", sr.SEGMENTS)
+@pytest.mark.parametrize("S", FULL)
 def test_runs_of_at_most_S_plus_1_give_the_position_orders_bytes(eng, ctxs, pel, S):
     case = sr.short_case(S)
     for dim, path, width in ((8, "sum", "i64"), (5, "weighted", "u32")):

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import grad_cases as gc  # noqa: E402
 import grad_order_cases as oc  # noqa: E402
 import grad_ref as gr  # noqa: E402
 import grad_seg_ref as sr  # noqa: E402
@@ -390,8 +391,8 @@ def test_slot_numbering_is_collision_free_over_enumerated_layouts(tmp_path):
 
 def test_slot_numbering_holds_on_the_test_cases_layouts():
     """The same formula in Python over the sorted layouts of the GPU cases: unique, below 2 * ceil(n / S)."""
-    for S in sr.SEGMENTS:
-        for case in seg_cases(S):
+    for S in sr.SEGMENTS + sr.WIDE_SEGMENTS + sr.MID_SEGMENTS:
+        for case in seg_cases(S) if S <= 64 else [sr.reduced_case(S)]:
             n, used = int(case.good.sum()), set()
             for _r, head, k in sr.sorted_layout(case):
                 if k <= S:
@@ -401,3 +402,259 @@ def test_slot_numbering_holds_on_the_test_cases_layouts():
                     assert slot not in used and slot < 2 * -(-n // S), (case.name, S, start)
                     used.add(slot)
             assert used
+
+
+# ---- the general reference: bags of any shape ----------------------------------------------------------------------------------------------
+from grad_gpu import check_state, check_table  # noqa: E402  (the assertions of the GPU tests; nothing in that module touches a GPU on import)
+
+FOREVER = 1 << 20                    # a segment longer than any run
+
+
+def seg_general(case, S, dim, path, narrow=False):
+    """seg_sparse_grad on a one-index case, fed what the kernels are fed."""
+    return sr.seg_sparse_grad(case.nr_rows, case.ids, case.offsets, case.grads(dim, narrow, weighted=path == "weighted"), S, "mean" if path == "mean" else "sum",
+                              case.weights() if path == "weighted" else None, case.pad)
+
+
+def test_seg_sparse_grad_is_fold_on_the_one_index_cases():
+    for S, case in ((8, sr.lengths_case(8, True)), (8, sr.placement_case(8, "bad")), (16, sr.placement_case(16, "end")), (16, sr.multi_cases(16)[2]),
+                    (8, sr.short_case(8))):
+        for dim, path, narrow in ((4, "sum", False), (5, "weighted", False), (8, "mean", False), (8, "sum", True)):
+            got = seg_general(case, S, dim, path, narrow)
+            oc.check_sparse(got[0], got[1], sr.fold(case, S, dim, path, narrow), (case.name, S, dim, path))
+            assert got[2] == case.n_bad
+    case = sr.placement_case(8, "bad")                    # ... and with bags of fixed_pooling = 1 in place of offsets
+    got = sr.seg_sparse_grad(case.nr_rows, case.ids, None, case.grads(4), 8, n_bags=case.n, fixed_pooling=1)
+    oc.check_sparse(got[0], got[1], case.seg_reference(8, 4), "fixed pooling")
+
+
+@pytest.mark.parametrize("mode_name", list(gc.MODES))
+def test_seg_sparse_grad_with_one_segment_per_run_is_grad_ref(mode_name):
+    for lead in (False, True):
+        got = sr.batch_reference(FOREVER, "i64", mode_name, 4, lead)
+        want = gc.reference("i64", mode_name, 4, lead, overflow=False)
+        oc.check_sparse(got[0], got[1], want, ("batch", mode_name, lead))
+        assert got[2] == want[2] == (4 if lead else 5)
+        case = sr.ragged_case(8)
+        got, want = case.reference(FOREVER, mode_name, "u32", 6, lead), case.reference(None, mode_name, "u32", 6, lead)
+        oc.check_sparse(got[0], got[1], want, (case.name, mode_name, lead))
+        assert got[2] == want[2] == case.n_bad(lead)
+    longest = max(sr.ragged_runs(8).values())             # S = the longest run and S + 1 = longest: still the position order
+    for S in (longest, longest - 1):
+        got = sr.ragged_case(8).reference(S, mode_name, "i64", 4)
+        oc.check_sparse(got[0], got[1], sr.ragged_case(8).reference(None, mode_name, "i64", 4), (S, mode_name))
+
+
+@pytest.mark.parametrize("S", sr.RAGGED_SEGMENTS)
+def test_on_grad_cases_batch_only_the_hot_row_differs_from_the_position_order(S):
+    for mode_name in gc.MODES:
+        rows, seg, _ = sr.batch_reference(S, "i64", mode_name, 4)
+        _, pos, _ = gc.reference("i64", mode_name, 4, overflow=False)
+        differs = (oc.bits(seg) != oc.bits(pos)).any(axis=1)
+        assert rows[differs].tolist() == [gc.HOT], (S, mode_name, rows[differs])
+
+
+# ---- the ragged case ------------------------------------------------------------------------------------------------------------------------
+def differing(a, b):
+    """The rows whose gradients differ in bits between two references of one batch."""
+    assert np.array_equal(a[0], b[0])
+    return a[0][(oc.bits(a[1]) != oc.bits(b[1])).any(axis=1)].tolist()
+
+
+@pytest.mark.parametrize("S", sr.RAGGED_SEGMENTS)
+def test_ragged_case_holds_what_its_docstring_says(S):
+    case, runs = sr.ragged_case(S), sr.ragged_runs(S)
+    ids, off, lens = case.bad_ids("i64"), case.offsets(), case.lens
+    assert abs(case.n - (16 * S + 300)) <= 120 and case.nr_rows == 499 and case.B & (case.B - 1) and len(off) == case.B
+    assert lens.min() == 0 and lens.max() == 13 and len(set(lens.tolist())) >= 13 and int(lens.sum()) == case.n
+    assert all(lens[b] == 0 and 0 < b < case.B - 1 for b in case.EMPTY) and lens[-1] == 0 and off[-1] == case.n      # empty bags inside, a trailing one
+    assert len(runs) >= 5 and {S + 2, 2 * S + 1, 3 * S + 5, 8 * S + 3, 2 * S} <= set(runs.values()) and {0, case.nr_rows - 1} <= set(runs)
+    bag_of = np.repeat(np.arange(case.B), lens)
+    for r, k in runs.items():
+        at = [p for p, v in enumerate(ids) if v == r]
+        assert len(at) == k and len(set(bag_of[at].tolist())) >= min(k, case.B) // 3, (r, k)      # spread over many bags
+        with_pad = [b for b in case.PAD_BAGS if r in ids[off[b]:off[b] + lens[b]]]
+        assert with_pad and all(case.pad in ids[off[b]:off[b] + lens[b]] for b in with_pad), r        # cnt != the bag's length
+    triple = ids[off[case.TRIPLE_BAG]:off[case.TRIPLE_BAG] + lens[case.TRIPLE_BAG]]
+    assert triple.count(sr.RAGGED_TRIPLE) == 3
+    assert ids[off[case.PAD_ONLY]:off[case.PAD_ONLY] + lens[case.PAD_ONLY]] == [case.pad] * 3
+    # the lead variant: positions 0 .. 2 without a bag; a long-run row and a bad id among them
+    assert case.offsets(True)[0] == 3 and ids[0] == 123 and case.bad_at[0] == 1 and len(case.bad_at) == 5
+    full, lead = case.reference(S, "sum", "i64", 4), case.reference(S, "sum", "i64", 4, lead=True)
+    assert full[2] == 5 and lead[2] == 4 and 123 in differing(full, (full[0], lead[1][np.searchsorted(lead[0], full[0])]))
+    for width in ("i64", "u32"):
+        bad = [case.bad_ids(width)[p] for p in case.bad_at]
+        assert all(v < 0 or v >= case.nr_rows for v in bad)
+        assert (min(bad) < 0 and max(bad) >= 2 ** 32 and {v % 2 ** 32 for v in bad} & set(runs)) if width == "i64" else max(bad) == 2 ** 32 - 1
+        assert case.ids_array(width).dtype == (np.int64 if width == "i64" else np.uint32)
+    G, w = case.grads(4), case.weights()
+    assert np.signbit(G[G == 0]).any() and ((G != 0) & (np.abs(G) < np.finfo(F).tiny)).any() and np.isfinite(G).all()
+    assert len(set(np.frexp(np.abs(G[G != 0]))[1].tolist())) > 16 and (w == 0).any() and (w < 0).any()
+    assert np.abs(case.grads(4, narrow=True)[9:]).max() < 2 ** 6
+
+
+@pytest.mark.parametrize("S", sr.RAGGED_SEGMENTS)
+def test_ragged_case_tells_the_orders_the_segment_lengths_cnt_and_the_weights_apart(S):
+    """What the batch has to show of the REFERENCE ALONE, so that a kernel with the wrong order, S, cnt or weight index cannot
+    pass: in every mode at least four rows differ from the position order, from S / 2, from 2 S and from segments cut by sorted
+    place; with every cnt replaced by the bag's length (mean + padding) and with w[bag(p)] for w[p] every long-run row differs.
+    Each wrong reference is rejected by the assertions the GPU tests call: check_sparse, and check_table / check_state behind a
+    step."""
+    case = sr.ragged_case(S)
+    long_rows = sorted(sr.ragged_runs(S))
+    for dim in (4, 6):
+        for mode_name in gc.MODES:
+            ref = case.reference(S, mode_name, "i64", dim)
+            wrongs = {"position": case.reference(None, mode_name, "i64", dim), "S/2": case.reference(S // 2, mode_name, "i64", dim),
+                      "2S": case.reference(2 * S, mode_name, "i64", dim), "by place": case.reference(S, mode_name, "i64", dim, by_place=True)}
+            for name, wrong in wrongs.items():
+                assert len(differing(ref, wrong)) >= 4, (S, dim, mode_name, name, differing(ref, wrong))
+                with pytest.raises(AssertionError):
+                    oc.check_sparse(wrong[0], wrong[1], ref, name)
+        ref = case.reference(S, "mean+pad", "u32", dim)
+        wrong = case.reference(S, "mean+pad", "u32", dim, cnt_of=lambda cnt, bags, p: int(case.lens[bags[p]]))
+        assert set(long_rows) <= set(differing(ref, wrong)), (S, dim, "cnt", differing(ref, wrong))
+        with pytest.raises(AssertionError):
+            oc.check_sparse(wrong[0], wrong[1], ref, "cnt")
+        for mode_name in ("weighted", "weighted+pad"):
+            ref = case.reference(S, mode_name, "u32", dim)
+            wrong = case.reference(S, mode_name, "u32", dim, weight_at=lambda p, bags: bags[p])
+            assert set(long_rows) <= set(differing(ref, wrong)), (S, dim, mode_name, differing(ref, wrong))
+            with pytest.raises(AssertionError):
+                oc.check_sparse(wrong[0], wrong[1], ref, "weights")
+    # behind a step, on the narrow gradients: the GPU tests call check_table AND check_state, a wrong sum has to fail one of them
+    dim = 4
+    init = case.step_table("f32", dim)
+    wrongs = lambda: (("position", case.reference(None, "mean+pad", "i64", dim, narrow=True)),  # noqa: E731
+                      ("S/2", case.reference(S // 2, "mean+pad", "i64", dim, narrow=True)), ("2S", case.reference(2 * S, "mean+pad", "i64", dim, narrow=True)),
+                      ("cnt", case.reference(S, "mean+pad", "i64", dim, narrow=True, cnt_of=lambda cnt, bags, p: int(case.lens[bags[p]]))))
+    ref = case.reference(S, "mean+pad", "i64", dim, narrow=True)
+    check_table(sr.sgd_table("f32", init, ref), sr.sgd_table("f32", init, ref).copy(), "the right table")
+    for name, wrong in wrongs():
+        assert rejects(check_table, sr.sgd_table("f32", init, wrong), sr.sgd_table("f32", init, ref)), (S, name, "sgd")
+    for rowwise in (False, True):
+        s0 = oc.init_state(case.nr_rows, dim, rowwise)
+        want_table, want_state = sr.adagrad_tables("f32", init, s0, ref, rowwise)
+        check_table(want_table, want_table.copy(), "the right table")
+        check_state(want_state, want_state.copy(), "the right state")
+        for name, wrong in wrongs():
+            got_table, got_state = sr.adagrad_tables("f32", init, s0, wrong, rowwise)
+            assert rejects(check_table, got_table, want_table) or rejects(check_state, got_state, want_state), (S, name, rowwise)
+
+
+def rejects(check, got, want):
+    try:
+        check(got, want, "a wrong reference")
+    except AssertionError:
+        return True
+    return False
+
+
+# ---- the wider segment lengths ------------------------------------------------------------------------------------------------------------------
+def wide_cases(S):
+    if S == 64:
+        return [sr.lengths_case(S, True), sr.placement_case(S, "bad"), sr.placement_case(S, "end"), sr.one_row_case(S), sr.short_case(S), sr.reduced_case(S)] + sr.multi_cases(S)
+    return [sr.reduced_case(S)]
+
+
+@pytest.mark.parametrize("S", sr.WIDE_SEGMENTS + sr.MID_SEGMENTS)
+def test_the_wider_cases_stay_finite_in_columns_0_to_2_in_the_right_order(S):
+    for case in wide_cases(S):
+        assert case.S == S and case.n <= 16384
+        for row in case.run_lengths():
+            seen, _g = partial_sums(case, S, row)
+            assert np.isfinite(seen).all() and set(np.unique(np.abs(seen)).tolist()) <= {0.0, float(oc.M)}, (case.name, row)
+        rows, grads, _ = case.seg_reference(S, 4)
+        assert np.isfinite(grads[:, :3]).all() and np.isfinite(grads).all(), case.name
+        if max(case.run_lengths().values()) > S + 1:
+            assert differing((rows, grads), case.fold(4, "sum")), case.name
+    if S == 64:                                           # what the cases promise for S = 8 and 16 holds here
+        case = sr.lengths_case(64, True)
+        assert case.n == 5523 and sorted(case.run_lengths().values()) == sorted(sr.run_lengths(64))
+        assert len(differing(case.seg_reference(64, 4), case.fold(4, "sum"))) == 7
+        lay = {r: (h, k) for r, h, k in sr.sorted_layout(sr.placement_case(64, "bad"))}
+        assert lay[7][0] + 2 * 64 == 328 and lay[8][0] == 331 and 328 // 64 == 331 // 64      # two segment starts in one 64-aligned block
+    else:
+        case = sr.reduced_case(S)
+        assert sorted(case.run_lengths().values()) == sorted(sr.reduced_run_lengths(S)) and case.n == 15 * S + 14 and case.n_bad == 3
+        assert -(-(9 * S + 3) // S) == 10
+    if S == 1024:                                         # column 2 is NOT exact in any order here: a run's sum of p + 1 passes 2^24
+        case = sr.reduced_case(S)
+        exact = np.bincount(case.ids[case.good], weights=np.flatnonzero(case.good) + 1.0)
+        assert exact.max() > 2 ** 24
+
+
+def row_partials(C, ps, S):
+    out = []
+    with np.errstate(over="ignore", invalid="ignore"):
+        for at in range(0, len(ps), S):
+            t = np.zeros(C.shape[1], F)
+            for p in ps[at:at + S]:
+                t = t + C[p]
+            out.append(t)
+    return out
+
+
+def row_with_exchange(C, ps, S, partials, j):
+    """The row's gradient with its occurrences j and j + 1 (1-based) exchanged: the fold of grad_seg_ref, with the segments the
+    exchange does not touch taken from `partials` (their sums are what they were)."""
+    ps = list(ps)
+    ps[j - 1], ps[j] = ps[j], ps[j - 1]
+    parts = list(partials)
+    for m in {(j - 1) // S, j // S}:
+        parts[m] = row_partials(C, ps[m * S:(m + 1) * S], S)[0]
+    with np.errstate(over="ignore", invalid="ignore"):
+        g = parts[0]
+        for t in parts[1:]:
+            g = g + t
+    return g
+
+
+def exchange_proof(case, S, js_of):
+    """For every row and every j of js_of(k): the exchange of the occurrences j and j + 1 makes column 0 or 1 infinite, and
+    check_sparse rejects the result.  Returns the number of exchanges tried."""
+    ref = case.seg_reference(S, 4)
+    C = case.contributions(4, "sum")
+    tried = 0
+    for row, k in case.run_lengths().items():
+        ps = [int(p) for p in case.order() if case.ids[p] == row]
+        partials = row_partials(C, ps, S)
+        at = int(np.flatnonzero(ref[0] == row)[0])
+        assert np.array_equal(oc.bits(row_with_exchange(C, ps, S, partials, 1)), oc.bits(ref[1][at]))      # (the first pair commutes: the fold is grad_seg_ref's)
+        for j in js_of(k):
+            g = row_with_exchange(C, ps, S, partials, j)
+            assert not np.isfinite(g[:2]).all(), (row, k, j)
+            wrong = ref[1].copy()
+            wrong[at] = g
+            with pytest.raises(AssertionError):
+                oc.check_sparse(ref[0], wrong, ref, (row, j))
+            tried += 1
+    return tried
+
+
+def test_every_exchange_inside_a_segment_of_64_gives_inf():
+    """As test_exchanging_two_neighbours_inside_a_segment_gives_inf, over EVERY run of lengths_case(64), the run of 65 S + 1
+    included: every j with j and j + 1 in one segment, but the first pair of a segment."""
+    S = 64
+    inside = lambda k: [j for j in range(2, k) if (j - 1) // S == j // S and j % S != 1]  # noqa: E731
+    tried = exchange_proof(sr.lengths_case(S, False), S, inside)
+    assert tried == sum(len(inside(k)) for k in sr.run_lengths(S)) > 5000
+    full = sr.fold(sr.lengths_case(S, False), S, 4, "sum", order=exchanged(sr.lengths_case(S, False), max(sr.lengths_case(S, False).run_lengths(), key=sr.lengths_case(S, False).run_lengths().get), 9 * S + 2))
+    assert not np.isfinite(full[1][:, :2]).all()          # (one of them through grad_seg_ref.fold itself)
+
+
+def test_sampled_exchanges_around_the_boundaries_of_segments_of_1024_give_inf():
+    """The quadratic proof is too slow at S = 1024.  THE SAMPLE: in every run of reduced_case(1024), every exchange (j, j + 1)
+    within two places of a segment boundary -- j mod S in {S - 2, S - 1, 0, 2, 3}: the two before it, the one across it, the two
+    behind the first pair of the next segment (that pair commutes and is no other sum) -- plus 40 seeded others per run, 240 in
+    all.  Every one of them changes the reference."""
+    S = 1024
+    rng = np.random.default_rng(1024)
+
+    def sample(k):
+        near = [j for j in range(2, k) if j % S in (S - 2, S - 1, 0, 2, 3)]
+        rest = [j for j in range(2, k) if j % S not in (S - 2, S - 1, 0, 1, 2, 3)]
+        return near + sorted(int(j) for j in rng.choice(rest, size=40, replace=False))
+
+    tried = exchange_proof(sr.reduced_case(S), S, sample)
+    assert tried >= 240 + 5 * 13
