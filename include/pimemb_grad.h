@@ -47,7 +47,8 @@
  *   EMB_POOL_MAX      needs the forward's per-element argmax, which no kernel records.
  * Prepared plans stay valid over a stepped table and read the new rows when launched behind the step.
  * emb_grad_step (below) is the same step with an optimizer that keeps state: Adagrad, and row-wise Adagrad.
- * Out of scope: the gradient with respect to per_sample_weights; max mode; optimizers other than SGD, Adagrad and row-wise
+ * emb_grad_weights (THE GRADIENT OF PER_SAMPLE_WEIGHTS, below) is the other gradient of a weighted sum: one value per position.
+ * Out of scope: max mode; optimizers other than SGD, Adagrad and row-wise
  * Adagrad (no momentum, no Adam), weight decay and lr_decay, optimizer state in anything but fp32; row-wise Adagrad off the
  * lane-group shape (the element-wise kernel has no row-wide view of g, and a second reduction is not built for it:
  * EMB_ERR_UNSUPPORTED); a multi-table emb_grad_sparse (it stays single; emb_grad_sgd_multi / emb_grad_step_multi below fuse the
@@ -289,6 +290,54 @@ uint32_t emb_grad_multi_groups(const emb_grad_multi_shape *shapes, uint32_t n, u
 int emb_grad_sgd_multi(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream);
 int emb_grad_step_multi(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype,
                         const emb_opt_spec *opt, void *stream);
+
+/* THE GRADIENT OF PER_SAMPLE_WEIGHTS (tests/psw_ref.py restates it as a loop over positions; the kernels are compared with that, bit
+ * for bit).  The second gradient of nn.EmbeddingBag(mode="sum", per_sample_weights=w): one fp32 value per position of the batch,
+ *       dw[p] = < G[bag(p)] , dec(W[ids[p]]) >
+ * Batch, bags, good / bad / padding / no-bag positions, dec, and G with its grad_ld are the ones defined at the top; the table is
+ * nr_rows x dim, any dim >= 1.  For a GOOD position p, with b = bag(p), r = ids[p] and pieces = ceil(dim / 4):
+ *       prod[d] = G[b][d] * dec(W[r][d])      d < dim: one fp32 multiply;   prod[d] = +0 for dim <= d < 4 * pieces
+ *       t[c]    = ((prod[4c] + prod[4c+1]) + prod[4c+2]) + prod[4c+3]                    c < pieces
+ *       v       = t, padded with +0 to L = min(64, pow2ceil(pieces)) entries;
+ *                 where pieces > 64:  v[l] = ((t[l] + t[l+64]) + t[l+128]) + ...  over all l + 64j < pieces, j ascending
+ *       while len(v) > 1:  v = [v[0] + v[1], v[2] + v[3], ...]
+ *       dw[p]   = v[0]
+ * Every operation is rounded on its own and never contracted into an FMA (csrc/pimemb_grad_dot.h: the one-element arithmetic and the
+ * serial form of the tree, compiled by the kernels and by a host check alike).  For dim % 4 == 0, dim <= 512 this is the pair tree
+ * of the row-wise Adagrad step above (tests/optim_ref.pair_tree), over products instead of squares.  The +0 padding is part of the
+ * definition: absent slots hold +0 and are added -- for G[b] all -0 and W[r] positive, dw[p] is -0 at dim 4 and dim 64 and +0 at
+ * dim 48 and dim 3.
+ * For a position that is NOT good (padding, no bag, or an id outside the table) dw[p] = +0.0f.  A bad position is counted for
+ * emb_grad_report, as in every other call: a backward that runs both this call and a step counts it twice.  Entries of dw at and
+ * beyond n_indices are not touched.  dw does not depend on the VALUES of per_sample_weights: pool.per_sample_weights may be NULL or
+ * not and is never read.  It does not depend on the context's order of additions either: a segmented context gives the same bits.
+ * NaN payloads are unspecified, as everywhere.
+ *
+ * emb_grad_weights runs descriptor after descriptor; dw_out[k] is a DEVICE float[descs[k].n_indices].  DEVICE pointers only; a pure
+ * enqueue on `stream` like the steps -- no allocation, no copy, no host wait: it can be captured in a graph.  ONE launch per
+ * non-empty descriptor and no pre-pass; of the context's scratch it uses the bad-position counter alone (the context is there for
+ * the device, the limits and the report).  Every descriptor is checked before anything is enqueued: a refused call writes nothing.
+ *   EMB_ERR_INVALID      a NULL context, descs or dw_out; a NULL (or not 4-byte aligned) dw_out[k] where n_indices > 0; n_indices or
+ *                        n_bags above the context's limits; unknown pool flag bits; a padding_idx outside the table.
+ *   EMB_ERR_UNSUPPORTED  a mode other than EMB_POOL_SUM (torch has no weights in mean or max mode either); EMB_F8_* / EMB_MXFP4 /
+ *                        EMB_FIXED32 tables (dec knows fp32 / fp16 / bf16); tables of 2^32 - 1 rows or more.
+ * A staged hot set does NOT refuse: the call only reads the table's own bytes, which are authoritative.  Issued before a fused
+ * step on the same stream it reads the rows the forward read.
+ * How it runs.  Lane-group shape (dim % 4 == 0, dim <= 512, grad 16-byte aligned, grad_ld % 4 == 0): one lane group per BAG, the
+ * forward's geometry -- bag(p) needs no search; lane l loads its pieces l and l + 64 of G[b] once, walks the bag's positions with the
+ * row gathers of eight of them in flight before the first multiply (the positions of a bag are independent here; the ids of the
+ * next eight are loaded meanwhile), decodes, multiplies, folds t, and sums over the group with the row-wise step's xor butterfly,
+ * the eight positions' butterflies side by side (lanes without a piece hold +0 and take part); one lane stores dw[p].  The group of bag 0 also writes the +0 of the positions before offsets[0].  Any other shape: one
+ * lane group per position, its bag by binary search, scalar element loads, the same tree and the same bits.
+ * Speed, measured on MI355X (tools/psw_probe.py, profiles/psw/README.md; medians of five alternating rounds, device pointers): dim 128,
+ * 2048 bags x 32, 4 M rows: 13.0 us on fp32 and 14.6 us on bf16 tables with uniform ids, 11.4 / 14.0 us with Zipf ids -- 3.3x faster
+ * than torch's GPU backward of the weights (42.5 us, host-bound and spread widely; none exists for bfloat16) and 2.2 - 2.6x SLOWER
+ * than the forward lookup of the same batch (4.7 - 6.1 us), the floor.  The Kaggle shape (dim 16, 39 292 one-index bags): 5.6 us
+ * against torch's 43.2 and the forward's 4.9.  The fallback kernel is not measured.
+ * Out of scope: fusing several descriptors into one launch (one launch per table: 26 launches for the Criteo-Kaggle set); fp8 /
+ * MXFP4 / fixed-point tables; mean and max mode; the ranged / sharded paths; a second-order gradient. */
+int emb_grad_weights(emb_grad *g, const emb_grad_desc *descs, float *const *dw_out, uint32_t n_descs, emb_index_type itype,
+                     void *stream);
 
 /* The number of BAD positions (an id outside the table) skipped since the last report; resets the count.  Waits for the
  * device first, so the count covers every call enqueued so far. */

@@ -13,7 +13,7 @@ MARSHAL_PATH = os.path.join(PKG_DIR, "lib", "_pimemb_marshal.so")
 SOURCES = ["pimemb_kernels.hip", "pimemb_strided_kernels.hip", "pimemb_engine.cpp", "pimemb_compat.cpp", "pimemb_comm.cpp", "pimemb_shard.cpp", "pimemb_peer.cpp", "pimemb_peer.h", "pimemb_internal.h", "pimemb_torch_marshal.cpp",
            "pimemb_bag_kernels.h", "pimemb_pool_kernels.inc", "pimemb_sum_kernels.inc", "pimemb_mx4_kernels.inc", "pimemb_xcd_map.h", "pimemb_hot_rows.h", "pimemb_hostcopy.h", "Makefile",
            "pimemb_rows.hip", "pimemb_rows_encode.h", os.path.join("..", "..", "include", "pimemb_rows.h"),
-           "pimemb_grad.hip", "pimemb_grad_step.h", "pimemb_grad_optim.h", "pimemb_grad_segments.h", os.path.join("..", "..", "include", "pimemb_grad.h"),
+           "pimemb_grad.hip", "pimemb_grad_step.h", "pimemb_grad_optim.h", "pimemb_grad_dot.h", "pimemb_grad_segments.h", os.path.join("..", "..", "include", "pimemb_grad.h"),
            os.path.join("..", "..", "include", "pimemb.h")]
 
 

@@ -24,6 +24,10 @@
 //   grad_seg_partials / grad_seg_multi_partials     one lane group per sorted place, working where a segment of a long run starts:
 //                       that segment's sum, stored into the context's partial buffer (csrc/pimemb_grad_segments.h numbers the slots)
 //   grad_seg_rows_group / grad_seg_multi_rows / grad_seg_rows_elem     the hot kernels' twins: a long run is the sum of its partials
+// The gradient of per_sample_weights (emb_grad_weights: no pre-pass, one launch per descriptor; csrc/pimemb_grad_dot.h):
+//   grad_psw_group      one lane group per BAG, the forward's geometry: its piece of G[b] loaded once, the row gathers of eight
+//                       positions in flight, products folded per piece and summed over the group by the row-wise xor butterfly
+//   grad_psw_elem       any other dim / alignment: one lane group per position, scalar element loads, the same tree
 // The Adagrad tails (csrc/pimemb_grad_optim.h) end the same kernels; the row-wise one sums the row's squares over its lane group
 // with an xor butterfly -- a fixed tree, stated over dim alone in the header: the same bits on every run.
 // Every fp32 operation of the definition is a statement of its own under `fp contract(off)` (and the unit is compiled with
@@ -40,6 +44,7 @@
 #include <vector>
 
 #include "pimemb_grad.h"
+#include "pimemb_grad_dot.h"
 #include "pimemb_grad_optim.h"
 #include "pimemb_grad_segments.h"
 #include "pimemb_grad_step.h"
@@ -878,6 +883,163 @@ __global__ __launch_bounds__(kBlock) void grad_seg_rows_elem(RowArgs a, uint32_t
     if (KIND == RES_ADAGRAD) *sp = st;
 }
 
+// ---- the gradient of per_sample_weights: dw[p] = < G[bag(p)] , dec(W[ids[p]]) > (csrc/pimemb_grad_dot.h) ------------------------
+// No pre-pass: nothing is sorted, a position's value depends on its own row and its bag's row of G alone.  The kernels above keep
+// their text; these read the batch as the forward does.
+
+struct PswArgs {
+    const void *ids;
+    const void *offsets;         // or NULL: bags of fixed_pooling positions
+    const float *grad;           // G
+    uint64_t ld;
+    const char *table;
+    float *dw;                   // [n]
+    unsigned long long *bad;
+    uint64_t pad_idx;
+    uint32_t n, n_bags, nr_rows, dim;
+    uint32_t stride;             // bytes from one table row to the next
+    int dtype;
+    uint32_t fixed_pooling, pad_on;
+};
+
+enum PswClass : int { PSW_GOOD = 0, PSW_BAD = 1, PSW_SKIP = 2, PSW_DEAD = 3 };      // (SKIP: padding or no bag; DEAD: no position)
+
+// The id of position p (< n) at full width: an int64 id as its bits, a uint32 id zero-extended.
+template <bool IDX64>
+__device__ __forceinline__ uint64_t psw_load_id(const PswArgs &a, uint32_t p) {
+    if (IDX64) return (uint64_t) static_cast<const long long *>(a.ids)[p];
+    return static_cast<const uint32_t *>(a.ids)[p];
+}
+
+// A position in a bag with this id: good, bad or padding; *row = its table row where it is good.  Ids are compared at full width
+// (a negative int64 id is a value of 2^63 or more here: outside every table).
+__device__ __forceinline__ int psw_class_of(const PswArgs &a, uint64_t id, uint32_t *row) {
+    const bool in_table = id < a.nr_rows;
+    *row = in_table ? (uint32_t)id : 0u;
+    if (a.pad_on && id == a.pad_idx) return PSW_SKIP;
+    return in_table ? PSW_GOOD : PSW_BAD;
+}
+
+// offsets[b] (b < n_bags), clamped into [0, n]: whatever the offsets hold, a walk stays inside the batch.
+template <bool IDX64>
+__device__ __forceinline__ uint32_t psw_bag_start(const PswArgs &a, uint32_t b) {
+    uint64_t o;
+    if (!a.offsets) o = (uint64_t)b * a.fixed_pooling;
+    else if (IDX64) o = (uint64_t) static_cast<const long long *>(a.offsets)[b];
+    else o = static_cast<const uint32_t *>(a.offsets)[b];
+    return o < a.n ? (uint32_t)o : a.n;
+}
+
+__device__ __forceinline__ float4 psw_dec(int, float4 w) { return w; }
+__device__ __forceinline__ float4 psw_dec(int dtype, u32x2 w) {
+    return make_float4(bits_f32(dec(dtype, w.x & 0xffffu)), bits_f32(dec(dtype, w.x >> 16)), bits_f32(dec(dtype, w.y & 0xffffu)),
+                       bits_f32(dec(dtype, w.y >> 16)));
+}
+
+// t[c] of the definition from a piece of G and the decoded piece of the row
+__device__ __forceinline__ float psw_piece(float4 g, float4 w) { return dot_fold4(dot_mul(g.x, w.x), dot_mul(g.y, w.y), dot_mul(g.z, w.z), dot_mul(g.w, w.w)); }
+
+// The positions [start, end) of one bag, eight at a time.  A round's ids are in registers when it starts -- the loads of the NEXT
+// round's ids are issued first and travel with this round's row gathers; then the row pieces of the good positions (RAW is a lane's
+// 16 bytes of an fp32 row or its 8 bytes of an fp16 / bf16 row), all in flight before the first multiply; then the products and the
+// fold per position, and the butterfly of the eight positions side by side: eight independent shuffles per xor distance.  A slot
+// without a good position holds +0 and takes part.  Everything that branches is uniform over the lane group: its lanes reach
+// every shuffle together, and the xor distances stay below `lanes`.
+template <bool IDX64, typename RAW>
+__device__ __forceinline__ void psw_walk(const PswArgs &a, uint32_t start, uint32_t end, uint32_t lg, uint32_t lanes, bool own0, bool own1, float4 g0,
+                                         float4 g1) {
+    uint64_t next[kAhead];
+#pragma unroll
+    for (uint32_t k = 0; k < kAhead; k++) next[k] = psw_load_id<IDX64>(a, start + k < end ? start + k : start);      // (start < end <= n)
+    for (uint32_t j = start; j < end; j += kAhead) {
+        int cls[kAhead];
+        RAW w0[kAhead], w1[kAhead];
+        uint32_t row[kAhead];
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {
+            row[k] = 0;
+            cls[k] = j + k < end ? psw_class_of(a, next[k], &row[k]) : (int)PSW_DEAD;
+            const uint32_t p = j + kAhead + k;                            // (a slot beyond the bag re-reads the round's first id)
+            next[k] = psw_load_id<IDX64>(a, p < end ? p : j);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {
+            const RAW *r = reinterpret_cast<const RAW *>(a.table + (uint64_t)row[k] * a.stride);
+            w0[k] = RAW{};
+            w1[k] = RAW{};
+            if (cls[k] == PSW_GOOD && own0) w0[k] = r[lg];
+            if (cls[k] == PSW_GOOD && own1) w1[k] = r[lg + lanes];
+        }
+        float v[kAhead];
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {
+            v[k] = 0.f;                                                   // (+0 in a lane without a piece, and for a position that is not good)
+            if (cls[k] == PSW_GOOD && own0) v[k] = psw_piece(g0, psw_dec(a.dtype, w0[k]));
+            if (cls[k] == PSW_GOOD && own1) v[k] = dot_add(v[k], psw_piece(g1, psw_dec(a.dtype, w1[k])));
+        }
+        for (uint32_t h = 1; h < lanes; h <<= 1) {
+#pragma unroll
+            for (uint32_t k = 0; k < kAhead; k++) v[k] = dot_add(v[k], __shfl_xor(v[k], (int)h));
+        }
+        if (lg == 0) {
+#pragma unroll
+            for (uint32_t k = 0; k < kAhead; k++) {
+                if (cls[k] == PSW_DEAD) continue;
+                a.dw[j + k] = cls[k] == PSW_GOOD ? v[k] : 0.f;
+                if (cls[k] == PSW_BAD) atomicAdd(a.bad, 1ull);
+            }
+        }
+    }
+}
+
+// One BAG per group of `lanes` lanes; lane lg owns the 16-byte pieces lg and lg + lanes (two only beyond dim 256) of G[b] and of
+// every row the bag names.  The group of bag 0 also writes the +0 of the positions before offsets[0] (all of them where there is
+// no bag at all: the launch has one group then).
+template <bool IDX64>
+__global__ __launch_bounds__(kBlock) void grad_psw_group(PswArgs a, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t b64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (b64 >= (a.n_bags ? a.n_bags : 1u)) return;
+    const uint32_t b = (uint32_t)b64;
+    const uint32_t start = a.n_bags ? psw_bag_start<IDX64>(a, b) : a.n;
+    if (b == 0)
+        for (uint32_t p = lg; p < start; p += lanes) a.dw[p] = 0.f;
+    if (!a.n_bags) return;
+    const uint32_t end = b + 1 < a.n_bags ? psw_bag_start<IDX64>(a, b + 1) : a.n;
+    if (start >= end) return;                                             // (uniform over the lane group, like everything above)
+    const bool own0 = lg < chunks, own1 = lg + lanes < chunks;
+    const float4 *g = reinterpret_cast<const float4 *>(a.grad + (uint64_t)b * a.ld);
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 g0 = own0 ? g[lg] : zero, g1 = own1 ? g[lg + lanes] : zero;
+    if (a.dtype == kStepF32) psw_walk<IDX64, float4>(a, start, end, lg, lanes, own0, own1, g0, g1);
+    else psw_walk<IDX64, u32x2>(a, start, end, lg, lanes, own0, own1, g0, g1);
+}
+
+// Any other shape: one POSITION per group of dot_lanes(dim) lanes, its bag by binary search, lane l the leaf v[l] of the tree with
+// scalar element loads (dot_leaf: the text the host check compiles), then the same butterfly.
+template <bool IDX64>
+__global__ __launch_bounds__(kBlock) void grad_psw_elem(PswArgs a, uint32_t lanes, uint32_t lanes_log2) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t p64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (p64 >= a.n) return;
+    const uint32_t p = (uint32_t)p64;
+    const uint32_t b = bag_of<IDX64>(a.offsets, a.fixed_pooling, a.n_bags, p);
+    uint32_t row = 0;
+    const int cls = b == kNoBag ? (int)PSW_SKIP : psw_class_of(a, psw_load_id<IDX64>(a, p), &row);      // (uniform over the lane group)
+    if (cls != PSW_GOOD) {
+        if (lg == 0) {
+            a.dw[p] = 0.f;
+            if (cls == PSW_BAD) atomicAdd(a.bad, 1ull);
+        }
+        return;
+    }
+    float v = dot_leaf(a.dtype, a.table + (uint64_t)row * a.stride, a.grad + (uint64_t)b * a.ld, a.dim, lg);
+    for (uint32_t h = 1; h < lanes; h <<= 1) v = dot_add(v, __shfl_xor(v, (int)h));
+    if (lg == 0) a.dw[p] = v;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 
 thread_local char t_err[512] = "";
@@ -1490,6 +1652,55 @@ int emb_grad_step(emb_grad *g, const emb_grad_desc *descs, float *const *states,
 int emb_grad_step_multi(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype,
                         const emb_opt_spec *opt, void *stream) {
     return opt_call(g, descs, states, n_descs, itype, opt, stream, true);
+}
+
+int emb_grad_weights(emb_grad *g, const emb_grad_desc *descs, float *const *dw_out, uint32_t n_descs, emb_index_type itype, void *stream) {
+    const char *who = "emb_grad_weights";
+    if (!descs || !dw_out) return fail(EMB_ERR_INVALID, "%s: descs or dw_out is NULL", who);
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
+    std::vector<TableShape> shapes(n_descs);
+    for (uint32_t k = 0; k < n_descs; k++) {     // the plan: every descriptor checked before anything is enqueued
+        const emb_grad_desc &d = descs[k];
+        TableShape &t = shapes[k];
+        if (int rc = check_desc(g, d, itype, nullptr, who, &t)) return rc;
+        if (d.pool.mode != EMB_POOL_SUM)
+            return fail(EMB_ERR_UNSUPPORTED, "%s: per_sample_weights go with EMB_POOL_SUM only, table %u pools by mode %u", who, d.table_id, d.pool.mode);
+        if (t.dtype != kF32 && t.dtype != kF16 && t.dtype != kBF16)
+            return fail(EMB_ERR_UNSUPPORTED, "%s: table %u is fp8 or MXFP4: this call decodes fp32, fp16 and bf16 rows only", who, d.table_id);
+        if (d.n_indices && (!dw_out[k] || (uintptr_t)dw_out[k] % 4))
+            return fail(EMB_ERR_INVALID, "%s: the output of table %u is NULL or not 4-byte aligned", who, d.table_id);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    for (uint32_t k = 0; k < n_descs; k++) {     // the enqueue: one launch per non-empty descriptor
+        const emb_grad_desc &d = descs[k];
+        const TableShape &t = shapes[k];
+        if (d.n_indices == 0) continue;
+        const PoolArgs pa = pool_args(d);
+        PswArgs a{};
+        a.ids = d.indices, a.offsets = d.offsets, a.fixed_pooling = d.fixed_pooling;
+        a.grad = d.grad, a.ld = d.grad_ld;
+        a.table = t.rows, a.stride = t.stride, a.dtype = t.dtype;
+        a.dw = dw_out[k], a.bad = &g->counters[0];
+        a.pad_on = pa.pad_on, a.pad_idx = pa.pad_idx;
+        a.n = (uint32_t)d.n_indices, a.n_bags = (uint32_t)d.n_bags, a.nr_rows = (uint32_t)t.nr_rows, a.dim = t.dim;
+        const bool idx64 = itype == EMB_IDX_I64;
+        if (lane_group_path(d, t, RES_SGD, nullptr, nullptr)) {
+            const LaneGeom l = lane_geom(t.dim, a.n_bags ? a.n_bags : 1u);      // a group per bag (n_bags <= 2^31 - 1, 64 lanes: below 2^29 workgroups)
+            if (idx64) grad_psw_group<true><<<dim3(l.blocks), dim3(kBlock), 0, s>>>(a, l.lanes, l.lanes_log2, l.chunks);
+            else grad_psw_group<false><<<dim3(l.blocks), dim3(kBlock), 0, s>>>(a, l.lanes, l.lanes_log2, l.chunks);
+        } else {
+            const uint32_t lanes = dot_lanes(t.dim);
+            uint32_t lanes_log2 = 0;
+            while ((1u << lanes_log2) < lanes) lanes_log2++;
+            const uint32_t blocks = (uint32_t)(((uint64_t)a.n * lanes + kBlock - 1) / kBlock);      // a group per position (n <= 2^30: below 2^28)
+            if (idx64) grad_psw_elem<true><<<dim3(blocks), dim3(kBlock), 0, s>>>(a, lanes, lanes_log2);
+            else grad_psw_elem<false><<<dim3(blocks), dim3(kBlock), 0, s>>>(a, lanes, lanes_log2);
+        }
+        GRAD_HIP(hipGetLastError());
+    }
+    return EMB_OK;
 }
 
 int emb_grad_report(emb_grad *g, uint64_t *n_bad) {

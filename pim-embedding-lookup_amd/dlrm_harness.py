@@ -143,15 +143,61 @@ class EmbeddingBagCollection:
             raise TypeError("weighted pooling takes torch CUDA index tensors")
         if check:      # (a wild index must not reach torch's gather either)
             self.validate(lS_o, lS_i)
-        ws = [v.gather(0, i.long()) for v, i in zip(self.v_W_l, lS_i)]
+        gathered = [v.gather(0, i.long()) for v, i in zip(self.v_W_l, lS_i)]
+        ws = [w.detach() for w in gathered]
+
+        def lookup():
+            if concat:
+                return self.engine.lookup_concat(self._ids, lS_i, lS_o, out=out, col=col, modes="sum", per_sample_weights=ws, check=check)
+            return self.engine.lookup_pooled(self._ids, lS_i, lS_o, "sum", per_sample_weights=ws, check=check, out_dtype=self._out)
+        if self._pooling_weights_trained():      # (enable_pooling_weight_grad: the result joins the graph on the gathered weights)
+            from . import torch_module as tm
+            return tm._WeightedLookup.apply(tm._anchor(self, self.device), lookup, lambda g: self._weights_grads(lS_o, lS_i, g, concat, col), None, *gathered)
+        return lookup()
+
+    def enable_pooling_weight_grad(self, on: bool = True):
+        """--weighted-pooling: make the per-row pooling weights v_W_l[k] leaves that require grad.  apply_emb's result then joins
+        the autograd graph on v_W_l[k].gather(0, indices): its backward computes the gradient of those per-sample weights on the
+        GPU (GradContext.weights_grad: one value per index, a fixed tree, the same bits on every run), and torch's own backward
+        of gather scatters it into v_W_l[k].grad -- that scatter is torch's, and so is its order of additions.  With a fused step
+        enabled the weights' gradient is enqueued first, the step behind it.  Returns self."""
+        if self.v_W_l is None:
+            raise ValueError("enable_pooling_weight_grad needs weighted_pooling")
+        self.v_W_l = [v.detach().requires_grad_(bool(on)) for v in self.v_W_l]
+        return self
+
+    def _pooling_weights_trained(self) -> bool:
+        return self.v_W_l is not None and self.torch.is_grad_enabled() and any(v.requires_grad for v in self.v_W_l)
+
+    def _table_grads(self, g, concat, col):
+        """Per table the [B, m] gradient of its pooled rows (None where there is none), read in place where it is ONE tensor."""
+        from . import torch_module as tm
         if concat:
-            return self.engine.lookup_concat(self._ids, lS_i, lS_o, out=out, col=col, modes="sum", per_sample_weights=ws, check=check)
-        return self.engine.lookup_pooled(self._ids, lS_i, lS_o, "sum", per_sample_weights=ws, check=check, out_dtype=self._out)
+            g = g if g.dtype == self.torch.float32 else g.float()
+            g = g if g.stride(1) == 1 and (g.shape[0] < 2 or g.stride(0) >= g.shape[1]) else g.contiguous()
+            return [g[:, col + k * self.m:col + (k + 1) * self.m] for k in range(len(self._ids))]
+        return [None if x is None else tm._grad_view(x, self.m) for x in g]
+
+    def _weights_grads(self, lS_o, lS_i, g, concat, col):
+        """float32 [n_k] per table: the gradient of the per-sample weights of one batch (None where a table has no gradient)."""
+        from . import torch_module as tm
+        grads = self._table_grads(g, concat, col)
+        live = [k for k, x in enumerate(grads) if x is not None]
+        out = [None] * len(grads)
+        if live:
+            order = ("segmented", self.m, int(self.segmented_sums)) if self.segmented_sums else ("position",)
+            size = sum if self.multi_table_step else max      # (the context the fused step behind this call uses: made once)
+            ctx = tm._grad_context(self.engine, size(i.shape[0] for i in lS_i), size(o.shape[0] for o in lS_o), *order)
+            dws = ctx.weights_grad([self._ids[k] for k in live], [lS_i[k] for k in live], [lS_o[k] for k in live], [grads[k] for k in live])
+            for k, dw in zip(live, dws):
+                out[k] = dw
+        return out
 
     def enable_fused_sgd(self, lr):
         """From now on apply_emb (lists of torch CUDA tensors; f32 / f16 / bf16 tables) returns tensors attached to the autograd
         graph whose backward applies W -= lr * grad to the served tables (GradContext.sgd_step): loss.backward() is the tables'
-        whole training step.  lr=None switches it off.  The per-row pooling weights of --weighted-pooling are not trained."""
+        whole training step.  lr=None switches it off.  The per-row pooling weights of --weighted-pooling get their gradient in the
+        same backward after enable_pooling_weight_grad(), computed before the step, at the table the forward read."""
         self._fused_lr = None if lr is None else float(lr)
         self._fused_adagrad = None
         return self
@@ -177,7 +223,8 @@ class EmbeddingBagCollection:
             raise TypeError("the fused SGD step takes lists of torch CUDA index tensors")
         if self.v_W_l is not None and check:
             self.validate(lS_o, lS_i)
-        ws = None if self.v_W_l is None else [v.gather(0, i.long()) for v, i in zip(self.v_W_l, lS_i)]
+        gathered = None if self.v_W_l is None else [v.gather(0, i.long()) for v, i in zip(self.v_W_l, lS_i)]
+        ws = None if gathered is None else [w.detach() for w in gathered]
         lr, ada = self._fused_lr, self._fused_adagrad
 
         def lookup():
@@ -186,11 +233,7 @@ class EmbeddingBagCollection:
             return self.engine.lookup_pooled(self._ids, lS_i, lS_o, "sum", per_sample_weights=ws, check=check, out_dtype=self._out)
 
         def step(g):
-            if concat:
-                g = g if g.stride(1) == 1 and (g.shape[0] < 2 or g.stride(0) >= g.shape[1]) else g.contiguous()
-                grads = [g[:, col + k * self.m:col + (k + 1) * self.m] for k in range(len(self._ids))]
-            else:
-                grads = [None if x is None else tm._grad_view(x, self.m) for x in g]
+            grads = self._table_grads(g, concat, col)
             live = [k for k, x in enumerate(grads) if x is not None]
             multi = bool(self.multi_table_step)      # (its context holds all tables' indices and bags at once)
             size = sum if multi else max
@@ -203,6 +246,8 @@ class EmbeddingBagCollection:
             else:
                 ctx.adagrad_step(*args, [self.adagrad_sum[k] for k in live], ada[0], eps=ada[1], rowwise=ada[2], per_sample_weights=w_live,
                                  multi=multi)
+        if self._pooling_weights_trained():      # the weights' gradient first, the step behind it
+            return tm._WeightedLookup.apply(tm._anchor(self, self.device), lookup, lambda g: self._weights_grads(lS_o, lS_i, g, concat, col), step, *gathered)
         return tm._FusedSGD.apply(tm._anchor(self, self.device), lookup, step)
 
     def validate(self, lS_o, lS_i) -> None:
@@ -378,6 +423,9 @@ def main(argv=None):
                     help="with one of the --fused-* flags: sum a row's occurrences in segments of S (a power of two, 8 .. 1024; "
                          "default: GradContext's), the segmented order of include/pimemb_grad.h -- for skewed ids, where some rows "
                          "occur thousands of times in a batch; as fixed as the position order, other bits")
+    ap.add_argument("--train-pooling-weights", type=float, default=None, metavar="LR",
+                    help="with --weighted-pooling: train the per-row pooling weights too -- their gradient comes out of the same "
+                         "backward (emb_grad_weights, then torch's scatter into the per-row weights) and torch.optim.SGD(lr=LR) steps them")
     args, ignored = ap.parse_known_args(argv)
     if ignored:   # MLP / training / logging flags of the reference command lines (README.md:6,10,14)
         print("ignored (outside the embedding path):", " ".join(ignored))
@@ -389,7 +437,9 @@ def main(argv=None):
         raise SystemExit("--multi-table-step goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
     if args.segmented_sums is not None and not fused:
         raise SystemExit("--segmented-sums goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
-    if not args.inference_only and not fused:
+    if args.train_pooling_weights is not None and args.weighted_pooling is None:
+        raise SystemExit("--train-pooling-weights goes with --weighted-pooling")
+    if not args.inference_only and not fused and args.train_pooling_weights is None:
         print("note: running the inference embedding path (--inference-only implied); --fused-sgd LR / --fused-adagrad LR / "
               "--fused-rowwise-adagrad LR train the tables")
     import torch
@@ -433,21 +483,29 @@ def main(argv=None):
     n_bags = int(ly.shape[0]) * len(ebc.ln_emb) if cat else sum(int(x.shape[0]) for x in ly)
     print(f"apply_emb{' (one [B, T * m] tensor)' if cat else ''}: {len(ebc.ln_emb)} tables, m={ebc.m}, batch {B}: {dt * 1e3:.4f} ms/batch, "
           f"{n_bags / dt:.3e} pooled lookups/s")
-    if fused:      # forward + dummy loss + backward = lookup + the fused step on every table
-        opt_name, opt_lr = fused[0]
+    if fused or args.train_pooling_weights is not None:      # forward + dummy loss + backward = lookup + the fused step on every table
+        opt_name, opt_lr = fused[0] if fused else (None, None)
         ebc.multi_table_step = bool(args.multi_table_step)
         if args.segmented_sums is not None:
             from .engine import GradContext
             ebc.segmented_sums = args.segmented_sums or GradContext.DEFAULT_SEGMENT
         if opt_name == "SGD":
             ebc.enable_fused_sgd(opt_lr)
-        else:
+        elif opt_name is not None:
             ebc.enable_fused_adagrad(opt_lr, rowwise=opt_name != "Adagrad")
+        w_opt = None
+        if args.train_pooling_weights is not None:      # the per-row pooling weights: plain torch.optim.SGD over v_W_l
+            ebc.enable_pooling_weight_grad()
+            w_opt = torch.optim.SGD(ebc.v_W_l, lr=args.train_pooling_weights)
 
         def train_step(o, i):
+            if w_opt is not None:
+                w_opt.zero_grad()
             ly = ebc.apply_emb(o, i, concat=cat)
             loss = ly.sum() if cat else sum(y.sum() for y in ly)
             loss.backward()
+            if w_opt is not None:
+                w_opt.step()
         train_step(*batches[0])
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -455,7 +513,10 @@ def main(argv=None):
             train_step(*batches[b % len(batches)])
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.num_batches
-        print(f"apply_emb + loss.backward() with the fused {opt_name} step (lr {opt_lr}){', multi-table' if args.multi_table_step else ''}"
+        what = f"the fused {opt_name} step (lr {opt_lr})" if fused else "no table step"
+        if w_opt is not None:
+            what += f", the pooling weights trained by torch.optim.SGD (lr {args.train_pooling_weights})"
+        print(f"apply_emb + loss.backward() with {what}{', multi-table' if args.multi_table_step else ''}"
               f"{', segmented sums of %d' % ebc.segmented_sums if ebc.segmented_sums else ''}: {dt * 1e3:.4f} ms/batch")
         ebc.close()
         return 0

@@ -596,6 +596,50 @@ class GradContext:
         finally:
             self._free(keep)
 
+    def weights_grad(self, table_ids, indices, offsets, grads, padding_idx=None, fixed_pooling: int = 0, outs=None, stream: int | None = None):
+        """The gradient of per_sample_weights of a mode-"sum" lookup (emb_grad_weights): per table one float32 value per index,
+        dw[p] = <grads[bag(p)], weight[indices[p]]> over the fixed tree of include/pimemb_grad.h; +0 for padding entries, entries
+        before the first bag and ids outside the table (those are counted for report()).  table_ids / indices / offsets / grads:
+        one entry per table, as sgd_step takes them -- or one table's number with its three arrays, which returns one array.
+        The tables are only read; fp32 / fp16 / bf16 tables.  Torch CUDA tensors: a pure enqueue on `stream` (torch's current one
+        by default), one launch per table, no pre-pass; outs: float32 CUDA tensors [n_k] to write into (contiguous; None: new
+        ones).  numpy arrays: copied to the device and back, and the call waits."""
+        single = not isinstance(table_ids, (list, tuple))
+        if single:
+            table_ids, indices, grads = [table_ids], [indices], [grads]
+            offsets = None if offsets is None else [offsets]
+            outs = None if outs is None else [outs]
+        if outs is not None and len(outs) != len(table_ids):
+            raise ValueError(f"{len(outs)} outputs for {len(table_ids)} tables")
+        keep, bufs = [], []
+        try:
+            arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, grads, "sum", None, padding_idx, fixed_pooling, stream, keep)
+            ptrs = (C.c_void_p * max(n, 1))()
+            res = []
+            for k in range(n):
+                n_k = int(arr[k].n_indices)
+                if dev:
+                    import torch
+                    o = torch.empty((n_k,), dtype=torch.float32, device=indices[k].device) if outs is None else outs[k]
+                    if not (_is_torch(o) and o.is_cuda) or o.dtype != torch.float32 or not o.is_contiguous() or o.numel() != n_k:
+                        raise TypeError(f"output {k} must be a contiguous float32 CUDA tensor of {n_k} values")
+                    ptrs[k] = o.data_ptr() if n_k else None
+                    res.append(o)
+                else:
+                    if outs is not None:
+                        raise TypeError("outs= goes with torch CUDA inputs")
+                    b = DeviceBuffer(self.engine, max(n_k, 1) * 4, np.float32, (max(n_k, 1),))
+                    bufs.append(b)
+                    ptrs[k] = b.ptr
+                    res.append(n_k)
+            _l.check_grad(self._G.emb_grad_weights(self._h, arr, ptrs, n, itype, stream))
+            if not dev:
+                self.engine.synchronize(stream)
+                res = [b.numpy()[:n_k].copy() for b, n_k in zip(bufs, res)]
+            return res[0] if single else res
+        finally:
+            self._free((*keep, *bufs))
+
     def report(self) -> int:
         """Positions skipped for an id outside the table since the last report (waits for the device; resets the count)."""
         bad = C.c_uint64()

@@ -260,6 +260,7 @@ GRAD_SIGNATURES = {
     "emb_grad_multi_groups": (_u32, [C.POINTER(EmbGradMultiShape), _u32, _u64, _u64, C.POINTER(_u32)]),
     "emb_grad_sgd_multi": (C.c_int, [_vp, C.POINTER(EmbGradDesc), _u32, C.c_int, C.c_float, _vp]),
     "emb_grad_step_multi": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbOptSpec), _vp]),
+    "emb_grad_weights": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, _vp]),
 }
 
 _lib = None

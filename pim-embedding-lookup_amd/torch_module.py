@@ -22,8 +22,12 @@ Training the tables: the Pooling modules have a backward pass on the GPU (libpim
 embedding modules do: loss.backward() updates the served table, there is no weight.grad and nothing for an optimizer to do.  Off
 by default: a module on which it was never called returns plain tensors, as before.  `enable_fused_adagrad(lr, eps, rowwise,
 initial_accumulator_value)` / `adagrad_step_` are the same with the fused Adagrad or row-wise Adagrad step; the fp32 state is
-`module.adagrad_sum` and, once it exists, `<prefix>adagrad_sum` in state_dict().  Not there: the gradient with respect to
-per_sample_weights, mode "max", momentum / Adam, weight decay, fp8 / MXFP4 weights.  max_norm is not supported by any module.
+`module.adagrad_sum` and, once it exists, `<prefix>adagrad_sum` in state_dict().  per_sample_weights that require grad are trained as well: forward()'s result joins
+the autograd graph on them, and backward leaves their gradient -- one value per index, <grad_output[bag], weight[index]> over a
+fixed tree (emb_grad_weights) -- in `.grad`, in their shape and dtype; with a fused step enabled it is computed first, at the
+table forward() read, and the step runs behind it.  `per_sample_weights_grad(input, offsets, grad_output)` is the explicit call.
+Not there: mode "max", momentum / Adam, weight decay, fp8 / MXFP4 weights, a second-order gradient.  max_norm is not supported
+by any module.
 
 Output dtype.  By default every module returns fp32 rows, whatever the table holds.  `out_dtype="weight"` makes a module
 with an fp16 / bf16 weight return the weight's dtype, as nn.EmbeddingBag does: the fp32 pooled value rounded once (the
@@ -331,6 +335,16 @@ class PoolingEmbeddingBag(torch.nn.Module):
             return self.engine.lookup_pooled(self._id_list, [idx], [off], self.mode, per_sample_weights=None if w is None else [w],
                                              padding_idx=self.padding_idx, check=self._check(), out_dtype=self._engine_out)[0]
         lr, ada = getattr(self, "_fused_lr", None), getattr(self, "_fused_adagrad", None)
+        if w is not None and per_sample_weights.requires_grad and torch.is_grad_enabled():
+            # the weights are trained: the result joins the graph on them, and backward enqueues their gradient FIRST -- at the
+            # table this forward read -- and the fused step, if one is enabled, behind it
+            w = w.detach()
+            step = None
+            if ada is not None:
+                step = lambda g: self._adagrad(idx, off, g, ada[0], ada[1], w)  # noqa: E731
+            elif lr is not None:
+                step = lambda g: self._step(idx, off, g, lr, w)  # noqa: E731
+            return _WeightedLookup.apply(_anchor(self, idx.device), lookup, lambda g: [self._weights_grad(idx, off, g)], step, per_sample_weights)
         if ada is not None:
             return _FusedSGD.apply(_anchor(self, idx.device), lookup, lambda g: self._adagrad(idx, off, g, ada[0], ada[1], w))
         if lr is None:
@@ -388,6 +402,24 @@ class PoolingEmbeddingBag(torch.nn.Module):
         state = _adagrad_state(self)
         self._context(idx, off, order).adagrad_step(self._id_list, [idx], [off], [g], [state], lr, eps=eps, rowwise=state.dim() == 1,
                                                     modes=self.mode, per_sample_weights=w, padding_idx=self.padding_idx)
+
+    def _weights_grad(self, idx, off, grad_output):
+        """float32 [len(idx)]: the gradient of per_sample_weights for one batch (None for a None gradient)."""
+        if grad_output is None:
+            return None
+        if self.mode != "sum":
+            raise NotImplementedError(f"per_sample_weights (and their gradient) are only supported for mode='sum' (got mode='{self.mode}')")
+        g = _grad_view(grad_output, self.embedding_dim)
+        return self._context(idx, off).weights_grad(self.table_id, idx, off, g, padding_idx=self.padding_idx)
+
+    def per_sample_weights_grad(self, input, offsets, grad_output):
+        """The gradient of per_sample_weights for one batch, a float32 tensor of input's shape: for every index
+        <grad_output[its bag], weight[index]>, summed over a fixed tree (include/pimemb_grad.h, emb_grad_weights: the same bits on
+        every run); +0 for padding_idx entries and for indices outside the table, which are counted
+        (engine._module_grad.report()).  It does not depend on the weights' values.  The table is only read."""
+        idx, off, _w = self._bags_on_device(input, offsets, None)
+        dw = self._weights_grad(idx, off, torch.as_tensor(grad_output).to(idx.device))
+        return dw.reshape(tuple(torch.as_tensor(input).shape))
 
     def adagrad_step_(self, input, offsets, grad_output, lr: float, eps: float = 1e-10, per_sample_weights=None, order: str = "position"):
         """One fused Adagrad step on the rows the batch names, in place and in stream order with forward(), on the module's state
@@ -529,6 +561,30 @@ class _FusedSGD(torch.autograd.Function):
         return None, None, None
 
 
+class _WeightedLookup(torch.autograd.Function):
+    """_FusedSGD with per_sample_weights that require grad as real tensor inputs: backward enqueues their gradients first
+    (weights_grad(g): one float32 [n] tensor, or None, per weight tensor -- at the table the forward read), then the fused step
+    (None: there is none, the table is left alone), on the same stream.  Each gradient is cast once into its weights' dtype and
+    shape.  The zero-sized anchor stays for the table side."""
+
+    @staticmethod
+    def forward(ctx, anchor, lookup, weights_grad, step, *weights):
+        out = lookup()
+        ctx.weights_grad, ctx.step, ctx.many = weights_grad, step, isinstance(out, (list, tuple))
+        ctx.like = [(tuple(w.shape), w.dtype) for w in weights]
+        return tuple(out) if ctx.many else out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        g = list(grads) if ctx.many else grads[0]
+        dws = ctx.weights_grad(g)
+        if ctx.step is not None:
+            ctx.step(g)
+        outs = [None if dw is None or not need else dw.reshape(shape).to(dtype)
+                for dw, (shape, dtype), need in zip(dws, ctx.like, ctx.needs_input_grad[4:])]
+        return (None, None, None, None, *outs)
+
+
 def _anchor(module, device):
     a = getattr(module, "_sgd_anchor", None)
     if a is None:      # (a plain attribute, not a Parameter: state_dict() keeps its keys)
@@ -617,6 +673,16 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             return self.engine.lookup_pooled(self._ids, idx, off, self._modes, per_sample_weights=wl, padding_idx=self._pads, check=check,
                                              out_dtype=self._outs)
         lr, ada = getattr(self, "_fused_lr", None), getattr(self, "_fused_adagrad", None)
+        trained = [] if lS_w is None or not torch.is_grad_enabled() else [k for k, w in enumerate(lS_w) if w is not None and w.requires_grad]
+        if trained:      # as PoolingEmbeddingBag.forward: the weights' gradients first, then the fused step if there is one
+            wl = [None if w is None else w.detach() for w in ws]
+            step = None
+            if ada is not None:
+                step = lambda g: self._adagrad(idx, off, g, ada[0], ada[1], wl, col)  # noqa: E731
+            elif lr is not None:
+                step = lambda g: self._step(idx, off, g, lr, wl, col)  # noqa: E731
+            return _WeightedLookup.apply(_anchor(self, idx[0].device), lookup, lambda g: self._weights_grads(idx, off, g, col, trained), step,
+                                         *[lS_w[k] for k in trained])
         if ada is not None:
             return _FusedSGD.apply(_anchor(self, idx[0].device), lookup, lambda g: self._adagrad(idx, off, g, ada[0], ada[1], wl, col))
         if lr is None:
@@ -657,23 +723,53 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         """The bags' Adagrad states, in table order (None where a bag has none)."""
         return [b.adagrad_sum for b in self.bags]
 
+    def _table_grads(self, grad_output, col):
+        """Per table the gradient of its pooled rows as the kernels read it ([B, m_k] float32, inner stride 1), None where
+        there is none: the entries of a list, or the column views of ONE [B, sum(m)] gradient."""
+        dims = [b.embedding_dim for b in self.bags]
+        if isinstance(grad_output, (list, tuple)):
+            if len(grad_output) != len(dims):
+                raise ValueError(f"{len(grad_output)} gradients for {len(dims)} tables")
+            return [None if g is None else _grad_view(g, d) for g, d in zip(grad_output, dims)]
+        # ONE [B, sum(m)] gradient (of a concat=True forward; of a wider buffer from column `col`): read in place, table by table
+        g = grad_output if grad_output.dtype == torch.float32 else grad_output.float()
+        if g.dim() != 2 or g.shape[1] < col + sum(dims):
+            raise ValueError(f"grad_output must be [n_bags, >= {col + sum(dims)}], got {tuple(g.shape)}")
+        if g.stride(1) != 1 or (g.shape[0] > 1 and g.stride(0) < g.shape[1]):
+            g = g.contiguous()
+        at = [col + sum(dims[:k]) for k in range(len(dims))]
+        return [g[:, a:a + d] for a, d in zip(at, dims)]
+
+    def _weights_grads(self, idx, off, grad_output, col, tables):
+        """The gradients of the per_sample_weights of `tables` (numbers in the module list), in that order: float32 [n_k]
+        tensors, None where a table has no output gradient.  One launch per table, on the modules' shared context."""
+        if grad_output is None:
+            return [None] * len(tables)
+        grads = self._table_grads(grad_output, col)
+        live = [k for k in tables if grads[k] is not None]
+        out = dict.fromkeys(tables)
+        if live:
+            order = getattr(self, "_fused_order", "position")
+            ctx = _grad_context(self.engine, max(idx[k].shape[0] for k in live), max(off[k].shape[0] for k in live), order,
+                                max(b.embedding_dim for b in self.bags))
+            dws = ctx.weights_grad([self._ids[k] for k in live], [idx[k] for k in live], [off[k] for k in live], [grads[k] for k in live],
+                                   padding_idx=[self._pads[k] for k in live])
+            out.update(zip(live, dws))
+        return [out[k] for k in tables]
+
+    def per_sample_weights_grad(self, lS_o, lS_i, grad_output, col: int = 0):
+        """PoolingEmbeddingBag.per_sample_weights_grad for all tables: a list of float32 tensors of the inputs' shapes.
+        grad_output: a list of [B, m_k] gradients, or the ONE [B, sum(m)] gradient of a concat=True forward (from column col)."""
+        idx, off, _ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, None)
+        dws = self._weights_grads(idx, off, g, col, list(range(len(self.bags))))
+        return [None if dw is None else dw.reshape(tuple(torch.as_tensor(i).shape)) for dw, i in zip(dws, lS_i)]
+
     def _live_grads(self, idx, off, grad_output, ws, col, multi=False, order=None):
         """What a step of either optimizer is called with: (the backward context, positional arguments, keyword arguments, the
         tables' numbers in the module list) over the tables that have a gradient, or None when none has.  multi: the context
         holds the live tables' indices and bags all at once (their sums), so that the multi-table step can fuse them."""
         dims = [b.embedding_dim for b in self.bags]
-        if isinstance(grad_output, (list, tuple)):
-            if len(grad_output) != len(dims):
-                raise ValueError(f"{len(grad_output)} gradients for {len(dims)} tables")
-            grads = [None if g is None else _grad_view(g, d) for g, d in zip(grad_output, dims)]
-        else:      # ONE [B, sum(m)] gradient (of a concat=True forward; of a wider buffer from column `col`): read in place, table by table
-            g = grad_output if grad_output.dtype == torch.float32 else grad_output.float()
-            if g.dim() != 2 or g.shape[1] < col + sum(dims):
-                raise ValueError(f"grad_output must be [n_bags, >= {col + sum(dims)}], got {tuple(g.shape)}")
-            if g.stride(1) != 1 or (g.shape[0] > 1 and g.stride(0) < g.shape[1]):
-                g = g.contiguous()
-            at = [col + sum(dims[:k]) for k in range(len(dims))]
-            grads = [g[:, a:a + d] for a, d in zip(at, dims)]
+        grads = self._table_grads(grad_output, col)
         live = [k for k, g in enumerate(grads) if g is not None]
         if not live:
             return None
