@@ -14,6 +14,7 @@
 //                       (key by CAS) and bids for it with atomicMax(p + 1); a write kernel stores position p only if it holds
 //                       its id's slot.  The MXFP4 flavour reads the source row first: a row with an inf or a NaN is bad, and a
 //                       bad row must not beat an earlier good one.
+//   rows_claim_clear    empties the hash before the claims
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdint.h>
@@ -90,6 +91,15 @@ __device__ inline void claim(unsigned long long *keys, uint32_t *win, uint32_t s
         }
         h = (h + 1) & mask;
     }
+}
+
+// Empties the hash before the claims: keys and bids are 12 bytes per slot, cleared 16 bytes per thread (slots is a power of two
+// >= 64: at most 3 * 2^30 pieces).  A kernel and not hipMemsetAsync: in a captured graph the memset became a memset node, and
+// replays of the graph wrote no row -- every position found its key gone and lost its bid (tests/test_gpu_train_loop.py replays
+// a captured update).  A kernel node keeps its place in the chain.
+__global__ __launch_bounds__(kBlock) void rows_claim_clear(uint4 *pieces, uint32_t n_pieces) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < n_pieces) pieces[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
 template <bool IDX64>
@@ -441,7 +451,8 @@ int enqueue_piece(emb_rows *w, const TableShape &t, const void *ids, bool idx64,
         unsigned long long *keys = reinterpret_cast<unsigned long long *>(w->scratch);
         uint32_t *win = reinterpret_cast<uint32_t *>(w->scratch + slots * 8);
         const uint32_t shift = 64 - log2of(slots), mask = (uint32_t)(slots - 1);
-        ROWS_HIP(hipMemsetAsync(w->scratch, 0, slots * 12, s));
+        const uint32_t pieces = (uint32_t)(slots * 12 / 16);
+        rows_claim_clear<<<dim3((pieces + kBlock - 1) / kBlock), dim3(kBlock), 0, s>>>(reinterpret_cast<uint4 *>(w->scratch), pieces);
         if (mx) {
             const uint64_t blocks = ((uint64_t)n * 16 + kBlock - 1) / kBlock;
             if (idx64) rows_claim_mx<true><<<dim3((uint32_t)blocks), dim3(kBlock), 0, s>>>(ids, src, a.src_stride, t.dim, n, t.nr_rows, keys, win, shift, mask);
