@@ -40,7 +40,8 @@
  * EMB_ERR_UNSUPPORTED for the step, on purpose:
  *   EMB_F8_E4M3 / EMB_F8_E5M2 / EMB_MXFP4   an SGD step in the stored precision mostly rounds away (two or three mantissa bits,
  *                     one for MXFP4), and an MXFP4 block shares one scale: a step on one element would re-quantise its 31
- *                     neighbours.  Keep fp32 master rows, take emb_grad_sparse, and write rows with emb_rows_update.
+ *                     neighbours.  Keep fp32 master rows, take emb_grad_sparse, and write rows with emb_rows_update -- or
+ *                     run all of that as one fused call: emb_grad_master_step (THE MASTER-WEIGHT STEPS, below).
  *   EMB_FIXED32       not a floating-point parameter.
  *   a hot set staged (emb_table_hot_count != 0)   as in the row writer: a hot set is a COPY of rows, lookups would go on serving
  *                     the old bytes: clear the set, step, set it again.
@@ -338,6 +339,79 @@ int emb_grad_step_multi(emb_grad *g, const emb_grad_desc *descs, float *const *s
  * MXFP4 / fixed-point tables; mean and max mode; the ranged / sharded paths; a second-order gradient. */
 int emb_grad_weights(emb_grad *g, const emb_grad_desc *descs, float *const *dw_out, uint32_t n_descs, emb_index_type itype,
                      void *stream);
+
+/* THE MASTER-WEIGHT STEPS: mixed-precision training with fp32 master rows, fused (tests/master_ref.py restates them as a loop; the
+ * kernels are compared with that, bit for bit).  This is the recipe above -- fp32 master rows, emb_grad_sparse, two torch ops,
+ * emb_rows_update -- in ONE pure enqueue, and the only step that trains EMB_F8_E4M3, EMB_F8_E5M2 and EMB_MXFP4 tables; for EMB_F16 and
+ * EMB_BF16 tables it keeps the updates that the in-place step loses below half an ulp of the stored value.
+ * g[r], U, good / bad / padding positions, the order of additions (position or segmented, as the context was created) and the
+ * bad-position count are the ones defined at the top.  M is float[nr_rows][dim], no padding, caller-owned, in device memory.
+ * For every r in U and every element d, every fp32 operation rounded on its own and never contracted into an FMA:
+ *   EMB_MASTER_SGD               M'[r][d] = M[r][d] - (lr * g[r][d])        one fp32 multiply, one fp32 subtract: step_f32 of
+ *                                csrc/pimemb_grad_step.h on the master element
+ *   EMB_MASTER_ADAGRAD           q = g * g;  S' = S[r][d] + q;  den = sqrt(S') + eps;  x = g / den;  M'[r][d] = M[r][d] - (lr * x);
+ *                                S[r][d] = S'           (EMB_OPT_ADAGRAD with dec(W[r][d]) replaced by M[r][d])
+ *   EMB_MASTER_ROWWISE_ADAGRAD   sq, t, v, m, S' and step as EMB_OPT_ROWWISE_ADAGRAD (the same pair tree over dim);
+ *                                M'[r][d] = M[r][d] - (step * g[r][d]);  S[r] = S'
+ *   S is fp32 as in emb_grad_step: float[nr_rows][dim], or float[nr_rows] row-wise.  M' -- the value enc would have taken -- is stored to M.
+ *   Table row                    W[r] = enc_T(M'[r]), enc_T the row writer's encoder of the table's dtype, bit for bit what formats.py
+ *                                writes: enc_f16 / enc_bf16 / enc_e4m3 / enc_e5m2 of csrc/pimemb_rows_encode.h element by element; for
+ *                                EMB_MXFP4 per block of 32 mx_scale_of over the block's amax, mx_code_of per element, scale 127 for a block
+ *                                that quantises to zeros, the scale bytes and the zero padding where pimemb.h puts them
+ *                                (csrc/pimemb_grad_master.h: the one-block arithmetic, compiled by the kernels and by a host check alike).
+ * The table row is NOT READ: the master is authoritative.  Keeping W == enc_T(M) outside the steps is the caller's job:
+ * emb_rows_update of fp32 rows together with a copy of the same rows into M does it.
+ * EMB_MXFP4 rows that cannot be encoded: a row whose M'[r] holds an inf or a NaN anywhere keeps its table bytes, as in the row
+ * writer; M'[r] (and S) are stored all the same, and the row is counted in a counter of its own (emb_grad_master_report).  For the
+ * other dtypes every value has an encoding and the row is written (an inf is fp16 / e5m2 inf and e4m3 0x7f | sign).
+ * Rows outside U keep their table, master and state bytes.  g is never written to memory.
+ *
+ * emb_grad_master_step runs descriptor after descriptor (a table named twice is stepped twice, in order): DEVICE pointers only;
+ * masters[k] is the master of descs[k]'s table, states[k] its state (states may be NULL for EMB_MASTER_SGD); every descriptor, master
+ * and state is checked before anything is enqueued -- a refused call leaves everything as it was; no allocation, no copy, no host
+ * wait: it can be captured in a graph.  It works on a context of either order.
+ *   Tables               EMB_F16, EMB_BF16, EMB_F8_E4M3, EMB_F8_E5M2, EMB_MXFP4.  EMB_F32 is EMB_ERR_UNSUPPORTED: the table is its own
+ *                        master, use emb_grad_sgd / emb_grad_step.  EMB_FIXED32, EMB_POOL_MAX, a staged hot set and the context's
+ *                        limits refuse as in emb_grad_step.
+ *   EMB_ERR_INVALID      a NULL or not 4-byte aligned master where n_indices > 0; a state likewise where the kind needs one; an unknown
+ *                        kind; reserved != 0; eps negative or NaN (checked before the context is looked at).
+ *   Kernel shape         the lane-group kernel runs where dim % 4 == 0, dim <= 512, grad AND MASTER 16-byte aligned, grad_ld % 4 == 0
+ *                        (EMB_MASTER_ADAGRAD: the state too).  Off that shape the 2-byte and 1-byte dtypes run an element-wise kernel
+ *                        with EMB_MASTER_SGD and EMB_MASTER_ADAGRAD, the same bits; EMB_MASTER_ROWWISE_ADAGRAD and EMB_MXFP4 are
+ *                        EMB_ERR_UNSUPPORTED there (no row-wide and no block-wide view).  EMB_MXFP4 beyond dim 512: EMB_ERR_UNSUPPORTED.
+ * How the tail runs.  A lane owns 4 elements per piece: one 16-byte load of M, the step, one 16-byte store of M', one 8-byte (fp16 /
+ * bf16) or 4-byte (fp8) store of the encoded piece -- adjacent lanes write adjacent bytes.  MXFP4: eight adjacent lanes hold a block;
+ * its amax (integer max of the magnitude bits: order-free) and the zeros rule by an xor butterfly over distances 1, 2 and 4, a lane's
+ * four codes packed into 16 bits, the block's 16 bytes and the row's scale piece (dim <= 512: at most 16 scale bytes, exactly one
+ * 16-byte tail piece with its padding) assembled with shuffles and stored by one lane per block and by lane 0; the row's inf / NaN flag
+ * is reduced over the group before the first table store, so -- as in the row-wise step -- every lane of a run-head group stays
+ * through the shuffles, lanes without a piece hold +0, and beyond dim 256 a lane keeps both pieces' sums.
+ * The kernels of these steps have a code object of their own, libpimemb_grad_master.so, built from the same source and found next to
+ * libpimemb_grad.so, which links against it: libpimemb_grad.so's own code object holds exactly the kernels it held before.
+ * The unencodable count lives in the second word of the context's 256-byte counter block: emb_grad_scratch_bytes(_ex) are unchanged.
+ * Speed, measured on MI355X (tools/master_probe.py, profiles/master/README.md; SGD, medians of five alternating rounds, device
+ * pointers; dim 128, 2048 bags x 32, 4 M rows).  Uniform ids: 75 / 76 / 90 us on bf16 / e4m3 / MXFP4 tables against 177 / 176 / 192 us
+ * for the no-wait recipe (fill, emb_grad_sparse, the torch ops, emb_rows_update): 2.1 - 2.4x faster; 1.05x SLOWER than the in-place
+ * bf16 emb_grad_sgd (71.5 us) -- the price of the master's extra 8 bytes per element.  Zipf ids, S = 64 context: 137 / 137 / 142 us
+ * against 388 / 311 / 398 (2.3 - 2.8x faster; level with the in-place step, 136 us); position-order context: 4.0 ms either way, the
+ * hot row's chain (1.04 - 1.06x faster than the recipe, 1.07x SLOWER than in place).  The Kaggle shape (dim 16, 39 292 one-index
+ * bags): 50 / 52 us on bf16 / e4m3 against 106 / 107.  The MXFP4 tail is 1.19x the e4m3 step on the uniform shape.
+ * Out of scope: a multi-table master step (the group record has no room for the master pointer, and the multi-table kernels keep
+ * their text); masters in anything but fp32; the ranged / sharded paths. */
+typedef enum { EMB_MASTER_SGD = 0, EMB_MASTER_ADAGRAD = 1, EMB_MASTER_ROWWISE_ADAGRAD = 2 } emb_master_kind;
+typedef struct emb_master_spec {
+    uint32_t kind;     /* an emb_master_kind */
+    float lr;
+    float eps;         /* >= 0; not used by EMB_MASTER_SGD */
+    uint32_t reserved; /* 0 */
+} emb_master_spec;
+
+int emb_grad_master_step(emb_grad *g, const emb_grad_desc *descs, float *const *masters, float *const *states, uint32_t n_descs,
+                         emb_index_type itype, const emb_master_spec *spec, void *stream);
+
+/* The number of EMB_MXFP4 rows master steps left unwritten (an inf or a NaN in the new master row) since the last such report;
+ * resets the count.  Waits for the device first, like emb_grad_report, whose count of bad positions is a separate one. */
+int emb_grad_master_report(emb_grad *g, uint64_t *n_unencodable);
 
 /* The number of BAD positions (an id outside the table) skipped since the last report; resets the count.  Waits for the
  * device first, so the count covers every call enqueued so far. */

@@ -45,6 +45,7 @@
 
 #include "pimemb_grad.h"
 #include "pimemb_grad_dot.h"
+#include "pimemb_grad_master.h"
 #include "pimemb_grad_optim.h"
 #include "pimemb_grad_segments.h"
 #include "pimemb_grad_step.h"
@@ -170,6 +171,7 @@ __global__ __launch_bounds__(kBlock) void grad_scan_chunks(const uint32_t *data,
 }
 
 // Level two: ONE workgroup scans the chunk sums in place; *total_out (may be NULL) = the sum of everything.
+#ifndef PIMEMB_GRAD_MASTER_UNIT      // (a kernel of libpimemb_grad.so alone: the master unit emits only its own)
 __global__ __launch_bounds__(kBlock) void grad_scan_sums(uint32_t *sums, uint32_t n_chunks, unsigned long long *total_out) {
     __shared__ uint32_t wave_sums[kBlock / 64];
     uint32_t carry = 0;
@@ -189,9 +191,11 @@ __global__ __launch_bounds__(kBlock) void grad_scan_sums(uint32_t *sums, uint32_
     }
     if (total_out && threadIdx.x == 0) *total_out = carry;
 }
+#endif
 
 // Digit counts of tile `blk`, stored digit-major -- hist[digit * n_tiles + blk] -- so that one exclusive scan over the whole
 // matrix gives every (digit, tile) pair the place of its first position.
+#ifndef PIMEMB_GRAD_MASTER_UNIT      // (a kernel of libpimemb_grad.so alone: the master unit emits only its own)
 __global__ __launch_bounds__(kBlock) void grad_sort_count(const uint32_t *keys, uint32_t n, uint32_t shift, uint32_t *hist, uint32_t n_tiles) {
     __shared__ uint32_t counts[256];
     counts[threadIdx.x] = 0;
@@ -205,11 +209,13 @@ __global__ __launch_bounds__(kBlock) void grad_sort_count(const uint32_t *keys, 
     __syncthreads();
     hist[(uint64_t)threadIdx.x * n_tiles + blockIdx.x] = counts[threadIdx.x];
 }
+#endif
 
 // The stable scatter of one pass.  A tile is 16 slices of 64 consecutive positions (round r of wavefront w: slice 4 r + w).  Inside
 // a slice, the lanes that hold the same digit find each other with 8 ballots: a position's rank among them is the number of
 // such lanes below it, and the lowest of them records their count.  Thread d then turns digit d's 16 slice counts into
 // offsets, and a position goes to   (scanned hist of its digit and tile) + (its slice's offset) + (its rank in the slice).
+#ifndef PIMEMB_GRAD_MASTER_UNIT      // (a kernel of libpimemb_grad.so alone: the master unit emits only its own)
 __global__ __launch_bounds__(kBlock) void grad_sort_scatter(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
                                                             uint32_t *vals_out, uint32_t n, uint32_t shift, const uint32_t *hist,
                                                             const uint32_t *sums, uint32_t n_tiles) {
@@ -264,6 +270,7 @@ __global__ __launch_bounds__(kBlock) void grad_sort_scatter(const uint32_t *keys
         }
     }
 }
+#endif
 
 // ---- the hot kernels --------------------------------------------------------------------------------------------------------
 
@@ -720,6 +727,7 @@ __device__ __forceinline__ void seg_partials_body(const RowArgs &a, const SegArg
 }
 
 // One lane group per sorted place, as grad_rows_group is launched; it works where a segment of a long run starts.
+#ifndef PIMEMB_GRAD_MASTER_UNIT      // (a kernel of libpimemb_grad.so alone: the master unit emits only its own)
 __global__ __launch_bounds__(kBlock) void grad_seg_partials(RowArgs a, SegArgs sg, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
     const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const uint64_t i64 = gid >> lanes_log2;
@@ -731,6 +739,7 @@ __global__ __launch_bounds__(kBlock) void grad_seg_partials(RowArgs a, SegArgs s
     const int kind = seg_start_kind(a.keys, a.n, i, row, sg.S);           // (uniform over the lane group)
     if (kind) seg_partials_body(a, sg, i, row, kind, lg, lanes, chunks);
 }
+#endif
 
 // What grad_rows_group does with a run, in the segmented order; `key` is what the run's places hold, `row` the table row it names.
 template <int KIND>
@@ -802,6 +811,7 @@ __device__ __forceinline__ RowArgs multi_row_args(const MultiArgs &m, uint32_t k
 }
 
 // grad_seg_partials over the runs of a group's composite keys: adjacent keys of two tables are two runs, as everywhere.
+#ifndef PIMEMB_GRAD_MASTER_UNIT      // (a kernel of libpimemb_grad.so alone: the master unit emits only its own)
 __global__ __launch_bounds__(kBlock) void grad_seg_multi_partials(const MultiArgs m, const uint32_t *keys, const uint32_t *vals, const uint32_t *bagof,
                                                                   const uint32_t *cnt, SegArgs sg, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
     const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -817,6 +827,7 @@ __global__ __launch_bounds__(kBlock) void grad_seg_multi_partials(const MultiArg
     const RowArgs a = multi_row_args(m, key, keys, vals, bagof, cnt, 0.f, 0.f, &row);
     seg_partials_body(a, sg, i, key, kind, lg, lanes, chunks);
 }
+#endif
 
 // grad_multi_rows in the segmented order.
 template <int KIND>
@@ -882,6 +893,269 @@ __global__ __launch_bounds__(kBlock) void grad_seg_rows_elem(RowArgs a, uint32_t
     }
     if (KIND == RES_ADAGRAD) *sp = st;
 }
+
+// ---- the master-weight steps: M' = step(M, g), W = enc_T(M') (csrc/pimemb_grad_master.h) -------------------------------------------
+// The same pre-pass, sort and run walk; the tail reads and writes the caller's fp32 master row where the kernels above decode the
+// table row, and stores the table row encoded from the new master: the table is never read.  The kernels above keep their text:
+// what is new travels in MasterArgs beside RowArgs (a.table / a.stride / a.lr / a.eps / a.state are used as they are, a.dtype is not).
+
+struct MasterArgs {
+    float *master;               // M: float[nr_rows][dim], no padding
+    int enc;                     // the table's dtype: kMasterF16 / kMasterBF16 / kMasterE4M3 / kMasterE5M2 / kMasterMXFP4
+    unsigned long long *unenc;   // MXFP4: rows whose new master holds an inf or a NaN (their table bytes are kept)
+};
+
+// (the master kinds are the step kinds plus this: the tails below are instantiated for these three alone)
+enum MasterKind : int { RES_MASTER_SGD = 4, RES_MASTER_ADAGRAD = 5, RES_MASTER_ROWWISE = 6 };
+
+// The kernels of the master steps are compiled into a code object of their own: this file is compiled a second time with
+// -DPIMEMB_GRAD_MASTER_UNIT into libpimemb_grad_master.so (csrc/Makefile), which holds them and exports their two launch functions;
+// libpimemb_grad.so's code object is the one it was (tests pin the set of its kernels), and its host side calls the launchers.
+#ifdef PIMEMB_GRAD_MASTER_UNIT
+
+// cnt[0 .. n) = 0 ahead of a mean-mode classify.  A kernel, not a memset node.  What was observed, on this runtime: a graph of
+// {prepared lookup, a copy, a mean-mode master step, prepared lookup} captured with hipMemsetAsync here replayed to tables that
+// differed from the reference in every named row, with SGD and row-wise alike, while the same graph in sum mode (no clear) and the
+// same mean-mode step uncaptured were exact; with this kernel the replays are exact (tests/test_gpu_master_step.py keeps both
+// modes).  The row writer's hash clear showed the same under capture and became a kernel too.  What was NOT observed: emb_grad_sgd /
+// emb_grad_step in mean mode under capture -- they keep their memset, tests/test_gpu_grad_graph.py replays a mean-mode batch through
+// them and passes; whether they can be affected in other graphs is an open question for an issue of its own, not settled here.
+__global__ __launch_bounds__(kBlock) void grad_master_clear(uint32_t *cnt, uint32_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) cnt[i] = 0u;
+}
+
+// One master element stepped.  `rate` is lr (SGD, Adagrad) or the row's step size (row-wise); Adagrad steps *st as adagrad_step does.
+template <int KIND>
+__device__ __forceinline__ float master_elem(float m, float g, float *st, float rate, float eps) {
+    if (KIND == RES_MASTER_ADAGRAD) return bits_f32(adagrad_step(kStepF32, f32_bits(m), g, st, rate, eps));
+    return step_f32(m, g, rate);
+}
+
+// The master tail of piece c: one 16-byte load of M, the step, one 16-byte store of M' (Adagrad: the same for the piece of S).
+// Returns M'[row][4c .. 4c + 3].
+template <int KIND>
+__device__ __forceinline__ float4 master_piece(const RowArgs &a, const MasterArgs &ma, uint32_t row, uint32_t c, float4 acc, float rate) {
+    float4 *sp = nullptr;
+    float4 st = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (KIND == RES_MASTER_ADAGRAD) {
+        sp = reinterpret_cast<float4 *>(a.state + (uint64_t)row * a.dim) + c;
+        st = *sp;
+    }
+    float4 *mp = reinterpret_cast<float4 *>(ma.master + (uint64_t)row * a.dim) + c;
+    float4 m = *mp;
+    m.x = master_elem<KIND>(m.x, acc.x, &st.x, rate, a.eps);
+    m.y = master_elem<KIND>(m.y, acc.y, &st.y, rate, a.eps);
+    m.z = master_elem<KIND>(m.z, acc.z, &st.z, rate, a.eps);
+    m.w = master_elem<KIND>(m.w, acc.w, &st.w, rate, a.eps);
+    *mp = m;
+    if (KIND == RES_MASTER_ADAGRAD) *sp = st;
+    return m;
+}
+
+// The encoded piece c of a 2-byte or 1-byte table row: ONE vector store of 8 or 4 bytes, adjacent lanes adjacent bytes.
+__device__ __forceinline__ void master_store_piece(const RowArgs &a, const MasterArgs &ma, uint32_t row, uint32_t c, float4 m) {
+    const uint32_t bits[4] = {f32_bits(m.x), f32_bits(m.y), f32_bits(m.z), f32_bits(m.w)};
+    char *w = a.table + (uint64_t)row * a.stride;
+    if (ma.enc == kMasterF16 || ma.enc == kMasterBF16) {
+        u32x2 o;
+        master_enc_piece16(ma.enc, bits, &o.x, &o.y);
+        reinterpret_cast<u32x2 *>(w)[c] = o;
+    } else {
+        reinterpret_cast<uint32_t *>(w)[c] = master_enc_piece8(ma.enc, bits);
+    }
+}
+
+struct u32x4 {
+    uint32_t x, y, z, w;
+} __attribute__((aligned(16)));
+
+// One block's share of the MXFP4 tail, for the pieces the group's lanes hold at one of their two slots (slot 0: piece lg, slot 1:
+// piece lg + 64): eight adjacent lanes are block `blk` (live: blk < nb; a lane without a piece holds +0).  Every lane of the group runs
+// every shuffle.  Returns the block's 16 element bytes in its leading lane (lg % 8 == 0) and *scale = its scale byte in all eight
+// (0 for a block past the row: padding); *amax_or collects the magnitudes for the row's inf / NaN flag.
+__device__ __forceinline__ u32x4 master_mx_block(float4 m, bool live, uint32_t *scale, uint32_t *amax_or) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t bits[4] = {f32_bits(m.x), f32_bits(m.y), f32_bits(m.z), f32_bits(m.w)};
+    uint32_t amax = mx_piece_amax(bits);
+    amax = mx_max(amax, (uint32_t)__shfl_xor((int)amax, 1));
+    amax = mx_max(amax, (uint32_t)__shfl_xor((int)amax, 2));
+    amax = mx_max(amax, (uint32_t)__shfl_xor((int)amax, 4));      // the block's amax, in all eight of its lanes
+    *amax_or = mx_max(*amax_or, amax);
+    uint32_t s = pimemb_rows::mx_scale_of(amax);
+    const uint32_t codes = mx_piece_codes(bits, s);
+    int zeros = mx_piece_zeros(codes);
+    zeros &= __shfl_xor(zeros, 1);
+    zeros &= __shfl_xor(zeros, 2);
+    zeros &= __shfl_xor(zeros, 4);
+    if (zeros) s = 127;
+    *scale = live ? s : 0u;
+    const int q = (int)(lane & ~7u);
+    uint32_t k[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) k[j] = (uint32_t)__shfl((int)codes, q + j);
+    return u32x4{k[0] | (k[1] << 16), k[2] | (k[3] << 16), k[4] | (k[5] << 16), k[6] | (k[7] << 16)};
+}
+
+// The MXFP4 tail of a row whose new master pieces the group holds (m0: piece lg, m1: piece lg + lanes, +0 where a lane has none).
+// dim <= 512: at most 16 blocks, their scale bytes are exactly one 16-byte tail piece with its zero padding.
+__device__ __forceinline__ void master_mx_row(const RowArgs &a, const MasterArgs &ma, uint32_t row, uint32_t lg, uint32_t lanes, float4 m0, float4 m1) {
+    const uint32_t nb = a.dim / 32u, blk = lg / 8u;
+    const uint32_t base = (threadIdx.x & 63u) & ~(lanes - 1u);
+    uint32_t s0, s1, amax = 0;
+    const u32x4 e0 = master_mx_block(m0, blk < nb, &s0, &amax);
+    const u32x4 e1 = master_mx_block(m1, blk + lanes / 8u < nb, &s1, &amax);      // (live only beyond dim 256, where lanes == 64)
+    for (uint32_t h = 8; h < lanes; h <<= 1) amax = mx_max(amax, (uint32_t)__shfl_xor((int)amax, (int)h));      // (blocks are uniform already)
+    // the tail piece: byte b = the scale of block b, from the lane that leads the block (slot 0: blocks 0 .. lanes / 8 - 1, slot 1: the next eight)
+    uint32_t t[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t b = 0; b < 8; b++) {
+        const uint32_t from = 8u * b;
+        const uint32_t v0 = (uint32_t)__shfl((int)s0, (int)(base + (from & (lanes - 1u))));
+        const uint32_t v1 = (uint32_t)__shfl((int)s1, (int)(base + (from & (lanes - 1u))));
+        if (from < lanes) {
+            t[b / 4] |= v0 << (8u * (b & 3u));
+            t[2 + b / 4] |= v1 << (8u * (b & 3u));      // (lanes == 64 where slot 1 is live: blocks 8 .. 15 are bytes 8 .. 15)
+        }
+    }
+    if (mx_non_finite(amax)) {                   // uniform over the group: the row keeps its table bytes and is counted
+        if (lg == 0) atomicAdd(ma.unenc, 1ull);
+        return;
+    }
+    u32x4 *dst = reinterpret_cast<u32x4 *>(a.table + (uint64_t)row * a.stride);
+    if ((lg & 7u) == 0) {
+        if (blk < nb) dst[blk] = e0;
+        if (blk + lanes / 8u < nb) dst[blk + lanes / 8u] = e1;
+    }
+    if (lg == 0) dst[nb] = u32x4{t[0], t[1], t[2], t[3]};
+}
+
+// grad_rows_group / grad_seg_rows_group with the master tail.  The row-wise kind and MXFP4 need the whole row before the first
+// table store (the row's step size; the blocks' amax and the row's inf / NaN flag): there every lane of a run-head group stays
+// through the shuffles, lanes without a piece hold +0, and beyond dim 256 a lane keeps both pieces' sums -- as in the row-wise
+// step.  All shuffles sit behind the run walk, with xor distances (and source lanes) inside the group.
+template <int KIND, bool SEG>
+__global__ __launch_bounds__(kBlock) void grad_master_rows_group(RowArgs a, SegArgs sg, MasterArgs ma, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    const bool wide = KIND == RES_MASTER_ROWWISE || ma.enc == kMasterMXFP4;      // (uniform over the launch)
+    if (i64 >= a.n || (!wide && lg >= chunks)) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;      // (uniform over the lane group)
+    if (!wide) {
+        for (uint32_t c = lg; c < chunks; c += lanes) {
+            const float4 acc = SEG ? seg_walk_piece(a, sg, i, row, c, chunks) : walk_piece(a, i, row, c);
+            master_store_piece(a, ma, row, c, master_piece<KIND>(a, ma, row, c, acc, a.lr));
+        }
+        return;
+    }
+    const bool own0 = lg < chunks, own1 = lg + lanes < chunks;            // (own1: beyond dim 256 only, where lanes == 64)
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 acc0 = zero, acc1 = zero;
+    if (own0) acc0 = SEG ? seg_walk_piece(a, sg, i, row, lg, chunks) : walk_piece(a, i, row, lg);
+    if (own1) acc1 = SEG ? seg_walk_piece(a, sg, i, row, lg + lanes, chunks) : walk_piece(a, i, row, lg + lanes);
+    float rate = a.lr;
+    if (KIND == RES_MASTER_ROWWISE) rate = rowwise_rate(a, row, lg, lanes, acc0, acc1, own1);
+    float4 m0 = zero, m1 = zero;
+    if (own0) m0 = master_piece<KIND>(a, ma, row, lg, acc0, rate);
+    if (own1) m1 = master_piece<KIND>(a, ma, row, lg + lanes, acc1, rate);
+    if (ma.enc == kMasterMXFP4) {
+        master_mx_row(a, ma, row, lg, lanes, m0, m1);
+        return;
+    }
+    if (own0) master_store_piece(a, ma, row, lg, m0);
+    if (own1) master_store_piece(a, ma, row, lg + lanes, m1);
+}
+
+// grad_rows_elem / grad_seg_rows_elem with the master tail: one thread per (sorted place, element), the 2-byte and 1-byte dtypes.
+// (No row-wise kind and no MXFP4: no thread here sees a whole row, or a whole block.)
+template <int KIND, bool SEG>
+__global__ __launch_bounds__(kBlock) void grad_master_rows_elem(RowArgs a, MasterArgs ma, uint32_t S) {
+    static_assert(KIND != RES_MASTER_ROWWISE, "the element-wise kernel has no row-wide view of g");
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid / a.dim;
+    const uint32_t c = (uint32_t)(gid - i64 * a.dim);
+    if (i64 >= a.n) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;
+    float acc = 0.f, t = 0.f;
+    uint32_t in_seg = 0;
+    bool first = true;                           // (SEG) t_0 is taken as it is: the sum of the partials starts from it
+    for (uint32_t j = i; j < a.n && a.keys[j] == row; j++) {
+        const uint32_t p = min(a.vals[j], a.n - 1u);
+        const uint32_t b = min(a.bagof[p], a.n_bags - 1u);
+        const float cp = contribution(a.coef, a.grad[(uint64_t)b * a.ld + c], coef_of(a, p, b));
+        if (!SEG) {
+            acc = add_in_order(acc, cp);
+            continue;
+        }
+        t = add_in_order(t, cp);
+        if (++in_seg == S) {
+            acc = first ? t : add_in_order(acc, t);
+            first = false;
+            t = 0.f;
+            in_seg = 0;
+        }
+    }
+    if (SEG && in_seg) acc = first ? t : add_in_order(acc, t);
+    float *sp = KIND == RES_MASTER_ADAGRAD ? a.state + (uint64_t)row * a.dim + c : nullptr;
+    float st = KIND == RES_MASTER_ADAGRAD ? *sp : 0.f;
+    float *mp = ma.master + (uint64_t)row * a.dim + c;
+    const float m = master_elem<KIND>(*mp, acc, &st, a.lr, a.eps);
+    *mp = m;
+    if (KIND == RES_MASTER_ADAGRAD) *sp = st;
+    const uint32_t o = master_enc(ma.enc, f32_bits(m));
+    char *w = a.table + (uint64_t)row * a.stride;
+    if (ma.enc == kMasterF16 || ma.enc == kMasterBF16) reinterpret_cast<uint16_t *>(w)[c] = (uint16_t)o;
+    else reinterpret_cast<uint8_t *>(w)[c] = (uint8_t)o;
+}
+
+}  // namespace
+
+// The two launch functions libpimemb_grad_master.so exports (plain C; the argument records are this file's own RowArgs, SegArgs and
+// MasterArgs, which both compilations lay out alike).  Errors are left to the caller's hipGetLastError().
+extern "C" __attribute__((visibility("default"))) void pimemb_grad_master_clear(uint32_t *cnt, uint32_t n, void *stream) {
+    grad_master_clear<<<dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, static_cast<hipStream_t>(stream)>>>(cnt, n);
+}
+
+// The hot launch of a master-weight step (a chain of one): the lane-group kernel or the element-wise one, in the context's order.
+// kind: RES_SGD / RES_ADAGRAD / RES_ROWWISE; lane: the lane-group kernel with this geometry, else elem_blocks workgroups element-wise.
+extern "C" __attribute__((visibility("default"))) void pimemb_grad_master_launch(const void *row_args, const void *seg_args, const void *master_args, int kind,
+                                                                                  int seg, int lane, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks,
+                                                                                  uint32_t blocks, uint32_t elem_blocks, uint32_t S, void *stream) {
+    const RowArgs &a = *static_cast<const RowArgs *>(row_args);
+    const SegArgs &sg = *static_cast<const SegArgs *>(seg_args);
+    const MasterArgs &ma = *static_cast<const MasterArgs *>(master_args);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 block(kBlock);
+    if (lane) {
+        const dim3 grid(blocks);
+        if (kind == RES_SGD && seg) grad_master_rows_group<RES_MASTER_SGD, true><<<grid, block, 0, s>>>(a, sg, ma, lanes, lanes_log2, chunks);
+        else if (kind == RES_SGD) grad_master_rows_group<RES_MASTER_SGD, false><<<grid, block, 0, s>>>(a, sg, ma, lanes, lanes_log2, chunks);
+        else if (kind == RES_ADAGRAD && seg) grad_master_rows_group<RES_MASTER_ADAGRAD, true><<<grid, block, 0, s>>>(a, sg, ma, lanes, lanes_log2, chunks);
+        else if (kind == RES_ADAGRAD) grad_master_rows_group<RES_MASTER_ADAGRAD, false><<<grid, block, 0, s>>>(a, sg, ma, lanes, lanes_log2, chunks);
+        else if (seg) grad_master_rows_group<RES_MASTER_ROWWISE, true><<<grid, block, 0, s>>>(a, sg, ma, lanes, lanes_log2, chunks);
+        else grad_master_rows_group<RES_MASTER_ROWWISE, false><<<grid, block, 0, s>>>(a, sg, ma, lanes, lanes_log2, chunks);
+        return;
+    }
+    const dim3 grid(elem_blocks);                // (the row-wise kind never gets here: the plan refused it)
+    if (kind == RES_SGD && seg) grad_master_rows_elem<RES_MASTER_SGD, true><<<grid, block, 0, s>>>(a, ma, S);
+    else if (kind == RES_SGD) grad_master_rows_elem<RES_MASTER_SGD, false><<<grid, block, 0, s>>>(a, ma, 0u);
+    else if (seg) grad_master_rows_elem<RES_MASTER_ADAGRAD, true><<<grid, block, 0, s>>>(a, ma, S);
+    else grad_master_rows_elem<RES_MASTER_ADAGRAD, false><<<grid, block, 0, s>>>(a, ma, 0u);
+}
+
+namespace {
+#else      // libpimemb_grad.so: the launchers are libpimemb_grad_master.so's
+}  // namespace
+extern "C" void pimemb_grad_master_clear(uint32_t *cnt, uint32_t n, void *stream);
+extern "C" void pimemb_grad_master_launch(const void *row_args, const void *seg_args, const void *master_args, int kind, int seg, int lane, uint32_t lanes,
+                                          uint32_t lanes_log2, uint32_t chunks, uint32_t blocks, uint32_t elem_blocks, uint32_t S, void *stream);
+namespace {
+#endif
 
 // ---- the gradient of per_sample_weights: dw[p] = < G[bag(p)] , dec(W[ids[p]]) > (csrc/pimemb_grad_dot.h) ------------------------
 // No pre-pass: nothing is sorted, a position's value depends on its own row and its bag's row of G alone.  The kernels above keep
@@ -1041,6 +1315,7 @@ __global__ __launch_bounds__(kBlock) void grad_psw_elem(PswArgs a, uint32_t lane
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
+#ifndef PIMEMB_GRAD_MASTER_UNIT      // (to the end of the file: the master unit holds kernels and their launchers alone)
 
 thread_local char t_err[512] = "";
 
@@ -1117,7 +1392,7 @@ struct emb_grad {
     uint64_t max_indices = 0, max_bags = 0;
     char *scratch = nullptr;
     Layout lay{};
-    unsigned long long *counters = nullptr;      // [0] bad positions since the last report
+    unsigned long long *counters = nullptr;      // [0] bad positions since the last report; [1] MXFP4 rows a master step could not encode
     emb_grad_config cfg{};                       // the order of additions of every call on this context
     uint32_t seg_log2 = 0;                       // EMB_GRAD_ORDER_SEGMENTED: log2 of cfg.segment
     bool segmented() const { return cfg.order == EMB_GRAD_ORDER_SEGMENTED; }
@@ -1267,6 +1542,7 @@ int check_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, const 
 struct StepSpec {
     int kind = RES_SPARSE;       // ResultKind
     float lr = 0.f, eps = 0.f;
+    float *const *masters = nullptr;      // emb_grad_master_step: one fp32 master per descriptor; the kind's master tail runs
 };
 struct SparseOut {               // where emb_grad_sparse writes; all NULL for a step (no unique numbering, no output arrays)
     long long *rows = nullptr;
@@ -1444,7 +1720,8 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
     const dim3 block(kBlock), pos_grid((n + kBlock - 1) / kBlock);
     unsigned long long *bad = &g->counters[0];
     MultiArgs m;                                 // (filled for a group only)
-    if (c.mean && c.n_bags) GRAD_HIP(hipMemsetAsync(sc.cnt, 0, (size_t)c.n_bags * 4, s));
+    if (c.mean && c.n_bags && spec.masters) pimemb_grad_master_clear(sc.cnt, c.n_bags, s);
+    else if (c.mean && c.n_bags) GRAD_HIP(hipMemsetAsync(sc.cnt, 0, (size_t)c.n_bags * 4, s));
     if (group) {
         fill_multi(m, descs, states, p, first);
         if (idx64) grad_multi_classify<true><<<pos_grid, block, 0, s>>>(m, sc.keys[0], sc.vals[0], sc.bagof, sc.cnt, bad);
@@ -1504,6 +1781,13 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
         GRAD_HIP(hipGetLastError());
         a.uidx = sc.uidx, a.usums = sc.sums, a.rows_out = out.rows, a.grads_out = out.grads;
     }
+    if (spec.masters) {
+        if (seg && c.lane) grad_seg_partials<<<dim3(l.blocks), block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
+        const MasterArgs ma{spec.masters[first], c.t.dtype, &g->counters[1]};
+        pimemb_grad_master_launch(&a, &sg, &ma, spec.kind, seg, c.lane, l.lanes, l.lanes_log2, l.chunks, l.blocks, c.elem_blocks, g->cfg.segment, s);
+        GRAD_HIP(hipGetLastError());
+        return EMB_OK;
+    }
     if (seg && c.lane) {
         const dim3 grid(l.blocks);
         grad_seg_partials<<<grid, block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
@@ -1529,6 +1813,46 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
         else grad_rows_elem<RES_SPARSE><<<grid, block, 0, s>>>(a);      // (RES_ROWWISE never gets here: the plan refused it)
     }
     GRAD_HIP(hipGetLastError());
+    return EMB_OK;
+}
+
+// The plan of emb_grad_master_step: every descriptor, master and state checked, in order; then one chain per non-empty descriptor.
+int plan_master(emb_grad *g, const emb_grad_desc *descs, float *const *masters, float *const *states, uint32_t n_descs, emb_index_type itype,
+                const StepSpec &spec, const char *who, Planned *plan) {
+    for (uint32_t k = 0; k < n_descs; k++) {
+        const emb_grad_desc &d = descs[k];
+        Planned &p = plan[k];
+        TableShape &t = p.t;
+        if (int rc = check_desc(g, d, itype, nullptr, who, &t)) return rc;
+        if (t.dtype == kF32)
+            return fail(EMB_ERR_UNSUPPORTED, "%s: table %u is EMB_F32: the table is its own master, use emb_grad_sgd / emb_grad_step", who, d.table_id);
+        if (t.dtype != kMasterF16 && t.dtype != kMasterBF16 && t.dtype != kMasterE4M3 && t.dtype != kMasterE5M2 && t.dtype != kMasterMXFP4)
+            return fail(EMB_ERR_UNSUPPORTED, "%s: table %u has dtype %d, which no master step encodes", who, d.table_id, t.dtype);
+        uint32_t n_hot = 0;
+        if (int rc = emb_table_hot_count(g->e, d.table_id, &n_hot)) return fail_engine(rc, who);
+        if (n_hot)
+            return fail(EMB_ERR_UNSUPPORTED,
+                        "%s: table %u has a hot set of %u rows staged, a copy taken when it was set that lookups would go on serving: "
+                        "clear the set (emb_set_hot_rows with n_rows = 0), step, then set it again", who, d.table_id, n_hot);
+        const bool mx = t.dtype == kMasterMXFP4;
+        if (mx && t.dim > 512) return fail(EMB_ERR_UNSUPPORTED, "%s: table %u is MXFP4 of dim %u, the master step takes MXFP4 rows up to dim 512", who, d.table_id, t.dim);
+        t.stride = mx ? EMB_MXFP4_ROW_STRIDE(t.dim) : t.dim * (t.dtype == kMasterF16 || t.dtype == kMasterBF16 ? 2u : 1u);
+        float *master = d.n_indices ? masters[k] : nullptr;
+        if (d.n_indices && (!master || (uintptr_t)master % 4))
+            return fail(EMB_ERR_INVALID, "%s: the master of table %u is NULL or not 4-byte aligned", who, d.table_id);
+        float *state = d.n_indices && states ? states[k] : nullptr;
+        if (d.n_indices && spec.kind != RES_SGD && (!state || (uintptr_t)state % 4))
+            return fail(EMB_ERR_INVALID, "%s: the state of table %u is NULL or not 4-byte aligned", who, d.table_id);
+        p.lane = lane_group_path(d, t, spec.kind, state, nullptr) && (uintptr_t)master % 16 == 0;
+        if (d.n_indices && !p.lane && (spec.kind == RES_ROWWISE || mx))
+            return fail(EMB_ERR_UNSUPPORTED,
+                        "%s: %s needs the lane-group shape (dim %% 4 == 0, dim <= 512, grad and master 16-byte aligned, grad_ld %% 4 == 0): table %u has "
+                        "dim %u, grad %p, grad_ld %llu, master %p -- the element-wise kernel has no row-wide or block-wide view", who,
+                        mx ? "an MXFP4 table" : "row-wise Adagrad", d.table_id, t.dim, (const void *)d.grad, (unsigned long long)d.grad_ld, (const void *)master);
+    }
+    for (uint32_t k = 0; k < n_descs; k++)
+        if (descs[k].n_indices)
+            if (int rc = plan_chain(g, descs, plan, k, k + 1)) return rc;
     return EMB_OK;
 }
 
@@ -1703,6 +2027,41 @@ int emb_grad_weights(emb_grad *g, const emb_grad_desc *descs, float *const *dw_o
     return EMB_OK;
 }
 
+int emb_grad_master_step(emb_grad *g, const emb_grad_desc *descs, float *const *masters, float *const *states, uint32_t n_descs, emb_index_type itype,
+                         const emb_master_spec *spec, void *stream) {
+    const char *who = "emb_grad_master_step";
+    if (!spec) return fail(EMB_ERR_INVALID, "%s: the master spec is NULL", who);
+    if (spec->kind != EMB_MASTER_SGD && spec->kind != EMB_MASTER_ADAGRAD && spec->kind != EMB_MASTER_ROWWISE_ADAGRAD)
+        return fail(EMB_ERR_INVALID, "%s: unknown master step kind %u", who, spec->kind);
+    if (spec->reserved != 0) return fail(EMB_ERR_INVALID, "%s: the spec's reserved field must be 0, got %u", who, spec->reserved);
+    if (!(spec->eps >= 0.f)) return fail(EMB_ERR_INVALID, "%s: eps must not be negative or NaN, got %g", who, (double)spec->eps);
+    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
+    const bool sgd = spec->kind == EMB_MASTER_SGD;
+    if (n_descs && (!descs || !masters || (!sgd && !states))) return fail(EMB_ERR_INVALID, "%s: descs, masters or states is NULL", who);
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    StepSpec st{sgd ? RES_SGD : spec->kind == EMB_MASTER_ADAGRAD ? RES_ADAGRAD : RES_ROWWISE, spec->lr, sgd ? 0.f : spec->eps};
+    st.masters = masters;
+    std::vector<Planned> plan(n_descs);
+    if (int rc = plan_master(g, descs, masters, states, n_descs, itype, st, who, plan.data())) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    for (uint32_t k = 0; k < n_descs; k++)
+        if (plan[k].k)
+            if (int rc = run_chain(g, descs, states, plan.data(), k, itype == EMB_IDX_I64, st, SparseOut{}, s)) return rc;
+    return EMB_OK;
+}
+
+int emb_grad_master_report(emb_grad *g, uint64_t *n_unencodable) {
+    if (!g) return fail(EMB_ERR_INVALID, "emb_grad_master_report: context is NULL");
+    DeviceGuard guard(g->device);
+    unsigned long long n = 0;
+    GRAD_HIP(hipDeviceSynchronize());
+    GRAD_HIP(hipMemcpy(&n, &g->counters[1], 8, hipMemcpyDeviceToHost));
+    GRAD_HIP(hipMemset(&g->counters[1], 0, 8));
+    if (n_unencodable) *n_unencodable = n;
+    return EMB_OK;
+}
+
 int emb_grad_report(emb_grad *g, uint64_t *n_bad) {
     if (!g) return fail(EMB_ERR_INVALID, "emb_grad_report: context is NULL");
     DeviceGuard guard(g->device);
@@ -1715,3 +2074,7 @@ int emb_grad_report(emb_grad *g, uint64_t *n_bad) {
 }
 
 }  // extern "C"
+
+#else
+}  // namespace
+#endif  // !PIMEMB_GRAD_MASTER_UNIT

@@ -8,7 +8,8 @@ empty submodule here; flags from README.md:6,10,14 and upmem/run.sh:72-82,111-12
 loss.backward() applies the fused SGD step of the backward pass (include/pimemb_grad.h) to the served tables;
 `--fused-adagrad LR` / `--fused-rowwise-adagrad LR` do the same with the fused Adagrad / row-wise Adagrad step (the three are
 mutually exclusive; `--multi-table-step` sends them through the multi-table entry points, `--segmented-sums [S]` makes them sum in the
-segmented order of additions).  No MLPs -- the rest of the model is out of scope.
+segmented order of additions; `--master-weights` keeps fp32 master rows and runs the fused master-weight step, with which fp8 and
+mxfp4 tables train).  No MLPs -- the rest of the model is out of scope.
 
     python -m pim_embedding_lookup_amd.dlrm_harness --arch-sparse-feature-size=16 \
         --arch-embedding-size=1460-583-10131227-… --mini-batch-size=39292 --inference-only
@@ -82,6 +83,7 @@ class EmbeddingBagCollection:
         self._plans = {}
         self._ids = list(range(len(self.ln_emb)))
         self._fused_lr = None
+        self.table_dtype, self.master_weight = dtype, None      # master_weight: the tables' fp32 masters while --master-weights is on (_set_masters)
         self.multi_table_step = False                           # the fused steps go through the multi-table entry points (--multi-table-step)
         self.segmented_sums = None                              # the fused steps' segment length in the segmented order of additions; None: position order (--segmented-sums)
         self._fused_adagrad, self.adagrad_sum = None, None      # (lr, eps, rowwise) and the per-table fp32 states of enable_fused_adagrad
@@ -193,23 +195,38 @@ class EmbeddingBagCollection:
                 out[k] = dw
         return out
 
-    def enable_fused_sgd(self, lr):
+    def _set_masters(self, on: bool) -> None:
+        """--master-weights: one fp32 master per table (self.master_weight), made from the served tables by exact widening when it is
+        switched on and dropped when it is switched off, so that a master is never older than its table."""
+        if not on:
+            self.master_weight = None
+        elif self.master_weight is None:
+            if self.table_dtype == "f32":
+                raise ValueError("master weights go with f16, bf16, fp8 and mxfp4 tables: an f32 table is its own master")
+            if self.multi_table_step:
+                raise ValueError("multi_table_step does not go with master weights: there is no multi-table master step")
+            self.master_weight = [self.engine.master_of(t, self.device) for t in self._ids]
+
+    def enable_fused_sgd(self, lr, master_weights: bool = False):
         """From now on apply_emb (lists of torch CUDA tensors; f32 / f16 / bf16 tables) returns tensors attached to the autograd
         graph whose backward applies W -= lr * grad to the served tables (GradContext.sgd_step): loss.backward() is the tables'
         whole training step.  lr=None switches it off.  The per-row pooling weights of --weighted-pooling get their gradient in the
         same backward after enable_pooling_weight_grad(), computed before the step, at the table the forward read."""
         self._fused_lr = None if lr is None else float(lr)
         self._fused_adagrad = None
+        self._set_masters(master_weights and lr is not None)
         return self
 
-    def enable_fused_adagrad(self, lr, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0):
+    def enable_fused_adagrad(self, lr, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0, master_weights: bool = False):
         """As enable_fused_sgd, with the fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row;
         GradContext.adagrad_step).  The fp32 states -- self.adagrad_sum, one tensor per table -- are allocated here, once per
         flavour, filled with initial_accumulator_value.  lr=None switches it off.  Switches a fused SGD off."""
         import torch
         if lr is None:
             self._fused_adagrad = None
+            self._set_masters(False)
             return self
+        self._set_masters(master_weights)
         if self.adagrad_sum is None or (self.adagrad_sum[0].dim() == 1) != bool(rowwise):
             shape = lambda n: (n,) if rowwise else (n, self.m)  # noqa: E731
             self.adagrad_sum = [torch.full(shape(int(n)), float(initial_accumulator_value), dtype=torch.float32, device=self.device) for n in self.ln_emb]
@@ -241,7 +258,16 @@ class EmbeddingBagCollection:
             ctx = tm._grad_context(self.engine, size(i.shape[0] for i in lS_i), size(o.shape[0] for o in lS_o), *order)
             args = ([self._ids[k] for k in live], [lS_i[k] for k in live], [lS_o[k] for k in live], [grads[k] for k in live])
             w_live = [None if ws is None else ws[k] for k in live]
-            if ada is None:
+            masters = self.master_weight
+            if masters is not None:      # the fused master-weight step (emb_grad_master_step): every table dtype but fp32, table after table
+                if multi:
+                    raise ValueError("multi_table_step does not go with master weights: there is no multi-table master step")
+                if ada is None:
+                    ctx.master_step(*args, [masters[k] for k in live], lr, optimizer="sgd", per_sample_weights=w_live)
+                else:
+                    ctx.master_step(*args, [masters[k] for k in live], ada[0], optimizer="rowwise" if ada[2] else "adagrad",
+                                    states=[self.adagrad_sum[k] for k in live], eps=ada[1], per_sample_weights=w_live)
+            elif ada is None:
                 ctx.sgd_step(*args, lr, per_sample_weights=w_live, multi=multi)
             else:
                 ctx.adagrad_step(*args, [self.adagrad_sum[k] for k in live], ada[0], eps=ada[1], rowwise=ada[2], per_sample_weights=w_live,
@@ -419,6 +445,14 @@ def main(argv=None):
     ap.add_argument("--multi-table-step", action="store_true",
                     help="with one of the --fused-* flags: step the tables through the multi-table entry points (one pre-pass and one "
                          "launch per group of up to 16 tables instead of per table; the same bytes)")
+    ap.add_argument("--table-dtype", type=str, default="f32", choices=["f32", "f16", "bf16", "fp8_e4m3", "fp8_e5m2", "mxfp4"],
+                    help="the dtype the tables are served in (fp32 weights are encoded into it; mxfp4: feature size a multiple of 32); "
+                         "fp8 and mxfp4 tables train with --master-weights only")
+    ap.add_argument("--master-weights", action="store_true",
+                    help="with one of the --fused-* flags: keep fp32 master rows and run the fused master-weight step "
+                         "(emb_grad_master_step): the master is stepped in fp32 and the table row is its encoding -- the way to train "
+                         "fp8 and mxfp4 tables, and f16 / bf16 ones without losing small updates; not for f32 tables, and not with "
+                         "--multi-table-step")
     ap.add_argument("--segmented-sums", type=int, nargs="?", const=0, default=None, metavar="S",
                     help="with one of the --fused-* flags: sum a row's occurrences in segments of S (a power of two, 8 .. 1024; "
                          "default: GradContext's), the segmented order of include/pimemb_grad.h -- for skewed ids, where some rows "
@@ -435,6 +469,14 @@ def main(argv=None):
         raise SystemExit("--fused-sgd, --fused-adagrad and --fused-rowwise-adagrad are mutually exclusive")
     if args.multi_table_step and not fused:
         raise SystemExit("--multi-table-step goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
+    if args.master_weights and not fused:
+        raise SystemExit("--master-weights goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
+    if args.master_weights and args.multi_table_step:
+        raise SystemExit("--master-weights does not go with --multi-table-step: there is no multi-table master step")
+    if args.master_weights and args.table_dtype == "f32":
+        raise SystemExit("--master-weights goes with --table-dtype f16, bf16, fp8_e4m3, fp8_e5m2 or mxfp4: an f32 table is its own master")
+    if fused and args.table_dtype in ("fp8_e4m3", "fp8_e5m2", "mxfp4") and not args.master_weights:
+        raise SystemExit(f"--table-dtype {args.table_dtype} trains with --master-weights only: a step in the stored precision mostly rounds away")
     if args.segmented_sums is not None and not fused:
         raise SystemExit("--segmented-sums goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
     if args.train_pooling_weights is not None and args.weighted_pooling is None:
@@ -454,12 +496,12 @@ def main(argv=None):
         ln_emb = [int(x) for x in args.arch_embedding_size.split("-")]
     if args.load_model:
         ebc = EmbeddingBagCollection.from_checkpoint(args.load_model, weighted_pooling=args.weighted_pooling,
-                                                     quantize_on_device=args.quantize_on_device)
+                                                     quantize_on_device=args.quantize_on_device, dtype=args.table_dtype)
     else:
         if args.weighted_pooling == "learned":
             raise SystemExit("--weighted-pooling learned needs --load-model (the per-row weights v_W_l come from it)")
         ebc = EmbeddingBagCollection(ln_emb, args.arch_sparse_feature_size, weighted_pooling=args.weighted_pooling,
-                                     quantize_on_device=args.quantize_on_device)
+                                     quantize_on_device=args.quantize_on_device, dtype=args.table_dtype)
     B = args.mini_batch_size
     batches = []
     for b in range(min(args.num_batches, 16)):
@@ -490,9 +532,9 @@ def main(argv=None):
             from .engine import GradContext
             ebc.segmented_sums = args.segmented_sums or GradContext.DEFAULT_SEGMENT
         if opt_name == "SGD":
-            ebc.enable_fused_sgd(opt_lr)
+            ebc.enable_fused_sgd(opt_lr, master_weights=args.master_weights)
         elif opt_name is not None:
-            ebc.enable_fused_adagrad(opt_lr, rowwise=opt_name != "Adagrad")
+            ebc.enable_fused_adagrad(opt_lr, rowwise=opt_name != "Adagrad", master_weights=args.master_weights)
         w_opt = None
         if args.train_pooling_weights is not None:      # the per-row pooling weights: plain torch.optim.SGD over v_W_l
             ebc.enable_pooling_weight_grad()

@@ -640,6 +640,65 @@ class GradContext:
         finally:
             self._free((*keep, *bufs))
 
+    def master_step(self, table_ids, indices, offsets, grads, masters, lr: float, optimizer: str = "sgd", states=None, eps: float = 1e-10,
+                    modes="sum", per_sample_weights=None, padding_idx=None, fixed_pooling: int = 0, stream: int | None = None) -> None:
+        """The fused master-weight step (emb_grad_master_step), table after table: for every row r the batch of its table names,
+        masters[k][r] is stepped in fp32 -- optimizer "sgd", "adagrad" or "rowwise" (row-wise Adagrad), the arithmetic of sgd_step /
+        adagrad_step on the master element -- and the table row becomes the new master row encoded in the table's dtype (fp16,
+        bf16, e4m3, e5m2, MXFP4), bit for bit what the row writer would store; the table row itself is never read.  masters: one
+        float32 [nr_rows, dim] per table, read and written in place (master_of makes one from a served table); states: as
+        adagrad_step takes them (None for "sgd").  Conventions as sgd_step: torch CUDA tensors are a pure enqueue on `stream`
+        (torch's current one by default), numpy arrays are copied to the device and back into the very arrays, and the call waits.
+        An MXFP4 row whose new master holds an inf or a NaN keeps its table bytes and is counted for master_report()."""
+        if optimizer not in _l.MASTER_KINDS:
+            raise ValueError(f"optimizer has to be one of {sorted(_l.MASTER_KINDS)}, got {optimizer!r}")
+        n_t = len(table_ids)
+        if len(masters) != n_t:
+            raise ValueError(f"{len(masters)} masters for {n_t} tables")
+        if optimizer != "sgd" and (states is None or len(states) != n_t):
+            raise ValueError(f"optimizer {optimizer!r} takes one state per table")
+        keep, back = [], []
+        try:
+            arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, grads, modes, per_sample_weights, padding_idx, fixed_pooling,
+                                                          stream, keep)
+
+            def pointer(x, want, what):
+                if x is None:
+                    return None
+                if dev:
+                    import torch
+                    if not (_is_torch(x) and x.is_cuda) or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != want:
+                        raise TypeError(f"{what} must be a contiguous float32 CUDA tensor of {want} values")
+                    return x.data_ptr()
+                if not isinstance(x, np.ndarray) or x.dtype != np.float32 or x.size != want or not x.flags.c_contiguous or not x.flags.writeable:
+                    raise TypeError(f"{what} must be a writeable C-contiguous float32 numpy array of {want} values")
+                buf = DeviceBuffer.from_numpy(self.engine, x)
+                keep.append(buf)
+                back.append((x, buf))
+                return buf.ptr
+
+            mptrs, sptrs = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))()
+            for k in range(n):
+                _ptr, rows, dim, _dt = self.engine.table_info(table_ids[k])
+                mptrs[k] = pointer(masters[k], rows * dim, f"master {k}")
+                if optimizer != "sgd":
+                    sptrs[k] = pointer(states[k], rows if optimizer == "rowwise" else rows * dim, f"state {k}")
+            spec = _l.EmbMasterSpec(_l.MASTER_KINDS[optimizer], float(lr), float(eps), 0)
+            _l.check_grad(self._G.emb_grad_master_step(self._h, arr, mptrs, None if optimizer == "sgd" else sptrs, n, itype, C.byref(spec), stream))
+            if not dev:
+                self.engine.synchronize(stream)
+                for x, buf in back:
+                    x[...] = buf.numpy().reshape(x.shape)
+        finally:
+            self._free(keep)
+
+    def master_report(self) -> int:
+        """MXFP4 rows that master steps left unwritten -- an inf or a NaN in the new master row -- since the last such report
+        (waits for the device; resets the count)."""
+        n = C.c_uint64()
+        _l.check_grad(self._G.emb_grad_master_report(self._h, C.byref(n)))
+        return n.value
+
     def report(self) -> int:
         """Positions skipped for an id outside the table since the last report (waits for the device; resets the count)."""
         bad = C.c_uint64()
@@ -851,6 +910,32 @@ class EmbeddingEngine:
         if dt in _F8_TORCH:
             return view.view(getattr(torch, _F8_TORCH[dt]))
         return view.view(torch.bfloat16) if dt == _l.EMB_BF16 else view
+
+    def master_of(self, table_id: int, torch_device=None):
+        """The fp32 master rows of a served table, [nr_rows, dim]: its bytes decoded, i.e. widened exactly, so that for every
+        dtype encoding the master gives the table's very bytes back -- the start of GradContext.master_step.  A numpy array, or with
+        torch_device (e.g. "cuda:0") a torch tensor there.  Decoded on the host by formats.py: one copy of the table crosses PCIe."""
+        from . import formats
+        ptr, n, d, dt = self.table_info(table_id)
+        if dt == _l.EMB_FIXED32:
+            raise ValueError("a fixed-point table has no floating-point master")
+        stride = formats.mxfp4_row_stride(d) if dt == _l.EMB_MXFP4 else d * {_l.EMB_F32: 4, _l.EMB_F16: 2, _l.EMB_BF16: 2}.get(dt, 1)
+        raw = np.empty((n, stride), dtype=np.uint8)
+        self.synchronize(None)
+        _l.check(self._L.emb_copy_to_host(self._h, raw.ctypes.data, ptr, raw.nbytes))
+        if dt == _l.EMB_MXFP4:
+            m = formats.from_mxfp4(raw, d)
+        elif dt in (_l.EMB_F8_E4M3, _l.EMB_F8_E5M2):
+            m = formats.from_f8_bits(raw, "e4m3" if dt == _l.EMB_F8_E4M3 else "e5m2")
+        elif dt == _l.EMB_BF16:
+            m = formats.from_bf16_bits(raw.view(np.uint16))
+        else:
+            m = raw.view(np.float32 if dt == _l.EMB_F32 else np.float16)
+        m = np.ascontiguousarray(m, dtype=np.float32).reshape(n, d)
+        if torch_device is None:
+            return m
+        import torch
+        return torch.from_numpy(m).to(torch_device)
 
     def table_info(self, table_id: int):
         ptr, n, d, dt = C.c_void_p(), C.c_uint64(), C.c_uint32(), C.c_int()

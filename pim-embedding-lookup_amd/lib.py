@@ -225,6 +225,14 @@ class EmbOptSpec(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("lr", C.c_float), ("eps", C.c_float), ("reserved", C.c_uint32)]
 
 
+EMB_MASTER_SGD, EMB_MASTER_ADAGRAD, EMB_MASTER_ROWWISE_ADAGRAD = 0, 1, 2
+MASTER_KINDS = {"sgd": EMB_MASTER_SGD, "adagrad": EMB_MASTER_ADAGRAD, "rowwise": EMB_MASTER_ROWWISE_ADAGRAD}
+
+
+class EmbMasterSpec(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("lr", C.c_float), ("eps", C.c_float), ("reserved", C.c_uint32)]
+
+
 EMB_GRAD_MULTI_MAX = 16
 EMB_GRAD_NO_GROUP = 0xFFFFFFFF      # emb_grad_multi_groups: an empty descriptor
 
@@ -261,6 +269,8 @@ GRAD_SIGNATURES = {
     "emb_grad_sgd_multi": (C.c_int, [_vp, C.POINTER(EmbGradDesc), _u32, C.c_int, C.c_float, _vp]),
     "emb_grad_step_multi": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbOptSpec), _vp]),
     "emb_grad_weights": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, _vp]),
+    "emb_grad_master_step": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbMasterSpec), _vp]),
+    "emb_grad_master_report": (C.c_int, [_vp, C.POINTER(_u64)]),
 }
 
 _lib = None

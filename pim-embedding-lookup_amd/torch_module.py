@@ -351,8 +351,12 @@ class PoolingEmbeddingBag(torch.nn.Module):
             return lookup()
         return _FusedSGD.apply(_anchor(self, idx.device), lookup, lambda g: self._step(idx, off, g, lr, w))
 
-    def enable_fused_sgd(self, lr: float, order: str = "position"):
-        """From now on forward() returns a tensor attached to the autograd graph, and its backward applies weight -= lr * grad
+    def enable_fused_sgd(self, lr: float, order: str = "position", master_weights: bool = False):
+        """master_weights=True: the module keeps fp32 master rows (master_weight, made from the table by exact widening on first
+        use and saved as `<prefix>master_weight`) and the step is the fused master-weight step of include/pimemb_grad.h: the master
+        is stepped in fp32 and the table row is its encoding -- the way to train fp8 and MXFP4 tables, and fp16 / bf16 ones without
+        losing small updates.  Off by default.
+        From now on forward() returns a tensor attached to the autograd graph, and its backward applies weight -= lr * grad
         to the served table (sgd_step_ with the inputs forward saw): loss.backward() is the whole training step of this table.
         lr=None switches it off again.  Switches a fused Adagrad off (its state stays).  order="segmented": a row's occurrences
         are summed in the segmented order of include/pimemb_grad.h (GradContext) -- for batches that name some rows thousands of
@@ -360,10 +364,16 @@ class PoolingEmbeddingBag(torch.nn.Module):
         object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
         object.__setattr__(self, "_fused_adagrad", None)
+        _set_master(self, master_weights)
         return self
 
+    @property
+    def master_weight(self):
+        """The fp32 master rows (float32 CUDA tensor [num_embeddings, embedding_dim]), or None while master weights are off."""
+        return getattr(self, "_master_weight", None) if getattr(self, "_fused_master", False) else None
+
     def enable_fused_adagrad(self, lr: float, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0,
-                             order: str = "position"):
+                             order: str = "position", master_weights: bool = False):
         """As enable_fused_sgd (order= included), with the fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row) of
         include/pimemb_grad.h: torch.optim.Adagrad(lr, eps=eps, initial_accumulator_value=...) without lr_decay and weight_decay.
         The fp32 state -- module.adagrad_sum, [num_embeddings, embedding_dim] or [num_embeddings] -- is allocated once, filled with
@@ -376,6 +386,7 @@ class PoolingEmbeddingBag(torch.nn.Module):
         _adagrad_state(self, bool(rowwise), float(initial_accumulator_value))
         object.__setattr__(self, "_fused_adagrad", (float(lr), float(eps)))
         object.__setattr__(self, "_fused_lr", None)
+        _set_master(self, master_weights)
         return self
 
     @property
@@ -392,6 +403,10 @@ class PoolingEmbeddingBag(torch.nn.Module):
         if grad_output is None:
             return
         g = _grad_view(grad_output, self.embedding_dim)
+        if self.master_weight is not None:
+            self._context(idx, off, order).master_step(self._id_list, [idx], [off], [g], [self.master_weight], lr, optimizer="sgd", modes=self.mode,
+                                                       per_sample_weights=w, padding_idx=self.padding_idx)
+            return
         self._context(idx, off, order).sgd_step(self._id_list, [idx], [off], [g], lr, modes=self.mode, per_sample_weights=w,
                                                 padding_idx=self.padding_idx)
 
@@ -400,6 +415,11 @@ class PoolingEmbeddingBag(torch.nn.Module):
             return
         g = _grad_view(grad_output, self.embedding_dim)
         state = _adagrad_state(self)
+        if self.master_weight is not None:
+            self._context(idx, off, order).master_step(self._id_list, [idx], [off], [g], [self.master_weight], lr,
+                                                       optimizer="rowwise" if state.dim() == 1 else "adagrad", states=[state], eps=eps, modes=self.mode,
+                                                       per_sample_weights=w, padding_idx=self.padding_idx)
+            return
         self._context(idx, off, order).adagrad_step(self._id_list, [idx], [off], [g], [state], lr, eps=eps, rowwise=state.dim() == 1,
                                                     modes=self.mode, per_sample_weights=w, padding_idx=self.padding_idx)
 
@@ -458,17 +478,36 @@ class PoolingEmbeddingBag(torch.nn.Module):
     def update_rows_(self, ids, rows):
         """weight[ids[p]] = rows[p] (float32 [n, embedding_dim], encoded into the weight's dtype on the GPU), in place and in
         stream order with forward(): lookups issued afterwards -- and state_dict() -- see the new rows.  The last occurrence of
-        a repeated id wins.  Returns self."""
-        _update_rows(self.engine, self.table_id, ids, rows)
+        a repeated id wins.  With master weights on, the master rows are written too (the fp32 rows themselves).  Returns self."""
+        try:
+            _update_rows(self.engine, self.table_id, ids, rows)      # validates, then writes the table (IndexError: after the valid rows were written)
+        except IndexError:
+            if self.master_weight is not None:
+                _update_master(self.master_weight, ids, rows)
+            raise
+        if self.master_weight is not None:                           # (behind the table: a refused update leaves both as they were)
+            _update_master(self.master_weight, ids, rows)
         return self
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         self._table._save_to_state_dict(destination, prefix, keep_vars)
         if self.adagrad_sum is not None:      # (only a module that has an Adagrad state gains the key)
             destination[prefix + "adagrad_sum"] = self.adagrad_sum.detach().clone()
+        if self.master_weight is not None:    # (only with master weights on)
+            destination[prefix + "master_weight"] = self.master_weight.detach().clone()
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         self._table._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        mkey = prefix + "master_weight"
+        if mkey in state_dict:
+            m = state_dict[mkey]
+            if tuple(m.shape) != (self.num_embeddings, self.embedding_dim):
+                error_msgs.append(f"size mismatch for {mkey}: {(self.num_embeddings, self.embedding_dim)} expected, got {tuple(m.shape)}")
+                return
+            object.__setattr__(self, "_master_weight", m.detach().to(device=torch.device("cuda", self.device_index), dtype=torch.float32).contiguous().clone())
+            object.__setattr__(self, "_fused_master", True)
+        elif self.master_weight is not None and strict:
+            missing_keys.append(mkey)
         key = prefix + "adagrad_sum"
         if key in state_dict:
             s = state_dict[key]
@@ -518,6 +557,35 @@ def _grad_context(engine: EmbeddingEngine, n_indices: int, n_bags: int, order: s
         g = engine.grad_context(max(_GRAD_INDICES, int(n_indices)), max(_GRAD_INDICES, int(n_bags)), **kw)
         setattr(engine, attr, g)
     return g
+
+
+def _set_master(bag, on: bool) -> None:
+    """Master weights on or off for one PoolingEmbeddingBag.  Switched on, the fp32 master is made from the served table by exact
+    widening (EmbeddingEngine.master_of); a bag on which they ARE on keeps its master (over enable_* calls, or as a checkpoint
+    loaded it).  Switched off, the master is dropped: whatever changes the table while they are off -- in-place steps,
+    update_rows_, a loaded weight -- is in the master that the next switching-on derives, never overwritten by a stale one."""
+    was_on = getattr(bag, "_fused_master", False) and getattr(bag, "_master_weight", None) is not None
+    object.__setattr__(bag, "_fused_master", bool(on))
+    if not on:
+        object.__setattr__(bag, "_master_weight", None)
+    elif not was_on:
+        if bag._table_dtype == torch.float32:
+            raise ValueError("master_weights=True goes with fp16, bf16, fp8 and MXFP4 tables: an fp32 table is its own master")
+        object.__setattr__(bag, "_master_weight", bag.engine.master_of(bag.table_id, torch.device("cuda", bag.device_index)))
+
+
+def _update_master(master, ids, rows) -> None:
+    """master[ids[p]] = rows[p], the last occurrence of a repeated id winning, ids outside the table skipped: what the row writer
+    does to the table, on torch's current stream."""
+    ids = torch.as_tensor(ids).to(master.device).reshape(-1).to(torch.int64)
+    rows = torch.as_tensor(rows).to(device=master.device, dtype=torch.float32)
+    n = master.shape[0]
+    at = torch.arange(ids.shape[0], device=master.device)
+    ok = (ids >= 0) & (ids < n)
+    last = torch.full((n + 1,), -1, dtype=torch.int64, device=master.device)
+    last.scatter_reduce_(0, torch.where(ok, ids, torch.full_like(ids, n)), at, "amax")
+    keep = ok & (last[torch.where(ok, ids, torch.full_like(ids, n))] == at)
+    master.index_copy_(0, ids[keep], rows[keep])
 
 
 def _adagrad_state(bag, rowwise=None, init: float = 0.0):
@@ -691,22 +759,46 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
 
     apply_emb = forward
 
-    def enable_fused_sgd(self, lr: float, multi_table: bool = False, order: str = "position"):
-        """As PoolingEmbeddingBag.enable_fused_sgd, for every table of the model: the backward of forward()'s result -- the list,
+    def enable_fused_sgd(self, lr: float, multi_table: bool = False, order: str = "position", master_weights: bool = False):
+        """master_weights=True: every bag keeps its fp32 master (bags[k].master_weight) and the step is the fused master-weight step,
+        table after table; there is no multi-table master step, so multi_table=True with it raises ValueError.
+        As PoolingEmbeddingBag.enable_fused_sgd, for every table of the model: the backward of forward()'s result -- the list,
         or the one [B, sum(m)] tensor of concat=True -- steps all of them.  multi_table=True: by the multi-table step (one
         pre-pass and one launch per group of up to 16 tables instead of per table; the same bytes).  order: as there.
         Returns self."""
+        self._set_masters(master_weights, multi_table)
         object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_multi", bool(multi_table))
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
         object.__setattr__(self, "_fused_adagrad", None)
         return self
 
+    def _set_masters(self, on: bool, multi_table: bool) -> None:
+        if on and multi_table:
+            raise ValueError("multi_table=True does not go with master_weights=True: there is no multi-table master step (the group record of the "
+                             "multi-table kernels has no room for the master pointer); the master step runs table after table")
+        for b in self.bags:
+            _set_master(b, on)
+
+    def _masters_on(self) -> bool:
+        """Whether the step is the master step: read from the bags, which own the masters (a checkpoint may have loaded them)."""
+        on = [b.master_weight is not None for b in self.bags]
+        if any(on) and not all(on):
+            raise ValueError("some tables of this model have master weights and some have not: call enable_fused_sgd / enable_fused_adagrad with "
+                             "master_weights=True (or False) to put them all in one state")
+        return all(on) and bool(on)
+
+    @property
+    def master_weight(self):
+        """The bags' fp32 masters, in table order (None where master weights are off)."""
+        return [b.master_weight for b in self.bags]
+
     def enable_fused_adagrad(self, lr: float, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0,
-                             multi_table: bool = False, order: str = "position"):
+                             multi_table: bool = False, order: str = "position", master_weights: bool = False):
         """As PoolingEmbeddingBag.enable_fused_adagrad, for every table of the model: each bag holds its own state
-        (bags[k].adagrad_sum, saved as `bags.<k>.adagrad_sum`), one call steps them all.  multi_table and order: as
+        (bags[k].adagrad_sum, saved as `bags.<k>.adagrad_sum`), one call steps them all.  multi_table, order and master_weights: as
         enable_fused_sgd.  Returns self."""
+        self._set_masters(master_weights, multi_table)
         object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_multi", bool(multi_table))
         if lr is None:
@@ -785,8 +877,17 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         multi = getattr(self, "_fused_multi", False) if multi is None else bool(multi)
         call = self._live_grads(idx, off, grad_output, ws, col, multi, order)
         if call is not None:
-            ctx, args, kw, _live = call
+            ctx, args, kw, live = call
+            if self._masters_on():
+                self._no_multi_master(multi)
+                ctx.master_step(*args, [self.bags[k].master_weight for k in live], lr, optimizer="sgd", **kw)
+                return
             ctx.sgd_step(*args, lr, multi=multi, **kw)
+
+    @staticmethod
+    def _no_multi_master(multi) -> None:
+        if multi:
+            raise ValueError("multi_table=True does not go with master weights: there is no multi-table master step")
 
     def _adagrad(self, idx, off, grad_output, lr, eps, ws, col=0, multi=None, order=None):
         multi = getattr(self, "_fused_multi", False) if multi is None else bool(multi)
@@ -799,6 +900,11 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             sel = [j for j, s in enumerate(states) if (s.dim() == 1) == rowwise]
             if sel:
                 pick = lambda v: [v[j] for j in sel]  # noqa: E731
+                if self._masters_on():
+                    self._no_multi_master(multi)
+                    ctx.master_step(*[pick(a) for a in args], [self.bags[live[j]].master_weight for j in sel], lr,
+                                    optimizer="rowwise" if rowwise else "adagrad", states=pick(states), eps=eps, **{k: pick(v) for k, v in kw.items()})
+                    continue
                 ctx.adagrad_step(*[pick(a) for a in args], pick(states), lr, eps=eps, rowwise=rowwise, multi=multi,
                                  **{k: pick(v) for k, v in kw.items()})
 
