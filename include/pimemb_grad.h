@@ -409,6 +409,78 @@ typedef struct emb_master_spec {
 int emb_grad_master_step(emb_grad *g, const emb_grad_desc *descs, float *const *masters, float *const *states, uint32_t n_descs,
                          emb_index_type itype, const emb_master_spec *spec, void *stream);
 
+/* THE STOCHASTICALLY ROUNDED STEPS: emb_grad_sgd / emb_grad_step on EMB_F16 and EMB_BF16 tables with the LAST rounding alone replaced
+ * (tests/sr_ref.py restates them as a loop; the kernels are compared with that, bit for bit).  The in-place step rounds to nearest
+ * even and so loses every update below half an ulp of the stored value, every time (a bf16 weight at 1.0 never moves under steps of
+ * 2^-12); the master-weight steps keep them at the price of an fp32 master, 4 more bytes per element.  Here the stored table itself is
+ * an unbiased accumulator and no master exists.
+ * g[r], U, good / bad / padding positions, the order of additions of the context, dec, the fp32 arithmetic of the SGD / Adagrad /
+ * row-wise Adagrad steps, the state S (fp32, exact as before) and the bad-position count are unchanged.  Where the in-place step stores
+ * enc_T(x), x being the fp32 value dec(W[r][d]) - (...), these steps store enc_sr_T(x, R), R a 32-bit word, T fp16 or bf16.
+ *
+ * enc_sr_T(x, R) (csrc/pimemb_grad_sr.h: the arithmetic, compiled by the kernels and by a host check alike):
+ *   x NaN or +-inf             enc_T(x), the row writer's encoder; R is not used.
+ *   fp16 and |x| >= 65536      +-inf, as enc_f16 overflows.
+ *   otherwise                  lo = the T value of x's sign nearest to x with |lo| <= |x| (truncation toward zero; -0 stays -0);
+ *                              hi = the next T value away from zero: +-inf beyond the largest finite one, which for the fraction
+ *                              counts as 2^128 (bf16) or 65536 (fp16);
+ *                              f = (|x| - |lo|) / (|hi| - |lo|) in [0, 1);  F = floor(f * 2^32);
+ *                              the result is hi if F + R >= 2^32, else lo.
+ *   Exactly F of the 2^32 words round away from zero; a representable x (F = 0) is stored as itself for every R.
+ *   On the bits, u the fp32 pattern:
+ *     bf16                     F = (u & 0xffff) << 16; the result is (u >> 16) + (F + R >= 2^32): the carry runs into the exponent and
+ *                              can give inf (0x7f80), never a NaN.
+ *     fp16, biased exponent e >= 113    F = (u & 0x1fff) << 19; on carry add 0x2000 to u; clear the low 13 bits: enc_f16 of that is
+ *                              exact, or inf.
+ *     fp16, below 2^-14        spacing 2^-24: with e' = max(e, 1), m the 24-bit significand (implicit one for e >= 1), s = 126 - e':
+ *                              lo = m >> s (0 for s >= 24); F = (m mod 2^s) << (32 - s) for s <= 32, (m mod 2^s) >> (s - 32) beyond
+ *                              (0 from s = 56); the result is the fp16 subnormal (or 2^-14) of magnitude lo + carry.
+ *                              For s > 32 this TRUNCATES a fraction finer than 2^-32: the one place where P(hi) is not exactly f (it is
+ *                              below f by less than 2^-32).
+ * The word R: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC 2011: multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 /
+ *   0xBB67AE85, ten rounds) with key (seed_lo, seed_hi) and counter (r, d div 4, t_lo, t_hi) -- r the row, d the element, t the step
+ *   number -- and R its output word d mod 4.  A lane that owns 4 consecutive elements runs Philox once per piece; the element-wise
+ *   kernel runs it per element and picks its word: the same bits.
+ * The step number: descriptor k of a call uses t = spec.step + (step_dev ? *step_dev : 0) + k, mod 2^64; empty descriptors keep their
+ *   k.  A table named twice in one call draws different words for its two steps; the caller advances `step` by n_descs per call.
+ *   step_dev is NULL or a DEVICE uint64_t the kernels read when they run: a captured graph replays with new words when the caller
+ *   advances it on the stream.  R depends on nothing else: not on the batch, the launch geometry, the order of additions, or which
+ *   kernel shape ran -- a stochastic step gives the same bits on every run, like every other call here.
+ *
+ * emb_grad_sgd_sr / emb_grad_step_sr are emb_grad_sgd / emb_grad_step in every other respect: DEVICE pointers only; a pure enqueue (no
+ * allocation, no copy, no host wait: capturable); every descriptor and state checked before anything is enqueued; a context of either
+ * order; EMB_OPT_ADAGRAD on both kernel shapes, EMB_OPT_ROWWISE_ADAGRAD on the lane-group shape only; the same refusals (fp8 / MXFP4 /
+ * fixed-point tables, a hot set staged, EMB_POOL_MAX, the context's limits, eps, an unknown kind).
+ *   Tables               EMB_F16 and EMB_BF16.  EMB_F32 is EMB_ERR_UNSUPPORTED: an fp32 step stores its fp32 result, there is nothing to
+ *                        round -- use emb_grad_sgd / emb_grad_step.
+ *   EMB_ERR_INVALID      a NULL sr, reserved != 0, a step_dev that is not 8-byte aligned (checked before the context is looked at).
+ * The kernels (grad_sr_rows_group, grad_sr_rows_elem: three kinds, two orders) have a code object of their own, libpimemb_grad_sr.so,
+ * built from the same source and found next to libpimemb_grad.so, which links against it; the other libraries' code objects hold the
+ * machine code they held.  The tail is one Philox block -- about sixty integer operations -- per 16 bytes stepped.
+ * Bytes moved per stepped element: 2 + 2 in place, 2 + 2 here, 4 + 4 + 2 with a master.
+ * Speed, measured on MI355X (tools/sr_probe.py, profiles/sr/README.md; medians of five alternating rounds, device pointers, the in-place
+ * step and emb_grad_master_step measured again in the same run; dim 128, 2048 bags x 32, 4 M rows).  Uniform ids, SGD: 72.4 us on bf16
+ * and 74.4 us on fp16 tables against 71.3 / 73.4 us in place -- 1.015x SLOWER -- and against 74.1 us for the bf16 master step: 1.02x
+ * faster; row-wise Adagrad 77.5 / 80.4 against 76.0 / 78.3 us in place: 1.02 - 1.03x SLOWER.  Zipf ids, S = 64 context: 134.5 / 135.7 us
+ * (SGD) against 133.4 / 135.5 in place (1.01x SLOWER on bf16, level on fp16) and 136.3 with a master; position-order context: the hot
+ * row's 3.7 - 4.0 ms chain either way (SGD 1.01x faster, row-wise 1.01x SLOWER than in place).  The Kaggle shape (dim 16, 39 292
+ * one-index bags): 50.3 / 50.6 us against 49.4 / 50.0 in place (1.01 - 1.02x SLOWER, within the rounds' spread) and 50.2 with a master
+ * (level).  No scratch and no spills; the Adagrad kernels take 66 / 71 VGPRs against 63 / 68 and lose one wave per SIMD of eight, the
+ * SGD and row-wise kernels keep their occupancy (codeobj.kernel_resources).
+ * Out of scope: SR in the _multi steps (the counter above makes a later multi-table form give the same bits), in the master steps and in
+ * emb_rows_update; fp8 and MXFP4 in place; optimizer state in anything but fp32; other generators; the ranged / sharded paths. */
+typedef struct emb_sr_spec {
+    uint64_t seed;
+    uint64_t step;            /* t of descriptor 0 */
+    const uint64_t *step_dev; /* NULL, or a DEVICE uint64_t added to step when the kernels run */
+    uint64_t reserved;        /* 0 */
+} emb_sr_spec;
+
+int emb_grad_sgd_sr(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, const emb_sr_spec *sr,
+                    void *stream);
+int emb_grad_step_sr(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype,
+                     const emb_opt_spec *opt, const emb_sr_spec *sr, void *stream);
+
 /* The number of EMB_MXFP4 rows master steps left unwritten (an inf or a NaN in the new master row) since the last such report;
  * resets the count.  Waits for the device first, like emb_grad_report, whose count of bad positions is a separate one. */
 int emb_grad_master_report(emb_grad *g, uint64_t *n_unencodable);

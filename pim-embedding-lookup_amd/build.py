@@ -10,16 +10,17 @@ LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb.so")
 ROWS_LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb_rows.so")     # the row writer (include/pimemb_rows.h): a companion library
 GRAD_LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb_grad.so")     # the backward pass (include/pimemb_grad.h): a companion library too
 GRAD_MASTER_LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb_grad_master.so")     # the kernels of the master-weight steps: libpimemb_grad.so links against it
+GRAD_SR_LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb_grad_sr.so")     # the kernels of the stochastically rounded steps: libpimemb_grad.so links against it too
 MARSHAL_PATH = os.path.join(PKG_DIR, "lib", "_pimemb_marshal.so")
 SOURCES = ["pimemb_kernels.hip", "pimemb_strided_kernels.hip", "pimemb_engine.cpp", "pimemb_compat.cpp", "pimemb_comm.cpp", "pimemb_shard.cpp", "pimemb_peer.cpp", "pimemb_peer.h", "pimemb_internal.h", "pimemb_torch_marshal.cpp",
            "pimemb_bag_kernels.h", "pimemb_pool_kernels.inc", "pimemb_sum_kernels.inc", "pimemb_mx4_kernels.inc", "pimemb_xcd_map.h", "pimemb_hot_rows.h", "pimemb_hostcopy.h", "Makefile",
            "pimemb_rows.hip", "pimemb_rows_encode.h", os.path.join("..", "..", "include", "pimemb_rows.h"),
-           "pimemb_grad.hip", "pimemb_grad_step.h", "pimemb_grad_optim.h", "pimemb_grad_dot.h", "pimemb_grad_master.h", "pimemb_grad_segments.h", os.path.join("..", "..", "include", "pimemb_grad.h"),
+           "pimemb_grad.hip", "pimemb_grad_step.h", "pimemb_grad_optim.h", "pimemb_grad_dot.h", "pimemb_grad_master.h", "pimemb_grad_sr.h", "pimemb_grad_segments.h", os.path.join("..", "..", "include", "pimemb_grad.h"),
            os.path.join("..", "..", "include", "pimemb.h")]
 
 
 def is_stale() -> bool:
-    libs = (LIB_PATH, ROWS_LIB_PATH, GRAD_LIB_PATH, GRAD_MASTER_LIB_PATH)
+    libs = (LIB_PATH, ROWS_LIB_PATH, GRAD_LIB_PATH, GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH)
     if not all(os.path.exists(p) for p in libs):
         return True
     built = min(os.path.getmtime(p) for p in libs)
@@ -74,6 +75,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("libpimemb_grad.so missing after build")
     if not os.path.exists(GRAD_MASTER_LIB_PATH):
         raise RuntimeError("libpimemb_grad_master.so missing after build")
+    if not os.path.exists(GRAD_SR_LIB_PATH):
+        raise RuntimeError("libpimemb_grad_sr.so missing after build")
     build_marshal(verbose)          # optional: a failure is a warning, never an error
     return LIB_PATH
 

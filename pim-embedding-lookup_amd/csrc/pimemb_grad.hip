@@ -28,6 +28,8 @@
 //   grad_psw_group      one lane group per BAG, the forward's geometry: its piece of G[b] loaded once, the row gathers of eight
 //                       positions in flight, products folded per piece and summed over the group by the row-wise xor butterfly
 //   grad_psw_elem       any other dim / alignment: one lane group per position, scalar element loads, the same tree
+// The stochastically rounded steps (emb_grad_sgd_sr / emb_grad_step_sr; csrc/pimemb_grad_sr.h; a code object of their own, libpimemb_grad_sr.so):
+//   grad_sr_rows_group / grad_sr_rows_elem     the hot kernels' twins in both orders: the same walk, the last rounding by a Philox word
 // The Adagrad tails (csrc/pimemb_grad_optim.h) end the same kernels; the row-wise one sums the row's squares over its lane group
 // with an xor butterfly -- a fixed tree, stated over dim alone in the header: the same bits on every run.
 // Every fp32 operation of the definition is a statement of its own under `fp contract(off)` (and the unit is compiled with
@@ -48,7 +50,14 @@
 #include "pimemb_grad_master.h"
 #include "pimemb_grad_optim.h"
 #include "pimemb_grad_segments.h"
+#include "pimemb_grad_sr.h"
 #include "pimemb_grad_step.h"
+
+// This file is compiled three times (csrc/Makefile): as libpimemb_grad.so, and with -DPIMEMB_GRAD_MASTER_UNIT / -DPIMEMB_GRAD_SR_UNIT as
+// the code objects of the master-weight and the stochastically rounded steps, which hold their own kernels and launchers alone.
+#if defined(PIMEMB_GRAD_MASTER_UNIT) || defined(PIMEMB_GRAD_SR_UNIT)
+#define PIMEMB_GRAD_KERNEL_UNIT 1
+#endif
 
 namespace {
 
@@ -171,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void grad_scan_chunks(const uint32_t *data,
 }
 
 // Level two: ONE workgroup scans the chunk sums in place; *total_out (may be NULL) = the sum of everything.
-#ifndef PIMEMB_GRAD_MASTER_UNIT      // (a kernel of libpimemb_grad.so alone: the master unit emits only its own)
+#ifndef PIMEMB_GRAD_KERNEL_UNIT      // (a kernel of libpimemb_grad.so alone: the master and SR units emit only their own)
 __global__ __launch_bounds__(kBlock) void grad_scan_sums(uint32_t *sums, uint32_t n_chunks, unsigned long long *total_out) {
     __shared__ uint32_t wave_sums[kBlock / 64];
     uint32_t carry = 0;
@@ -195,7 +204,7 @@ __global__ __launch_bounds__(kBlock) void grad_scan_sums(uint32_t *sums, uint32_
 
 // Digit counts of tile `blk`, stored digit-major -- hist[digit * n_tiles + blk] -- so that one exclusive scan over the whole
 // matrix gives every (digit, tile) pair the place of its first position.
-#ifndef PIMEMB_GRAD_MASTER_UNIT      // (a kernel of libpimemb_grad.so alone: the master unit emits only its own)
+#ifndef PIMEMB_GRAD_KERNEL_UNIT      // (a kernel of libpimemb_grad.so alone: the master and SR units emit only their own)
 __global__ __launch_bounds__(kBlock) void grad_sort_count(const uint32_t *keys, uint32_t n, uint32_t shift, uint32_t *hist, uint32_t n_tiles) {
     __shared__ uint32_t counts[256];
     counts[threadIdx.x] = 0;
@@ -215,7 +224,7 @@ __global__ __launch_bounds__(kBlock) void grad_sort_count(const uint32_t *keys, 
 // a slice, the lanes that hold the same digit find each other with 8 ballots: a position's rank among them is the number of
 // such lanes below it, and the lowest of them records their count.  Thread d then turns digit d's 16 slice counts into
 // offsets, and a position goes to   (scanned hist of its digit and tile) + (its slice's offset) + (its rank in the slice).
-#ifndef PIMEMB_GRAD_MASTER_UNIT      // (a kernel of libpimemb_grad.so alone: the master unit emits only its own)
+#ifndef PIMEMB_GRAD_KERNEL_UNIT      // (a kernel of libpimemb_grad.so alone: the master and SR units emit only their own)
 __global__ __launch_bounds__(kBlock) void grad_sort_scatter(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
                                                             uint32_t *vals_out, uint32_t n, uint32_t shift, const uint32_t *hist,
                                                             const uint32_t *sums, uint32_t n_tiles) {
@@ -727,7 +736,7 @@ __device__ __forceinline__ void seg_partials_body(const RowArgs &a, const SegArg
 }
 
 // One lane group per sorted place, as grad_rows_group is launched; it works where a segment of a long run starts.
-#ifndef PIMEMB_GRAD_MASTER_UNIT      // (a kernel of libpimemb_grad.so alone: the master unit emits only its own)
+#ifndef PIMEMB_GRAD_KERNEL_UNIT      // (a kernel of libpimemb_grad.so alone: the master and SR units emit only their own)
 __global__ __launch_bounds__(kBlock) void grad_seg_partials(RowArgs a, SegArgs sg, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
     const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const uint64_t i64 = gid >> lanes_log2;
@@ -811,7 +820,7 @@ __device__ __forceinline__ RowArgs multi_row_args(const MultiArgs &m, uint32_t k
 }
 
 // grad_seg_partials over the runs of a group's composite keys: adjacent keys of two tables are two runs, as everywhere.
-#ifndef PIMEMB_GRAD_MASTER_UNIT      // (a kernel of libpimemb_grad.so alone: the master unit emits only its own)
+#ifndef PIMEMB_GRAD_KERNEL_UNIT      // (a kernel of libpimemb_grad.so alone: the master and SR units emit only their own)
 __global__ __launch_bounds__(kBlock) void grad_seg_multi_partials(const MultiArgs m, const uint32_t *keys, const uint32_t *vals, const uint32_t *bagof,
                                                                   const uint32_t *cnt, SegArgs sg, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
     const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -1157,6 +1166,159 @@ extern "C" void pimemb_grad_master_launch(const void *row_args, const void *seg_
 namespace {
 #endif
 
+// ---- the stochastically rounded steps: W' = enc_sr_T(dec(W) - ..., R) (csrc/pimemb_grad_sr.h) ---------------------------------------
+// emb_grad_sgd / emb_grad_step on fp16 and bf16 tables with the last rounding alone replaced: the same pre-pass, sort, segment launch
+// and run walk; the tail computes ONE Philox block per piece -- counter (row, piece, t), the lane's four elements take its four words --
+// and stores the encoded piece with the vector store of step_piece.  The kernels above keep their text: what is new travels in SrArgs.
+
+struct SrArgs {
+    uint64_t seed;
+    uint64_t step;               // spec.step + the descriptor's number in its call
+    const uint64_t *step_dev;    // or NULL: a device word added to `step` when the kernel runs (a captured graph replays with new words)
+};
+
+// Like the master steps' kernels these live in a code object of their own: this file compiled with -DPIMEMB_GRAD_SR_UNIT into
+// libpimemb_grad_sr.so (csrc/Makefile), which exports their launch function; libpimemb_grad.so's host side calls it.
+#ifdef PIMEMB_GRAD_SR_UNIT
+
+// The step number of this launch: read once per thread, the same word in every lane (a uniform load).
+__device__ __forceinline__ uint64_t sr_step_of(const SrArgs &sr) { return sr.step + (sr.step_dev ? *sr.step_dev : 0ull); }
+
+// step_piece with the stochastic encoder, on the 2-byte dtypes (the plan refuses fp32: nothing to round).
+template <int KIND>
+__device__ __forceinline__ void sr_step_piece(const RowArgs &a, uint64_t seed, uint64_t t, uint32_t row, uint32_t c, float4 acc, float rate) {
+    float4 *sp = nullptr;
+    float4 st = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (KIND == RES_ADAGRAD) {
+        sp = reinterpret_cast<float4 *>(a.state + (uint64_t)row * a.dim) + c;
+        st = *sp;
+    }
+    u32x2 *w = reinterpret_cast<u32x2 *>(a.table + (uint64_t)row * a.stride) + c;
+    const u32x2 v = *w;
+    uint32_t R[4];
+    sr_words(seed, t, row, c, R);
+    u32x2 o;
+    if (KIND == RES_ADAGRAD) {
+        o.x = adagrad_step_sr(a.dtype, v.x & 0xffffu, acc.x, &st.x, rate, a.eps, R[0]) | (adagrad_step_sr(a.dtype, v.x >> 16, acc.y, &st.y, rate, a.eps, R[1]) << 16);
+        o.y = adagrad_step_sr(a.dtype, v.y & 0xffffu, acc.z, &st.z, rate, a.eps, R[2]) | (adagrad_step_sr(a.dtype, v.y >> 16, acc.w, &st.w, rate, a.eps, R[3]) << 16);
+    } else {
+        o.x = step_sr(a.dtype, v.x & 0xffffu, acc.x, rate, R[0]) | (step_sr(a.dtype, v.x >> 16, acc.y, rate, R[1]) << 16);
+        o.y = step_sr(a.dtype, v.y & 0xffffu, acc.z, rate, R[2]) | (step_sr(a.dtype, v.y >> 16, acc.w, rate, R[3]) << 16);
+    }
+    *w = o;
+    if (KIND == RES_ADAGRAD) *sp = st;
+}
+
+// grad_rows_group / grad_seg_rows_group with the stochastic tail: the same exits, the same walks, the same row-wise butterfly.
+template <int KIND, bool SEG>
+__global__ __launch_bounds__(kBlock) void grad_sr_rows_group(RowArgs a, SegArgs sg, SrArgs sr, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    static_assert(KIND == RES_SGD || KIND == RES_ADAGRAD || KIND == RES_ROWWISE, "a stepping kind");
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= a.n || (KIND != RES_ROWWISE && lg >= chunks)) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;      // (uniform over the lane group)
+    const uint64_t t = sr_step_of(sr);
+    if (KIND == RES_ROWWISE) {
+        const bool own0 = lg < chunks, own1 = lg + lanes < chunks;        // (own1: beyond dim 256 only, where lanes == 64)
+        float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
+        if (own0) acc0 = SEG ? seg_walk_piece(a, sg, i, row, lg, chunks) : walk_piece(a, i, row, lg);
+        if (own1) acc1 = SEG ? seg_walk_piece(a, sg, i, row, lg + lanes, chunks) : walk_piece(a, i, row, lg + lanes);
+        const float rate = rowwise_rate(a, row, lg, lanes, acc0, acc1, own1);
+        if (own0) sr_step_piece<KIND>(a, sr.seed, t, row, lg, acc0, rate);
+        if (own1) sr_step_piece<KIND>(a, sr.seed, t, row, lg + lanes, acc1, rate);
+        return;
+    }
+    for (uint32_t c = lg; c < chunks; c += lanes) {
+        const float4 acc = SEG ? seg_walk_piece(a, sg, i, row, c, chunks) : walk_piece(a, i, row, c);
+        sr_step_piece<KIND>(a, sr.seed, t, row, c, acc, a.lr);
+    }
+}
+
+// grad_rows_elem / grad_seg_rows_elem with the stochastic tail: the thread of element c runs the block of its piece c / 4 and takes
+// word c % 4 -- the bits of the lane-group kernel.  (The word is chosen by selects: an indexed array would live in scratch.)
+template <int KIND, bool SEG>
+__global__ __launch_bounds__(kBlock) void grad_sr_rows_elem(RowArgs a, SrArgs sr, uint32_t S) {
+    static_assert(KIND == RES_SGD || KIND == RES_ADAGRAD, "the element-wise kernel has no row-wide view of g");
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid / a.dim;
+    const uint32_t c = (uint32_t)(gid - i64 * a.dim);
+    if (i64 >= a.n) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;
+    float acc = 0.f, t = 0.f;
+    uint32_t in_seg = 0;
+    bool first = true;                           // (SEG) t_0 is taken as it is: the sum of the partials starts from it
+    for (uint32_t j = i; j < a.n && a.keys[j] == row; j++) {
+        const uint32_t p = min(a.vals[j], a.n - 1u);
+        const uint32_t b = min(a.bagof[p], a.n_bags - 1u);
+        const float cp = contribution(a.coef, a.grad[(uint64_t)b * a.ld + c], coef_of(a, p, b));
+        if (!SEG) {
+            acc = add_in_order(acc, cp);
+            continue;
+        }
+        t = add_in_order(t, cp);
+        if (++in_seg == S) {
+            acc = first ? t : add_in_order(acc, t);
+            first = false;
+            t = 0.f;
+            in_seg = 0;
+        }
+    }
+    if (SEG && in_seg) acc = first ? t : add_in_order(acc, t);
+    uint32_t R[4];
+    sr_words(sr.seed, sr_step_of(sr), row, c >> 2, R);
+    const uint32_t j = c & 3u;
+    const uint32_t word = j == 0 ? R[0] : j == 1 ? R[1] : j == 2 ? R[2] : R[3];
+    float *sp = KIND == RES_ADAGRAD ? a.state + (uint64_t)row * a.dim + c : nullptr;
+    float st = KIND == RES_ADAGRAD ? *sp : 0.f;
+    uint16_t *w = reinterpret_cast<uint16_t *>(a.table + (uint64_t)row * a.stride) + c;
+    if (KIND == RES_ADAGRAD) *w = (uint16_t)adagrad_step_sr(a.dtype, *w, acc, &st, a.lr, a.eps, word);
+    else *w = (uint16_t)step_sr(a.dtype, *w, acc, a.lr, word);
+    if (KIND == RES_ADAGRAD) *sp = st;
+}
+
+}  // namespace
+
+// The launch function libpimemb_grad_sr.so exports (plain C; RowArgs, SegArgs and SrArgs are this file's own, which every compilation
+// lays out alike).  The hot launch of a stochastically rounded step (a chain of one): the lane-group kernel or the element-wise one, in
+// the context's order.  kind: RES_SGD / RES_ADAGRAD / RES_ROWWISE.  Errors are left to the caller's hipGetLastError().
+extern "C" __attribute__((visibility("default"))) void pimemb_grad_sr_launch(const void *row_args, const void *seg_args, const void *sr_args, int kind, int seg,
+                                                                              int lane, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks, uint32_t blocks,
+                                                                              uint32_t elem_blocks, uint32_t S, void *stream) {
+    const RowArgs &a = *static_cast<const RowArgs *>(row_args);
+    const SegArgs &sg = *static_cast<const SegArgs *>(seg_args);
+    const SrArgs &sr = *static_cast<const SrArgs *>(sr_args);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 block(kBlock);
+    if (lane) {
+        const dim3 grid(blocks);
+        if (kind == RES_SGD && seg) grad_sr_rows_group<RES_SGD, true><<<grid, block, 0, s>>>(a, sg, sr, lanes, lanes_log2, chunks);
+        else if (kind == RES_SGD) grad_sr_rows_group<RES_SGD, false><<<grid, block, 0, s>>>(a, sg, sr, lanes, lanes_log2, chunks);
+        else if (kind == RES_ADAGRAD && seg) grad_sr_rows_group<RES_ADAGRAD, true><<<grid, block, 0, s>>>(a, sg, sr, lanes, lanes_log2, chunks);
+        else if (kind == RES_ADAGRAD) grad_sr_rows_group<RES_ADAGRAD, false><<<grid, block, 0, s>>>(a, sg, sr, lanes, lanes_log2, chunks);
+        else if (seg) grad_sr_rows_group<RES_ROWWISE, true><<<grid, block, 0, s>>>(a, sg, sr, lanes, lanes_log2, chunks);
+        else grad_sr_rows_group<RES_ROWWISE, false><<<grid, block, 0, s>>>(a, sg, sr, lanes, lanes_log2, chunks);
+        return;
+    }
+    const dim3 grid(elem_blocks);                // (the row-wise kind never gets here: the plan refused it)
+    if (kind == RES_SGD && seg) grad_sr_rows_elem<RES_SGD, true><<<grid, block, 0, s>>>(a, sr, S);
+    else if (kind == RES_SGD) grad_sr_rows_elem<RES_SGD, false><<<grid, block, 0, s>>>(a, sr, 0u);
+    else if (seg) grad_sr_rows_elem<RES_ADAGRAD, true><<<grid, block, 0, s>>>(a, sr, S);
+    else grad_sr_rows_elem<RES_ADAGRAD, false><<<grid, block, 0, s>>>(a, sr, 0u);
+}
+
+namespace {
+#else      // libpimemb_grad.so (and the master unit, which never calls it): the launcher is libpimemb_grad_sr.so's
+}  // namespace
+extern "C" void pimemb_grad_sr_launch(const void *row_args, const void *seg_args, const void *sr_args, int kind, int seg, int lane, uint32_t lanes,
+                                      uint32_t lanes_log2, uint32_t chunks, uint32_t blocks, uint32_t elem_blocks, uint32_t S, void *stream);
+namespace {
+#endif
+
 // ---- the gradient of per_sample_weights: dw[p] = < G[bag(p)] , dec(W[ids[p]]) > (csrc/pimemb_grad_dot.h) ------------------------
 // No pre-pass: nothing is sorted, a position's value depends on its own row and its bag's row of G alone.  The kernels above keep
 // their text; these read the batch as the forward does.
@@ -1315,7 +1477,7 @@ __global__ __launch_bounds__(kBlock) void grad_psw_elem(PswArgs a, uint32_t lane
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-#ifndef PIMEMB_GRAD_MASTER_UNIT      // (to the end of the file: the master unit holds kernels and their launchers alone)
+#ifndef PIMEMB_GRAD_KERNEL_UNIT      // (to the end of the file: the master and SR units hold kernels and their launchers alone)
 
 thread_local char t_err[512] = "";
 
@@ -1543,6 +1705,7 @@ struct StepSpec {
     int kind = RES_SPARSE;       // ResultKind
     float lr = 0.f, eps = 0.f;
     float *const *masters = nullptr;      // emb_grad_master_step: one fp32 master per descriptor; the kind's master tail runs
+    const emb_sr_spec *sr = nullptr;      // emb_grad_sgd_sr / emb_grad_step_sr: the kind's stochastically rounded tail runs
 };
 struct SparseOut {               // where emb_grad_sparse writes; all NULL for a step (no unique numbering, no output arrays)
     long long *rows = nullptr;
@@ -1633,6 +1796,9 @@ int plan_step(emb_grad *g, const emb_grad_desc *descs, float *const *states, uin
         const emb_grad_desc &d = descs[k];
         Planned &p = plan[k];
         if (int rc = check_desc(g, d, itype, step, who, &p.t)) return rc;
+        if (spec.sr && p.t.dtype == kF32)
+            return fail(EMB_ERR_UNSUPPORTED, "%s: table %u is EMB_F32: an fp32 step stores its fp32 result, there is nothing to round -- use %s", who,
+                        d.table_id, spec.kind == RES_SGD ? "emb_grad_sgd" : "emb_grad_step");
         float *state = d.n_indices && states ? states[k] : nullptr;
         if (d.n_indices && spec.kind != RES_SGD && (!state || (uintptr_t)state % 4))
             return fail(EMB_ERR_INVALID, "%s: the state of table %u is NULL or not 4-byte aligned", who, d.table_id);
@@ -1720,7 +1886,7 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
     const dim3 block(kBlock), pos_grid((n + kBlock - 1) / kBlock);
     unsigned long long *bad = &g->counters[0];
     MultiArgs m;                                 // (filled for a group only)
-    if (c.mean && c.n_bags && spec.masters) pimemb_grad_master_clear(sc.cnt, c.n_bags, s);
+    if (c.mean && c.n_bags && (spec.masters || spec.sr)) pimemb_grad_master_clear(sc.cnt, c.n_bags, s);      // (a kernel: the note at grad_master_clear)
     else if (c.mean && c.n_bags) GRAD_HIP(hipMemsetAsync(sc.cnt, 0, (size_t)c.n_bags * 4, s));
     if (group) {
         fill_multi(m, descs, states, p, first);
@@ -1785,6 +1951,13 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
         if (seg && c.lane) grad_seg_partials<<<dim3(l.blocks), block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
         const MasterArgs ma{spec.masters[first], c.t.dtype, &g->counters[1]};
         pimemb_grad_master_launch(&a, &sg, &ma, spec.kind, seg, c.lane, l.lanes, l.lanes_log2, l.chunks, l.blocks, c.elem_blocks, g->cfg.segment, s);
+        GRAD_HIP(hipGetLastError());
+        return EMB_OK;
+    }
+    if (spec.sr) {
+        if (seg && c.lane) grad_seg_partials<<<dim3(l.blocks), block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
+        const SrArgs sr{spec.sr->seed, spec.sr->step + first, spec.sr->step_dev};      // (descriptor k of the call: t = step + *step_dev + k, mod 2^64)
+        pimemb_grad_sr_launch(&a, &sg, &sr, spec.kind, seg, c.lane, l.lanes, l.lanes_log2, l.chunks, l.blocks, c.elem_blocks, g->cfg.segment, s);
         GRAD_HIP(hipGetLastError());
         return EMB_OK;
     }
@@ -1939,14 +2112,23 @@ int emb_grad_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype
 
 namespace {
 
+// Everything that can be refused about an emb_sr_spec; NULL text: it is fine.
+const char *sr_fault(const emb_sr_spec *sr) {
+    if (!sr) return "the stochastic-rounding spec is NULL";
+    if (sr->reserved != 0) return "the stochastic-rounding spec's reserved field must be 0";
+    if ((uintptr_t)sr->step_dev % 8) return "step_dev is not 8-byte aligned";
+    return nullptr;
+}
+
 int opt_call(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype, const emb_opt_spec *opt,
-             void *stream, bool multi) {
-    const char *who = multi ? "emb_grad_step_multi" : "emb_grad_step";
+             void *stream, bool multi, const emb_sr_spec *sr = nullptr) {
+    const char *who = sr ? "emb_grad_step_sr" : multi ? "emb_grad_step_multi" : "emb_grad_step";
     if (!opt) return fail(EMB_ERR_INVALID, "%s: the optimizer spec is NULL", who);
     if (opt->kind != EMB_OPT_ADAGRAD && opt->kind != EMB_OPT_ROWWISE_ADAGRAD) return fail(EMB_ERR_INVALID, "%s: unknown optimizer kind %u", who, opt->kind);
     if (opt->reserved != 0) return fail(EMB_ERR_INVALID, "%s: the spec's reserved field must be 0, got %u", who, opt->reserved);
     if (!(opt->eps >= 0.f)) return fail(EMB_ERR_INVALID, "%s: eps must not be negative or NaN, got %g", who, (double)opt->eps);
-    const StepSpec st{opt->kind == EMB_OPT_ROWWISE_ADAGRAD ? RES_ROWWISE : RES_ADAGRAD, opt->lr, opt->eps};
+    StepSpec st{opt->kind == EMB_OPT_ROWWISE_ADAGRAD ? RES_ROWWISE : RES_ADAGRAD, opt->lr, opt->eps};
+    st.sr = sr;
     return step_call(g, descs, states, n_descs, itype, st, "an Adagrad", who, multi, stream);
 }
 
@@ -1976,6 +2158,19 @@ int emb_grad_step(emb_grad *g, const emb_grad_desc *descs, float *const *states,
 int emb_grad_step_multi(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype,
                         const emb_opt_spec *opt, void *stream) {
     return opt_call(g, descs, states, n_descs, itype, opt, stream, true);
+}
+
+int emb_grad_sgd_sr(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, const emb_sr_spec *sr, void *stream) {
+    if (const char *fault = sr_fault(sr)) return fail(EMB_ERR_INVALID, "emb_grad_sgd_sr: %s", fault);
+    StepSpec st{RES_SGD, lr, 0.f};
+    st.sr = sr;
+    return step_call(g, descs, nullptr, n_descs, itype, st, "an SGD", "emb_grad_sgd_sr", false, stream);
+}
+
+int emb_grad_step_sr(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype, const emb_opt_spec *opt,
+                     const emb_sr_spec *sr, void *stream) {
+    if (const char *fault = sr_fault(sr)) return fail(EMB_ERR_INVALID, "emb_grad_step_sr: %s", fault);
+    return opt_call(g, descs, states, n_descs, itype, opt, stream, false, sr);
 }
 
 int emb_grad_weights(emb_grad *g, const emb_grad_desc *descs, float *const *dw_out, uint32_t n_descs, emb_index_type itype, void *stream) {
@@ -2077,4 +2272,4 @@ int emb_grad_report(emb_grad *g, uint64_t *n_bad) {
 
 #else
 }  // namespace
-#endif  // !PIMEMB_GRAD_MASTER_UNIT
+#endif  // !PIMEMB_GRAD_KERNEL_UNIT

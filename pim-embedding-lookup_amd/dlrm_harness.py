@@ -9,7 +9,8 @@ loss.backward() applies the fused SGD step of the backward pass (include/pimemb_
 `--fused-adagrad LR` / `--fused-rowwise-adagrad LR` do the same with the fused Adagrad / row-wise Adagrad step (the three are
 mutually exclusive; `--multi-table-step` sends them through the multi-table entry points, `--segmented-sums [S]` makes them sum in the
 segmented order of additions; `--master-weights` keeps fp32 master rows and runs the fused master-weight step, with which fp8 and
-mxfp4 tables train).  No MLPs -- the rest of the model is out of scope.
+mxfp4 tables train; `--stochastic-rounding [SEED]` rounds the last operation of a step on f16 / bf16 tables stochastically instead,
+with no master).  No MLPs -- the rest of the model is out of scope.
 
     python -m pim_embedding_lookup_amd.dlrm_harness --arch-sparse-feature-size=16 \
         --arch-embedding-size=1460-583-10131227-… --mini-batch-size=39292 --inference-only
@@ -87,6 +88,7 @@ class EmbeddingBagCollection:
         self.multi_table_step = False                           # the fused steps go through the multi-table entry points (--multi-table-step)
         self.segmented_sums = None                              # the fused steps' segment length in the segmented order of additions; None: position order (--segmented-sums)
         self._fused_adagrad, self.adagrad_sum = None, None      # (lr, eps, rowwise) and the per-table fp32 states of enable_fused_adagrad
+        self.sr_seed, self.sr_step = None, 0                    # --stochastic-rounding: the seed while it is on, and the step number of the next table stepped
         # DLRM --weighted-pooling: v_W_l[k] is a weight per ROW of table k (ones for "fixed", the checkpoint's for "learned");
         # a bag entry is weighted by its row's weight, gathered with torch (dlrm_s_pytorch.py: v_W_l[k].gather(0, indices))
         if weighted_pooling not in (None, "fixed", "learned"):
@@ -207,21 +209,46 @@ class EmbeddingBagCollection:
                 raise ValueError("multi_table_step does not go with master weights: there is no multi-table master step")
             self.master_weight = [self.engine.master_of(t, self.device) for t in self._ids]
 
-    def enable_fused_sgd(self, lr, master_weights: bool = False):
+    def _set_sr(self, on: bool, seed: int, master_weights: bool) -> None:
+        """--stochastic-rounding: the fused steps round their last operation stochastically (GradContext's sr=; f16 and bf16 tables);
+        sr_step counts the tables stepped and is kept over enable_* calls."""
+        if on:
+            if master_weights:
+                raise ValueError("stochastic rounding does not go with master weights: they are alternatives")
+            if self.multi_table_step:
+                raise ValueError("stochastic rounding does not go with multi_table_step: there is no stochastically rounded multi-table step")
+            if self.table_dtype not in ("f16", "bf16"):
+                raise ValueError("stochastic rounding goes with f16 and bf16 tables: an f32 table stores its fp32 result, there is nothing to round")
+        self.sr_seed = int(seed) % (1 << 64) if on else None
+
+    def _sr_take(self, n: int):
+        """sr= of one context call over n tables (None while stochastic rounding is off); advances sr_step by n."""
+        if self.sr_seed is None:
+            return None
+        if self.multi_table_step:
+            raise ValueError("stochastic rounding does not go with multi_table_step: there is no stochastically rounded multi-table step")
+        step = self.sr_step
+        self.sr_step = (step + n) % (1 << 64)
+        return (self.sr_seed, step)
+
+    def enable_fused_sgd(self, lr, master_weights: bool = False, stochastic_rounding: bool = False, sr_seed: int = 0):
         """From now on apply_emb (lists of torch CUDA tensors; f32 / f16 / bf16 tables) returns tensors attached to the autograd
         graph whose backward applies W -= lr * grad to the served tables (GradContext.sgd_step): loss.backward() is the tables'
         whole training step.  lr=None switches it off.  The per-row pooling weights of --weighted-pooling get their gradient in the
         same backward after enable_pooling_weight_grad(), computed before the step, at the table the forward read."""
+        self._set_sr(stochastic_rounding and lr is not None, sr_seed, master_weights)
         self._fused_lr = None if lr is None else float(lr)
         self._fused_adagrad = None
         self._set_masters(master_weights and lr is not None)
         return self
 
-    def enable_fused_adagrad(self, lr, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0, master_weights: bool = False):
+    def enable_fused_adagrad(self, lr, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0, master_weights: bool = False,
+                             stochastic_rounding: bool = False, sr_seed: int = 0):
         """As enable_fused_sgd, with the fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row;
         GradContext.adagrad_step).  The fp32 states -- self.adagrad_sum, one tensor per table -- are allocated here, once per
         flavour, filled with initial_accumulator_value.  lr=None switches it off.  Switches a fused SGD off."""
         import torch
+        self._set_sr(stochastic_rounding and lr is not None, sr_seed, master_weights)
         if lr is None:
             self._fused_adagrad = None
             self._set_masters(False)
@@ -268,10 +295,10 @@ class EmbeddingBagCollection:
                     ctx.master_step(*args, [masters[k] for k in live], ada[0], optimizer="rowwise" if ada[2] else "adagrad",
                                     states=[self.adagrad_sum[k] for k in live], eps=ada[1], per_sample_weights=w_live)
             elif ada is None:
-                ctx.sgd_step(*args, lr, per_sample_weights=w_live, multi=multi)
+                ctx.sgd_step(*args, lr, per_sample_weights=w_live, multi=multi, sr=self._sr_take(len(live)))
             else:
                 ctx.adagrad_step(*args, [self.adagrad_sum[k] for k in live], ada[0], eps=ada[1], rowwise=ada[2], per_sample_weights=w_live,
-                                 multi=multi)
+                                 multi=multi, sr=self._sr_take(len(live)))
         if self._pooling_weights_trained():      # the weights' gradient first, the step behind it
             return tm._WeightedLookup.apply(tm._anchor(self, self.device), lookup, lambda g: self._weights_grads(lS_o, lS_i, g, concat, col), step, *gathered)
         return tm._FusedSGD.apply(tm._anchor(self, self.device), lookup, step)
@@ -453,6 +480,11 @@ def main(argv=None):
                          "(emb_grad_master_step): the master is stepped in fp32 and the table row is its encoding -- the way to train "
                          "fp8 and mxfp4 tables, and f16 / bf16 ones without losing small updates; not for f32 tables, and not with "
                          "--multi-table-step")
+    ap.add_argument("--stochastic-rounding", type=lambda v: int(v, 0), nargs="?", const=0, default=None, metavar="SEED",
+                    help="with one of the --fused-* flags and --table-dtype f16 or bf16: the fused step rounds its last operation "
+                         "stochastically (emb_grad_sgd_sr / emb_grad_step_sr; Philox words of SEED, default 0, and the step number), so the "
+                         "stored table keeps on average the updates that rounding to nearest loses -- the alternative to --master-weights, "
+                         "without a master; not with --multi-table-step")
     ap.add_argument("--segmented-sums", type=int, nargs="?", const=0, default=None, metavar="S",
                     help="with one of the --fused-* flags: sum a row's occurrences in segments of S (a power of two, 8 .. 1024; "
                          "default: GradContext's), the segmented order of include/pimemb_grad.h -- for skewed ids, where some rows "
@@ -477,6 +509,15 @@ def main(argv=None):
         raise SystemExit("--master-weights goes with --table-dtype f16, bf16, fp8_e4m3, fp8_e5m2 or mxfp4: an f32 table is its own master")
     if fused and args.table_dtype in ("fp8_e4m3", "fp8_e5m2", "mxfp4") and not args.master_weights:
         raise SystemExit(f"--table-dtype {args.table_dtype} trains with --master-weights only: a step in the stored precision mostly rounds away")
+    if args.stochastic_rounding is not None:
+        if not fused:
+            raise SystemExit("--stochastic-rounding goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
+        if args.master_weights:
+            raise SystemExit("--stochastic-rounding does not go with --master-weights: they are alternatives")
+        if args.multi_table_step:
+            raise SystemExit("--stochastic-rounding does not go with --multi-table-step: there is no stochastically rounded multi-table step")
+        if args.table_dtype not in ("f16", "bf16"):
+            raise SystemExit("--stochastic-rounding goes with --table-dtype f16 or bf16: an f32 table stores its fp32 result, there is nothing to round")
     if args.segmented_sums is not None and not fused:
         raise SystemExit("--segmented-sums goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
     if args.train_pooling_weights is not None and args.weighted_pooling is None:
@@ -531,10 +572,11 @@ def main(argv=None):
         if args.segmented_sums is not None:
             from .engine import GradContext
             ebc.segmented_sums = args.segmented_sums or GradContext.DEFAULT_SEGMENT
+        sr_kw = {} if args.stochastic_rounding is None else dict(stochastic_rounding=True, sr_seed=args.stochastic_rounding)
         if opt_name == "SGD":
-            ebc.enable_fused_sgd(opt_lr, master_weights=args.master_weights)
+            ebc.enable_fused_sgd(opt_lr, master_weights=args.master_weights, **sr_kw)
         elif opt_name is not None:
-            ebc.enable_fused_adagrad(opt_lr, rowwise=opt_name != "Adagrad", master_weights=args.master_weights)
+            ebc.enable_fused_adagrad(opt_lr, rowwise=opt_name != "Adagrad", master_weights=args.master_weights, **sr_kw)
         w_opt = None
         if args.train_pooling_weights is not None:      # the per-row pooling weights: plain torch.optim.SGD over v_W_l
             ebc.enable_pooling_weight_grad()

@@ -516,23 +516,49 @@ class GradContext:
             self._free((rows_b, grads_b, count_b, *keep))
 
     def sgd_step(self, table_ids, indices, offsets, grads, lr: float, modes="sum", per_sample_weights=None, padding_idx=None,
-                 stream: int | None = None, fixed_pooling: int = 0, multi: bool = False) -> None:
+                 stream: int | None = None, fixed_pooling: int = 0, multi: bool = False, sr=None) -> None:
         """W[r] = enc(dec(W[r]) - lr * g[r]) for every row r the batch of its table names, in place, table after table (fp32,
         fp16 and bf16 tables).  table_ids / indices / offsets / grads: one entry per table; modes, per_sample_weights and
         padding_idx one value for all or one per table.  Each gradient is [n_bags, dim], and may be a column view of a wider
         buffer (the [B, T*dim] gradient of a concatenated output is read in place).  Torch CUDA tensors: a pure enqueue on
         `stream` (torch's current one by default); numpy arrays: copied to the device, and the call waits.  multi=True: the
-        multi-table step (emb_grad_sgd_multi) -- one pre-pass and one launch per group of tables (multi_groups), the same bytes."""
+        multi-table step (emb_grad_sgd_multi) -- one pre-pass and one launch per group of tables (multi_groups), the same bytes.
+        sr=(seed, step) or (seed, step, step_dev_tensor): the stochastically rounded step (emb_grad_sgd_sr; fp16 and bf16 tables) --
+        the last rounding goes up or down by a Philox word of (seed, step + k, row, element), k the table's place in the call;
+        step_dev_tensor is an int64 CUDA tensor of one element the kernels add to step when they run.  Not with multi=True."""
+        sr_spec = self._sr_spec(sr, multi)
         keep = []
         try:
             arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, grads, modes, per_sample_weights, padding_idx, fixed_pooling,
                                                           stream, keep)
-            call = self._G.emb_grad_sgd_multi if multi else self._G.emb_grad_sgd
-            _l.check_grad(call(self._h, arr, n, itype, float(lr), stream))
+            if sr_spec is not None:
+                _l.check_grad(self._G.emb_grad_sgd_sr(self._h, arr, n, itype, float(lr), C.byref(sr_spec), stream))
+            else:
+                call = self._G.emb_grad_sgd_multi if multi else self._G.emb_grad_sgd
+                _l.check_grad(call(self._h, arr, n, itype, float(lr), stream))
             if not dev:
                 self.engine.synchronize(stream)
         finally:
             self._free(keep)
+
+    @staticmethod
+    def _sr_spec(sr, multi):
+        """The emb_sr_spec of sr=(seed, step[, step_dev_tensor]); None for sr=None."""
+        if sr is None:
+            return None
+        if multi:
+            raise ValueError("sr= does not go with multi=True: there is no stochastically rounded multi-table step")
+        if not isinstance(sr, (tuple, list)) or len(sr) not in (2, 3):
+            raise ValueError("sr has to be (seed, step) or (seed, step, step_dev_tensor)")
+        dev_ptr = None
+        if len(sr) == 3 and sr[2] is not None:
+            import torch
+            t = sr[2]
+            if not (_is_torch(t) and t.is_cuda) or t.dtype != torch.int64 or t.numel() != 1:
+                raise TypeError("step_dev_tensor must be an int64 CUDA tensor of one element")
+            dev_ptr = t.data_ptr()
+        mask = (1 << 64) - 1
+        return _l.EmbSrSpec(int(sr[0]) & mask, int(sr[1]) & mask, dev_ptr, 0)
 
     def multi_groups(self, table_ids, n_indices, n_bags, lane_group=True) -> list:
         """How a multi=True step over these tables would be split in this context (emb_grad_multi_groups): the group number of
@@ -556,12 +582,15 @@ class GradContext:
         return shape
 
     def adagrad_step(self, table_ids, indices, offsets, grads, states, lr: float, eps: float = 1e-10, rowwise: bool = False, modes="sum",
-                     per_sample_weights=None, padding_idx=None, stream: int | None = None, fixed_pooling: int = 0, multi: bool = False) -> None:
+                     per_sample_weights=None, padding_idx=None, stream: int | None = None, fixed_pooling: int = 0, multi: bool = False,
+                     sr=None) -> None:
         """The fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row) of include/pimemb_grad.h, table after
         table: conventions as sgd_step.  states: one per table, state_shape(table, rowwise) float32 values, read and written in
         place -- float32 CUDA tensors of that numel (any shape, contiguous) with torch inputs; numpy float32 arrays with numpy
         inputs, copied to the device and back into the very arrays.  The caller initialises them (zeros, or torch's
-        initial_accumulator_value).  multi=True: the multi-table step (emb_grad_step_multi), the same bytes."""
+        initial_accumulator_value).  multi=True: the multi-table step (emb_grad_step_multi), the same bytes.  sr: as in sgd_step
+        (emb_grad_step_sr); the state stays exact fp32."""
+        sr_spec = self._sr_spec(sr, multi)
         if len(states) != len(table_ids):
             raise ValueError(f"{len(states)} states for {len(table_ids)} tables")
         keep, back = [], []
@@ -587,8 +616,11 @@ class GradContext:
                     back.append((st, buf))
                     ptrs[k] = buf.ptr
             spec = _l.EmbOptSpec(_l.EMB_OPT_ROWWISE_ADAGRAD if rowwise else _l.EMB_OPT_ADAGRAD, float(lr), float(eps), 0)
-            call = self._G.emb_grad_step_multi if multi else self._G.emb_grad_step
-            _l.check_grad(call(self._h, arr, ptrs, n, itype, C.byref(spec), stream))
+            if sr_spec is not None:
+                _l.check_grad(self._G.emb_grad_step_sr(self._h, arr, ptrs, n, itype, C.byref(spec), C.byref(sr_spec), stream))
+            else:
+                call = self._G.emb_grad_step_multi if multi else self._G.emb_grad_step
+                _l.check_grad(call(self._h, arr, ptrs, n, itype, C.byref(spec), stream))
             if not dev:
                 self.engine.synchronize(stream)
                 for st, buf in back:

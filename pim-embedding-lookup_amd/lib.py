@@ -233,6 +233,11 @@ class EmbMasterSpec(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("lr", C.c_float), ("eps", C.c_float), ("reserved", C.c_uint32)]
 
 
+class EmbSrSpec(C.Structure):
+    """emb_sr_spec: the seed and step number of a stochastically rounded step; step_dev NULL or a device uint64 added to step."""
+    _fields_ = [("seed", C.c_uint64), ("step", C.c_uint64), ("step_dev", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 EMB_GRAD_MULTI_MAX = 16
 EMB_GRAD_NO_GROUP = 0xFFFFFFFF      # emb_grad_multi_groups: an empty descriptor
 
@@ -271,6 +276,8 @@ GRAD_SIGNATURES = {
     "emb_grad_weights": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, _vp]),
     "emb_grad_master_step": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbMasterSpec), _vp]),
     "emb_grad_master_report": (C.c_int, [_vp, C.POINTER(_u64)]),
+    "emb_grad_sgd_sr": (C.c_int, [_vp, C.POINTER(EmbGradDesc), _u32, C.c_int, C.c_float, C.POINTER(EmbSrSpec), _vp]),
+    "emb_grad_step_sr": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbOptSpec), C.POINTER(EmbSrSpec), _vp]),
 }
 
 _lib = None
@@ -344,7 +351,12 @@ def load_grad() -> C.CDLL:
     load()
     if _grad_lib is not None:          # (load() came here itself)
         return _grad_lib
-    from .build import GRAD_LIB_PATH
+    from .build import GRAD_LIB_PATH, GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH
+    for dep in (GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH):      # libpimemb_grad.so links against both (RUNPATH $ORIGIN): name the one that is missing
+        if not os.path.exists(dep):
+            raise FileNotFoundError(
+                f"{dep} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(hipcc --offload-arch=gfx950).  There is no fallback path.")
     if not os.path.exists(GRAD_LIB_PATH):
         raise FileNotFoundError(
             f"{GRAD_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "

@@ -351,8 +351,13 @@ class PoolingEmbeddingBag(torch.nn.Module):
             return lookup()
         return _FusedSGD.apply(_anchor(self, idx.device), lookup, lambda g: self._step(idx, off, g, lr, w))
 
-    def enable_fused_sgd(self, lr: float, order: str = "position", master_weights: bool = False):
-        """master_weights=True: the module keeps fp32 master rows (master_weight, made from the table by exact widening on first
+    def enable_fused_sgd(self, lr: float, order: str = "position", master_weights: bool = False, stochastic_rounding: bool = False, sr_seed: int = 0):
+        """stochastic_rounding=True (fp16 and bf16 tables): the step is the stochastically rounded one of include/pimemb_grad.h -- the last
+        rounding goes up or down by a Philox word of (sr_seed, sr_step, row, element), so the stored table keeps, on average, the updates
+        that rounding to nearest loses below half an ulp, without a master.  The module counts its steps in sr_step (a host integer, one
+        per table stepped), and state_dict() carries `<prefix>sr_seed` / `<prefix>sr_step` while it is on: a resumed run continues the
+        stream.  It is the alternative to master_weights=True (both: ValueError).  Off by default.
+        master_weights=True: the module keeps fp32 master rows (master_weight, made from the table by exact widening on first
         use and saved as `<prefix>master_weight`) and the step is the fused master-weight step of include/pimemb_grad.h: the master
         is stepped in fp32 and the table row is its encoding -- the way to train fp8 and MXFP4 tables, and fp16 / bf16 ones without
         losing small updates.  Off by default.
@@ -361,6 +366,7 @@ class PoolingEmbeddingBag(torch.nn.Module):
         lr=None switches it off again.  Switches a fused Adagrad off (its state stays).  order="segmented": a row's occurrences
         are summed in the segmented order of include/pimemb_grad.h (GradContext) -- for batches that name some rows thousands of
         times; as fixed as the position order, other bits.  Returns self."""
+        _set_sr(self, stochastic_rounding, sr_seed, [self._table_dtype], master_weights)
         object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
         object.__setattr__(self, "_fused_adagrad", None)
@@ -368,17 +374,28 @@ class PoolingEmbeddingBag(torch.nn.Module):
         return self
 
     @property
+    def sr_step(self) -> int:
+        """The step number the next stochastically rounded step of this module uses (advanced by one per table stepped)."""
+        return getattr(self, "_sr_step", 0)
+
+    @property
+    def sr_seed(self):
+        """The seed of the module's stochastically rounded steps, or None while stochastic rounding is off."""
+        return getattr(self, "_sr_seed", None)
+
+    @property
     def master_weight(self):
         """The fp32 master rows (float32 CUDA tensor [num_embeddings, embedding_dim]), or None while master weights are off."""
         return getattr(self, "_master_weight", None) if getattr(self, "_fused_master", False) else None
 
     def enable_fused_adagrad(self, lr: float, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0,
-                             order: str = "position", master_weights: bool = False):
-        """As enable_fused_sgd (order= included), with the fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row) of
+                             order: str = "position", master_weights: bool = False, stochastic_rounding: bool = False, sr_seed: int = 0):
+        """As enable_fused_sgd (order=, stochastic_rounding= and sr_seed= included), with the fused Adagrad step (rowwise=True: row-wise Adagrad, one accumulator per row) of
         include/pimemb_grad.h: torch.optim.Adagrad(lr, eps=eps, initial_accumulator_value=...) without lr_decay and weight_decay.
         The fp32 state -- module.adagrad_sum, [num_embeddings, embedding_dim] or [num_embeddings] -- is allocated once, filled with
         initial_accumulator_value, kept over later calls (a change of `rowwise` allocates it anew), and saved by state_dict() as
         `<prefix>adagrad_sum`.  lr=None switches the step off (the state stays).  Switches a fused SGD off.  Returns self."""
+        _set_sr(self, stochastic_rounding and lr is not None, sr_seed, [self._table_dtype], master_weights)
         object.__setattr__(self, "_fused_order", _order(order))
         if lr is None:
             object.__setattr__(self, "_fused_adagrad", None)
@@ -399,29 +416,34 @@ class PoolingEmbeddingBag(torch.nn.Module):
         order = getattr(self, "_fused_order", "position") if order is None else _order(order)
         return _grad_context(self.engine, idx.shape[0], off.shape[0], order, self.embedding_dim)
 
-    def _step(self, idx, off, grad_output, lr, w, order=None):
+    def _step(self, idx, off, grad_output, lr, w, order=None, sr_seed=None):
+        """sr_seed None: as enable_fused_* set it; False: a plain step; an integer: a stochastically rounded step with that seed."""
         if grad_output is None:
             return
         g = _grad_view(grad_output, self.embedding_dim)
+        if sr_seed not in (None, False):
+            _check_sr([self._table_dtype], self.master_weight is not None)
         if self.master_weight is not None:
             self._context(idx, off, order).master_step(self._id_list, [idx], [off], [g], [self.master_weight], lr, optimizer="sgd", modes=self.mode,
                                                        per_sample_weights=w, padding_idx=self.padding_idx)
             return
         self._context(idx, off, order).sgd_step(self._id_list, [idx], [off], [g], lr, modes=self.mode, per_sample_weights=w,
-                                                padding_idx=self.padding_idx)
+                                                padding_idx=self.padding_idx, sr=_sr_take(self, 1, sr_seed))
 
-    def _adagrad(self, idx, off, grad_output, lr, eps, w, order=None):
+    def _adagrad(self, idx, off, grad_output, lr, eps, w, order=None, sr_seed=None):
         if grad_output is None:
             return
         g = _grad_view(grad_output, self.embedding_dim)
         state = _adagrad_state(self)
+        if sr_seed not in (None, False):
+            _check_sr([self._table_dtype], self.master_weight is not None)
         if self.master_weight is not None:
             self._context(idx, off, order).master_step(self._id_list, [idx], [off], [g], [self.master_weight], lr,
                                                        optimizer="rowwise" if state.dim() == 1 else "adagrad", states=[state], eps=eps, modes=self.mode,
                                                        per_sample_weights=w, padding_idx=self.padding_idx)
             return
         self._context(idx, off, order).adagrad_step(self._id_list, [idx], [off], [g], [state], lr, eps=eps, rowwise=state.dim() == 1,
-                                                    modes=self.mode, per_sample_weights=w, padding_idx=self.padding_idx)
+                                                    modes=self.mode, per_sample_weights=w, padding_idx=self.padding_idx, sr=_sr_take(self, 1, sr_seed))
 
     def _weights_grad(self, idx, off, grad_output):
         """float32 [len(idx)]: the gradient of per_sample_weights for one batch (None for a None gradient)."""
@@ -441,12 +463,14 @@ class PoolingEmbeddingBag(torch.nn.Module):
         dw = self._weights_grad(idx, off, torch.as_tensor(grad_output).to(idx.device))
         return dw.reshape(tuple(torch.as_tensor(input).shape))
 
-    def adagrad_step_(self, input, offsets, grad_output, lr: float, eps: float = 1e-10, per_sample_weights=None, order: str = "position"):
+    def adagrad_step_(self, input, offsets, grad_output, lr: float, eps: float = 1e-10, per_sample_weights=None, order: str = "position",
+                      stochastic_rounding: bool = False, sr_seed: int = 0):
         """One fused Adagrad step on the rows the batch names, in place and in stream order with forward(), on the module's state
         (adagrad_sum; of the flavour enable_fused_adagrad chose, or element-wise zeros if there is none yet).  order: as
-        enable_fused_sgd.  Returns self."""
+        enable_fused_sgd.  stochastic_rounding / sr_seed: this one step rounds stochastically, at the module's sr_step, which it
+        advances.  Returns self."""
         idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
-        self._adagrad(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), float(eps), w, order)
+        self._adagrad(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), float(eps), w, order, int(sr_seed) if stochastic_rounding else False)
         return self
 
     def _bags_on_device(self, input, offsets, per_sample_weights):
@@ -466,13 +490,15 @@ class PoolingEmbeddingBag(torch.nn.Module):
             self.table_id, idx, off, g, mode=self.mode, per_sample_weights=w, padding_idx=self.padding_idx)
         return torch.sparse_coo_tensor(rows.unsqueeze(0), grads, size=(self.num_embeddings, self.embedding_dim), is_coalesced=True)
 
-    def sgd_step_(self, input, offsets, grad_output, lr: float, per_sample_weights=None, order: str = "position"):
+    def sgd_step_(self, input, offsets, grad_output, lr: float, per_sample_weights=None, order: str = "position", stochastic_rounding: bool = False,
+                  sr_seed: int = 0):
         """weight[r] -= lr * grad[r] for every row the batch names, in place and in stream order with forward(): one fp32
         multiply and one fp32 subtract per element, rounded once into the weight's dtype (fp32 / fp16 / bf16).  Entries whose
         index lies outside the table are skipped and counted (engine._module_grad.report()).  order: as enable_fused_sgd.
+        stochastic_rounding / sr_seed: this one step rounds stochastically (fp16 / bf16), at the module's sr_step, which it advances.
         Returns self."""
         idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
-        self._step(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), w, order)
+        self._step(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), w, order, int(sr_seed) if stochastic_rounding else False)
         return self
 
     def update_rows_(self, ids, rows):
@@ -495,9 +521,11 @@ class PoolingEmbeddingBag(torch.nn.Module):
             destination[prefix + "adagrad_sum"] = self.adagrad_sum.detach().clone()
         if self.master_weight is not None:    # (only with master weights on)
             destination[prefix + "master_weight"] = self.master_weight.detach().clone()
+        _save_sr(self, destination, prefix)   # (only with stochastic rounding on)
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         self._table._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        _load_sr(self, state_dict, prefix, strict, missing_keys)
         mkey = prefix + "master_weight"
         if mkey in state_dict:
             m = state_dict[mkey]
@@ -572,6 +600,56 @@ def _set_master(bag, on: bool) -> None:
         if bag._table_dtype == torch.float32:
             raise ValueError("master_weights=True goes with fp16, bf16, fp8 and MXFP4 tables: an fp32 table is its own master")
         object.__setattr__(bag, "_master_weight", bag.engine.master_of(bag.table_id, torch.device("cuda", bag.device_index)))
+
+
+_U64 = 1 << 64
+
+
+def _check_sr(table_dtypes, master: bool, multi_table: bool = False) -> None:
+    """What stochastic rounding does not go with: master weights (the alternative), the multi-table step, any table but fp16 / bf16."""
+    if master:
+        raise ValueError("stochastic_rounding=True does not go with master_weights=True: they are alternatives (a master keeps every update exactly, "
+                         "stochastic rounding keeps them on average without one)")
+    if multi_table:
+        raise ValueError("stochastic_rounding=True does not go with multi_table=True: there is no stochastically rounded multi-table step")
+    if any(dt not in (torch.float16, torch.bfloat16) for dt in table_dtypes):
+        raise ValueError("stochastic_rounding=True goes with fp16 and bf16 tables: an fp32 table stores its fp32 result, there is nothing to round "
+                         "(fp8 and MXFP4 tables train with master_weights=True)")
+
+
+def _set_sr(mod, on: bool, seed: int, table_dtypes, master: bool, multi_table: bool = False) -> None:
+    """Stochastic rounding on or off for a module: _sr_seed is the seed while it is on, else None; _sr_step is kept over enable_* calls."""
+    if on:
+        _check_sr(table_dtypes, master, multi_table)
+    object.__setattr__(mod, "_sr_seed", int(seed) % _U64 if on else None)
+
+
+def _sr_take(mod, n: int, seed=None):
+    """(seed, step) for a stochastically rounded call over n descriptors -- seed None: the module's, False: none -- or None for a plain
+    call; advances the module's sr_step by n."""
+    seed = getattr(mod, "_sr_seed", None) if seed is None else seed
+    if seed is None or seed is False:
+        return None
+    step = getattr(mod, "_sr_step", 0)
+    object.__setattr__(mod, "_sr_step", (step + int(n)) % _U64)
+    return (int(seed) % _U64, step)
+
+
+def _save_sr(mod, destination, prefix) -> None:
+    if getattr(mod, "_sr_seed", None) is not None:
+        signed = lambda v: v - _U64 if v >= 1 << 63 else v  # noqa: E731 -- (int64 tensors: the 64 bits as they are)
+        destination[prefix + "sr_seed"] = torch.tensor(signed(mod._sr_seed), dtype=torch.int64)
+        destination[prefix + "sr_step"] = torch.tensor(signed(getattr(mod, "_sr_step", 0)), dtype=torch.int64)
+
+
+def _load_sr(mod, state_dict, prefix, strict, missing_keys) -> None:
+    """A checkpoint that carries sr_seed / sr_step switches stochastic rounding on with them: the resumed run continues the stream."""
+    skey, tkey = prefix + "sr_seed", prefix + "sr_step"
+    if skey in state_dict and tkey in state_dict:
+        object.__setattr__(mod, "_sr_seed", int(state_dict[skey]) % _U64)
+        object.__setattr__(mod, "_sr_step", int(state_dict[tkey]) % _U64)
+    elif getattr(mod, "_sr_seed", None) is not None and strict:
+        missing_keys += [k for k in (skey, tkey) if k not in state_dict]
 
 
 def _update_master(master, ids, rows) -> None:
@@ -759,13 +837,18 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
 
     apply_emb = forward
 
-    def enable_fused_sgd(self, lr: float, multi_table: bool = False, order: str = "position", master_weights: bool = False):
-        """master_weights=True: every bag keeps its fp32 master (bags[k].master_weight) and the step is the fused master-weight step,
+    def enable_fused_sgd(self, lr: float, multi_table: bool = False, order: str = "position", master_weights: bool = False,
+                         stochastic_rounding: bool = False, sr_seed: int = 0):
+        """stochastic_rounding=True: as PoolingEmbeddingBag.enable_fused_sgd, for all tables (all fp16 / bf16), table after table: table k
+        of a step uses step number sr_step + k, and the MODEL's sr_step advances by the number of tables stepped; saved as `sr_seed` /
+        `sr_step` under the model's prefix.  ValueError with master_weights=True and with multi_table=True.
+        master_weights=True: every bag keeps its fp32 master (bags[k].master_weight) and the step is the fused master-weight step,
         table after table; there is no multi-table master step, so multi_table=True with it raises ValueError.
         As PoolingEmbeddingBag.enable_fused_sgd, for every table of the model: the backward of forward()'s result -- the list,
         or the one [B, sum(m)] tensor of concat=True -- steps all of them.  multi_table=True: by the multi-table step (one
         pre-pass and one launch per group of up to 16 tables instead of per table; the same bytes).  order: as there.
         Returns self."""
+        _set_sr(self, stochastic_rounding, sr_seed, [b._table_dtype for b in self.bags], master_weights, multi_table)
         self._set_masters(master_weights, multi_table)
         object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_multi", bool(multi_table))
@@ -794,10 +877,12 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         return [b.master_weight for b in self.bags]
 
     def enable_fused_adagrad(self, lr: float, eps: float = 1e-10, rowwise: bool = False, initial_accumulator_value: float = 0.0,
-                             multi_table: bool = False, order: str = "position", master_weights: bool = False):
+                             multi_table: bool = False, order: str = "position", master_weights: bool = False, stochastic_rounding: bool = False,
+                             sr_seed: int = 0):
         """As PoolingEmbeddingBag.enable_fused_adagrad, for every table of the model: each bag holds its own state
-        (bags[k].adagrad_sum, saved as `bags.<k>.adagrad_sum`), one call steps them all.  multi_table, order and master_weights: as
-        enable_fused_sgd.  Returns self."""
+        (bags[k].adagrad_sum, saved as `bags.<k>.adagrad_sum`), one call steps them all.  multi_table, order, master_weights,
+        stochastic_rounding and sr_seed: as enable_fused_sgd.  Returns self."""
+        _set_sr(self, stochastic_rounding and lr is not None, sr_seed, [b._table_dtype for b in self.bags], master_weights, multi_table)
         self._set_masters(master_weights, multi_table)
         object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_multi", bool(multi_table))
@@ -814,6 +899,34 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
     def adagrad_sum(self):
         """The bags' Adagrad states, in table order (None where a bag has none)."""
         return [b.adagrad_sum for b in self.bags]
+
+    @property
+    def sr_step(self) -> int:
+        """The step number the first table of the model's next stochastically rounded step uses."""
+        return getattr(self, "_sr_step", 0)
+
+    @property
+    def sr_seed(self):
+        """The seed of the model's stochastically rounded steps, or None while stochastic rounding is off."""
+        return getattr(self, "_sr_seed", None)
+
+    def _sr_call(self, n: int, multi: bool, sr_seed):
+        """The sr= of one context call over n tables (None: a plain call), with what it does not go with refused."""
+        if sr_seed is False or (sr_seed is None and getattr(self, "_sr_seed", None) is None):
+            return None
+        _check_sr([b._table_dtype for b in self.bags], self._masters_on(), multi)
+        return _sr_take(self, n, sr_seed)
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        _save_sr(self, destination, prefix)   # (only with stochastic rounding on)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        for key in (prefix + "sr_seed", prefix + "sr_step"):      # (the model's own keys, not a parameter's or a buffer's)
+            if key in unexpected_keys:
+                unexpected_keys.remove(key)
+        _load_sr(self, state_dict, prefix, strict, missing_keys)
 
     def _table_grads(self, grad_output, col):
         """Per table the gradient of its pooled rows as the kernels read it ([B, m_k] float32, inner stride 1), None where
@@ -873,11 +986,15 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
                   padding_idx=[self._pads[k] for k in live])
         return ctx, args, kw, live
 
-    def _step(self, idx, off, grad_output, lr, ws, col=0, multi=None, order=None):
+    def _step(self, idx, off, grad_output, lr, ws, col=0, multi=None, order=None, sr_seed=None):
         multi = getattr(self, "_fused_multi", False) if multi is None else bool(multi)
         call = self._live_grads(idx, off, grad_output, ws, col, multi, order)
         if call is not None:
             ctx, args, kw, live = call
+            sr = self._sr_call(len(live), multi, sr_seed)
+            if sr is not None:
+                ctx.sgd_step(*args, lr, sr=sr, **kw)
+                return
             if self._masters_on():
                 self._no_multi_master(multi)
                 ctx.master_step(*args, [self.bags[k].master_weight for k in live], lr, optimizer="sgd", **kw)
@@ -889,7 +1006,7 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         if multi:
             raise ValueError("multi_table=True does not go with master weights: there is no multi-table master step")
 
-    def _adagrad(self, idx, off, grad_output, lr, eps, ws, col=0, multi=None, order=None):
+    def _adagrad(self, idx, off, grad_output, lr, eps, ws, col=0, multi=None, order=None, sr_seed=None):
         multi = getattr(self, "_fused_multi", False) if multi is None else bool(multi)
         call = self._live_grads(idx, off, grad_output, ws, col, multi, order)
         if call is None:
@@ -900,6 +1017,10 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             sel = [j for j, s in enumerate(states) if (s.dim() == 1) == rowwise]
             if sel:
                 pick = lambda v: [v[j] for j in sel]  # noqa: E731
+                sr = self._sr_call(len(sel), multi, sr_seed)
+                if sr is not None:
+                    ctx.adagrad_step(*[pick(a) for a in args], pick(states), lr, eps=eps, rowwise=rowwise, sr=sr, **{k: pick(v) for k, v in kw.items()})
+                    continue
                 if self._masters_on():
                     self._no_multi_master(multi)
                     ctx.master_step(*[pick(a) for a in args], [self.bags[live[j]].master_weight for j in sel], lr,
@@ -921,20 +1042,23 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             grad_output = torch.as_tensor(grad_output).to(dev)
         return idx, off, None if lS_w is None else ws, grad_output
 
-    def sgd_step_(self, lS_o, lS_i, grad_output, lr: float, lS_w=None, multi_table: bool = False, order: str = "position"):
+    def sgd_step_(self, lS_o, lS_i, grad_output, lr: float, lS_w=None, multi_table: bool = False, order: str = "position",
+                  stochastic_rounding: bool = False, sr_seed: int = 0):
         """PoolingEmbeddingBag.sgd_step_ for all tables in one call.  grad_output: a list of [B, m_k] gradients, or the ONE
         [B, sum(m)] gradient of a concat=True forward, which is read in place (each table's columns through the row stride).
-        multi_table and order: as enable_fused_sgd."""
+        multi_table and order: as enable_fused_sgd.  stochastic_rounding / sr_seed: this one step rounds stochastically, at the model's
+        sr_step, which it advances by the number of tables stepped."""
         idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
-        self._step(idx, off, g, float(lr), ws, multi=multi_table, order=order)
+        self._step(idx, off, g, float(lr), ws, multi=multi_table, order=order, sr_seed=int(sr_seed) if stochastic_rounding else False)
         return self
 
     def adagrad_step_(self, lS_o, lS_i, grad_output, lr: float, eps: float = 1e-10, lS_w=None, multi_table: bool = False,
-                      order: str = "position"):
+                      order: str = "position", stochastic_rounding: bool = False, sr_seed: int = 0):
         """PoolingEmbeddingBag.adagrad_step_ for all tables in one call, on the bags' states; grad_output as sgd_step_ takes it: the
-        ONE [B, sum(m)] gradient of a concat=True forward is read in place.  multi_table and order: as enable_fused_sgd."""
+        ONE [B, sum(m)] gradient of a concat=True forward is read in place.  multi_table and order: as enable_fused_sgd;
+        stochastic_rounding / sr_seed: as sgd_step_."""
         idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
-        self._adagrad(idx, off, g, float(lr), float(eps), ws, multi=multi_table, order=order)
+        self._adagrad(idx, off, g, float(lr), float(eps), ws, multi=multi_table, order=order, sr_seed=int(sr_seed) if stochastic_rounding else False)
         return self
 
     def update_rows_(self, table: int, ids, rows):
