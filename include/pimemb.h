@@ -626,8 +626,9 @@ int emb_comm_rank(const emb_comm *c, int32_t *rank, int32_t *world);
  * one POSIX shared-memory segment (`/pimemb-<tag>`, unlinked again once every rank has mapped it) and HIP IPC handles:
  * each rank allocates an ARENA of arena_bytes -- one device allocation (fine-grained where the runtime can export it) that
  * every peer maps -- and everything a peer may touch (index / offset arrays, output rows) must be carved from it with
- * emb_peer_alloc (a bump allocator: nothing is freed before emb_peer_destroy).  The segment also carries small mailboxes
- * [dst][src][slot] for the per-batch handshake: written by tiny kernels in stream order, read by the host with plain loads.
+ * emb_peer_alloc (a bump allocator: nothing is freed before emb_peer_destroy).  Each rank also keeps small mailboxes
+ * [src][slot] for the per-batch handshake in device memory its peers map: written by tiny kernels of the sender in stream
+ * order, read by the receiver's host with small device-to-host copies (the segment itself is never mapped into a GPU).
  * Exercised with 2-4 processes on ONE GPU; never over xGMI (link rates and cross-link visibility are unmeasured). */
 typedef struct emb_peer emb_peer;
 int emb_peer_create(emb_engine *e, const char *job_tag, int32_t rank, int32_t world, uint64_t arena_bytes, emb_peer **out);

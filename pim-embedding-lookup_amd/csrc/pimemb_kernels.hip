@@ -977,7 +977,7 @@ hipError_t launch_store_word(volatile unsigned long long *dst, unsigned long lon
     return hipGetLastError();
 }
 
-// ---- collective-free exchange: the per-batch handshake through the job's shared segment (pimemb_peer.h) -----------------
+// ---- collective-free exchange: the per-batch handshake through the ranks' mailboxes (pimemb_peer.h) ---------------------
 // One workgroup.  For every remote destination p: the message = p's counts out of `meta` (+ where p's piece and p's partial
 // rows sit), then this rank's host-written constants for p; all of it stored into mailbox [p][me][slot], a system-scope
 // fence, then the `posted` word.  Runs on the caller's stream behind the router and behind whatever produced the caller's

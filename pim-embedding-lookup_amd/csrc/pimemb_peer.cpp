@@ -6,11 +6,13 @@
 // into the requester's HBM -- the reference's result pull lands directly in the caller's final_results too
 // (upmem/include/emb_host.h:312-321).  No collectives library is involved, and none is needed to set the group up:
 //
-//   * one POSIX shared-memory segment per job (`/pimemb-<tag>`) holds, per rank, the IPC handle of its ARENA -- one device
-//     allocation everything a peer may touch is carved from -- and a grid of small MAILBOXES [dst][src][slot] for the
-//     per-batch handshake (what a rank asks a peer for, where its buffers are, "your rows are in place");
-//   * every rank maps the segment into its GPU's address space (hipHostRegister), so mailbox words are written by tiny kernels
-//     in stream order behind the data they announce, and read by the host with plain loads (no event, no copy engine).
+//   * one POSIX shared-memory segment per job (`/pimemb-<tag>`) holds, per rank, the IPC handles of its ARENA -- the device
+//     memory everything a peer may touch is carved from -- and of its MAILBOXES;
+//   * the mailboxes [dst][src][slot] carry the per-batch handshake (what a rank asks a peer for, where its buffers are, "your
+//     rows are in place").  Rank dst keeps the boxes addressed to it in device memory of its own, mapped into its peers like
+//     the arena: mailbox words are written by tiny kernels of src in stream order behind the data they announce, and read by
+//     dst's host with small device-to-host copies on a stream of the group's own (peer_box_read).  The segment itself is
+//     host memory only: no GPU ever addresses it (a runtime need not be able to map memory a process already has).
 //
 // STATUS: exercised with 2-4 processes sharing the development box's one GPU (peer mappings of the same device); never
 // over xGMI.  Visibility of peer stores across real links rests on the arena being fine-grained memory and on kernel
@@ -46,7 +48,7 @@ double now_s() {
     return duration<double>(steady_clock::now().time_since_epoch()).count();
 }
 
-constexpr uint64_t kMagic = 0x70696d656d623034ull;     // "pimemb04"
+constexpr uint64_t kMagic = 0x70696d656d623035ull;     // "pimemb05"
 
 // PIMEMB_PEER_TRACE=1: a line per set-up step on stderr (which call is a group stuck in?)
 void trace(int rank, const char *what) {
@@ -71,11 +73,13 @@ struct RankInfo {
     int32_t device, pid;
     uint32_t n_chunks, pad0;
     hipIpcMemHandle_t handle[kMaxChunks];
+    hipIpcMemHandle_t box_handle;      // this rank's mailboxes [src][slot]
 };
 
 struct ShmHeader {
     std::atomic<uint64_t> magic;
-    uint32_t world, msg_bytes, slots, pad;
+    uint32_t world, msg_bytes, slots;
+    std::atomic<uint32_t> failed;      // a rank of the group gave its set-up up: nobody waits for it (or for the others) any longer
 };
 
 size_t header_bytes(int world) { return 4096 + (size_t)world * sizeof(RankInfo); }
@@ -100,6 +104,7 @@ struct MapWatchdog {
     std::mutex mu;
     std::condition_variable cv;
     bool done = false;
+    static constexpr unsigned kMailboxes = ~0u;    // enter(p, kMailboxes): the call maps rank p's mailboxes, not a chunk of its arena
     int rank = 0, peer = -1;
     unsigned chunk = 0;
     double call_t0 = 0.0;       // 0: no mapping call is out
@@ -112,9 +117,11 @@ struct MapWatchdog {
             while (!done) {
                 cv.wait_for(lk, std::chrono::milliseconds(50));
                 if (!done && call_t0 > 0.0 && now_s() - call_t0 > limit_s) {
-                    fprintf(stderr, "emb_peer_create: rank %d: hipIpcOpenMemHandle of rank %d's arena (chunk %u) has not returned within %.0f s -- "
+                    char what[32] = "mailboxes";
+                    if (chunk != kMailboxes) snprintf(what, sizeof what, "arena (chunk %u)", chunk);
+                    fprintf(stderr, "emb_peer_create: rank %d: hipIpcOpenMemHandle of rank %d's %s has not returned within %.0f s -- "
                             "the runtime cannot map that allocation (seen for IPC mappings above 2 GiB on ROCm 7.0 / 7.2); this process "
-                            "is ended so the job fails instead of hanging (PIMEMB_SHARD_TIMEOUT_S sets the limit)\n", rank, peer, chunk, limit_s);
+                            "is ended so the job fails instead of hanging (PIMEMB_SHARD_TIMEOUT_S sets the limit)\n", rank, peer, what, limit_s);
                     fflush(stderr);
                     if (!unlink_name.empty()) (void)shm_unlink(unlink_name.c_str());
                     // PIMEMB_PEER_WATCHDOG=report: a caller with a deadline of its own (bench.py's peer-store leg) ends the
@@ -154,9 +161,13 @@ struct emb_peer {
     std::string shm_name;
     int fd = -1;
     char *shm = nullptr;           // host mapping of the segment
-    char *shm_dev = nullptr;       // the same bytes as the GPU addresses them
     size_t shm_bytes = 0;
-    bool registered = false, creator = false, unlinked = false;
+    bool creator = false, unlinked = false;
+    char *boxes = nullptr;         // the mailboxes addressed to this rank, [src][slot]: device memory
+    std::vector<char *> box_base;  // box_base[p]: rank p's mailboxes as THIS process addresses them
+    hipStream_t box_stream = nullptr;      // peer_box_read's copies
+    char *box_stage = nullptr;     // ... and where they land (pinned, one mailbox)
+    std::mutex box_mu;
     std::vector<char *> chunks;    // this rank's arena
     uint64_t arena_bytes = 0, arena_used = 0;
     bool fine_grained = false;
@@ -171,13 +182,18 @@ namespace pimemb {
 ShmHeader *peer_header(emb_peer *p) { return reinterpret_cast<ShmHeader *>(p->shm); }
 RankInfo *peer_rank_info(emb_peer *p, int r) { return reinterpret_cast<RankInfo *>(p->shm + 4096) + r; }
 
-PeerMsg *peer_box(emb_peer *p, int dst, int src, uint32_t slot) {
-    const size_t at = header_bytes(p->world) + (((size_t)dst * p->world + src) * kPeerSlots + slot) * kPeerMsgBytes;
-    return reinterpret_cast<PeerMsg *>(p->shm + at);
-}
 PeerMsg *peer_box_dev(emb_peer *p, int dst, int src, uint32_t slot) {
-    const size_t at = header_bytes(p->world) + (((size_t)dst * p->world + src) * kPeerSlots + slot) * kPeerMsgBytes;
-    return reinterpret_cast<PeerMsg *>(p->shm_dev + at);
+    return reinterpret_cast<PeerMsg *>(p->box_base[(size_t)dst] + ((size_t)src * kPeerSlots + slot) * kPeerMsgBytes);
+}
+int peer_box_read(emb_peer *p, int src, uint32_t slot, size_t at, void *dst, size_t bytes) {
+    if (src < 0 || src >= p->world || slot >= kPeerSlots || at + bytes > kPeerMsgBytes) return fail(EMB_ERR_INVALID, "peer_box_read: outside the mailbox");
+    DeviceGuard g(p->device);
+    std::lock_guard<std::mutex> lk(p->box_mu);
+    hipError_t err = hipMemcpyAsync(p->box_stage, p->boxes + ((size_t)src * kPeerSlots + slot) * kPeerMsgBytes + at, bytes, hipMemcpyDeviceToHost, p->box_stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(p->box_stream);
+    if (err != hipSuccess) return fail(EMB_ERR_DEVICE, "emb_peer: reading the mailbox of rank %d: %s", src, hipGetErrorString(err));
+    memcpy(dst, p->box_stage, bytes);
+    return EMB_OK;
 }
 int peer_rank(const emb_peer *p) { return p->rank; }
 int peer_world(const emb_peer *p) { return p->world; }
@@ -225,27 +241,35 @@ int emb_peer_create(emb_engine *e, const char *job_tag, int32_t rank, int32_t wo
     }
     p->device = dev;
     DeviceGuard g(dev);
+    hipError_t err = hipSuccess;
+    bool joined = false;       // the mapped segment is this group's (its header has been checked)
+    // A rank that gives up says so in the segment first: a creator that fails takes the NAME with it (emb_peer_destroy), and
+    // whoever holds the segment already would otherwise wait the whole timeout for a rank that is gone.
     auto bail = [&](int code) {
+        if (joined) pimemb::peer_header(p)->failed.store(1, std::memory_order_release);
         (void)emb_peer_destroy(p);
         return code;
     };
-    // ---- the shared segment: whoever comes first creates and sizes it (ftruncate zero-fills), everyone maps it
+    // ---- the shared segment: whoever comes first creates and sizes it (ftruncate zero-fills), everyone maps it.  The name
+    // may go again between a rank's two attempts (its creator failed and unlinked it): that rank then creates it afresh.
     p->shm_name = std::string("/pimemb-") + job_tag;
-    p->shm_bytes = header_bytes(world) + (size_t)world * world * pimemb::kPeerSlots * pimemb::kPeerMsgBytes;
-    p->shm_bytes = (p->shm_bytes + 4095) / 4096 * 4096;
-    p->fd = shm_open(p->shm_name.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600);
-    if (p->fd >= 0) {
-        p->creator = true;
-        if (ftruncate(p->fd, (off_t)p->shm_bytes) != 0) return bail(fail(EMB_ERR_NOMEM, "emb_peer_create: ftruncate(%s, %zu) failed", p->shm_name.c_str(), p->shm_bytes));
-    } else {
-        const double t0 = now_s();
+    p->shm_bytes = (header_bytes(world) + 4095) / 4096 * 4096;
+    for (const double t0 = now_s();;) {
+        p->fd = shm_open(p->shm_name.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600);
+        if (p->fd >= 0) {
+            p->creator = true;
+            if (ftruncate(p->fd, (off_t)p->shm_bytes) != 0) return bail(fail(EMB_ERR_NOMEM, "emb_peer_create: ftruncate(%s, %zu) failed", p->shm_name.c_str(), p->shm_bytes));
+            break;
+        }
+        p->fd = shm_open(p->shm_name.c_str(), O_RDWR, 0600);
         struct stat st {};
-        for (;;) {       // the creator may not have sized it yet
-            if (p->fd < 0) p->fd = shm_open(p->shm_name.c_str(), O_RDWR, 0600);
-            if (p->fd >= 0 && fstat(p->fd, &st) == 0 && (size_t)st.st_size >= p->shm_bytes) break;
-            if (now_s() - t0 > p->timeout_s) return bail(fail(EMB_ERR_DEVICE, "emb_peer_create: %s did not appear within %.0f s", p->shm_name.c_str(), p->timeout_s));
+        while (p->fd >= 0 && !(fstat(p->fd, &st) == 0 && (size_t)st.st_size >= p->shm_bytes)) {       // the creator may not have sized it yet
+            if (now_s() - t0 > p->timeout_s) return bail(fail(EMB_ERR_DEVICE, "emb_peer_create: %s was not sized within %.0f s", p->shm_name.c_str(), p->timeout_s));
             std::this_thread::sleep_for(std::chrono::milliseconds(1));
         }
+        if (p->fd >= 0) break;
+        if (now_s() - t0 > p->timeout_s) return bail(fail(EMB_ERR_DEVICE, "emb_peer_create: %s did not appear within %.0f s", p->shm_name.c_str(), p->timeout_s));
+        std::this_thread::sleep_for(std::chrono::milliseconds(1));
     }
     void *m = mmap(nullptr, p->shm_bytes, PROT_READ | PROT_WRITE, MAP_SHARED, p->fd, 0);
     if (m == MAP_FAILED) return bail(fail(EMB_ERR_NOMEM, "emb_peer_create: mmap of %s failed", p->shm_name.c_str()));
@@ -265,15 +289,8 @@ int emb_peer_create(emb_engine *e, const char *job_tag, int32_t rank, int32_t wo
         if ((int)h->world != world || h->msg_bytes != pimemb::kPeerMsgBytes)
             return bail(fail(EMB_ERR_INVALID, "emb_peer_create: %s belongs to a group of %u ranks (this one: %d) -- use a fresh job tag", p->shm_name.c_str(), h->world, world));
     }
-    trace(rank, "segment mapped; hipHostRegister");
-    // the GPU writes mailbox words: map the segment into the device's address space
-    hipError_t err = hipHostRegister(p->shm, p->shm_bytes, hipHostRegisterMapped);
-    if (err != hipSuccess) return bail(fail(EMB_ERR_DEVICE, "emb_peer_create: hipHostRegister of the shared segment: %s", hipGetErrorString(err)));
-    p->registered = true;
-    void *dptr = nullptr;
-    err = hipHostGetDevicePointer(&dptr, p->shm, 0);
-    if (err != hipSuccess) return bail(fail(EMB_ERR_DEVICE, "emb_peer_create: hipHostGetDevicePointer: %s", hipGetErrorString(err)));
-    p->shm_dev = static_cast<char *>(dptr);
+    joined = true;
+    trace(rank, "segment mapped");
 
     // ---- the arena: everything a peer may read or write lives here, in chunks of at most 1 GiB (see RankInfo).  Fine-grained
     // by default (stores of one agent are visible to another without waiting for a cache write-back);
@@ -315,6 +332,26 @@ int emb_peer_create(emb_engine *e, const char *job_tag, int32_t rank, int32_t wo
         }
     }
     p->arena_bytes = arena_bytes;
+    // ---- the mailboxes addressed to this rank: memory of the arena's kind, zeroed (no flag value is ever 0) before anyone maps it.
+    // With an ordinary (coarse-grained) arena they inherit its limit -- ranks sharing one device only: the host's copy does not
+    // read through the GPU's L2, so a word a peer stored is seen here only because the tiny kernel that stored it ends right
+    // behind the store and its end writes the cache back; nothing promises that for another GPU's stores.
+    {
+        const size_t box_bytes = (size_t)world * pimemb::kPeerSlots * pimemb::kPeerMsgBytes;
+        void *a = nullptr;
+        err = p->fine_grained ? hipExtMallocWithFlags(&a, box_bytes, hipDeviceMallocFinegrained) : hipMalloc(&a, box_bytes);
+        if (err != hipSuccess) return bail(fail(err == hipErrorOutOfMemory ? EMB_ERR_NOMEM : EMB_ERR_DEVICE, "emb_peer_create: %zu bytes of mailboxes: %s", box_bytes, hipGetErrorString(err)));
+        p->boxes = static_cast<char *>(a);
+        err = hipMemset(a, 0, box_bytes);
+        if (err == hipSuccess) err = hipDeviceSynchronize();
+        if (err == hipSuccess) err = hipIpcGetMemHandle(&me->box_handle, a);
+        if (err == hipSuccess) err = hipStreamCreateWithFlags(&p->box_stream, hipStreamNonBlocking);
+        if (err == hipSuccess) {
+            err = hipHostMalloc(&a, pimemb::kPeerMsgBytes, hipHostMallocDefault);
+            if (err == hipSuccess) p->box_stage = static_cast<char *>(a);
+        }
+        if (err != hipSuccess) return bail(fail(EMB_ERR_DEVICE, "emb_peer_create: setting up the mailboxes: %s", hipGetErrorString(err)));
+    }
     trace(rank, p->fine_grained ? "arena allocated (fine-grained), handles taken" : "arena allocated (ordinary), handles taken");
     me->arena_bytes = arena_bytes;
     me->n_chunks = n_chunks;
@@ -326,6 +363,8 @@ int emb_peer_create(emb_engine *e, const char *job_tag, int32_t rank, int32_t wo
     p->base.assign((size_t)world, {});
     p->peer_bytes.assign((size_t)world, 0);
     p->base[(size_t)rank] = p->chunks;
+    p->box_base.assign((size_t)world, nullptr);
+    p->box_base[(size_t)rank] = p->boxes;
     p->peer_bytes[(size_t)rank] = arena_bytes;
     const double t0 = now_s();
     std::unique_ptr<MapWatchdog> dog(world > 1 ? new MapWatchdog(rank, p->timeout_s, p->shm_name) : nullptr);
@@ -333,6 +372,7 @@ int emb_peer_create(emb_engine *e, const char *job_tag, int32_t rank, int32_t wo
         if (r == rank) continue;
         RankInfo *ri = pimemb::peer_rank_info(p, r);
         while (ri->ready.load(std::memory_order_acquire) < 1) {
+            if (h->failed.load(std::memory_order_acquire)) return bail(fail(EMB_ERR_DEVICE, "emb_peer_create: another rank of %s gave its set-up up (its own error says why)", p->shm_name.c_str()));
             if (now_s() - t0 > p->timeout_s) return bail(fail(EMB_ERR_DEVICE, "emb_peer_create: rank %d did not join %s within %.0f s", r, p->shm_name.c_str(), p->timeout_s));
             std::this_thread::sleep_for(std::chrono::milliseconds(1));
         }
@@ -344,6 +384,12 @@ int emb_peer_create(emb_engine *e, const char *job_tag, int32_t rank, int32_t wo
             if (err != hipSuccess) return bail(fail(EMB_ERR_DEVICE, "emb_peer_create: hipIpcOpenMemHandle of rank %d's arena (chunk %u): %s", r, c, hipGetErrorString(err)));
             p->base[(size_t)r].push_back(static_cast<char *>(mapped));
         }
+        void *mapped = nullptr;
+        dog->enter(r, MapWatchdog::kMailboxes);
+        err = hipIpcOpenMemHandle(&mapped, ri->box_handle, hipIpcMemLazyEnablePeerAccess);
+        dog->leave();
+        if (err != hipSuccess) return bail(fail(EMB_ERR_DEVICE, "emb_peer_create: hipIpcOpenMemHandle of rank %d's mailboxes: %s", r, hipGetErrorString(err)));
+        p->box_base[(size_t)r] = static_cast<char *>(mapped);
         p->peer_bytes[(size_t)r] = ri->arena_bytes;
     }
     trace(rank, "peers mapped; barrier");
@@ -395,6 +441,7 @@ int emb_peer_barrier(emb_peer *p) {
     const double t0 = now_s();
     for (int r = 0; r < p->world; r++)
         while (pimemb::peer_rank_info(p, r)->barrier.load(std::memory_order_acquire) < gen) {
+            if (pimemb::peer_header(p)->failed.load(std::memory_order_acquire)) return fail(EMB_ERR_DEVICE, "emb_peer_barrier: a rank of the group gave its set-up up");
             if (now_s() - t0 > p->timeout_s) return fail(EMB_ERR_DEVICE, "emb_peer_barrier: rank %d did not arrive within %.0f s", r, p->timeout_s);
             std::this_thread::yield();
         }
@@ -408,8 +455,12 @@ int emb_peer_destroy(emb_peer *p) {
     for (int r = 0; r < (int)p->base.size(); r++)
         if (r != p->rank)
             for (char *c : p->base[(size_t)r]) (void)hipIpcCloseMemHandle(c);
+    for (int r = 0; r < (int)p->box_base.size(); r++)
+        if (r != p->rank && p->box_base[(size_t)r]) (void)hipIpcCloseMemHandle(p->box_base[(size_t)r]);
     for (char *c : p->chunks) (void)hipFree(c);
-    if (p->registered) (void)hipHostUnregister(p->shm);
+    if (p->boxes) (void)hipFree(p->boxes);
+    if (p->box_stream) (void)hipStreamDestroy(p->box_stream);
+    if (p->box_stage) (void)hipHostFree(p->box_stage);
     if (p->shm) (void)munmap(p->shm, p->shm_bytes);
     if (p->fd >= 0) (void)close(p->fd);
     if (p->creator && !p->unlinked && !p->shm_name.empty()) (void)shm_unlink(p->shm_name.c_str());   // a set-up that failed half-way leaves no segment behind

@@ -9,8 +9,8 @@ constexpr uint32_t kPeerSlots = 8;          // mailbox slots per (dst, src): a b
 constexpr uint32_t kPeerMsgBytes = 32768;   // one mailbox: two flag words + the request message (up to ~680 whole tables per owner)
 constexpr uint32_t kPeerMsgWords = (kPeerMsgBytes - 64) / 4;
 
-// mailbox [dst][src][slot], in the job's shared segment: written by SRC's GPU (tiny kernels, in stream order behind the
-// data they announce), read by DST's host with plain loads
+// mailbox [dst][src][slot], in device memory of DST that its peers map: written by SRC's GPU (tiny kernels, in stream order
+// behind the data they announce), read by DST's host with peer_box_read
 struct PeerMsg {
     volatile unsigned long long posted;    // = seq + 1 once `words` describe what src asks dst for in batch seq
     volatile unsigned long long served;    // = seq + 1 once everything src OWES dst for batch seq is in dst's HBM
@@ -27,8 +27,11 @@ struct PeerPostArgs {
     uint32_t n_consts[64];
 };
 
-PeerMsg *peer_box(emb_peer *p, int dst, int src, uint32_t slot);
+// mailbox [dst][src][slot] as this rank's GPU addresses it
 PeerMsg *peer_box_dev(emb_peer *p, int dst, int src, uint32_t slot);
+// `bytes` at byte `at` of mailbox [this rank][src][slot] -> dst (host memory): one small device-to-host copy on the group's
+// own stream, waited for.  Words of one call are not ordered among themselves: read a flag first, what it announces after it.
+int peer_box_read(emb_peer *p, int src, uint32_t slot, size_t at, void *dst, size_t bytes);
 int peer_rank(const emb_peer *p);
 int peer_world(const emb_peer *p);
 // `bytes` at arena offset `off` of rank r as this process addresses them (nullptr: outside the arena / across two of its chunks)

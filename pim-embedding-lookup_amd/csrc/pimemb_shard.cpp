@@ -153,6 +153,7 @@ struct emb_shard {
     emb_peer *peer = nullptr;
     bool peer_mode = false;
     uint64_t peer_tag = 0;                           // (epoch of this object among the group's users) << 40: added to every flag value
+    std::vector<uint32_t> box_words;                 // a peer's message, copied out of its mailbox (stage_request)
     int device = 0;
     int rank = 0, N = 1;
     uint32_t T = 0, dim = 0, depth = 2, flags = 0;
@@ -277,14 +278,18 @@ inline Via via(const emb_shard *s, int p) {
 inline bool via_comm(const emb_shard *s, int p) { return via(s, p) == COMM; }
 inline uint64_t arena_off(const emb_shard *s, const void *ptr) { return pimemb::peer_offset(s->peer, ptr, 1); }
 
-// Poll a mailbox word until it carries `want` (written by a peer's GPU through the job's shared segment).
-int poll_word(emb_shard *s, volatile unsigned long long *w, unsigned long long want, const char *what, int peer, uint64_t seq) {
+// Poll a flag word (byte `at` of the mailbox `peer` writes for batch seq) until it carries `want`: written by the peer's GPU
+// into this rank's device memory, every look is a small copy (peer_box_read).
+int poll_word(emb_shard *s, size_t at, unsigned long long want, const char *what, int peer, uint64_t seq) {
     const double t0 = now_us(), limit = pimemb::peer_timeout_s(s->peer) * 1e6;
-    for (uint64_t spin = 0; *w != want; spin++)
-        if ((spin & 0xfff) == 0xfff && now_us() - t0 > limit)
+    for (uint64_t spin = 0;; spin++) {
+        unsigned long long v = 0;
+        EMB_TRY(pimemb::peer_box_read(s->peer, peer, (uint32_t)(seq % pimemb::kPeerSlots), at, &v, sizeof v));
+        if (v == want) return EMB_OK;
+        if ((spin & 0xf) == 0xf && now_us() - t0 > limit)
             return fail(EMB_ERR_DEVICE, "emb_shard: rank %d %s batch %llu within %.0f s -- it is missing, or the ranks did not make the same calls",
                         peer, what, (unsigned long long)seq, limit / 1e6);
-    return EMB_OK;
+    }
 }
 
 int exchange(emb_shard *s) {
@@ -713,10 +718,11 @@ int stage_request(emb_shard *s, Batch &b) {
         const double t0 = now_us();
         for (uint32_t p = 0; p < N; p++) {
             if (via(s, (int)p) != PEER) continue;
-            pimemb::PeerMsg *box = pimemb::peer_box(s->peer, s->rank, (int)p, (uint32_t)(b.seq % pimemb::kPeerSlots));
-            EMB_TRY(poll_word(s, &box->posted, s->peer_tag + b.seq + 1, "did not post its requests of", (int)p, b.seq));
-            std::atomic_thread_fence(std::memory_order_acquire);
-            const uint32_t *w = box->words;
+            EMB_TRY(poll_word(s, offsetof(pimemb::PeerMsg, posted), s->peer_tag + b.seq + 1, "did not post its requests of", (int)p, b.seq));
+            // the message behind the flag: as many words as the longest one takes (a shorter one leaves the rest unread below)
+            s->box_words.resize(std::min<size_t>(pimemb::kPeerMsgWords, (Kr ? 2 * (Kr + 1) + 2 : 0) + kPeerConstHead + (size_t)M * kWholeWords + 4 * (size_t)Kr));
+            EMB_TRY(pimemb::peer_box_read(s->peer, (int)p, (uint32_t)(b.seq % pimemb::kPeerSlots), offsetof(pimemb::PeerMsg, words), s->box_words.data(), s->box_words.size() * 4));
+            const uint32_t *w = s->box_words.data();
             uint32_t at = 0;
             if (Kr) {
                 memcpy(recv + (size_t)p * (Kr + 1) * 2, w, (size_t)(Kr + 1) * 8);
@@ -1165,15 +1171,26 @@ int check_served_counts(emb_shard *s, Batch &b, bool wait = true) {
     bool probing = !wait, not_ready = false;
     // one entry: poll the self-describing word until it carries this batch's tag (the kernel that stores it was enqueued a
     // call or more ago; a peer's: its "served" word has been seen, the entries are on their way), hand back the count
-    auto entry = [&](volatile unsigned long long *w, const char *what, uint32_t who) -> uint32_t {
+    // (w: a pinned word of this rank; w == nullptr: entry i in the tail of the mailbox rank `who` writes, every look a small copy)
+    auto entry = [&](volatile unsigned long long *w, uint32_t i, const char *what, uint32_t who) -> uint32_t {
         for (uint64_t spin = 0;; spin++) {
-            const unsigned long long v = *w;
+            unsigned long long v = 0;
+            if (w) {
+                v = *w;
+            } else {
+                const int rd = pimemb::peer_box_read(s->peer, (int)who, (uint32_t)(b.seq % pimemb::kPeerSlots),
+                                                     offsetof(pimemb::PeerMsg, words) + 4 * (size_t)served_tail(s) + 8 * (size_t)i, &v, sizeof v);
+                if (rd != EMB_OK) {
+                    if (rc == EMB_OK) rc = rd;
+                    return 0xffffffffu;
+                }
+            }
             if ((uint32_t)(v >> 32) == tag) return (uint32_t)v;
             if (probing) {
                 not_ready = true;
                 return 0u;
             }
-            if ((spin & 0xfff) == 0xfff && now_us() - t0 > s->timeout_s * 1e6) {
+            if ((spin & (w ? 0xfffu : 0xfu)) == (w ? 0xfffu : 0xfu) && now_us() - t0 > s->timeout_s * 1e6) {
                 if (rc == EMB_OK)
                     rc = fail(EMB_ERR_DEVICE, "emb_shard: the served counts of batch %llu (%s, rank %u) did not arrive within %.0f s", (unsigned long long)b.seq, what, who, s->timeout_s);
                 return 0xffffffffu;
@@ -1191,17 +1208,14 @@ int check_served_counts(emb_shard *s, Batch &b, bool wait = true) {
     // what shard / owner q published for this rank's i-th piece (0xffffffff: not counted -- q validated it itself)
     auto word_from = [&](uint32_t q, uint32_t i) -> uint32_t {
         const Via how = via(s, (int)q);
-        if (how == SELF) return b.self_published ? entry(b.chk_host + R + i, "this rank's own pieces", q) : 0xffffffffu;
-        if (how == PEER) {
-            pimemb::PeerMsg *box = pimemb::peer_box(s->peer, s->rank, (int)q, (uint32_t)(b.seq % pimemb::kPeerSlots));
-            return entry(reinterpret_cast<volatile unsigned long long *>(box->words + served_tail(s)) + i, "a peer's", q);
-        }
+        if (how == SELF) return b.self_published ? entry(b.chk_host + R + i, 0, "this rank's own pieces", q) : 0xffffffffu;
+        if (how == PEER) return entry(nullptr, i, "a peer's", q);
         return 0xffffffffu;
     };
     auto pass = [&]() {
         if (b.rep_counted)
             for (uint32_t r = 0; r < R; r++) {
-                const uint32_t w = entry(b.chk_host + r, "replicated tables", (uint32_t)s->rank);
+                const uint32_t w = entry(b.chk_host + r, 0, "replicated tables", (uint32_t)s->rank);
                 if (rc == EMB_OK && w != b.n_bags) bad(s->rep[r], w);
             }
         for (uint32_t q = 0; q < N && rc == EMB_OK; q++)
@@ -1242,11 +1256,7 @@ int stage_unroute(emb_shard *s, Batch &b) {
     if (s->peer_mode) {        // every peer has stored what it owes this rank for the batch (host poll: nothing to enqueue)
         const double t0 = now_us();
         for (uint32_t p = 0; p < (uint32_t)s->N && late == EMB_OK; p++)
-            if (via(s, (int)p) == PEER) {
-                pimemb::PeerMsg *box = pimemb::peer_box(s->peer, s->rank, (int)p, (uint32_t)(b.seq % pimemb::kPeerSlots));
-                late = poll_word(s, &box->served, s->peer_tag + b.seq + 1, "did not serve", (int)p, b.seq);
-            }
-        std::atomic_thread_fence(std::memory_order_acquire);
+            if (via(s, (int)p) == PEER) late = poll_word(s, offsetof(pimemb::PeerMsg, served), s->peer_tag + b.seq + 1, "did not serve", (int)p, b.seq);
         s->st.us_host_wait_served += now_us() - t0;
     }
     if (b.ret_recorded) HIP_TRY(hipStreamWaitEvent(s->cs, b.ev_ret, 0));       // the rows are back (whole tables: already in place)

@@ -411,9 +411,6 @@ hipError_t hipExtMallocWithFlags(void **p, size_t n, unsigned int) {
     if (g_no_finegrained.load()) { track("hipExtMallocWithFlags"); return hipErrorNotSupported; }
     return hipMalloc(p, n);
 }
-hipError_t hipHostRegister(void *, size_t, unsigned int) { track("hipHostRegister"); return hipSuccess; }
-hipError_t hipHostUnregister(void *) { track("hipHostUnregister"); return hipSuccess; }
-hipError_t hipHostGetDevicePointer(void **dev, void *host, unsigned int) { track("hipHostGetDevicePointer"); *dev = host; return hipSuccess; }
 hipError_t hipIpcGetMemHandle(hipIpcMemHandle_t *h, void *p) {
     track("hipIpcGetMemHandle");
     memset(h, 0, sizeof(*h));
