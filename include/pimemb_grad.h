@@ -45,11 +45,12 @@
  *   EMB_FIXED32       not a floating-point parameter.
  *   a hot set staged (emb_table_hot_count != 0)   as in the row writer: a hot set is a COPY of rows, lookups would go on serving
  *                     the old bytes: clear the set, step, set it again.
- *   EMB_POOL_MAX      needs the forward's per-element argmax, which no kernel records.
+ *   EMB_POOL_MAX      needs the forward's per-element argmax, which no kernel records.  (These calls keep refusing it; the calls of
+ *                     THE MAX-MODE BACKWARD, below, record it themselves.)
  * Prepared plans stay valid over a stepped table and read the new rows when launched behind the step.
  * emb_grad_step (below) is the same step with an optimizer that keeps state: Adagrad, and row-wise Adagrad.
  * emb_grad_weights (THE GRADIENT OF PER_SAMPLE_WEIGHTS, below) is the other gradient of a weighted sum: one value per position.
- * Out of scope: max mode; optimizers other than SGD, Adagrad and row-wise
+ * Out of scope: optimizers other than SGD, Adagrad and row-wise
  * Adagrad (no momentum, no Adam), weight decay and lr_decay, optimizer state in anything but fp32; row-wise Adagrad off the
  * lane-group shape (the element-wise kernel has no row-wide view of g, and a second reduction is not built for it:
  * EMB_ERR_UNSUPPORTED); a multi-table emb_grad_sparse (it stays single; emb_grad_sgd_multi / emb_grad_step_multi below fuse the
@@ -480,6 +481,70 @@ int emb_grad_sgd_sr(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, e
                     void *stream);
 int emb_grad_step_sr(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype,
                      const emb_opt_spec *opt, const emb_sr_spec *sr, void *stream);
+
+/* THE MAX-MODE BACKWARD: the backward of nn.EmbeddingBag(mode="max") (tests/grad_max_ref.py restates it as a loop; the kernels are compared
+ * with that, bit for bit).  Batch, bags, good / bad / padding / no-bag positions, dec, G with its grad_ld, U, the bad-position count and the
+ * two orders of additions are the ones defined at the top.  What is new:
+ *   Winner.  For a bag b and an element d, walk the GOOD positions of b in position order.  The first one becomes the current winner with
+ *     the value x = dec(W[ids[p]][d]); a later good position q replaces it only if dec(W[ids[q]][d]) > x, ONE strict fp32 compare
+ *     (csrc/pimemb_grad_max.h: the one-element rule, compiled by the kernels and by a host check alike).  That is the forward's rule --
+ *     it "starts at the first non-padding row and keeps the first of equal values" -- so ties go to the first position: between two rows,
+ *     between one row named twice in a bag, and between -0 and +0.  win[b][d] is that position, a uint32 index into the batch; it is
+ *     0xffffffff for a bag with no good position (empty, padding only, bad ids only).  NaN ordering is out of scope, as in the forward: a
+ *     compare with a NaN is false and whatever holds the place keeps it.  Whatever the values hold, win[b][d] is a position of bag b or the
+ *     sentinel, and no access leaves the batch, the bags or the table.
+ *   Contribution.  c_p[d] = G[bag(p)][d] if win[bag(p)][d] == p, else +0.0f.  No weights, no division.  The zeros ARE added: g[r] is the
+ *     chain of the context's order (position or segmented) over ALL good positions of r, exactly as for a sum.  A chain that starts from
+ *     +0 is never -0, so the added zeros change no bits, and the definition stays one sentence.
+ *   U is every row with at least one good position, including rows that win nowhere (their g is all +0): the rows of the dense weight.grad
+ *     torch leaves in max mode (torch refuses sparse=True there: there is no coalesce() form to match).  Such a row is still stepped.  SGD
+ *     leaves its bytes as they are: x - (lr * +0) is x, and enc(dec(W)) is W.  Adagrad follows its definition with g = 0: S' = S + 0, and
+ *     the quotient is 0 / (sqrt(S') + eps) -- with S' = 0 and eps = 0 that is 0 / 0, a NaN, the case the existing step already has for a
+ *     row whose G is all zero; eps > 0 or a positive state avoids it, here as there.
+ * The winners buffer.  winners[k] is a caller-owned DEVICE uint32[n_bags][dim], no padding (emb_grad_max_winner_words), 4-byte aligned,
+ * owned as the states are.  Every call below COMPUTES the winners itself and leaves them there: scratch going in, a documented result coming
+ * out -- torch's max_indices, as positions.  The context's scratch and emb_grad_scratch_bytes(_ex) are what they were.
+ * Order within a call: the winners of ALL descriptors are enqueued before the first step, so a table named twice is judged at the bytes the
+ * forward read, not at its half-stepped self.  emb_grad_max_winners reads no gradient (grad may be NULL) and counts no bad position; the
+ * other three count them once, in their pre-pass.
+ * Descriptors: pool.mode must be EMB_POOL_MAX and per_sample_weights NULL (else EMB_ERR_INVALID); flags 0 or EMB_POOL_PADDING.  Tables:
+ * EMB_F32, EMB_F16, EMB_BF16 -- for emb_grad_max_sparse too: here the result depends on the table's values.  fp8, MXFP4 and fixed-point
+ * tables, a staged hot set (the two steps only), the context's limits, a NULL or misaligned state and EMB_OPT_ROWWISE_ADAGRAD off the
+ * lane-group shape refuse as emb_grad_sgd / emb_grad_step do; a NULL or not 4-byte aligned winners buffer where n_bags > 0 is
+ * EMB_ERR_INVALID.  Everything is checked before anything is enqueued: a refused call leaves tables, states and winners as they were.  A
+ * pure enqueue: no allocation, no copy, no host wait; it can be captured in a graph.  The calls follow the order of their context.
+ * How it runs.  ONE launch per descriptor finds the winners: one lane group per BAG, the forward's geometry (bag(p) needs no search); lane l
+ * owns the 16-byte pieces l and l + 64 of win[b] (the second beyond dim 256 only, walked on its own), holds four current maxima and four
+ * winner positions per piece in registers, and walks the bag with the row gathers of eight positions in flight before the first compare,
+ * the ids of the next eight loaded meanwhile; padding and out-of-table ids are skipped by predicate (their slot loads nothing); one
+ * 16-byte store ends it.  No shuffles and no LDS: lanes never need each other's data, and no row is used twice inside a bag.  Then the
+ * pre-pass as it is (classify with the plain-sum coefficient, sort, scans) and the hot kernels' twins: the run walk loads the G piece AND
+ * the winners piece of every occurrence, 32 bytes a lane, eight occurrences in flight, and adds win == p ? g : +0 in order; the tails are
+ * the existing ones (step_piece, the row-wise pair tree).  On a segmented context the partials launch has the same select and the fold
+ * of the partials is the existing one.  Lane-group shape: the existing one plus the winners buffer 16-byte aligned (dim % 4 == 0, dim <=
+ * 512, grad 16-byte aligned, grad_ld % 4 == 0); anything else runs one thread per (bag, element) and per (row, element), the same bits.
+ * The kernels (grad_max_*) have a code object of their own, libpimemb_grad_max.so, built from the same source and found next to
+ * libpimemb_grad.so, which links against it; the other libraries' code objects hold the machine code they held.
+ * Speed, measured on MI355X (tools/max_grad_probe.py, profiles/grad_max/README.md; medians of five alternating rounds, device pointers; dim
+ * 128, 2048 bags x 32, 4 M rows).  Uniform ids: one emb_grad_max_sgd takes 99.9 us on fp32 and 102.5 us on bf16 tables, 1.39x / 1.43x SLOWER
+ * than emb_grad_sgd in sum mode on the same batch (72.1 / 71.4 us) -- the winners launch (8.9 / 11.1 us) and the doubled bytes of the walk --
+ * and 15x faster than torch's max-mode backward plus its dense SGD step (1 529 us; none exists for bfloat16).  Zipf ids, S = 64 context:
+ * 152 / 153 us, 1.15x SLOWER than the sum step (133 us), 10x faster than torch.  The Kaggle shape (dim 16, 39 292 one-index bags): 56.5 us,
+ * 1.12x SLOWER than the sum step (50.3 us), 8.5x faster than torch (482 us).  The winners launch against the max-mode forward lookup of the
+ * same batch: 2.0 - 2.4x faster at dim 128 (18.1 / 26.5 us), 2.2x SLOWER on the Kaggle shape (8.6 against 3.8 us).  The element-wise
+ * kernels and the Adagrad steps are not measured.
+ * Out of scope: _multi, master-weight and stochastically rounded forms of the max step; fp8 / MXFP4 tables; the ranged / sharded paths; NaN
+ * ordering. */
+uint64_t emb_grad_max_winner_words(uint64_t n_bags, uint32_t dim); /* n_bags * dim: a pure function */
+int emb_grad_max_winners(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *winners, uint32_t n_descs, emb_index_type itype,
+                         void *stream);
+/* rows_out / grads_out / capacity / n_unique_dev as emb_grad_sparse takes them */
+int emb_grad_max_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype, uint32_t *winners, int64_t *rows_out, float *grads_out,
+                        uint64_t capacity, uint64_t *n_unique_dev, void *stream);
+int emb_grad_max_sgd(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *winners, uint32_t n_descs, emb_index_type itype, float lr,
+                     void *stream);
+int emb_grad_max_step(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *winners, float *const *states, uint32_t n_descs,
+                      emb_index_type itype, const emb_opt_spec *opt, void *stream);
 
 /* The number of EMB_MXFP4 rows master steps left unwritten (an inf or a NaN in the new master row) since the last such report;
  * resets the count.  Waits for the device first, like emb_grad_report, whose count of bad positions is a separate one. */

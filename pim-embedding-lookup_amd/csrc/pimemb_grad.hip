@@ -32,6 +32,12 @@
 //   grad_sr_rows_group / grad_sr_rows_elem     the hot kernels' twins in both orders: the same walk, the last rounding by a Philox word
 // The Adagrad tails (csrc/pimemb_grad_optim.h) end the same kernels; the row-wise one sums the row's squares over its lane group
 // with an xor butterfly -- a fixed tree, stated over dim alone in the header: the same bits on every run.
+// The max-mode backward (emb_grad_max_*; csrc/pimemb_grad_max.h; a code object of its own, libpimemb_grad_max.so):
+//   grad_max_winners_group / grad_max_winners_elem     one lane group per BAG (or one thread per bag element): the position that won
+//                       every element of the forward's max, the row gathers of eight positions in flight before the first compare
+//   grad_max_rows_group / grad_max_rows_elem, grad_max_seg_partials / grad_max_seg_rows_group / grad_max_seg_rows_elem
+//                       the hot kernels' twins in both orders: the walk loads the G piece and the winners piece of every occurrence
+//                       and adds  win == p ? g : +0  in order
 // Every fp32 operation of the definition is a statement of its own under `fp contract(off)` (and the unit is compiled with
 // -ffp-contract=off): nothing is fused into an FMA.
 // The host side works in two phases.  The PLAN checks every descriptor of a call and lays out its launch chains (one per descriptor,
@@ -48,14 +54,16 @@
 #include "pimemb_grad.h"
 #include "pimemb_grad_dot.h"
 #include "pimemb_grad_master.h"
+#include "pimemb_grad_max.h"
 #include "pimemb_grad_optim.h"
 #include "pimemb_grad_segments.h"
 #include "pimemb_grad_sr.h"
 #include "pimemb_grad_step.h"
 
-// This file is compiled three times (csrc/Makefile): as libpimemb_grad.so, and with -DPIMEMB_GRAD_MASTER_UNIT / -DPIMEMB_GRAD_SR_UNIT as
-// the code objects of the master-weight and the stochastically rounded steps, which hold their own kernels and launchers alone.
-#if defined(PIMEMB_GRAD_MASTER_UNIT) || defined(PIMEMB_GRAD_SR_UNIT)
+// This file is compiled four times (csrc/Makefile): as libpimemb_grad.so, and with -DPIMEMB_GRAD_MASTER_UNIT / -DPIMEMB_GRAD_SR_UNIT /
+// -DPIMEMB_GRAD_MAX_UNIT as the code objects of the master-weight steps, the stochastically rounded steps and the max-mode backward,
+// which hold their own kernels and launchers alone.
+#if defined(PIMEMB_GRAD_MASTER_UNIT) || defined(PIMEMB_GRAD_SR_UNIT) || defined(PIMEMB_GRAD_MAX_UNIT)
 #define PIMEMB_GRAD_KERNEL_UNIT 1
 #endif
 
@@ -1476,8 +1484,332 @@ __global__ __launch_bounds__(kBlock) void grad_psw_elem(PswArgs a, uint32_t lane
     if (lg == 0) a.dw[p] = v;
 }
 
+// ---- the max-mode backward: the winners of the forward's max, and the run walk that selects by them (csrc/pimemb_grad_max.h) ---------
+// Two steps.  The winners launch reads the batch as the forward does (a PswArgs: ids, offsets, the table) and leaves win[b][d], the
+// position whose row gave element d of bag b, in the caller's buffer.  The hot kernels' twins then walk the sorted runs as before and
+// add  win[bag(p)][d] == p ? G[bag(p)][d] : +0  in the context's order.  The kernels above keep their text: the buffer travels in MaxArgs.
+
+struct MaxArgs {
+    uint32_t *winners;           // win: uint32[n_bags][dim], no padding
+};
+
+// Like the master and SR kernels these live in a code object of their own: this file compiled with -DPIMEMB_GRAD_MAX_UNIT into
+// libpimemb_grad_max.so (csrc/Makefile), which exports their two launch functions; libpimemb_grad.so's host side calls them.
+#ifdef PIMEMB_GRAD_MAX_UNIT
+
+struct u32x4 {
+    uint32_t x, y, z, w;
+} __attribute__((aligned(16)));
+
+// The positions [start, end) of one bag for ONE 16-byte piece of the winners: eight at a time, as psw_walk goes.  A round's ids are in
+// registers when it starts (the loads of the next round's ids are issued first and travel with this round's gathers); then the row
+// pieces of the good positions (RAW: 16 bytes of an fp32 row, 8 bytes of an fp16 / bf16 row), all in flight before the first compare
+// -- a slot that is padding, outside the table or beyond the bag loads nothing; then decode and compare, in position order.
+template <bool IDX64, typename RAW>
+__device__ __forceinline__ u32x4 max_walk_bag(const PswArgs &a, uint32_t start, uint32_t end, uint32_t c) {
+    float4 cur = make_float4(0.f, 0.f, 0.f, 0.f);
+    u32x4 win{kMaxNoWinner, kMaxNoWinner, kMaxNoWinner, kMaxNoWinner};
+    uint64_t next[kAhead];
+#pragma unroll
+    for (uint32_t k = 0; k < kAhead; k++) next[k] = psw_load_id<IDX64>(a, start + k < end ? start + k : start);      // (start < end <= n)
+    for (uint32_t j = start; j < end; j += kAhead) {
+        bool good[kAhead];
+        uint32_t row[kAhead];
+        RAW w[kAhead];
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {
+            row[k] = 0;
+            good[k] = j + k < end && psw_class_of(a, next[k], &row[k]) == PSW_GOOD;
+            const uint32_t p = j + kAhead + k;                            // (a slot beyond the bag re-reads the round's first id)
+            next[k] = psw_load_id<IDX64>(a, p < end ? p : j);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {
+            w[k] = RAW{};
+            if (good[k]) w[k] = reinterpret_cast<const RAW *>(a.table + (uint64_t)row[k] * a.stride)[c];      // (row < nr_rows, c < dim / 4)
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {      // the compares, in position order
+            if (good[k]) {
+                const float4 x = psw_dec(a.dtype, w[k]);
+                max_visit(x.x, j + k, &cur.x, &win.x);
+                max_visit(x.y, j + k, &cur.y, &win.y);
+                max_visit(x.z, j + k, &cur.z, &win.z);
+                max_visit(x.w, j + k, &cur.w, &win.w);
+            }
+        }
+    }
+    return win;
+}
+
+// One BAG per group of `lanes` lanes, the forward's geometry; lane lg owns the 16-byte pieces lg and lg + lanes (the second beyond dim
+// 256 only: it walks the bag once per piece, the second walk's loads reuse the first's registers).  It ends with one 16-byte store of
+// win[b][4c .. 4c + 3]; a bag with no good position stores the sentinel.  No shuffles, no LDS: lanes never need each other's data.
+template <bool IDX64>
+__global__ __launch_bounds__(kBlock) void grad_max_winners_group(PswArgs a, MaxArgs mx, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t b64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (b64 >= a.n_bags || lg >= chunks) return;
+    const uint32_t b = (uint32_t)b64;
+    const uint32_t start = psw_bag_start<IDX64>(a, b);
+    const uint32_t end = b + 1 < a.n_bags ? psw_bag_start<IDX64>(a, b + 1) : a.n;
+    for (uint32_t c = lg; c < chunks; c += lanes) {
+        u32x4 win{kMaxNoWinner, kMaxNoWinner, kMaxNoWinner, kMaxNoWinner};
+        if (start < end) win = a.dtype == kStepF32 ? max_walk_bag<IDX64, float4>(a, start, end, c) : max_walk_bag<IDX64, u32x2>(a, start, end, c);
+        *reinterpret_cast<u32x4 *>(mx.winners + (uint64_t)b * a.dim + 4u * c) = win;
+    }
+}
+
+// Any other dim or alignment: one thread per (bag, element), scalar loads, the same rule and the same bits.
+template <bool IDX64>
+__global__ __launch_bounds__(kBlock) void grad_max_winners_elem(PswArgs a, MaxArgs mx) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t b64 = gid / a.dim;
+    const uint32_t d = (uint32_t)(gid - b64 * a.dim);
+    if (b64 >= a.n_bags) return;
+    const uint32_t b = (uint32_t)b64;
+    const uint32_t start = psw_bag_start<IDX64>(a, b);
+    const uint32_t end = b + 1 < a.n_bags ? psw_bag_start<IDX64>(a, b + 1) : a.n;
+    float cur = 0.f;
+    uint32_t win = kMaxNoWinner;
+    for (uint32_t p = start; p < end; p++) {
+        uint32_t row = 0;
+        if (psw_class_of(a, psw_load_id<IDX64>(a, p), &row) != PSW_GOOD) continue;
+        const char *r = a.table + (uint64_t)row * a.stride;
+        const uint32_t stored = a.dtype == kStepF32 ? reinterpret_cast<const uint32_t *>(r)[d] : reinterpret_cast<const uint16_t *>(r)[d];
+        max_visit(bits_f32(dec(a.dtype, stored)), p, &cur, &win);
+    }
+    mx.winners[(uint64_t)b * a.dim + d] = win;
+}
+
+// walk_piece / walk_segment with the select: the run that starts at sorted place i, up to `end` (a.n, or the segment's end), summed in
+// position order; per occurrence the G piece AND the winners piece of its bag, 32 bytes a lane, eight occurrences in flight.
+__device__ __forceinline__ float4 max_walk_run(const RowArgs &a, const MaxArgs &mx, uint32_t i, uint32_t row, uint32_t c, uint32_t end) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint32_t j = i;
+    for (;;) {
+        bool live[kAhead];
+        float4 g[kAhead];
+        u32x4 w[kAhead];
+        uint32_t pos[kAhead];
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {      // (a dead slot re-reads the round's first occurrence)
+            live[k] = k == 0 || (live[k - 1] && j + k < end && a.keys[j + k] == row);
+            const uint32_t p = min(a.vals[live[k] ? j + k : j], a.n - 1u);      // (the bounds of the loads, as in walk_piece)
+            const uint32_t b = min(a.bagof[p], a.n_bags - 1u);
+            pos[k] = p;
+            g[k] = *reinterpret_cast<const float4 *>(a.grad + (uint64_t)b * a.ld + 4u * c);
+            w[k] = *reinterpret_cast<const u32x4 *>(mx.winners + (uint64_t)b * a.dim + 4u * c);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k++) {      // the adds, in position order: the zeros of the definition are added
+            if (live[k]) {
+                acc.x = add_in_order(acc.x, max_pick(w[k].x, pos[k], g[k].x));
+                acc.y = add_in_order(acc.y, max_pick(w[k].y, pos[k], g[k].y));
+                acc.z = add_in_order(acc.z, max_pick(w[k].z, pos[k], g[k].z));
+                acc.w = add_in_order(acc.w, max_pick(w[k].w, pos[k], g[k].w));
+            }
+        }
+        if (!live[kAhead - 1]) break;
+        j += kAhead;
+        if (j >= end || a.keys[j] != row) break;
+    }
+    return acc;
+}
+
+// g[row][4c .. 4c + 3] in the context's order.  SEG: a run longer than S is the sum of its partials, folded by seg_walk_piece as it is
+// (grad_max_seg_partials stored them); any other run is walked here.
+template <bool SEG>
+__device__ __forceinline__ float4 max_piece(const RowArgs &a, const SegArgs &sg, const MaxArgs &mx, uint32_t i, uint32_t row, uint32_t c, uint32_t chunks) {
+    if (SEG && i + sg.S < a.n && a.keys[i + sg.S] == row) return seg_walk_piece(a, sg, i, row, c, chunks);
+    return max_walk_run(a, mx, i, row, c, a.n);
+}
+
+// grad_rows_group / grad_seg_rows_group with the select in the walk: the same exits, the same tails (step_piece, rowwise_rate).
+template <int KIND, bool SEG>
+__device__ __forceinline__ void max_rows_group_body(const RowArgs &a, const SegArgs &sg, const MaxArgs &mx, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= a.n || (KIND != RES_ROWWISE && lg >= chunks)) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;      // (uniform over the lane group)
+    if (KIND == RES_ROWWISE) {
+        const bool own0 = lg < chunks, own1 = lg + lanes < chunks;        // (own1: beyond dim 256 only, where lanes == 64)
+        float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
+        if (own0) acc0 = max_piece<SEG>(a, sg, mx, i, row, lg, chunks);
+        if (own1) acc1 = max_piece<SEG>(a, sg, mx, i, row, lg + lanes, chunks);
+        const float rate = rowwise_rate(a, row, lg, lanes, acc0, acc1, own1);      // (lanes without a piece stay for the shuffles)
+        if (own0) step_piece<KIND>(a, row, lg, acc0, rate);
+        if (own1) step_piece<KIND>(a, row, lg + lanes, acc1, rate);
+        return;
+    }
+    for (uint32_t c = lg; c < chunks; c += lanes) {
+        const float4 acc = max_piece<SEG>(a, sg, mx, i, row, c, chunks);
+        if (KIND == RES_SPARSE) {
+            const uint32_t u = a.uidx[i] + a.usums[i / kTile];
+            if (c == 0) a.rows_out[u] = (long long)row;
+            *reinterpret_cast<float4 *>(a.grads_out + (uint64_t)u * a.dim + 4u * c) = acc;
+        } else {
+            step_piece<KIND>(a, row, c, acc, a.lr);
+        }
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void grad_max_rows_group(RowArgs a, MaxArgs mx, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    max_rows_group_body<KIND, false>(a, SegArgs{}, mx, lanes, lanes_log2, chunks);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void grad_max_seg_rows_group(RowArgs a, SegArgs sg, MaxArgs mx, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    max_rows_group_body<KIND, true>(a, sg, mx, lanes, lanes_log2, chunks);
+}
+
+// grad_seg_partials with the select: t_j of every segment of every long run, into the context's partial buffer.
+__global__ __launch_bounds__(kBlock) void grad_max_seg_partials(RowArgs a, SegArgs sg, MaxArgs mx, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= a.n || lg >= chunks) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows) return;
+    const int kind = seg_start_kind(a.keys, a.n, i, row, sg.S);           // (uniform over the lane group)
+    if (!kind) return;
+    const uint32_t slot = min(seg_slot(i, sg.S_log2, kind == 2), sg.n_slots - 1u);
+    for (uint32_t c = lg; c < chunks; c += lanes) sg.partials[(uint64_t)slot * chunks + c] = max_walk_run(a, mx, i, row, c, min(i + sg.S, a.n));
+}
+
+// grad_rows_elem / grad_seg_rows_elem with the select: one thread per (sorted place, element), scalar loads.  (No row-wise kind.)
+template <int KIND, bool SEG>
+__device__ __forceinline__ void max_rows_elem_body(const RowArgs &a, const MaxArgs &mx, uint32_t S) {
+    static_assert(KIND != RES_ROWWISE, "the element-wise kernel has no row-wide view of g");
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid / a.dim;
+    const uint32_t c = (uint32_t)(gid - i64 * a.dim);
+    if (i64 >= a.n) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;
+    float acc = 0.f, t = 0.f;
+    uint32_t in_seg = 0;
+    bool first = true;                           // (SEG) t_0 is taken as it is: the sum of the partials starts from it
+    for (uint32_t j = i; j < a.n && a.keys[j] == row; j++) {
+        const uint32_t p = min(a.vals[j], a.n - 1u);
+        const uint32_t b = min(a.bagof[p], a.n_bags - 1u);
+        const float cp = max_pick(mx.winners[(uint64_t)b * a.dim + c], p, a.grad[(uint64_t)b * a.ld + c]);
+        if (!SEG) {
+            acc = add_in_order(acc, cp);
+            continue;
+        }
+        t = add_in_order(t, cp);
+        if (++in_seg == S) {
+            acc = first ? t : add_in_order(acc, t);
+            first = false;
+            t = 0.f;
+            in_seg = 0;
+        }
+    }
+    if (SEG && in_seg) acc = first ? t : add_in_order(acc, t);
+    if (KIND == RES_SPARSE) {
+        const uint32_t u = a.uidx[i] + a.usums[i / kTile];
+        if (c == 0) a.rows_out[u] = (long long)row;
+        a.grads_out[(uint64_t)u * a.dim + c] = acc;
+        return;
+    }
+    float *sp = KIND == RES_ADAGRAD ? a.state + (uint64_t)row * a.dim + c : nullptr;
+    float st = KIND == RES_ADAGRAD ? *sp : 0.f;
+    if (a.dtype == kStepF32) {
+        float *w = reinterpret_cast<float *>(a.table + (uint64_t)row * a.stride) + c;
+        if (KIND == RES_ADAGRAD) *w = bits_f32(adagrad_step(kStepF32, f32_bits(*w), acc, &st, a.lr, a.eps));
+        else *w = step_f32(*w, acc, a.lr);
+    } else {
+        uint16_t *w = reinterpret_cast<uint16_t *>(a.table + (uint64_t)row * a.stride) + c;
+        if (KIND == RES_ADAGRAD) *w = (uint16_t)adagrad_step(a.dtype, *w, acc, &st, a.lr, a.eps);
+        else *w = (uint16_t)step(a.dtype, *w, acc, a.lr);
+    }
+    if (KIND == RES_ADAGRAD) *sp = st;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void grad_max_rows_elem(RowArgs a, MaxArgs mx) {
+    max_rows_elem_body<KIND, false>(a, mx, 0u);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void grad_max_seg_rows_elem(RowArgs a, MaxArgs mx, uint32_t S) {
+    max_rows_elem_body<KIND, true>(a, mx, S);
+}
+
+}  // namespace
+
+// The two launch functions libpimemb_grad_max.so exports (plain C; PswArgs, RowArgs, SegArgs and MaxArgs are this file's own, which every
+// compilation lays out alike).  Errors are left to the caller's hipGetLastError().
+// The winners launch of one descriptor: a lane group per bag, else elem_blocks workgroups of one thread per (bag, element).
+extern "C" __attribute__((visibility("default"))) void pimemb_grad_max_winners(const void *psw_args, const void *max_args, int idx64, int lane, uint32_t lanes,
+                                                                                uint32_t lanes_log2, uint32_t chunks, uint32_t blocks, uint32_t elem_blocks,
+                                                                                void *stream) {
+    const PswArgs &a = *static_cast<const PswArgs *>(psw_args);
+    const MaxArgs &mx = *static_cast<const MaxArgs *>(max_args);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 block(kBlock);
+    if (lane && idx64) grad_max_winners_group<true><<<dim3(blocks), block, 0, s>>>(a, mx, lanes, lanes_log2, chunks);
+    else if (lane) grad_max_winners_group<false><<<dim3(blocks), block, 0, s>>>(a, mx, lanes, lanes_log2, chunks);
+    else if (idx64) grad_max_winners_elem<true><<<dim3(elem_blocks), block, 0, s>>>(a, mx);
+    else grad_max_winners_elem<false><<<dim3(elem_blocks), block, 0, s>>>(a, mx);
+}
+
+// The hot launch of a max-mode chain behind the sort (and, on the lane-group kernels of a segmented context, the partials launch before
+// it).  kind: RES_SPARSE / RES_SGD / RES_ADAGRAD / RES_ROWWISE.
+extern "C" __attribute__((visibility("default"))) void pimemb_grad_max_launch(const void *row_args, const void *seg_args, const void *max_args, int kind, int seg,
+                                                                               int lane, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks, uint32_t blocks,
+                                                                               uint32_t elem_blocks, uint32_t S, void *stream) {
+    const RowArgs &a = *static_cast<const RowArgs *>(row_args);
+    const SegArgs &sg = *static_cast<const SegArgs *>(seg_args);
+    const MaxArgs &mx = *static_cast<const MaxArgs *>(max_args);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 block(kBlock);
+    if (lane && seg) {
+        const dim3 grid(blocks);
+        grad_max_seg_partials<<<grid, block, 0, s>>>(a, sg, mx, lanes, lanes_log2, chunks);
+        if (kind == RES_SGD) grad_max_seg_rows_group<RES_SGD><<<grid, block, 0, s>>>(a, sg, mx, lanes, lanes_log2, chunks);
+        else if (kind == RES_ADAGRAD) grad_max_seg_rows_group<RES_ADAGRAD><<<grid, block, 0, s>>>(a, sg, mx, lanes, lanes_log2, chunks);
+        else if (kind == RES_ROWWISE) grad_max_seg_rows_group<RES_ROWWISE><<<grid, block, 0, s>>>(a, sg, mx, lanes, lanes_log2, chunks);
+        else grad_max_seg_rows_group<RES_SPARSE><<<grid, block, 0, s>>>(a, sg, mx, lanes, lanes_log2, chunks);
+    } else if (lane) {
+        const dim3 grid(blocks);
+        if (kind == RES_SGD) grad_max_rows_group<RES_SGD><<<grid, block, 0, s>>>(a, mx, lanes, lanes_log2, chunks);
+        else if (kind == RES_ADAGRAD) grad_max_rows_group<RES_ADAGRAD><<<grid, block, 0, s>>>(a, mx, lanes, lanes_log2, chunks);
+        else if (kind == RES_ROWWISE) grad_max_rows_group<RES_ROWWISE><<<grid, block, 0, s>>>(a, mx, lanes, lanes_log2, chunks);
+        else grad_max_rows_group<RES_SPARSE><<<grid, block, 0, s>>>(a, mx, lanes, lanes_log2, chunks);
+    } else if (seg) {
+        const dim3 grid(elem_blocks);            // (the row-wise kind never gets here: the plan refused it)
+        if (kind == RES_SGD) grad_max_seg_rows_elem<RES_SGD><<<grid, block, 0, s>>>(a, mx, S);
+        else if (kind == RES_ADAGRAD) grad_max_seg_rows_elem<RES_ADAGRAD><<<grid, block, 0, s>>>(a, mx, S);
+        else grad_max_seg_rows_elem<RES_SPARSE><<<grid, block, 0, s>>>(a, mx, S);
+    } else {
+        const dim3 grid(elem_blocks);
+        if (kind == RES_SGD) grad_max_rows_elem<RES_SGD><<<grid, block, 0, s>>>(a, mx);
+        else if (kind == RES_ADAGRAD) grad_max_rows_elem<RES_ADAGRAD><<<grid, block, 0, s>>>(a, mx);
+        else grad_max_rows_elem<RES_SPARSE><<<grid, block, 0, s>>>(a, mx);
+    }
+}
+
+namespace {
+#else      // libpimemb_grad.so (and the master and SR units, which never call them): the launchers are libpimemb_grad_max.so's
+}  // namespace
+extern "C" void pimemb_grad_max_winners(const void *psw_args, const void *max_args, int idx64, int lane, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks,
+                                        uint32_t blocks, uint32_t elem_blocks, void *stream);
+extern "C" void pimemb_grad_max_launch(const void *row_args, const void *seg_args, const void *max_args, int kind, int seg, int lane, uint32_t lanes,
+                                       uint32_t lanes_log2, uint32_t chunks, uint32_t blocks, uint32_t elem_blocks, uint32_t S, void *stream);
+namespace {
+#endif
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
-#ifndef PIMEMB_GRAD_KERNEL_UNIT      // (to the end of the file: the master and SR units hold kernels and their launchers alone)
+#ifndef PIMEMB_GRAD_KERNEL_UNIT     // (to the end of the file: the master and SR units hold kernels and their launchers alone)
 
 thread_local char t_err[512] = "";
 
@@ -1654,7 +1986,8 @@ struct TableShape {
 };
 
 // Everything that can be refused about one descriptor, before anything is enqueued.
-int check_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, const char *step /* "an SGD", "an Adagrad"; NULL: no step */, const char *who, TableShape *t) {
+int check_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, const char *step /* "an SGD", "an Adagrad"; NULL: no step */, const char *who, TableShape *t,
+               bool need_grad = true /* false: emb_grad_max_winners, which reads no gradient */) {
     void *rows = nullptr;
     emb_dtype dt;
     if (int rc = emb_table_info(g->e, d.table_id, &rows, &t->nr_rows, &t->dim, &dt)) return fail_engine(rc, who);
@@ -1692,9 +2025,9 @@ int check_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, const 
         return fail(EMB_ERR_INVALID, "%s: %llu bags in one call, the context was created for %llu", who, (unsigned long long)d.n_bags,
                     (unsigned long long)g->max_bags);
     if (d.n_indices == 0) return EMB_OK;
-    if (!d.indices || !d.grad) return fail(EMB_ERR_INVALID, "%s: indices or grad is NULL", who);
+    if (!d.indices || (need_grad && !d.grad)) return fail(EMB_ERR_INVALID, "%s: indices or grad is NULL", who);
     if (!d.offsets && d.fixed_pooling == 0) return fail(EMB_ERR_INVALID, "%s: offsets is NULL and fixed_pooling is 0", who);
-    if (d.grad_ld < t->dim) return fail(EMB_ERR_INVALID, "%s: grad_ld %llu is below the table's dim %u", who, (unsigned long long)d.grad_ld, t->dim);
+    if (need_grad && d.grad_ld < t->dim) return fail(EMB_ERR_INVALID, "%s: grad_ld %llu is below the table's dim %u", who, (unsigned long long)d.grad_ld, t->dim);
     const size_t isz = itype == EMB_IDX_I64 ? 8 : 4;
     if ((uintptr_t)d.indices % isz || (uintptr_t)d.offsets % isz || (uintptr_t)d.grad % 4 || (uintptr_t)d.pool.per_sample_weights % 4)
         return fail(EMB_ERR_INVALID, "%s: indices, offsets, grad and weights must be naturally aligned", who);
@@ -1706,6 +2039,7 @@ struct StepSpec {
     float lr = 0.f, eps = 0.f;
     float *const *masters = nullptr;      // emb_grad_master_step: one fp32 master per descriptor; the kind's master tail runs
     const emb_sr_spec *sr = nullptr;      // emb_grad_sgd_sr / emb_grad_step_sr: the kind's stochastically rounded tail runs
+    uint32_t *const *winners = nullptr;   // emb_grad_max_*: one winners buffer per descriptor; the kind's walk selects by it
 };
 struct SparseOut {               // where emb_grad_sparse writes; all NULL for a step (no unique numbering, no output arrays)
     long long *rows = nullptr;
@@ -1946,6 +2280,12 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
         grad_scan_sums<<<dim3(1), block, 0, s>>>(sc.sums, tiles, out.n_unique);
         GRAD_HIP(hipGetLastError());
         a.uidx = sc.uidx, a.usums = sc.sums, a.rows_out = out.rows, a.grads_out = out.grads;
+    }
+    if (spec.winners) {                          // (the partials launch of a segmented context is the launcher's own)
+        const MaxArgs mx{spec.winners[first]};
+        pimemb_grad_max_launch(&a, &sg, &mx, spec.kind, seg, c.lane, l.lanes, l.lanes_log2, l.chunks, l.blocks, c.elem_blocks, g->cfg.segment, s);
+        GRAD_HIP(hipGetLastError());
+        return EMB_OK;
     }
     if (spec.masters) {
         if (seg && c.lane) grad_seg_partials<<<dim3(l.blocks), block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
@@ -2244,6 +2584,157 @@ int emb_grad_master_step(emb_grad *g, const emb_grad_desc *descs, float *const *
         if (plan[k].k)
             if (int rc = run_chain(g, descs, states, plan.data(), k, itype == EMB_IDX_I64, st, SparseOut{}, s)) return rc;
     return EMB_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- the max-mode backward: emb_grad_max_winners / _sparse / _sgd / _step ---------------------------------------------------------
+
+// Whether a descriptor's winners launch and hot launch run on the lane-group kernels: the step's shape, and the winners 16-byte aligned.
+bool max_lane_shape(const TableShape &t, const uint32_t *winners) { return t.dim % 4 == 0 && t.dim <= 512 && (uintptr_t)winners % 16 == 0; }
+
+struct MaxPlanned {              // what the winners launch of one descriptor needs beside its Planned
+    bool lane;
+    LaneGeom geo;
+    uint32_t elem_blocks;
+};
+
+// The plan of a max-mode call: every descriptor, winners buffer and state checked, in order; then one chain per non-empty descriptor.
+// kind < 0: emb_grad_max_winners (no gradient is read, no chain is planned).
+int plan_max(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *winners, float *const *states, uint32_t n_descs, emb_index_type itype, int kind,
+             const float *grads_out, const char *step, const char *who, Planned *plan, MaxPlanned *wp) {
+    for (uint32_t k = 0; k < n_descs; k++) {
+        const emb_grad_desc &d = descs[k];
+        Planned &p = plan[k];
+        if (d.pool.mode != EMB_POOL_MAX)
+            return fail(EMB_ERR_INVALID, "%s: this call takes EMB_POOL_MAX descriptors, table %u pools by mode %u", who, d.table_id, d.pool.mode);
+        if (d.pool.per_sample_weights) return fail(EMB_ERR_INVALID, "%s: per_sample_weights do not go with EMB_POOL_MAX (table %u)", who, d.table_id);
+        emb_grad_desc plain = d;                 // everything else is checked as for a plain sum: the same refusals, the same texts
+        plain.pool.mode = EMB_POOL_SUM;
+        if (int rc = check_desc(g, plain, itype, step, who, &p.t, kind >= 0)) return rc;
+        if (p.t.dtype != kF32 && p.t.dtype != kF16 && p.t.dtype != kBF16)
+            return fail(EMB_ERR_UNSUPPORTED, "%s: table %u is fp8 or MXFP4: the winners are decided on decoded fp32, fp16 and bf16 rows only", who, d.table_id);
+        const uint32_t *win = winners[k];
+        if (d.n_bags && (!win || (uintptr_t)win % 4))
+            return fail(EMB_ERR_INVALID, "%s: the winners buffer of table %u is NULL or not 4-byte aligned", who, d.table_id);
+        float *state = d.n_indices && states ? states[k] : nullptr;
+        if (d.n_indices && (kind == RES_ADAGRAD || kind == RES_ROWWISE) && (!state || (uintptr_t)state % 4))
+            return fail(EMB_ERR_INVALID, "%s: the state of table %u is NULL or not 4-byte aligned", who, d.table_id);
+        wp[k].lane = max_lane_shape(p.t, win);
+        p.lane = kind >= 0 && wp[k].lane && lane_group_path(d, p.t, kind, state, grads_out);
+        if (d.n_indices && kind == RES_ROWWISE && !p.lane)
+            return fail(EMB_ERR_UNSUPPORTED,
+                        "%s: row-wise Adagrad needs the lane-group shape (dim %% 4 == 0, dim <= 512, grad and winners 16-byte aligned, grad_ld %% 4 == 0): "
+                        "table %u has dim %u, grad %p, grad_ld %llu, winners %p -- the element-wise kernel has no row-wide view of g", who, d.table_id, p.t.dim,
+                        (const void *)d.grad, (unsigned long long)d.grad_ld, (const void *)win);
+        if (kind >= 0) wp[k].lane = p.lane;      // (a step's two launches take the same shape)
+        const uint64_t blocks = (d.n_bags * p.t.dim + kBlock - 1) / kBlock;
+        if (!wp[k].lane && blocks > 0x7fffffffull)
+            return fail(EMB_ERR_UNSUPPORTED, "%s: %llu bags of dim %u are more elements than one launch of the element-wise kernel takes", who,
+                        (unsigned long long)d.n_bags, p.t.dim);
+        wp[k].elem_blocks = (uint32_t)blocks;
+        if (wp[k].lane) wp[k].geo = lane_geom(p.t.dim, (uint32_t)d.n_bags);      // a group per bag (n_bags <= 2^31 - 1, 64 lanes: below 2^29 workgroups)
+    }
+    for (uint32_t k = 0; kind >= 0 && k < n_descs; k++)
+        if (descs[k].n_indices)
+            if (int rc = plan_chain(g, descs, plan, k, k + 1)) return rc;
+    return EMB_OK;
+}
+
+// The winners launches of a call, ALL of them ahead of the first step: a table named twice is judged at the bytes the forward read.
+int enqueue_winners(const emb_grad_desc *descs, uint32_t *const *winners, uint32_t n_descs, bool idx64, const Planned *plan, const MaxPlanned *wp,
+                    hipStream_t s) {
+    for (uint32_t k = 0; k < n_descs; k++) {
+        const emb_grad_desc &d = descs[k];
+        const TableShape &t = plan[k].t;
+        if (d.n_bags == 0 || t.dim == 0) continue;
+        const PoolArgs pa = pool_args(d);
+        PswArgs a{};
+        a.ids = d.indices, a.offsets = d.offsets, a.fixed_pooling = d.fixed_pooling;
+        if (d.n_indices == 0) a.offsets = nullptr, a.fixed_pooling = 0;      // (no position: every bag starts at n = 0, and nothing of the batch is read)
+        a.table = t.rows, a.stride = t.stride, a.dtype = t.dtype;
+        a.pad_on = pa.pad_on, a.pad_idx = pa.pad_idx;
+        a.n = (uint32_t)d.n_indices, a.n_bags = (uint32_t)d.n_bags, a.nr_rows = (uint32_t)t.nr_rows, a.dim = t.dim;
+        const MaxArgs mx{winners[k]};
+        const LaneGeom &l = wp[k].geo;
+        pimemb_grad_max_winners(&a, &mx, idx64, wp[k].lane, l.lanes, l.lanes_log2, l.chunks, l.blocks, wp[k].elem_blocks, s);
+        GRAD_HIP(hipGetLastError());
+    }
+    return EMB_OK;
+}
+
+int max_call(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *winners, float *const *states, uint32_t n_descs, emb_index_type itype,
+             const StepSpec &spec, int kind, const char *step, const char *who, void *stream) {
+    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
+    if (n_descs && (!descs || !winners)) return fail(EMB_ERR_INVALID, "%s: descs or winners is NULL", who);
+    if (n_descs && (kind == RES_ADAGRAD || kind == RES_ROWWISE) && !states) return fail(EMB_ERR_INVALID, "%s: states is NULL", who);
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    std::vector<Planned> plan(n_descs);
+    std::vector<MaxPlanned> wp(n_descs);
+    if (int rc = plan_max(g, descs, winners, states, n_descs, itype, kind, nullptr, step, who, plan.data(), wp.data())) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    if (int rc = enqueue_winners(descs, winners, n_descs, itype == EMB_IDX_I64, plan.data(), wp.data(), s)) return rc;
+    for (uint32_t k = 0; kind >= 0 && k < n_descs; k++)
+        if (plan[k].k)
+            if (int rc = run_chain(g, descs, states, plan.data(), k, itype == EMB_IDX_I64, spec, SparseOut{}, s)) return rc;
+    return EMB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t emb_grad_max_winner_words(uint64_t n_bags, uint32_t dim) { return n_bags * dim; }
+
+int emb_grad_max_winners(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *winners, uint32_t n_descs, emb_index_type itype, void *stream) {
+    return max_call(g, descs, winners, nullptr, n_descs, itype, StepSpec{}, -1, nullptr, "emb_grad_max_winners", stream);
+}
+
+int emb_grad_max_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype, uint32_t *winners, int64_t *rows_out, float *grads_out,
+                        uint64_t capacity, uint64_t *n_unique_dev, void *stream) {
+    const char *who = "emb_grad_max_sparse";
+    if (!g || !desc) return fail(EMB_ERR_INVALID, "%s: context or descriptor is NULL", who);
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    if (!n_unique_dev || (uintptr_t)n_unique_dev % 8) return fail(EMB_ERR_INVALID, "%s: n_unique_dev is NULL or not 8-byte aligned", who);
+    if (capacity < desc->n_indices)
+        return fail(EMB_ERR_INVALID, "%s: room for %llu rows, %llu indices may name as many", who, (unsigned long long)capacity, (unsigned long long)desc->n_indices);
+    if (desc->n_indices && (!rows_out || !grads_out || (uintptr_t)rows_out % 8 || (uintptr_t)grads_out % 4))
+        return fail(EMB_ERR_INVALID, "%s: rows_out or grads_out is NULL or not naturally aligned", who);
+    Planned p{};                                 // the plan: a chain of one, with the unique numbering switched on
+    MaxPlanned wp{};
+    if (int rc = plan_max(g, desc, &winners, nullptr, 1, itype, RES_SPARSE, grads_out, nullptr, who, &p, &wp)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    if (int rc = enqueue_winners(desc, &winners, 1, itype == EMB_IDX_I64, &p, &wp, s)) return rc;
+    if (desc->n_indices == 0) {
+        GRAD_HIP(hipMemsetAsync(n_unique_dev, 0, 8, s));
+        return EMB_OK;
+    }
+    StepSpec spec{};
+    spec.winners = &winners;
+    const SparseOut out{reinterpret_cast<long long *>(rows_out), grads_out, reinterpret_cast<unsigned long long *>(n_unique_dev)};
+    return run_chain(g, desc, nullptr, &p, 0, itype == EMB_IDX_I64, spec, out, s);
+}
+
+int emb_grad_max_sgd(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *winners, uint32_t n_descs, emb_index_type itype, float lr, void *stream) {
+    StepSpec spec{RES_SGD, lr, 0.f};
+    spec.winners = winners;
+    return max_call(g, descs, winners, nullptr, n_descs, itype, spec, RES_SGD, "an SGD", "emb_grad_max_sgd", stream);
+}
+
+int emb_grad_max_step(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *winners, float *const *states, uint32_t n_descs, emb_index_type itype,
+                      const emb_opt_spec *opt, void *stream) {
+    const char *who = "emb_grad_max_step";
+    if (!opt) return fail(EMB_ERR_INVALID, "%s: the optimizer spec is NULL", who);
+    if (opt->kind != EMB_OPT_ADAGRAD && opt->kind != EMB_OPT_ROWWISE_ADAGRAD) return fail(EMB_ERR_INVALID, "%s: unknown optimizer kind %u", who, opt->kind);
+    if (opt->reserved != 0) return fail(EMB_ERR_INVALID, "%s: the spec's reserved field must be 0, got %u", who, opt->reserved);
+    if (!(opt->eps >= 0.f)) return fail(EMB_ERR_INVALID, "%s: eps must not be negative or NaN, got %g", who, (double)opt->eps);
+    StepSpec spec{opt->kind == EMB_OPT_ROWWISE_ADAGRAD ? RES_ROWWISE : RES_ADAGRAD, opt->lr, opt->eps};
+    spec.winners = winners;
+    return max_call(g, descs, winners, states, n_descs, itype, spec, spec.kind, "an Adagrad", who, stream);
 }
 
 int emb_grad_master_report(emb_grad *g, uint64_t *n_unencodable) {

@@ -422,6 +422,14 @@ class GradContext:
         if mode not in ("sum", "mean", "max"):
             raise ValueError(f"mode has to be one of sum, mean or max, got {mode!r}")
         dev = _is_torch(indices) and indices.is_cuda
+        if grad is None:                 # (max_winners: no gradient is read; the bags come from offsets or fixed_pooling)
+            n_idx = int(indices.shape[0])
+            bags = int(offsets.shape[0]) if offsets is not None else n_idx // max(int(fixed_pooling), 1)
+            if dev:
+                import torch
+                grad = torch.empty((bags, 0), dtype=torch.float32, device=indices.device)
+            else:
+                grad = np.empty((bags, 0), dtype=np.float32)
         if dev:
             import torch
             if not (_is_torch(grad) and grad.is_cuda) or grad.dtype != torch.float32 or grad.dim() != 2 or (grad.shape[1] > 1 and grad.stride(1) != 1):
@@ -597,24 +605,7 @@ class GradContext:
         try:
             arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, grads, modes, per_sample_weights, padding_idx, fixed_pooling,
                                                           stream, keep)
-            ptrs = (C.c_void_p * max(n, 1))()
-            for k in range(n):
-                want = int(np.prod(self.state_shape(table_ids[k], rowwise)))
-                st = states[k]
-                if st is None:
-                    ptrs[k] = None
-                elif dev:
-                    import torch
-                    if not (_is_torch(st) and st.is_cuda) or st.dtype != torch.float32 or not st.is_contiguous() or st.numel() != want:
-                        raise TypeError(f"state {k} must be a contiguous float32 CUDA tensor of {want} values")
-                    ptrs[k] = st.data_ptr()
-                else:
-                    if not isinstance(st, np.ndarray) or st.dtype != np.float32 or st.size != want or not st.flags.c_contiguous or not st.flags.writeable:
-                        raise TypeError(f"state {k} must be a writeable C-contiguous float32 numpy array of {want} values")
-                    buf = DeviceBuffer.from_numpy(self.engine, st)
-                    keep.append(buf)
-                    back.append((st, buf))
-                    ptrs[k] = buf.ptr
+            ptrs = self._state_ptrs(table_ids, states, n, rowwise, dev, keep, back)
             spec = _l.EmbOptSpec(_l.EMB_OPT_ROWWISE_ADAGRAD if rowwise else _l.EMB_OPT_ADAGRAD, float(lr), float(eps), 0)
             if sr_spec is not None:
                 _l.check_grad(self._G.emb_grad_step_sr(self._h, arr, ptrs, n, itype, C.byref(spec), C.byref(sr_spec), stream))
@@ -625,6 +616,146 @@ class GradContext:
                 self.engine.synchronize(stream)
                 for st, buf in back:
                     st[...] = buf.numpy().reshape(st.shape)
+        finally:
+            self._free(keep)
+
+    def _state_ptrs(self, table_ids, states, n, rowwise, dev, keep, back):
+        """The device pointers of one Adagrad state per table: CUDA tensors in place; numpy arrays copied into DeviceBuffers, which
+        `keep` holds and `back` pairs with their arrays for the copy home."""
+        ptrs = (C.c_void_p * max(n, 1))()
+        for k in range(n):
+            want = int(np.prod(self.state_shape(table_ids[k], rowwise)))
+            st = states[k]
+            if st is None:
+                ptrs[k] = None
+            elif dev:
+                import torch
+                if not (_is_torch(st) and st.is_cuda) or st.dtype != torch.float32 or not st.is_contiguous() or st.numel() != want:
+                    raise TypeError(f"state {k} must be a contiguous float32 CUDA tensor of {want} values")
+                ptrs[k] = st.data_ptr()
+            else:
+                if not isinstance(st, np.ndarray) or st.dtype != np.float32 or st.size != want or not st.flags.c_contiguous or not st.flags.writeable:
+                    raise TypeError(f"state {k} must be a writeable C-contiguous float32 numpy array of {want} values")
+                buf = DeviceBuffer.from_numpy(self.engine, st)
+                keep.append(buf)
+                back.append((st, buf))
+                ptrs[k] = buf.ptr
+        return ptrs
+
+    # ---- the max-mode backward (emb_grad_max_*): the existing methods above keep refusing mode="max" ----
+    def _winner_bufs(self, arr, n, table_ids, indices, dev, winners, keep):
+        """One winners buffer [n_bags, dim] per table: the caller's (`winners`: int32 CUDA tensors, contiguous) or new ones -- int32
+        CUDA tensors with torch inputs (a bag without a valid entry holds -1, the header's 0xffffffff), DeviceBuffers otherwise.
+        Returns (the pointer array, the buffers)."""
+        if winners is not None and len(winners) != n:
+            raise ValueError(f"{len(winners)} winners buffers for {n} tables")
+        ptrs, bufs = (C.c_void_p * max(n, 1))(), []
+        for k in range(n):
+            B, dim = int(arr[k].n_bags), self.engine.table_info(table_ids[k])[2]
+            assert self._G.emb_grad_max_winner_words(B, dim) == B * dim
+            if dev:
+                import torch
+                w = torch.empty((B, dim), dtype=torch.int32, device=indices[k].device) if winners is None else winners[k]
+                if not (_is_torch(w) and w.is_cuda) or w.dtype != torch.int32 or not w.is_contiguous() or w.numel() != B * dim:
+                    raise TypeError(f"winners buffer {k} must be a contiguous int32 CUDA tensor of {B * dim} values")
+                ptrs[k] = w.data_ptr() if B * dim else None
+            else:
+                if winners is not None:
+                    raise TypeError("winners= goes with torch CUDA inputs")
+                w = DeviceBuffer(self.engine, max(B * dim, 1) * 4, np.uint32, (B, dim))
+                keep.append(w)
+                ptrs[k] = w.ptr
+            bufs.append(w)
+        return ptrs, bufs
+
+    @staticmethod
+    def _winners_home(bufs, dev):
+        return list(bufs) if dev else [b.numpy().copy() for b in bufs]
+
+    def max_winners(self, table_ids, indices, offsets, padding_idx=None, fixed_pooling: int = 0, winners=None, stream: int | None = None) -> list:
+        """The winners of a mode-"max" lookup (emb_grad_max_winners), per table [n_bags, dim]: for every bag and element the POSITION in
+        `indices` whose row gave the forward's maximum -- the first valid entry, replaced only by a strictly greater value -- torch's
+        max_indices as positions; 0xffffffff (-1 in the int32 tensors of the torch path) for a bag without a valid entry.  One entry per
+        table as sgd_step takes them; winners: buffers to write into (torch path).  Counts nothing for report()."""
+        keep = []
+        try:
+            arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, [None] * len(table_ids), "max", None, padding_idx, fixed_pooling,
+                                                          stream, keep)
+            ptrs, bufs = self._winner_bufs(arr, n, table_ids, indices, dev, winners, keep)
+            _l.check_grad(self._G.emb_grad_max_winners(self._h, arr, ptrs, n, itype, stream))
+            if not dev:
+                self.engine.synchronize(stream)
+            return self._winners_home(bufs, dev)
+        finally:
+            self._free(keep)
+
+    def max_sparse_grad(self, table: int, indices, offsets, grad, padding_idx=None, stream: int | None = None, fixed_pooling: int = 0, winners=None,
+                        return_winners: bool = False):
+        """sparse_grad for a mode-"max" lookup (emb_grad_max_sparse): (rows, grads) -- every row with a valid entry, ascending, and its
+        gradient: the bag's gradient at the elements the entry won, +0 elsewhere, summed in the context's order.  Scattered dense it is
+        the weight.grad torch leaves in max mode (torch has no sparse form there).  winners: a buffer to use (torch path);
+        return_winners=True: (rows, grads, winners)."""
+        keep = []
+        try:
+            arr, n, itype, dev, stream = self._step_descs([table], [indices], None if offsets is None else [offsets], [grad], "max", None, padding_idx,
+                                                          fixed_pooling, stream, keep)
+            ptrs, bufs = self._winner_bufs(arr, 1, [table], [indices], dev, None if winners is None else [winners], keep)
+            d, cnt, dim = arr[0], int(arr[0].n_indices), self.engine.table_info(table)[2]
+            if dev:
+                import torch
+                rows = torch.empty((cnt,), dtype=torch.int64, device=indices.device)
+                grads = torch.empty((cnt, dim), dtype=torch.float32, device=indices.device)
+                count = torch.zeros((1,), dtype=torch.int64, device=indices.device)
+                _l.check_grad(self._G.emb_grad_max_sparse(self._h, C.byref(d), itype, ptrs[0], rows.data_ptr(), grads.data_ptr(), cnt, count.data_ptr(), stream))
+                u = int(count.item())
+                res = (rows[:u], grads[:u])
+            else:
+                rows_b = DeviceBuffer(self.engine, max(cnt, 1) * 8, np.int64, (max(cnt, 1),))
+                grads_b = DeviceBuffer(self.engine, max(cnt * dim, 1) * 4, np.float32, (max(cnt, 1), dim))
+                count_b = DeviceBuffer(self.engine, 8, np.uint64, (1,))
+                keep += [rows_b, grads_b, count_b]
+                _l.check_grad(self._G.emb_grad_max_sparse(self._h, C.byref(d), itype, ptrs[0], rows_b.ptr, grads_b.ptr, cnt, count_b.ptr, stream))
+                self.engine.synchronize(stream)
+                u = int(count_b.numpy()[0])
+                res = (rows_b.numpy()[:u].copy(), grads_b.numpy()[:u].copy())
+            return res + (self._winners_home(bufs, dev)[0],) if return_winners else res
+        finally:
+            self._free(keep)
+
+    def max_sgd_step(self, table_ids, indices, offsets, grads, lr: float, padding_idx=None, stream: int | None = None, fixed_pooling: int = 0,
+                     winners=None) -> list:
+        """sgd_step for mode-"max" lookups (emb_grad_max_sgd; fp32, fp16 and bf16 tables): the winners of ALL tables are computed first, at
+        the rows the forward read, then table after table is stepped with the max-mode gradient.  A row the batch names is stepped even
+        where it won nothing (its bytes stay).  Returns the winners, one [n_bags, dim] per table (max_winners)."""
+        keep = []
+        try:
+            arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, grads, "max", None, padding_idx, fixed_pooling, stream, keep)
+            ptrs, bufs = self._winner_bufs(arr, n, table_ids, indices, dev, winners, keep)
+            _l.check_grad(self._G.emb_grad_max_sgd(self._h, arr, ptrs, n, itype, float(lr), stream))
+            if not dev:
+                self.engine.synchronize(stream)
+            return self._winners_home(bufs, dev)
+        finally:
+            self._free(keep)
+
+    def max_adagrad_step(self, table_ids, indices, offsets, grads, states, lr: float, eps: float = 1e-10, rowwise: bool = False, padding_idx=None,
+                         stream: int | None = None, fixed_pooling: int = 0, winners=None) -> list:
+        """adagrad_step for mode-"max" lookups (emb_grad_max_step): states as there; a row the batch names that won nothing is stepped with
+        g = 0.  Returns the winners as max_sgd_step does."""
+        if len(states) != len(table_ids):
+            raise ValueError(f"{len(states)} states for {len(table_ids)} tables")
+        keep, back = [], []
+        try:
+            arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, grads, "max", None, padding_idx, fixed_pooling, stream, keep)
+            ptrs, bufs = self._winner_bufs(arr, n, table_ids, indices, dev, winners, keep)
+            sptrs = self._state_ptrs(table_ids, states, n, rowwise, dev, keep, back)
+            spec = _l.EmbOptSpec(_l.EMB_OPT_ROWWISE_ADAGRAD if rowwise else _l.EMB_OPT_ADAGRAD, float(lr), float(eps), 0)
+            _l.check_grad(self._G.emb_grad_max_step(self._h, arr, ptrs, sptrs, n, itype, C.byref(spec), stream))
+            if not dev:
+                self.engine.synchronize(stream)
+                for st, buf in back:
+                    st[...] = buf.numpy().reshape(st.shape)
+            return self._winners_home(bufs, dev)
         finally:
             self._free(keep)
 

@@ -278,6 +278,11 @@ GRAD_SIGNATURES = {
     "emb_grad_master_report": (C.c_int, [_vp, C.POINTER(_u64)]),
     "emb_grad_sgd_sr": (C.c_int, [_vp, C.POINTER(EmbGradDesc), _u32, C.c_int, C.c_float, C.POINTER(EmbSrSpec), _vp]),
     "emb_grad_step_sr": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbOptSpec), C.POINTER(EmbSrSpec), _vp]),
+    "emb_grad_max_winner_words": (_u64, [_u64, _u32]),
+    "emb_grad_max_winners": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, _vp]),
+    "emb_grad_max_sparse": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.c_int, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "emb_grad_max_sgd": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, C.c_float, _vp]),
+    "emb_grad_max_step": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbOptSpec), _vp]),
 }
 
 _lib = None
@@ -351,8 +356,8 @@ def load_grad() -> C.CDLL:
     load()
     if _grad_lib is not None:          # (load() came here itself)
         return _grad_lib
-    from .build import GRAD_LIB_PATH, GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH
-    for dep in (GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH):      # libpimemb_grad.so links against both (RUNPATH $ORIGIN): name the one that is missing
+    from .build import GRAD_LIB_PATH, GRAD_MASTER_LIB_PATH, GRAD_MAX_LIB_PATH, GRAD_SR_LIB_PATH
+    for dep in (GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH, GRAD_MAX_LIB_PATH):      # libpimemb_grad.so links against all three (RUNPATH $ORIGIN): name the one that is missing
         if not os.path.exists(dep):
             raise FileNotFoundError(
                 f"{dep} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "

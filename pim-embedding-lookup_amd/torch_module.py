@@ -26,7 +26,11 @@ initial_accumulator_value)` / `adagrad_step_` are the same with the fused Adagra
 the autograd graph on them, and backward leaves their gradient -- one value per index, <grad_output[bag], weight[index]> over a
 fixed tree (emb_grad_weights) -- in `.grad`, in their shape and dtype; with a fused step enabled it is computed first, at the
 table forward() read, and the step runs behind it.  `per_sample_weights_grad(input, offsets, grad_output)` is the explicit call.
-Not there: mode "max", momentum / Adam, weight decay, fp8 / MXFP4 weights, a second-order gradient.  max_norm is not supported
+Mode "max" trains through the max-mode backward (emb_grad_max_*): sparse_grad, sgd_step_, adagrad_step_ and the two enable_fused_*
+of a mode="max" module compute the forward's winners first, then the gradient that flows to them alone; master_weights=True and
+stochastic_rounding=True raise ValueError there, and so does multi_table=True of a fused model that holds such a table (it is
+stepped on its own, through the same call).
+Not there: momentum / Adam, weight decay, fp8 / MXFP4 weights, a second-order gradient.  max_norm is not supported
 by any module.
 
 Output dtype.  By default every module returns fp32 rows, whatever the table holds.  `out_dtype="weight"` makes a module
@@ -366,6 +370,7 @@ class PoolingEmbeddingBag(torch.nn.Module):
         lr=None switches it off again.  Switches a fused Adagrad off (its state stays).  order="segmented": a row's occurrences
         are summed in the segmented order of include/pimemb_grad.h (GradContext) -- for batches that name some rows thousands of
         times; as fixed as the position order, other bits.  Returns self."""
+        _no_max_variants([self.mode], master_weights, stochastic_rounding)
         _set_sr(self, stochastic_rounding, sr_seed, [self._table_dtype], master_weights)
         object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
@@ -395,6 +400,7 @@ class PoolingEmbeddingBag(torch.nn.Module):
         The fp32 state -- module.adagrad_sum, [num_embeddings, embedding_dim] or [num_embeddings] -- is allocated once, filled with
         initial_accumulator_value, kept over later calls (a change of `rowwise` allocates it anew), and saved by state_dict() as
         `<prefix>adagrad_sum`.  lr=None switches the step off (the state stays).  Switches a fused SGD off.  Returns self."""
+        _no_max_variants([self.mode], master_weights, stochastic_rounding)
         _set_sr(self, stochastic_rounding and lr is not None, sr_seed, [self._table_dtype], master_weights)
         object.__setattr__(self, "_fused_order", _order(order))
         if lr is None:
@@ -421,6 +427,10 @@ class PoolingEmbeddingBag(torch.nn.Module):
         if grad_output is None:
             return
         g = _grad_view(grad_output, self.embedding_dim)
+        if self.mode == "max":
+            _no_max_variants([self.mode], self.master_weight is not None, sr_seed not in (None, False))
+            self._context(idx, off, order).max_sgd_step(self._id_list, [idx], [off], [g], lr, padding_idx=self.padding_idx)
+            return
         if sr_seed not in (None, False):
             _check_sr([self._table_dtype], self.master_weight is not None)
         if self.master_weight is not None:
@@ -435,6 +445,11 @@ class PoolingEmbeddingBag(torch.nn.Module):
             return
         g = _grad_view(grad_output, self.embedding_dim)
         state = _adagrad_state(self)
+        if self.mode == "max":
+            _no_max_variants([self.mode], self.master_weight is not None, sr_seed not in (None, False))
+            self._context(idx, off, order).max_adagrad_step(self._id_list, [idx], [off], [g], [state], lr, eps=eps, rowwise=state.dim() == 1,
+                                                            padding_idx=self.padding_idx)
+            return
         if sr_seed not in (None, False):
             _check_sr([self._table_dtype], self.master_weight is not None)
         if self.master_weight is not None:
@@ -486,8 +501,11 @@ class PoolingEmbeddingBag(torch.nn.Module):
         padding entries.  The weight is not changed."""
         idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
         g = _grad_view(torch.as_tensor(grad_output).to(idx.device), self.embedding_dim)
-        rows, grads = self._context(idx, off, order).sparse_grad(
-            self.table_id, idx, off, g, mode=self.mode, per_sample_weights=w, padding_idx=self.padding_idx)
+        if self.mode == "max":           # (the rows the batch names, all-zero ones included: scattered dense it is torch's weight.grad)
+            rows, grads = self._context(idx, off, order).max_sparse_grad(self.table_id, idx, off, g, padding_idx=self.padding_idx)
+        else:
+            rows, grads = self._context(idx, off, order).sparse_grad(
+                self.table_id, idx, off, g, mode=self.mode, per_sample_weights=w, padding_idx=self.padding_idx)
         return torch.sparse_coo_tensor(rows.unsqueeze(0), grads, size=(self.num_embeddings, self.embedding_dim), is_coalesced=True)
 
     def sgd_step_(self, input, offsets, grad_output, lr: float, per_sample_weights=None, order: str = "position", stochastic_rounding: bool = False,
@@ -680,6 +698,13 @@ def _adagrad_state(bag, rowwise=None, init: float = 0.0):
     return s
 
 
+def _no_max_variants(modes, master_weights, stochastic_rounding, multi_table=False) -> None:
+    """The max-mode backward has the plain fused steps alone (include/pimemb_grad.h names what is not built)."""
+    if "max" in modes and (master_weights or stochastic_rounding or multi_table):
+        raise ValueError("a mode='max' table trains with the plain fused SGD / Adagrad steps only: there is no master-weight, stochastically "
+                         "rounded or multi-table form of the max-mode backward")
+
+
 def _grad_view(grad_output, dim: int):
     """A gradient the kernels can read in place: float32, [B, dim], inner stride 1, rows that do not overlap (the gradient of
     out.sum() is an expanded scalar: stride 0 -- that one is materialised)."""
@@ -848,6 +873,7 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         or the one [B, sum(m)] tensor of concat=True -- steps all of them.  multi_table=True: by the multi-table step (one
         pre-pass and one launch per group of up to 16 tables instead of per table; the same bytes).  order: as there.
         Returns self."""
+        _no_max_variants(self._modes, master_weights, stochastic_rounding, multi_table)
         _set_sr(self, stochastic_rounding, sr_seed, [b._table_dtype for b in self.bags], master_weights, multi_table)
         self._set_masters(master_weights, multi_table)
         object.__setattr__(self, "_fused_order", _order(order))
@@ -882,6 +908,7 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         """As PoolingEmbeddingBag.enable_fused_adagrad, for every table of the model: each bag holds its own state
         (bags[k].adagrad_sum, saved as `bags.<k>.adagrad_sum`), one call steps them all.  multi_table, order, master_weights,
         stochastic_rounding and sr_seed: as enable_fused_sgd.  Returns self."""
+        _no_max_variants(self._modes, master_weights, stochastic_rounding, multi_table)
         _set_sr(self, stochastic_rounding and lr is not None, sr_seed, [b._table_dtype for b in self.bags], master_weights, multi_table)
         self._set_masters(master_weights, multi_table)
         object.__setattr__(self, "_fused_order", _order(order))
@@ -975,7 +1002,7 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         holds the live tables' indices and bags all at once (their sums), so that the multi-table step can fuse them."""
         dims = [b.embedding_dim for b in self.bags]
         grads = self._table_grads(grad_output, col)
-        live = [k for k, g in enumerate(grads) if g is not None]
+        live = [k for k, g in enumerate(grads) if g is not None and self._modes[k] != "max"]      # (max-mode tables: _max_tables)
         if not live:
             return None
         size = sum if multi else max
@@ -986,8 +1013,20 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
                   padding_idx=[self._pads[k] for k in live])
         return ctx, args, kw, live
 
+    def _max_tables(self, grad_output, col, multi, order, sr_seed, step) -> None:
+        """The max-mode tables of the model, each stepped on its own through its bag (the max-mode backward has no multi-table form):
+        step(bag, k, gradient, order)."""
+        if "max" not in self._modes:
+            return
+        _no_max_variants(self._modes, self._masters_on(), sr_seed not in (None, False) or (sr_seed is None and self.sr_seed is not None), multi)
+        order = getattr(self, "_fused_order", "position") if order is None else _order(order)
+        for k, g in enumerate(self._table_grads(grad_output, col)):
+            if g is not None and self._modes[k] == "max":
+                step(self.bags[k], k, g, order)
+
     def _step(self, idx, off, grad_output, lr, ws, col=0, multi=None, order=None, sr_seed=None):
         multi = getattr(self, "_fused_multi", False) if multi is None else bool(multi)
+        self._max_tables(grad_output, col, multi, order, sr_seed, lambda b, k, g, o: b._step(idx[k], off[k], g, lr, None, o, False))
         call = self._live_grads(idx, off, grad_output, ws, col, multi, order)
         if call is not None:
             ctx, args, kw, live = call
@@ -1008,6 +1047,7 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
 
     def _adagrad(self, idx, off, grad_output, lr, eps, ws, col=0, multi=None, order=None, sr_seed=None):
         multi = getattr(self, "_fused_multi", False) if multi is None else bool(multi)
+        self._max_tables(grad_output, col, multi, order, sr_seed, lambda b, k, g, o: b._adagrad(idx[k], off[k], g, lr, eps, None, o, False))
         call = self._live_grads(idx, off, grad_output, ws, col, multi, order)
         if call is None:
             return
