@@ -1,6 +1,7 @@
 /*
  * pimemb_grad.h -- C ABI of the backward pass (libpimemb_grad.so): from the gradient of a pooled lookup's output to the
- * sparse gradient of the table, or straight to new table rows by a fused SGD, Adagrad or row-wise Adagrad step -- on the GPU,
+ * sparse gradient of the table, or straight to new table rows by a fused SGD, Adagrad, row-wise Adagrad, SparseAdam or row-wise Adam
+ * step -- on the GPU,
  * in stream order with the lookups and the row writer, every sum in a fixed order: results are the same bits on every run.
  *
  * A companion library like libpimemb_rows.so, not part of libpimemb.so: it carries its own gfx950 code object and reaches tables
@@ -50,8 +51,10 @@
  * Prepared plans stay valid over a stepped table and read the new rows when launched behind the step.
  * emb_grad_step (below) is the same step with an optimizer that keeps state: Adagrad, and row-wise Adagrad.
  * emb_grad_weights (THE GRADIENT OF PER_SAMPLE_WEIGHTS, below) is the other gradient of a weighted sum: one value per position.
- * Out of scope: optimizers other than SGD, Adagrad and row-wise
- * Adagrad (no momentum, no Adam), weight decay and lr_decay, optimizer state in anything but fp32; row-wise Adagrad off the
+ * emb_grad_adam_step (THE ADAM STEPS, below) is the step with SparseAdam or row-wise Adam: two states and an enum, a spec and an entry
+ * point of their own.
+ * Out of scope: optimizers other than SGD, Adagrad, row-wise Adagrad, SparseAdam and row-wise Adam (no momentum SGD, no amsgrad),
+ * weight decay and lr_decay, optimizer state in anything but fp32; row-wise Adagrad off the
  * lane-group shape (the element-wise kernel has no row-wide view of g, and a second reduction is not built for it:
  * EMB_ERR_UNSUPPORTED); a multi-table emb_grad_sparse (it stays single; emb_grad_sgd_multi / emb_grad_step_multi below fuse the
  * steps of several tables); fusing descriptors of different dim, or of the element-wise shape, into one launch (they run on
@@ -545,6 +548,88 @@ int emb_grad_max_sgd(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *w
                      void *stream);
 int emb_grad_max_step(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *winners, float *const *states, uint32_t n_descs,
                       emb_index_type itype, const emb_opt_spec *opt, void *stream);
+
+/* THE ADAM STEPS (tests/adam_ref.py restates them as loops; the kernels are compared with that, bit for bit).  g[r], U, good / bad /
+ * padding positions, dec, enc and the context's order of additions (position or segmented) are the ones defined at the top.  Every fp32
+ * operation below is rounded on its own and never contracted into an FMA; division and square root are the IEEE correctly rounded ones of
+ * csrc/pimemb_grad_optim.h (csrc/pimemb_grad_adam.h: the one-element arithmetic, compiled by the kernels and by a host check alike).  Both
+ * states are fp32 whatever the table's dtype, live in buffers of the caller's, and are initialised by the caller (torch: zeros).
+ *
+ * Constants, computed once per call on the HOST, in double, then rounded to fp32 (emb_adam_constants returns them):
+ *       om1 = (float)(1.0 - beta1)
+ *       om2 = (float)(1.0 - beta2)
+ *       ss  = (float)(lr * sqrt(1.0 - pow(beta2, t)) / (1.0 - pow(beta1, t)))           t = step >= 1
+ *   -- what torch.optim.SparseAdam computes in Python floats and then casts; the spec therefore carries lr, beta1 and beta2 as double.
+ *
+ * EMB_ADAM: torch.optim.SparseAdam, the "lazy" Adam: only the rows of U move, their moments included.  M (exp_avg) and V (exp_avg_sq) are
+ * float[nr_rows][dim] each, no padding.  For every r in U and every element d, with g = g[r][d], M = M[r][d], V = V[r][d]:
+ *       dm  = g - M;    um = dm * om1;    M' = M + um
+ *       q   = g * g;    dv = q - V;       uv = dv * om2;    V' = V + uv
+ *       den = sqrt(V') + eps
+ *       x   = M' / den
+ *       W'[r][d] = enc(dec(W[r][d]) - (ss * x))          M[r][d] = M',  V[r][d] = V'
+ *
+ * EMB_ROWWISE_ADAM: the FBGEMM "partial row-wise" form, one second moment per row.  M is float[nr_rows][dim], V is float[nr_rows]: a
+ * [4 M, 128] table carries 2 GB + 16 MB of state instead of 4 GB.  For every r in U:
+ *       ms   = EMB_OPT_ROWWISE_ADAGRAD's m of g[r], exactly: the same squares, the same 4-fold t[c], the same pair tree v, v[0] / (float)dim
+ *       dv   = ms - V[r];    uv = dv * om2;    V' = V[r] + uv
+ *       rate = ss / (sqrt(V') + eps)                      (one division per row)
+ *       M'[d] as above;    W'[r][d] = enc(dec(W[r][d]) - (rate * M'[d]))         M[r][d] = M'[d],  V[r] = V'
+ * Rows outside U keep their table, M and V bytes.  g is never written to memory.  NaN payloads are unspecified.  V' = 0 with eps = 0 gives
+ * 0 / 0 or ss / 0 as the arithmetic says (a NaN, an inf): eps > 0 avoids it, as in the Adagrad steps.
+ *
+ * emb_grad_adam_step runs descriptor after descriptor (a table named twice is stepped twice, in order, with the same t): DEVICE pointers
+ * only; exp_avg[k] / exp_avg_sq[k] are the states of descs[k]'s table, emb_adam_state_floats floats each; a pure enqueue on `stream` -- no
+ * allocation, no copy, no host wait: it can be captured in a graph.  Everything is checked before anything is enqueued: a refused call leaves
+ * every table and state as it was.
+ *   step_size_dev        NULL, or a DEVICE float the kernels read INSTEAD of ss when they run: how a captured graph replays with a new t --
+ *                        the caller writes emb_adam_constants' third value for the new t into that word between replays (om1 and om2 do
+ *                        not depend on t).
+ *   Refused as emb_grad_step refuses: fp8 / MXFP4 / fixed-point tables, a staged hot set, EMB_POOL_MAX, the context's limits.
+ *   EMB_ERR_INVALID      a NULL or not 4-byte aligned M or V where n_indices > 0; an unknown kind; reserved != 0; a beta outside [0, 1);
+ *                        eps negative or NaN; lr not finite; step 0; a step_size_dev that is not 4-byte aligned (the spec is checked
+ *                        before the context is looked at).
+ *   Kernel shape         EMB_ROWWISE_ADAM needs the lane-group shape (dim % 4 == 0, dim <= 512, grad 16-byte aligned, grad_ld % 4 == 0) with
+ *                        a 16-byte aligned M, and is EMB_ERR_UNSUPPORTED otherwise.  EMB_ADAM runs the lane-group kernel where that shape
+ *                        holds and M and V are 16-byte aligned, the element-wise kernel otherwise, with the same bits.
+ *   Tables EMB_F32, EMB_F16, EMB_BF16; uint32 and int64 ids; sum, weighted sum, mean and padding; a context of either order.
+ * How the tail runs.  It moves three streams -- the table piece, the piece of M, the piece of V (row-wise: V[r]) -- where the Adagrad tail
+ * moves two; their loads are issued together behind the run walk.  Issuing them at the run head, before the walk, was built and measured
+ * and LOST: 12 more registers across the walk cost the SparseAdam kernels two waves per SIMD of seven, and the step was 10 % slower on the
+ * uniform shape and 2 - 3 % on the Kaggle one (profiles/adam/README.md).  Beyond dim 256, where a lane owns two pieces, SparseAdam takes
+ * them one after the other; row-wise Adam walks both, keeps both sums, and steps piece after piece once the row's rate is known.  V[r] is
+ * loaded by every lane at the run head and stored by lane 0; M pieces are stored as 16-byte vectors, the table piece as step_piece packs it.
+ * No scratch, no spills, no LDS; grad_adam_rows_group takes 65 / 70 VGPRs (SparseAdam: position / segmented order) and 63 / 64 (row-wise):
+ * 7 and 8 waves per SIMD, what the Adagrad kernels leave (63 - 68).
+ * Speed, measured on MI355X (tools/adam_probe.py, profiles/adam/README.md; medians of five alternating rounds, device pointers, the Adagrad
+ * steps measured again in the same run; dim 128, 2048 bags x 32, 4 M rows).  Uniform ids: SparseAdam 89.9 us on fp32 and 87.3 us on bf16
+ * tables, 1.13x SLOWER than the Adagrad step (79.7 / 77.5 us); row-wise Adam 85.4 / 82.0 us, 1.13x / 1.08x SLOWER than row-wise Adagrad
+ * (75.3 / 75.9 us); torch's GPU sparse backward + SparseAdam.step(): 484 us (fp32), 5.4x slower.  The Kaggle shape (dim 16, 39 292 one-index
+ * bags): 58.7 / 62.9 us against 51.7 / 51.8 for Adagrad (1.14x / 1.21x SLOWER), row-wise 59.6 / 63.0 against 50.4 / 52.2; torch 359 us.
+ * Zipf ids, S = 64 context: 142.5 / 140.9 us against 136.8 / 136.4 for Adagrad, 1.04x / 1.03x SLOWER; row-wise 139.7 / 139.5 against 136.4 /
+ * 136.6; torch 5.7 ms.
+ * The kernels (grad_adam_rows_group: two kinds, two orders; grad_adam_rows_elem: EMB_ADAM, two orders) have a code object of their own,
+ * libpimemb_grad_adam.so, built from the same source and found next to libpimemb_grad.so, which links against it; the other libraries'
+ * code objects hold the machine code they held.
+ * Out of scope: multi-table, master-weight, stochastically rounded and max-mode forms of the Adam steps; amsgrad, weight_decay and
+ * maximize; state in anything but fp32; the ranged / sharded paths. */
+typedef enum { EMB_ADAM = 1, EMB_ROWWISE_ADAM = 2 } emb_adam_kind;
+typedef struct emb_adam_spec {
+    uint32_t kind;              /* an emb_adam_kind */
+    float eps;                  /* >= 0 */
+    double lr, beta1, beta2;    /* lr finite; the betas in [0, 1) */
+    uint64_t step;              /* t >= 1 */
+    const float *step_size_dev; /* NULL, or a DEVICE float the kernels read INSTEAD of ss */
+    uint64_t reserved;          /* 0 */
+} emb_adam_spec;
+
+/* out = {om1, om2, ss} of the spec: a pure host function (EMB_ERR_INVALID for a spec emb_grad_adam_step refuses, or a NULL out). */
+int emb_adam_constants(const emb_adam_spec *spec, float out[3]);
+/* Floats of state a table of nr_rows x dim needs; which: 0 = M (exp_avg), 1 = V (exp_avg_sq).  nr_rows * dim, but nr_rows for the V of
+ * EMB_ROWWISE_ADAM; 0 for an unknown kind or which.  A pure function. */
+uint64_t emb_adam_state_floats(uint32_t kind, uint64_t nr_rows, uint32_t dim, int which);
+int emb_grad_adam_step(emb_grad *g, const emb_grad_desc *descs, float *const *exp_avg, float *const *exp_avg_sq, uint32_t n_descs,
+                       emb_index_type itype, const emb_adam_spec *spec, void *stream);
 
 /* The number of EMB_MXFP4 rows master steps left unwritten (an inf or a NaN in the new master row) since the last such report;
  * resets the count.  Waits for the device first, like emb_grad_report, whose count of bad positions is a separate one. */

@@ -32,6 +32,9 @@
 //   grad_sr_rows_group / grad_sr_rows_elem     the hot kernels' twins in both orders: the same walk, the last rounding by a Philox word
 // The Adagrad tails (csrc/pimemb_grad_optim.h) end the same kernels; the row-wise one sums the row's squares over its lane group
 // with an xor butterfly -- a fixed tree, stated over dim alone in the header: the same bits on every run.
+// The Adam steps (emb_grad_adam_step; csrc/pimemb_grad_adam.h; a code object of their own, libpimemb_grad_adam.so):
+//   grad_adam_rows_group / grad_adam_rows_elem     the hot kernels' twins in both orders with the SparseAdam and row-wise Adam tails: the
+//                       table piece, the piece of exp_avg and the piece of exp_avg_sq (row-wise: V[r]) loaded together behind the walk
 // The max-mode backward (emb_grad_max_*; csrc/pimemb_grad_max.h; a code object of its own, libpimemb_grad_max.so):
 //   grad_max_winners_group / grad_max_winners_elem     one lane group per BAG (or one thread per bag element): the position that won
 //                       every element of the forward's max, the row gathers of eight positions in flight before the first compare
@@ -52,6 +55,7 @@
 #include <vector>
 
 #include "pimemb_grad.h"
+#include "pimemb_grad_adam.h"
 #include "pimemb_grad_dot.h"
 #include "pimemb_grad_master.h"
 #include "pimemb_grad_max.h"
@@ -60,10 +64,10 @@
 #include "pimemb_grad_sr.h"
 #include "pimemb_grad_step.h"
 
-// This file is compiled four times (csrc/Makefile): as libpimemb_grad.so, and with -DPIMEMB_GRAD_MASTER_UNIT / -DPIMEMB_GRAD_SR_UNIT /
-// -DPIMEMB_GRAD_MAX_UNIT as the code objects of the master-weight steps, the stochastically rounded steps and the max-mode backward,
-// which hold their own kernels and launchers alone.
-#if defined(PIMEMB_GRAD_MASTER_UNIT) || defined(PIMEMB_GRAD_SR_UNIT) || defined(PIMEMB_GRAD_MAX_UNIT)
+// This file is compiled five times (csrc/Makefile): as libpimemb_grad.so, and with -DPIMEMB_GRAD_MASTER_UNIT / -DPIMEMB_GRAD_SR_UNIT /
+// -DPIMEMB_GRAD_MAX_UNIT / -DPIMEMB_GRAD_ADAM_UNIT as the code objects of the master-weight steps, the stochastically rounded steps, the
+// max-mode backward and the Adam steps, which hold their own kernels and launchers alone.
+#if defined(PIMEMB_GRAD_MASTER_UNIT) || defined(PIMEMB_GRAD_SR_UNIT) || defined(PIMEMB_GRAD_MAX_UNIT) || defined(PIMEMB_GRAD_ADAM_UNIT)
 #define PIMEMB_GRAD_KERNEL_UNIT 1
 #endif
 
@@ -1327,6 +1331,199 @@ extern "C" void pimemb_grad_sr_launch(const void *row_args, const void *seg_args
 namespace {
 #endif
 
+// ---- the Adam steps: SparseAdam and row-wise Adam (csrc/pimemb_grad_adam.h) ----------------------------------------------------------
+// The same pre-pass, sort, segment launch and run walk.  The tail moves three streams where step_piece moves one or two -- the table
+// piece, the piece of exp_avg and the piece of exp_avg_sq (row-wise: V[r]) -- and issues their loads together, BEHIND the walk, before
+// the first of them is used.  Issuing them at the run head, before the walk, was built and measured (profiles/adam/README.md): the 12
+// registers held across the walk took the SparseAdam kernels from 65 / 70 to 85 / 92 VGPRs -- from 7 waves per SIMD to 5 -- and the step
+// was 10 % SLOWER on the uniform shape and 2 - 3 % on the Kaggle one, so the loads stay behind the walk; V[r] alone, one register, is
+// loaded at the head.  The kernels above keep their text: what is new travels in AdamArgs beside RowArgs, of which a.table / a.stride /
+// a.dtype / a.dim are used and a.lr / a.eps / a.state are not.
+
+struct AdamArgs {
+    float *m;                    // exp_avg: float[nr_rows][dim], no padding
+    float *v;                    // exp_avg_sq: float[nr_rows][dim], or float[nr_rows] row-wise
+    float om1, om2, ss, eps;     // 1 - beta1, 1 - beta2, the step size of this call's t, eps
+    const float *step_size_dev;  // or NULL: a device float read INSTEAD of ss when the kernel runs (a captured graph replays with a new t)
+};
+
+enum AdamKind : int { ADAM_ELEMENTS = EMB_ADAM, ADAM_ROWWISE = EMB_ROWWISE_ADAM };
+
+// Like the master, SR and max kernels these live in a code object of their own: this file compiled with -DPIMEMB_GRAD_ADAM_UNIT into
+// libpimemb_grad_adam.so (csrc/Makefile), which exports their launch function; libpimemb_grad.so's host side calls it.
+#ifdef PIMEMB_GRAD_ADAM_UNIT
+
+// The step size of this launch: one uniform load (or none), the same word in every lane.
+__device__ __forceinline__ float adam_step_size(const AdamArgs &ad) { return ad.step_size_dev ? *ad.step_size_dev : ad.ss; }
+
+// What a lane loads of piece c of a stepped row for the tail: the table piece as it lies in memory (16 bytes of an fp32 row, or 8 bytes
+// of an fp16 / bf16 row in w.x and w.y), the piece of M, and (ADAM_ELEMENTS) the piece of V.
+struct AdamRaw {
+    uint32_t x, y, z, w;
+} __attribute__((aligned(16)));
+struct AdamPiece {
+    AdamRaw w;
+    float4 m, v;
+};
+
+// The loads of the tail: two or three independent vector loads, issued together -- nothing here uses what they return.
+template <int KIND>
+__device__ __forceinline__ AdamPiece adam_load_piece(const RowArgs &a, const AdamArgs &ad, uint32_t row, uint32_t c) {
+    AdamPiece h;
+    h.v = make_float4(0.f, 0.f, 0.f, 0.f);
+    h.w = AdamRaw{0u, 0u, 0u, 0u};
+    h.m = reinterpret_cast<const float4 *>(ad.m + (uint64_t)row * a.dim)[c];
+    if (KIND == ADAM_ELEMENTS) h.v = reinterpret_cast<const float4 *>(ad.v + (uint64_t)row * a.dim)[c];
+    if (a.dtype == kStepF32) {
+        h.w = reinterpret_cast<const AdamRaw *>(a.table + (uint64_t)row * a.stride)[c];
+    } else {
+        const u32x2 half = reinterpret_cast<const u32x2 *>(a.table + (uint64_t)row * a.stride)[c];
+        h.w.x = half.x, h.w.y = half.y;
+    }
+    return h;
+}
+
+// One element of the tail.  `rate` is the call's step size ss (ADAM_ELEMENTS) or the row's rate (ADAM_ROWWISE, whose V is the row's).
+template <int KIND>
+__device__ __forceinline__ uint32_t adam_elem(const RowArgs &a, const AdamArgs &ad, uint32_t stored, float g, float *m, float *v, float rate) {
+    if (KIND == ADAM_ELEMENTS) return adam_step(a.dtype, stored, g, m, v, ad.om1, ad.om2, rate, ad.eps);
+    return rowwise_adam_step(a.dtype, stored, g, m, ad.om1, rate);
+}
+
+// The tail of piece c: the arithmetic on what adam_load_piece loaded and the stores -- M' (and V') as 16-byte vectors, the table piece as ONE
+// vector store of 16 bytes (fp32) or 8 bytes (fp16 / bf16), packed as step_piece packs it.
+template <int KIND>
+__device__ __forceinline__ void adam_store_piece(const RowArgs &a, const AdamArgs &ad, uint32_t row, uint32_t c, AdamPiece h, float4 g, float rate) {
+    if (a.dtype == kStepF32) {
+        AdamRaw w;
+        w.x = adam_elem<KIND>(a, ad, h.w.x, g.x, &h.m.x, &h.v.x, rate);
+        w.y = adam_elem<KIND>(a, ad, h.w.y, g.y, &h.m.y, &h.v.y, rate);
+        w.z = adam_elem<KIND>(a, ad, h.w.z, g.z, &h.m.z, &h.v.z, rate);
+        w.w = adam_elem<KIND>(a, ad, h.w.w, g.w, &h.m.w, &h.v.w, rate);
+        reinterpret_cast<AdamRaw *>(a.table + (uint64_t)row * a.stride)[c] = w;
+    } else {
+        u32x2 o;
+        o.x = adam_elem<KIND>(a, ad, h.w.x & 0xffffu, g.x, &h.m.x, &h.v.x, rate) | (adam_elem<KIND>(a, ad, h.w.x >> 16, g.y, &h.m.y, &h.v.y, rate) << 16);
+        o.y = adam_elem<KIND>(a, ad, h.w.y & 0xffffu, g.z, &h.m.z, &h.v.z, rate) | (adam_elem<KIND>(a, ad, h.w.y >> 16, g.w, &h.m.w, &h.v.w, rate) << 16);
+        reinterpret_cast<u32x2 *>(a.table + (uint64_t)row * a.stride)[c] = o;
+    }
+    reinterpret_cast<float4 *>(ad.m + (uint64_t)row * a.dim)[c] = h.m;
+    if (KIND == ADAM_ELEMENTS) reinterpret_cast<float4 *>(ad.v + (uint64_t)row * a.dim)[c] = h.v;
+}
+
+// grad_rows_group / grad_seg_rows_group with the Adam tails: the same exits, the same walks, the same row-wise butterfly (idle lanes hold
+// +0 and take part).  Row-wise, every lane loads V[r] at the head of the run -- before lane 0 stores V' -- and nothing else is loaded before
+// the walk.  Beyond dim 256 a lane owns two pieces: SparseAdam takes them one after the other; row-wise Adam holds both sums until the
+// row's rate is known, then loads and steps piece after piece.
+template <int KIND, bool SEG>
+__global__ __launch_bounds__(kBlock) void grad_adam_rows_group(RowArgs a, SegArgs sg, AdamArgs ad, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    static_assert(KIND == ADAM_ELEMENTS || KIND == ADAM_ROWWISE, "an Adam kind");
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= a.n || (KIND != ADAM_ROWWISE && lg >= chunks)) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;      // (uniform over the lane group)
+    const float ss = adam_step_size(ad);
+    if (KIND == ADAM_ROWWISE) {
+        const bool own0 = lg < chunks, own1 = lg + lanes < chunks;        // (own1: beyond dim 256 only, where lanes == 64)
+        float vr = ad.v[row];                                             // (every lane's own copy of V[r]: loaded before lane 0 stores V')
+        float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
+        if (own0) acc0 = SEG ? seg_walk_piece(a, sg, i, row, lg, chunks) : walk_piece(a, i, row, lg);
+        if (own1) acc1 = SEG ? seg_walk_piece(a, sg, i, row, lg + lanes, chunks) : walk_piece(a, i, row, lg + lanes);
+        float sum = piece_squares(acc0);                                  // (+0 in a lane without a piece)
+        if (own1) sum = adagrad_add(sum, piece_squares(acc1));
+        for (uint32_t h = 1; h < lanes; h <<= 1) sum = adagrad_add(sum, __shfl_xor(sum, (int)h));      // the pair tree: the same bits in every lane
+        const float rate = rowwise_adam_rate(sum, a.dim, &vr, ad.om2, ss, ad.eps);
+        if (lg == 0) ad.v[row] = vr;
+        if (own0) adam_store_piece<KIND>(a, ad, row, lg, adam_load_piece<KIND>(a, ad, row, lg), acc0, rate);
+        if (own1) adam_store_piece<KIND>(a, ad, row, lg + lanes, adam_load_piece<KIND>(a, ad, row, lg + lanes), acc1, rate);
+        return;
+    }
+    for (uint32_t c = lg; c < chunks; c += lanes) {
+        const float4 acc = SEG ? seg_walk_piece(a, sg, i, row, c, chunks) : walk_piece(a, i, row, c);
+        adam_store_piece<KIND>(a, ad, row, c, adam_load_piece<KIND>(a, ad, row, c), acc, ss);
+    }
+}
+
+// grad_rows_elem / grad_seg_rows_elem with the SparseAdam tail: one thread per (sorted place, element), the segments of a run folded in
+// that thread.  (No row-wise kind: no thread here sees a whole row of g.)
+template <int KIND, bool SEG>
+__global__ __launch_bounds__(kBlock) void grad_adam_rows_elem(RowArgs a, AdamArgs ad, uint32_t S) {
+    static_assert(KIND == ADAM_ELEMENTS, "the element-wise kernel has no row-wide view of g");
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid / a.dim;
+    const uint32_t c = (uint32_t)(gid - i64 * a.dim);
+    if (i64 >= a.n) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;
+    float *mp = ad.m + (uint64_t)row * a.dim + c, *vp = ad.v + (uint64_t)row * a.dim + c;
+    char *wp = a.table + (uint64_t)row * a.stride;
+    float m = *mp, v = *vp;                      // the head's loads, as in the lane-group kernel
+    const uint32_t stored = a.dtype == kStepF32 ? reinterpret_cast<const uint32_t *>(wp)[c] : reinterpret_cast<const uint16_t *>(wp)[c];
+    float acc = 0.f, t = 0.f;
+    uint32_t in_seg = 0;
+    bool first = true;                           // (SEG) t_0 is taken as it is: the sum of the partials starts from it
+    for (uint32_t j = i; j < a.n && a.keys[j] == row; j++) {
+        const uint32_t p = min(a.vals[j], a.n - 1u);
+        const uint32_t b = min(a.bagof[p], a.n_bags - 1u);
+        const float cp = contribution(a.coef, a.grad[(uint64_t)b * a.ld + c], coef_of(a, p, b));
+        if (!SEG) {
+            acc = add_in_order(acc, cp);
+            continue;
+        }
+        t = add_in_order(t, cp);
+        if (++in_seg == S) {
+            acc = first ? t : add_in_order(acc, t);
+            first = false;
+            t = 0.f;
+            in_seg = 0;
+        }
+    }
+    if (SEG && in_seg) acc = first ? t : add_in_order(acc, t);
+    const uint32_t o = adam_step(a.dtype, stored, acc, &m, &v, ad.om1, ad.om2, adam_step_size(ad), ad.eps);
+    if (a.dtype == kStepF32) reinterpret_cast<uint32_t *>(wp)[c] = o;
+    else reinterpret_cast<uint16_t *>(wp)[c] = (uint16_t)o;
+    *mp = m;
+    *vp = v;
+}
+
+}  // namespace
+
+// The launch function libpimemb_grad_adam.so exports (plain C; RowArgs, SegArgs and AdamArgs are this file's own, which every compilation
+// lays out alike).  The hot launch of an Adam step (a chain of one): the lane-group kernel or the element-wise one, in the context's
+// order.  kind: an emb_adam_kind.  Errors are left to the caller's hipGetLastError().
+extern "C" __attribute__((visibility("default"))) void pimemb_grad_adam_launch(const void *row_args, const void *seg_args, const void *adam_args, int kind,
+                                                                                int seg, int lane, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks,
+                                                                                uint32_t blocks, uint32_t elem_blocks, uint32_t S, void *stream) {
+    const RowArgs &a = *static_cast<const RowArgs *>(row_args);
+    const SegArgs &sg = *static_cast<const SegArgs *>(seg_args);
+    const AdamArgs &ad = *static_cast<const AdamArgs *>(adam_args);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 block(kBlock);
+    if (lane) {
+        const dim3 grid(blocks);
+        if (kind == ADAM_ELEMENTS && seg) grad_adam_rows_group<ADAM_ELEMENTS, true><<<grid, block, 0, s>>>(a, sg, ad, lanes, lanes_log2, chunks);
+        else if (kind == ADAM_ELEMENTS) grad_adam_rows_group<ADAM_ELEMENTS, false><<<grid, block, 0, s>>>(a, sg, ad, lanes, lanes_log2, chunks);
+        else if (seg) grad_adam_rows_group<ADAM_ROWWISE, true><<<grid, block, 0, s>>>(a, sg, ad, lanes, lanes_log2, chunks);
+        else grad_adam_rows_group<ADAM_ROWWISE, false><<<grid, block, 0, s>>>(a, sg, ad, lanes, lanes_log2, chunks);
+        return;
+    }
+    const dim3 grid(elem_blocks);                // (the row-wise kind never gets here: the plan refused it)
+    if (seg) grad_adam_rows_elem<ADAM_ELEMENTS, true><<<grid, block, 0, s>>>(a, ad, S);
+    else grad_adam_rows_elem<ADAM_ELEMENTS, false><<<grid, block, 0, s>>>(a, ad, 0u);
+}
+
+namespace {
+#else      // libpimemb_grad.so (and the other units, which never call it): the launcher is libpimemb_grad_adam.so's
+}  // namespace
+extern "C" void pimemb_grad_adam_launch(const void *row_args, const void *seg_args, const void *adam_args, int kind, int seg, int lane, uint32_t lanes,
+                                        uint32_t lanes_log2, uint32_t chunks, uint32_t blocks, uint32_t elem_blocks, uint32_t S, void *stream);
+namespace {
+#endif
+
 // ---- the gradient of per_sample_weights: dw[p] = < G[bag(p)] , dec(W[ids[p]]) > (csrc/pimemb_grad_dot.h) ------------------------
 // No pre-pass: nothing is sorted, a position's value depends on its own row and its bag's row of G alone.  The kernels above keep
 // their text; these read the batch as the forward does.
@@ -2040,6 +2237,12 @@ struct StepSpec {
     float *const *masters = nullptr;      // emb_grad_master_step: one fp32 master per descriptor; the kind's master tail runs
     const emb_sr_spec *sr = nullptr;      // emb_grad_sgd_sr / emb_grad_step_sr: the kind's stochastically rounded tail runs
     uint32_t *const *winners = nullptr;   // emb_grad_max_*: one winners buffer per descriptor; the kind's walk selects by it
+    const struct AdamCall *adam = nullptr;      // emb_grad_adam_step: the Adam tails run (kind is RES_ADAGRAD or RES_ROWWISE, by the shape of V)
+};
+struct AdamCall {                // what emb_grad_adam_step hands the chains: the states of every descriptor and the call's constants
+    float *const *m, *const *v;
+    int kind;                    // an emb_adam_kind
+    AdamArgs consts;             // om1, om2, ss, eps, step_size_dev (m and v are filled per descriptor)
 };
 struct SparseOut {               // where emb_grad_sparse writes; all NULL for a step (no unique numbering, no output arrays)
     long long *rows = nullptr;
@@ -2220,7 +2423,7 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
     const dim3 block(kBlock), pos_grid((n + kBlock - 1) / kBlock);
     unsigned long long *bad = &g->counters[0];
     MultiArgs m;                                 // (filled for a group only)
-    if (c.mean && c.n_bags && (spec.masters || spec.sr)) pimemb_grad_master_clear(sc.cnt, c.n_bags, s);      // (a kernel: the note at grad_master_clear)
+    if (c.mean && c.n_bags && (spec.masters || spec.sr || spec.adam)) pimemb_grad_master_clear(sc.cnt, c.n_bags, s);      // (a kernel: the note at grad_master_clear)
     else if (c.mean && c.n_bags) GRAD_HIP(hipMemsetAsync(sc.cnt, 0, (size_t)c.n_bags * 4, s));
     if (group) {
         fill_multi(m, descs, states, p, first);
@@ -2298,6 +2501,14 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
         if (seg && c.lane) grad_seg_partials<<<dim3(l.blocks), block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
         const SrArgs sr{spec.sr->seed, spec.sr->step + first, spec.sr->step_dev};      // (descriptor k of the call: t = step + *step_dev + k, mod 2^64)
         pimemb_grad_sr_launch(&a, &sg, &sr, spec.kind, seg, c.lane, l.lanes, l.lanes_log2, l.chunks, l.blocks, c.elem_blocks, g->cfg.segment, s);
+        GRAD_HIP(hipGetLastError());
+        return EMB_OK;
+    }
+    if (spec.adam) {
+        if (seg && c.lane) grad_seg_partials<<<dim3(l.blocks), block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
+        AdamArgs ad = spec.adam->consts;
+        ad.m = spec.adam->m[first], ad.v = spec.adam->v[first];
+        pimemb_grad_adam_launch(&a, &sg, &ad, spec.adam->kind, seg, c.lane, l.lanes, l.lanes_log2, l.chunks, l.blocks, c.elem_blocks, g->cfg.segment, s);
         GRAD_HIP(hipGetLastError());
         return EMB_OK;
     }
@@ -2735,6 +2946,87 @@ int emb_grad_max_step(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *
     StepSpec spec{opt->kind == EMB_OPT_ROWWISE_ADAGRAD ? RES_ROWWISE : RES_ADAGRAD, opt->lr, opt->eps};
     spec.winners = winners;
     return max_call(g, descs, winners, states, n_descs, itype, spec, spec.kind, "an Adagrad", who, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- the Adam steps: emb_adam_constants / emb_adam_state_floats / emb_grad_adam_step -----------------------------------------------
+
+// Everything that can be refused about an emb_adam_spec; NULL text: it is fine.
+const char *adam_fault(const emb_adam_spec *sp) {
+    if (!sp) return "the Adam spec is NULL";
+    if (sp->kind != EMB_ADAM && sp->kind != EMB_ROWWISE_ADAM) return "unknown Adam kind";
+    if (sp->reserved != 0) return "the spec's reserved field must be 0";
+    if (!(sp->beta1 >= 0.0 && sp->beta1 < 1.0) || !(sp->beta2 >= 0.0 && sp->beta2 < 1.0)) return "beta1 and beta2 must lie in [0, 1)";
+    if (!(sp->eps >= 0.f)) return "eps must not be negative or NaN";
+    if (!(sp->lr - sp->lr == 0.0)) return "lr must be finite";
+    if (sp->step == 0) return "step counts from 1";
+    if ((uintptr_t)sp->step_size_dev % 4) return "step_size_dev is not 4-byte aligned";
+    return nullptr;
+}
+
+// The plan of emb_grad_adam_step: every descriptor and both states checked, in order; then one chain per non-empty descriptor.
+int plan_adam(emb_grad *g, const emb_grad_desc *descs, const AdamCall &call, uint32_t n_descs, emb_index_type itype, const char *who, Planned *plan) {
+    const bool rowwise = call.kind == EMB_ROWWISE_ADAM;
+    for (uint32_t k = 0; k < n_descs; k++) {
+        const emb_grad_desc &d = descs[k];
+        Planned &p = plan[k];
+        if (int rc = check_desc(g, d, itype, "an Adam", who, &p.t)) return rc;
+        if (d.n_indices == 0) continue;
+        const float *m = call.m[k], *v = call.v[k];
+        if (!m || !v || (uintptr_t)m % 4 || (uintptr_t)v % 4)
+            return fail(EMB_ERR_INVALID, "%s: exp_avg or exp_avg_sq of table %u is NULL or not 4-byte aligned", who, d.table_id);
+        p.lane = lane_group_path(d, p.t, RES_SGD, nullptr, nullptr) && (uintptr_t)m % 16 == 0 && (rowwise || (uintptr_t)v % 16 == 0);
+        if (rowwise && !p.lane)
+            return fail(EMB_ERR_UNSUPPORTED,
+                        "%s: row-wise Adam needs the lane-group shape (dim %% 4 == 0, dim <= 512, grad and exp_avg 16-byte aligned, grad_ld %% 4 == 0): "
+                        "table %u has dim %u, grad %p, grad_ld %llu, exp_avg %p -- the element-wise kernel has no row-wide view of g", who, d.table_id,
+                        p.t.dim, (const void *)d.grad, (unsigned long long)d.grad_ld, (const void *)m);
+    }
+    for (uint32_t k = 0; k < n_descs; k++)
+        if (descs[k].n_indices)
+            if (int rc = plan_chain(g, descs, plan, k, k + 1)) return rc;
+    return EMB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int emb_adam_constants(const emb_adam_spec *spec, float out[3]) {
+    if (const char *fault = adam_fault(spec)) return fail(EMB_ERR_INVALID, "emb_adam_constants: %s", fault);
+    if (!out) return fail(EMB_ERR_INVALID, "emb_adam_constants: out is NULL");
+    adam_constants(spec->lr, spec->beta1, spec->beta2, spec->step, out);
+    return EMB_OK;
+}
+
+uint64_t emb_adam_state_floats(uint32_t kind, uint64_t nr_rows, uint32_t dim, int which) {
+    if ((kind != EMB_ADAM && kind != EMB_ROWWISE_ADAM) || (which != 0 && which != 1)) return 0;
+    return kind == EMB_ROWWISE_ADAM && which == 1 ? nr_rows : nr_rows * dim;
+}
+
+int emb_grad_adam_step(emb_grad *g, const emb_grad_desc *descs, float *const *exp_avg, float *const *exp_avg_sq, uint32_t n_descs, emb_index_type itype,
+                       const emb_adam_spec *spec, void *stream) {
+    const char *who = "emb_grad_adam_step";
+    if (const char *fault = adam_fault(spec)) return fail(EMB_ERR_INVALID, "%s: %s", who, fault);
+    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
+    if (n_descs && (!descs || !exp_avg || !exp_avg_sq)) return fail(EMB_ERR_INVALID, "%s: descs, exp_avg or exp_avg_sq is NULL", who);
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    float c[3];
+    adam_constants(spec->lr, spec->beta1, spec->beta2, spec->step, c);
+    const AdamCall call{exp_avg, exp_avg_sq, (int)spec->kind, AdamArgs{nullptr, nullptr, c[0], c[1], c[2], spec->eps, spec->step_size_dev}};
+    StepSpec st{spec->kind == EMB_ROWWISE_ADAM ? RES_ROWWISE : RES_ADAGRAD, 0.f, spec->eps};
+    st.adam = &call;
+    std::vector<Planned> plan(n_descs);
+    if (int rc = plan_adam(g, descs, call, n_descs, itype, who, plan.data())) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    for (uint32_t k = 0; k < n_descs; k++)
+        if (plan[k].k)
+            if (int rc = run_chain(g, descs, nullptr, plan.data(), k, itype == EMB_IDX_I64, st, SparseOut{}, s)) return rc;
+    return EMB_OK;
 }
 
 int emb_grad_master_report(emb_grad *g, uint64_t *n_unencodable) {

@@ -88,6 +88,7 @@ class EmbeddingBagCollection:
         self.multi_table_step = False                           # the fused steps go through the multi-table entry points (--multi-table-step)
         self.segmented_sums = None                              # the fused steps' segment length in the segmented order of additions; None: position order (--segmented-sums)
         self._fused_adagrad, self.adagrad_sum = None, None      # (lr, eps, rowwise) and the per-table fp32 states of enable_fused_adagrad
+        self._fused_adam, self.adam_exp_avg, self.adam_exp_avg_sq, self.adam_step = None, None, None, 0      # enable_fused_adam's
         self.sr_seed, self.sr_step = None, 0                    # --stochastic-rounding: the seed while it is on, and the step number of the next table stepped
         # DLRM --weighted-pooling: v_W_l[k] is a weight per ROW of table k (ones for "fixed", the checkpoint's for "learned");
         # a bag entry is weighted by its row's weight, gathered with torch (dlrm_s_pytorch.py: v_W_l[k].gather(0, indices))
@@ -129,7 +130,7 @@ class EmbeddingBagCollection:
             raise ValueError("out= / col= need concat=True")
         if concat and self._out is not None:
             raise ValueError('concat=True returns one fp32 tensor: it does not combine with out_dtype="weight"')
-        if self._fused_lr is not None or self._fused_adagrad is not None:
+        if self._fused_lr is not None or self._fused_adagrad is not None or self._fused_adam is not None:
             return self._apply_emb_fused_sgd(lS_o, lS_i, check, concat, out, col)
         if self.v_W_l is not None:
             return self._apply_emb_weighted(lS_o, lS_i, check, concat, out, col)
@@ -238,7 +239,7 @@ class EmbeddingBagCollection:
         same backward after enable_pooling_weight_grad(), computed before the step, at the table the forward read."""
         self._set_sr(stochastic_rounding and lr is not None, sr_seed, master_weights)
         self._fused_lr = None if lr is None else float(lr)
-        self._fused_adagrad = None
+        self._fused_adagrad = self._fused_adam = None
         self._set_masters(master_weights and lr is not None)
         return self
 
@@ -257,7 +258,26 @@ class EmbeddingBagCollection:
         if self.adagrad_sum is None or (self.adagrad_sum[0].dim() == 1) != bool(rowwise):
             shape = lambda n: (n,) if rowwise else (n, self.m)  # noqa: E731
             self.adagrad_sum = [torch.full(shape(int(n)), float(initial_accumulator_value), dtype=torch.float32, device=self.device) for n in self.ln_emb]
-        self._fused_adagrad, self._fused_lr = (float(lr), float(eps), bool(rowwise)), None
+        self._fused_adagrad, self._fused_lr, self._fused_adam = (float(lr), float(eps), bool(rowwise)), None, None
+        return self
+
+    def enable_fused_adam(self, lr, betas=(0.9, 0.999), eps: float = 1e-8, rowwise: bool = False):
+        """As enable_fused_sgd, with the fused Adam step (torch.optim.SparseAdam; rowwise=True: row-wise Adam, one second moment per row;
+        GradContext.adam_step).  The fp32 states -- self.adam_exp_avg / self.adam_exp_avg_sq, one tensor each per table -- are allocated
+        here as zeros, once per flavour, and self.adam_step counts the steps.  lr=None switches it off.  Switches the other fused steps,
+        master weights and stochastic rounding off: the Adam steps have no such forms, and no multi-table one."""
+        import torch
+        if lr is None:
+            self._fused_adam = None
+            return self
+        self._set_sr(False, 0, False)
+        self._set_masters(False)
+        if self.adam_exp_avg is None or (self.adam_exp_avg_sq[0].dim() == 1) != bool(rowwise):
+            zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)  # noqa: E731
+            self.adam_exp_avg = [zeros(int(n), self.m) for n in self.ln_emb]
+            self.adam_exp_avg_sq = [zeros(int(n)) if rowwise else zeros(int(n), self.m) for n in self.ln_emb]
+            self.adam_step = 0
+        self._fused_adam, self._fused_lr, self._fused_adagrad = (float(lr), (float(betas[0]), float(betas[1])), float(eps), bool(rowwise)), None, None
         return self
 
     def _apply_emb_fused_sgd(self, lS_o, lS_i, check, concat, out, col):
@@ -269,7 +289,7 @@ class EmbeddingBagCollection:
             self.validate(lS_o, lS_i)
         gathered = None if self.v_W_l is None else [v.gather(0, i.long()) for v, i in zip(self.v_W_l, lS_i)]
         ws = None if gathered is None else [w.detach() for w in gathered]
-        lr, ada = self._fused_lr, self._fused_adagrad
+        lr, ada, adam = self._fused_lr, self._fused_adagrad, self._fused_adam
 
         def lookup():
             if concat:
@@ -285,6 +305,13 @@ class EmbeddingBagCollection:
             ctx = tm._grad_context(self.engine, size(i.shape[0] for i in lS_i), size(o.shape[0] for o in lS_o), *order)
             args = ([self._ids[k] for k in live], [lS_i[k] for k in live], [lS_o[k] for k in live], [grads[k] for k in live])
             w_live = [None if ws is None else ws[k] for k in live]
+            if adam is not None:         # the fused Adam step (emb_grad_adam_step): table after table, one t for the whole model
+                if multi:
+                    raise ValueError("multi_table_step does not go with the fused Adam steps: there is no multi-table Adam step")
+                self.adam_step += 1
+                ctx.adam_step(*args, [self.adam_exp_avg[k] for k in live], [self.adam_exp_avg_sq[k] for k in live], adam[0], betas=adam[1], eps=adam[2],
+                              step=self.adam_step, rowwise=adam[3], per_sample_weights=w_live)
+                return
             masters = self.master_weight
             if masters is not None:      # the fused master-weight step (emb_grad_master_step): every table dtype but fp32, table after table
                 if multi:
@@ -469,6 +496,11 @@ def main(argv=None):
                     help="as --fused-sgd, with the fused Adagrad step (eps 1e-10, fp32 state of the tables' shape)")
     ap.add_argument("--fused-rowwise-adagrad", type=float, default=None, metavar="LR",
                     help="as --fused-sgd, with the fused row-wise Adagrad step (one fp32 accumulator per row; feature size a multiple of 4)")
+    ap.add_argument("--fused-adam", type=float, default=None, metavar="LR",
+                    help="as --fused-sgd, with the fused SparseAdam step (betas 0.9 / 0.999, eps 1e-8, two fp32 states of the tables' shape); "
+                         "not with --multi-table-step, --master-weights or --stochastic-rounding")
+    ap.add_argument("--fused-rowwise-adam", type=float, default=None, metavar="LR",
+                    help="as --fused-adam, with the fused row-wise Adam step (one fp32 second moment per row; feature size a multiple of 4)")
     ap.add_argument("--multi-table-step", action="store_true",
                     help="with one of the --fused-* flags: step the tables through the multi-table entry points (one pre-pass and one "
                          "launch per group of up to 16 tables instead of per table; the same bytes)")
@@ -495,10 +527,13 @@ def main(argv=None):
     args, ignored = ap.parse_known_args(argv)
     if ignored:   # MLP / training / logging flags of the reference command lines (README.md:6,10,14)
         print("ignored (outside the embedding path):", " ".join(ignored))
-    fused = [(name, lr) for name, lr in (("SGD", args.fused_sgd), ("Adagrad", args.fused_adagrad), ("row-wise Adagrad", args.fused_rowwise_adagrad))
-             if lr is not None]
+    fused = [(name, lr) for name, lr in (("SGD", args.fused_sgd), ("Adagrad", args.fused_adagrad), ("row-wise Adagrad", args.fused_rowwise_adagrad),
+                                         ("Adam", args.fused_adam), ("row-wise Adam", args.fused_rowwise_adam)) if lr is not None]
     if len(fused) > 1:
-        raise SystemExit("--fused-sgd, --fused-adagrad and --fused-rowwise-adagrad are mutually exclusive")
+        raise SystemExit("--fused-sgd, --fused-adagrad and --fused-rowwise-adagrad are mutually exclusive, and so are --fused-adam and --fused-rowwise-adam")
+    if fused and "Adam" in fused[0][0] and (args.multi_table_step or args.master_weights or args.stochastic_rounding is not None):
+        raise SystemExit("--fused-adam and --fused-rowwise-adam do not go with --multi-table-step, --master-weights or --stochastic-rounding: "
+                         "the Adam steps have no such forms")
     if args.multi_table_step and not fused:
         raise SystemExit("--multi-table-step goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
     if args.master_weights and not fused:
@@ -575,6 +610,8 @@ def main(argv=None):
         sr_kw = {} if args.stochastic_rounding is None else dict(stochastic_rounding=True, sr_seed=args.stochastic_rounding)
         if opt_name == "SGD":
             ebc.enable_fused_sgd(opt_lr, master_weights=args.master_weights, **sr_kw)
+        elif opt_name is not None and "Adam" in opt_name:
+            ebc.enable_fused_adam(opt_lr, rowwise=opt_name != "Adam")
         elif opt_name is not None:
             ebc.enable_fused_adagrad(opt_lr, rowwise=opt_name != "Adagrad", master_weights=args.master_weights, **sr_kw)
         w_opt = None

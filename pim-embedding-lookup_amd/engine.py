@@ -642,6 +642,78 @@ class GradContext:
                 ptrs[k] = buf.ptr
         return ptrs
 
+    # ---- the Adam steps (emb_grad_adam_step) ----
+    @staticmethod
+    def _adam_spec(lr, betas, eps, step, rowwise, step_size_dev=None):
+        dev_ptr = None
+        if step_size_dev is not None:
+            import torch
+            if not (_is_torch(step_size_dev) and step_size_dev.is_cuda) or step_size_dev.dtype != torch.float32 or step_size_dev.numel() != 1:
+                raise TypeError("step_size_dev must be a float32 CUDA tensor of one element")
+            dev_ptr = step_size_dev.data_ptr()
+        return _l.EmbAdamSpec(_l.EMB_ROWWISE_ADAM if rowwise else _l.EMB_ADAM, float(eps), float(lr), float(betas[0]), float(betas[1]), int(step),
+                              dev_ptr, 0)
+
+    def adam_constants(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, step: int = 1) -> tuple:
+        """(om1, om2, ss) of include/pimemb_grad.h's THE ADAM STEPS as Python floats holding fp32 values: 1 - beta1, 1 - beta2 and the step
+        size of step t -- the value to write into a step_size_dev tensor before a captured graph is replayed for that t."""
+        out = (C.c_float * 3)()
+        _l.check_grad(self._G.emb_adam_constants(C.byref(self._adam_spec(lr, betas, eps, step, False)), out))
+        return tuple(float(x) for x in out)
+
+    def adam_state_shapes(self, table: int, rowwise: bool = False) -> tuple:
+        """(shape of exp_avg, shape of exp_avg_sq) adam_step keeps for `table`: (nr_rows, dim) twice, or row-wise (nr_rows, dim) and (nr_rows,)."""
+        _ptr, n, dim, _dt = self.engine.table_info(table)
+        shapes = ((n, dim), (n,) if rowwise else (n, dim))
+        kind = _l.EMB_ROWWISE_ADAM if rowwise else _l.EMB_ADAM
+        for which, shape in enumerate(shapes):
+            assert self._G.emb_adam_state_floats(kind, n, dim, which) == int(np.prod(shape, dtype=np.uint64)), (which, shape)
+        return shapes
+
+    def adam_step(self, table_ids, indices, offsets, grads, exp_avgs, exp_avg_sqs, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, step: int = 1,
+                  rowwise: bool = False, step_size_dev=None, modes="sum", per_sample_weights=None, padding_idx=None, fixed_pooling: int = 0,
+                  stream: int | None = None) -> None:
+        """The fused SparseAdam step (rowwise=True: row-wise Adam, one second moment per row) of include/pimemb_grad.h, table after table:
+        conventions as sgd_step.  exp_avgs / exp_avg_sqs: one state each per table, adam_state_shapes(table, rowwise) float32 values, read
+        and written in place -- CUDA tensors with torch inputs, numpy arrays (copied to the device and back) with numpy inputs; the caller
+        initialises them (zeros).  step: t >= 1, the same for every table of the call.  step_size_dev: a float32 CUDA tensor of one element
+        the kernels read instead of the step size of `step` (adam_constants(...)[2]): what a captured graph replays with."""
+        if len(exp_avgs) != len(table_ids) or len(exp_avg_sqs) != len(table_ids):
+            raise ValueError(f"{len(exp_avgs)} exp_avg and {len(exp_avg_sqs)} exp_avg_sq states for {len(table_ids)} tables")
+        spec = self._adam_spec(lr, betas, eps, step, rowwise, step_size_dev)
+        keep, back = [], []
+        try:
+            arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, grads, modes, per_sample_weights, padding_idx, fixed_pooling,
+                                                          stream, keep)
+            ptrs = []
+            for which, states in enumerate((exp_avgs, exp_avg_sqs)):
+                p = (C.c_void_p * max(n, 1))()
+                for k in range(n):
+                    want = int(np.prod(self.adam_state_shapes(table_ids[k], rowwise)[which]))
+                    st = states[k]
+                    if st is None:
+                        p[k] = None
+                    elif dev:
+                        import torch
+                        if not (_is_torch(st) and st.is_cuda) or st.dtype != torch.float32 or not st.is_contiguous() or st.numel() != want:
+                            raise TypeError(f"Adam state {k} must be a contiguous float32 CUDA tensor of {want} values")
+                        p[k] = st.data_ptr()
+                    else:
+                        if not isinstance(st, np.ndarray) or st.dtype != np.float32 or st.size != want or not st.flags.c_contiguous or not st.flags.writeable:
+                            raise TypeError(f"Adam state {k} must be a writeable C-contiguous float32 numpy array of {want} values")
+                        buf = DeviceBuffer.from_numpy(self.engine, st)
+                        keep.append(buf)
+                        back.append((st, buf))
+                        p[k] = buf.ptr
+                ptrs.append(p)
+            _l.check_grad(self._G.emb_grad_adam_step(self._h, arr, ptrs[0], ptrs[1], n, itype, C.byref(spec), stream))
+            if not dev:
+                self.engine.synchronize(stream)
+                for st, buf in back:
+                    st[...] = buf.numpy().reshape(st.shape)
+        finally:
+            self._free(keep)
+
     # ---- the max-mode backward (emb_grad_max_*): the existing methods above keep refusing mode="max" ----
     def _winner_bufs(self, arr, n, table_ids, indices, dev, winners, keep):
         """One winners buffer [n_bags, dim] per table: the caller's (`winners`: int32 CUDA tensors, contiguous) or new ones -- int32

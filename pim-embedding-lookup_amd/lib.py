@@ -238,6 +238,16 @@ class EmbSrSpec(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("step", C.c_uint64), ("step_dev", C.c_void_p), ("reserved", C.c_uint64)]
 
 
+EMB_ADAM, EMB_ROWWISE_ADAM = 1, 2
+
+
+class EmbAdamSpec(C.Structure):
+    """emb_adam_spec: lr and the betas as double (the constants are computed on the host, in double); step_size_dev NULL or a device
+    float the kernels read instead of the step size of `step`."""
+    _fields_ = [("kind", C.c_uint32), ("eps", C.c_float), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("step", C.c_uint64), ("step_size_dev", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 EMB_GRAD_MULTI_MAX = 16
 EMB_GRAD_NO_GROUP = 0xFFFFFFFF      # emb_grad_multi_groups: an empty descriptor
 
@@ -283,6 +293,9 @@ GRAD_SIGNATURES = {
     "emb_grad_max_sparse": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.c_int, _vp, _vp, _vp, _u64, _vp, _vp]),
     "emb_grad_max_sgd": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), _u32, C.c_int, C.c_float, _vp]),
     "emb_grad_max_step": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbOptSpec), _vp]),
+    "emb_adam_constants": (C.c_int, [C.POINTER(EmbAdamSpec), C.POINTER(C.c_float)]),
+    "emb_adam_state_floats": (_u64, [_u32, _u64, _u32, C.c_int]),
+    "emb_grad_adam_step": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbAdamSpec), _vp]),
 }
 
 _lib = None
@@ -356,8 +369,8 @@ def load_grad() -> C.CDLL:
     load()
     if _grad_lib is not None:          # (load() came here itself)
         return _grad_lib
-    from .build import GRAD_LIB_PATH, GRAD_MASTER_LIB_PATH, GRAD_MAX_LIB_PATH, GRAD_SR_LIB_PATH
-    for dep in (GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH, GRAD_MAX_LIB_PATH):      # libpimemb_grad.so links against all three (RUNPATH $ORIGIN): name the one that is missing
+    from .build import GRAD_ADAM_LIB_PATH, GRAD_LIB_PATH, GRAD_MASTER_LIB_PATH, GRAD_MAX_LIB_PATH, GRAD_SR_LIB_PATH
+    for dep in (GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH, GRAD_MAX_LIB_PATH, GRAD_ADAM_LIB_PATH):      # libpimemb_grad.so links against all four (RUNPATH $ORIGIN): name the one that is missing
         if not os.path.exists(dep):
             raise FileNotFoundError(
                 f"{dep} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "

@@ -30,7 +30,11 @@ Mode "max" trains through the max-mode backward (emb_grad_max_*): sparse_grad, s
 of a mode="max" module compute the forward's winners first, then the gradient that flows to them alone; master_weights=True and
 stochastic_rounding=True raise ValueError there, and so does multi_table=True of a fused model that holds such a table (it is
 stepped on its own, through the same call).
-Not there: momentum / Adam, weight decay, fp8 / MXFP4 weights, a second-order gradient.  max_norm is not supported
+`enable_fused_adam(lr, betas, eps, rowwise)` / `adam_step_` are the same with the fused SparseAdam or row-wise Adam step
+(emb_grad_adam_step); the fp32 states are `module.adam_exp_avg` / `adam_exp_avg_sq`, the counter `module.adam_step`, and all three
+are in state_dict() once they exist.  Enabling one fused optimizer disables the others; master_weights, stochastic_rounding,
+multi_table and mode="max" raise ValueError with Adam.
+Not there: momentum SGD / amsgrad, weight decay, fp8 / MXFP4 weights, a second-order gradient.  max_norm is not supported
 by any module.
 
 Output dtype.  By default every module returns fp32 rows, whatever the table holds.  `out_dtype="weight"` makes a module
@@ -338,17 +342,21 @@ class PoolingEmbeddingBag(torch.nn.Module):
         def lookup():
             return self.engine.lookup_pooled(self._id_list, [idx], [off], self.mode, per_sample_weights=None if w is None else [w],
                                              padding_idx=self.padding_idx, check=self._check(), out_dtype=self._engine_out)[0]
-        lr, ada = getattr(self, "_fused_lr", None), getattr(self, "_fused_adagrad", None)
+        lr, ada, adam = getattr(self, "_fused_lr", None), getattr(self, "_fused_adagrad", None), getattr(self, "_fused_adam", None)
         if w is not None and per_sample_weights.requires_grad and torch.is_grad_enabled():
             # the weights are trained: the result joins the graph on them, and backward enqueues their gradient FIRST -- at the
             # table this forward read -- and the fused step, if one is enabled, behind it
             w = w.detach()
             step = None
-            if ada is not None:
+            if adam is not None:
+                step = lambda g: self._adam(idx, off, g, *adam, w)  # noqa: E731
+            elif ada is not None:
                 step = lambda g: self._adagrad(idx, off, g, ada[0], ada[1], w)  # noqa: E731
             elif lr is not None:
                 step = lambda g: self._step(idx, off, g, lr, w)  # noqa: E731
             return _WeightedLookup.apply(_anchor(self, idx.device), lookup, lambda g: [self._weights_grad(idx, off, g)], step, per_sample_weights)
+        if adam is not None:
+            return _FusedSGD.apply(_anchor(self, idx.device), lookup, lambda g: self._adam(idx, off, g, *adam, w))
         if ada is not None:
             return _FusedSGD.apply(_anchor(self, idx.device), lookup, lambda g: self._adagrad(idx, off, g, ada[0], ada[1], w))
         if lr is None:
@@ -375,6 +383,7 @@ class PoolingEmbeddingBag(torch.nn.Module):
         object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
         object.__setattr__(self, "_fused_adagrad", None)
+        object.__setattr__(self, "_fused_adam", None)
         _set_master(self, master_weights)
         return self
 
@@ -409,6 +418,7 @@ class PoolingEmbeddingBag(torch.nn.Module):
         _adagrad_state(self, bool(rowwise), float(initial_accumulator_value))
         object.__setattr__(self, "_fused_adagrad", (float(lr), float(eps)))
         object.__setattr__(self, "_fused_lr", None)
+        object.__setattr__(self, "_fused_adam", None)
         _set_master(self, master_weights)
         return self
 
@@ -416,6 +426,62 @@ class PoolingEmbeddingBag(torch.nn.Module):
     def adagrad_sum(self):
         """The Adagrad state (float32 CUDA tensor), or None before enable_fused_adagrad / adagrad_step_ made one."""
         return getattr(self, "_adagrad_sum", None)
+
+    def enable_fused_adam(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, rowwise: bool = False, order: str = "position",
+                          master_weights: bool = False, stochastic_rounding: bool = False, multi_table: bool = False):
+        """As enable_fused_sgd, with the fused Adam step of include/pimemb_grad.h: torch.optim.SparseAdam(lr, betas, eps) -- only the rows
+        a batch names move, their moments included -- or, rowwise=True, row-wise Adam with one second moment per row.  The fp32 states --
+        module.adam_exp_avg [num_embeddings, embedding_dim] and module.adam_exp_avg_sq, the same or [num_embeddings] -- are allocated
+        once as zeros, kept over later calls (a change of `rowwise` makes them and the counter anew) and saved by state_dict() as
+        `<prefix>adam_exp_avg`, `<prefix>adam_exp_avg_sq` and `<prefix>adam_step`, the number of steps taken.  lr=None switches the step
+        off (the states stay).  Switches every other fused optimizer off, master weights and stochastic rounding included; there is no
+        master-weight, stochastically rounded, multi-table or max-mode Adam step: ValueError.  Returns self."""
+        _no_adam_variants([self.mode], master_weights, stochastic_rounding, multi_table)
+        object.__setattr__(self, "_fused_order", _order(order))
+        if lr is None:
+            object.__setattr__(self, "_fused_adam", None)
+            return self
+        _adam_state(self, bool(rowwise))
+        object.__setattr__(self, "_fused_adam", (float(lr), (float(betas[0]), float(betas[1])), float(eps)))
+        object.__setattr__(self, "_fused_lr", None)
+        object.__setattr__(self, "_fused_adagrad", None)
+        _set_sr(self, False, 0, [self._table_dtype], False)
+        _set_master(self, False)
+        return self
+
+    @property
+    def adam_exp_avg(self):
+        """The first moment of the fused Adam step (float32 CUDA tensor), or None before enable_fused_adam / adam_step_ made one."""
+        return getattr(self, "_adam_exp_avg", None)
+
+    @property
+    def adam_exp_avg_sq(self):
+        """The second moment: [num_embeddings, embedding_dim], or [num_embeddings] row-wise; None like adam_exp_avg."""
+        return getattr(self, "_adam_exp_avg_sq", None)
+
+    @property
+    def adam_step(self) -> int:
+        """The number of fused Adam steps this module has taken: the next one runs with t = adam_step + 1."""
+        return getattr(self, "_adam_step", 0)
+
+    def _adam(self, idx, off, grad_output, lr, betas, eps, w, order=None):
+        if grad_output is None:
+            return
+        _no_adam_variants([self.mode], self.master_weight is not None, False, False)
+        g = _grad_view(grad_output, self.embedding_dim)
+        m, v = _adam_state(self)
+        t = self.adam_step + 1
+        self._context(idx, off, order).adam_step(self._id_list, [idx], [off], [g], [m], [v], lr, betas=betas, eps=eps, step=t, rowwise=v.dim() == 1,
+                                                 modes=self.mode, per_sample_weights=w, padding_idx=self.padding_idx)
+        object.__setattr__(self, "_adam_step", t)
+
+    def adam_step_(self, input, offsets, grad_output, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, per_sample_weights=None,
+                   order: str = "position"):
+        """One fused Adam step on the rows the batch names, in place and in stream order with forward(), on the module's states (of the
+        flavour enable_fused_adam chose, or SparseAdam's zeros if there are none yet) at t = adam_step + 1.  Returns self."""
+        idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
+        self._adam(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), (float(betas[0]), float(betas[1])), float(eps), w, order)
+        return self
 
     def _context(self, idx, off, order=None):
         """The engine's backward context of `order` (None: the one enable_fused_* chose; the position order if none did)."""
@@ -540,6 +606,10 @@ class PoolingEmbeddingBag(torch.nn.Module):
         if self.master_weight is not None:    # (only with master weights on)
             destination[prefix + "master_weight"] = self.master_weight.detach().clone()
         _save_sr(self, destination, prefix)   # (only with stochastic rounding on)
+        if self.adam_exp_avg is not None:     # (only a module that has Adam states gains the keys)
+            destination[prefix + "adam_exp_avg"] = self.adam_exp_avg.detach().clone()
+            destination[prefix + "adam_exp_avg_sq"] = self.adam_exp_avg_sq.detach().clone()
+            destination[prefix + "adam_step"] = torch.tensor(self.adam_step, dtype=torch.int64)
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         self._table._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
@@ -571,6 +641,20 @@ class PoolingEmbeddingBag(torch.nn.Module):
             object.__setattr__(self, "_adagrad_sum", s.detach().to(device=dev, dtype=torch.float32).contiguous().clone())
         elif self.adagrad_sum is not None and strict:
             missing_keys.append(key)
+        akeys = [prefix + k for k in ("adam_exp_avg", "adam_exp_avg_sq", "adam_step")]
+        if all(k in state_dict for k in akeys):
+            m, v = state_dict[akeys[0]], state_dict[akeys[1]]
+            full = (self.num_embeddings, self.embedding_dim)
+            if tuple(m.shape) != full or tuple(v.shape) not in (full, full[:1]):
+                error_msgs.append(f"size mismatch for {akeys[0]} / {akeys[1]}: {full} and {full} or, row-wise, {full[:1]} expected, got "
+                                  f"{tuple(m.shape)} and {tuple(v.shape)}")
+                return
+            dev = torch.device("cuda", self.device_index)
+            object.__setattr__(self, "_adam_exp_avg", m.detach().to(device=dev, dtype=torch.float32).contiguous().clone())
+            object.__setattr__(self, "_adam_exp_avg_sq", v.detach().to(device=dev, dtype=torch.float32).contiguous().clone())
+            object.__setattr__(self, "_adam_step", int(state_dict[akeys[2]]))
+        elif self.adam_exp_avg is not None and strict:
+            missing_keys += [k for k in akeys if k not in state_dict]
 
     def extra_repr(self) -> str:
         return (f"{self.num_embeddings}, {self.embedding_dim}, mode={self.mode!r}, padding_idx={self.padding_idx}, "
@@ -696,6 +780,26 @@ def _adagrad_state(bag, rowwise=None, init: float = 0.0):
     s = torch.full(shape, float(init), dtype=torch.float32, device=torch.device("cuda", bag.device_index))
     object.__setattr__(bag, "_adagrad_sum", s)
     return s
+
+
+def _adam_state(bag, rowwise=None):
+    """A PoolingEmbeddingBag's Adam states (exp_avg, exp_avg_sq), made as zeros on first use -- exp_avg_sq [num_embeddings] row-wise --
+    with the step counter at 0.  rowwise None: whatever is there (SparseAdam's if nothing is).  Plain attributes like the Adagrad state."""
+    m, v = getattr(bag, "_adam_exp_avg", None), getattr(bag, "_adam_exp_avg_sq", None)
+    if m is not None and (rowwise is None or (v.dim() == 1) == rowwise):
+        return m, v
+    shapes = _grad_context(bag.engine, 1, 1).adam_state_shapes(bag.table_id, bool(rowwise))
+    m, v = (torch.zeros(s, dtype=torch.float32, device=torch.device("cuda", bag.device_index)) for s in shapes)
+    object.__setattr__(bag, "_adam_exp_avg", m)
+    object.__setattr__(bag, "_adam_exp_avg_sq", v)
+    object.__setattr__(bag, "_adam_step", 0)
+    return m, v
+
+
+def _no_adam_variants(modes, master_weights, stochastic_rounding, multi_table) -> None:
+    """The Adam steps are the plain in-place ones alone (include/pimemb_grad.h names what is not built)."""
+    if "max" in modes or master_weights or stochastic_rounding or multi_table:
+        raise ValueError("the fused Adam steps have no master-weight, stochastically rounded, multi-table or mode='max' form")
 
 
 def _no_max_variants(modes, master_weights, stochastic_rounding, multi_table=False) -> None:
@@ -843,17 +947,21 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
                                                  padding_idx=self._pads, check=check)
             return self.engine.lookup_pooled(self._ids, idx, off, self._modes, per_sample_weights=wl, padding_idx=self._pads, check=check,
                                              out_dtype=self._outs)
-        lr, ada = getattr(self, "_fused_lr", None), getattr(self, "_fused_adagrad", None)
+        lr, ada, adam = getattr(self, "_fused_lr", None), getattr(self, "_fused_adagrad", None), getattr(self, "_fused_adam", None)
         trained = [] if lS_w is None or not torch.is_grad_enabled() else [k for k, w in enumerate(lS_w) if w is not None and w.requires_grad]
         if trained:      # as PoolingEmbeddingBag.forward: the weights' gradients first, then the fused step if there is one
             wl = [None if w is None else w.detach() for w in ws]
             step = None
-            if ada is not None:
+            if adam is not None:
+                step = lambda g: self._adam(idx, off, g, *adam, wl, col)  # noqa: E731
+            elif ada is not None:
                 step = lambda g: self._adagrad(idx, off, g, ada[0], ada[1], wl, col)  # noqa: E731
             elif lr is not None:
                 step = lambda g: self._step(idx, off, g, lr, wl, col)  # noqa: E731
             return _WeightedLookup.apply(_anchor(self, idx[0].device), lookup, lambda g: self._weights_grads(idx, off, g, col, trained), step,
                                          *[lS_w[k] for k in trained])
+        if adam is not None:
+            return _FusedSGD.apply(_anchor(self, idx[0].device), lookup, lambda g: self._adam(idx, off, g, *adam, wl, col))
         if ada is not None:
             return _FusedSGD.apply(_anchor(self, idx[0].device), lookup, lambda g: self._adagrad(idx, off, g, ada[0], ada[1], wl, col))
         if lr is None:
@@ -880,6 +988,7 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         object.__setattr__(self, "_fused_multi", bool(multi_table))
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
         object.__setattr__(self, "_fused_adagrad", None)
+        object.__setattr__(self, "_fused_adam", None)
         return self
 
     def _set_masters(self, on: bool, multi_table: bool) -> None:
@@ -920,12 +1029,48 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             _adagrad_state(b, bool(rowwise), float(initial_accumulator_value))
         object.__setattr__(self, "_fused_adagrad", (float(lr), float(eps)))
         object.__setattr__(self, "_fused_lr", None)
+        object.__setattr__(self, "_fused_adam", None)
         return self
 
     @property
     def adagrad_sum(self):
         """The bags' Adagrad states, in table order (None where a bag has none)."""
         return [b.adagrad_sum for b in self.bags]
+
+    def enable_fused_adam(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, rowwise: bool = False, order: str = "position",
+                          master_weights: bool = False, stochastic_rounding: bool = False, multi_table: bool = False):
+        """As PoolingEmbeddingBag.enable_fused_adam, for every table of the model: each bag holds its own states and counter
+        (bags[k].adam_exp_avg / adam_exp_avg_sq / adam_step, saved as `bags.<k>.adam_*`), one call steps them all, table after table.
+        Returns self."""
+        _no_adam_variants(self._modes, master_weights, stochastic_rounding, multi_table)
+        object.__setattr__(self, "_fused_order", _order(order))
+        if lr is None:
+            object.__setattr__(self, "_fused_adam", None)
+            return self
+        for b in self.bags:
+            _adam_state(b, bool(rowwise))
+        object.__setattr__(self, "_fused_adam", (float(lr), (float(betas[0]), float(betas[1])), float(eps)))
+        object.__setattr__(self, "_fused_lr", None)
+        object.__setattr__(self, "_fused_adagrad", None)
+        object.__setattr__(self, "_fused_multi", False)
+        _set_sr(self, False, 0, [b._table_dtype for b in self.bags], False)
+        self._set_masters(False, False)
+        return self
+
+    def _adam(self, idx, off, grad_output, lr, betas, eps, ws, col=0, order=None):
+        """Table after table through the bags, which own the states and the counters: bags that have taken different numbers of steps run
+        with different t."""
+        _no_adam_variants(self._modes, False, False, False)
+        for k, g in enumerate(self._table_grads(grad_output, col)):
+            if g is not None:
+                self.bags[k]._adam(idx[k], off[k], g, lr, betas, eps, None if ws is None else ws[k],
+                                   getattr(self, "_fused_order", "position") if order is None else order)
+
+    def adam_step_(self, lS_o, lS_i, grad_output, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, lS_w=None, order: str = "position"):
+        """PoolingEmbeddingBag.adam_step_ for all tables in one call, on the bags' states; grad_output as sgd_step_ takes it."""
+        idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
+        self._adam(idx, off, g, float(lr), (float(betas[0]), float(betas[1])), float(eps), ws, order=order)
+        return self
 
     @property
     def sr_step(self) -> int:
