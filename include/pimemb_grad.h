@@ -400,6 +400,7 @@ int emb_grad_weights(emb_grad *g, const emb_grad_desc *descs, float *const *dw_o
  * against 388 / 311 / 398 (2.3 - 2.8x faster; level with the in-place step, 136 us); position-order context: 4.0 ms either way, the
  * hot row's chain (1.04 - 1.06x faster than the recipe, 1.07x SLOWER than in place).  The Kaggle shape (dim 16, 39 292 one-index
  * bags): 50 / 52 us on bf16 / e4m3 against 106 / 107.  The MXFP4 tail is 1.19x the e4m3 step on the uniform shape.
+ * SparseAdam and row-wise Adam on master rows are a call of their own: emb_grad_master_adam_step (THE MASTER-WEIGHT ADAM STEPS, below).
  * Out of scope: a multi-table master step (the group record has no room for the master pointer, and the multi-table kernels keep
  * their text); masters in anything but fp32; the ranged / sharded paths. */
 typedef enum { EMB_MASTER_SGD = 0, EMB_MASTER_ADAGRAD = 1, EMB_MASTER_ROWWISE_ADAGRAD = 2 } emb_master_kind;
@@ -611,7 +612,8 @@ int emb_grad_max_step(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *
  * The kernels (grad_adam_rows_group: two kinds, two orders; grad_adam_rows_elem: EMB_ADAM, two orders) have a code object of their own,
  * libpimemb_grad_adam.so, built from the same source and found next to libpimemb_grad.so, which links against it; the other libraries'
  * code objects hold the machine code they held.
- * Out of scope: multi-table, master-weight, stochastically rounded and max-mode forms of the Adam steps; amsgrad, weight_decay and
+ * The master-weight form is emb_grad_master_adam_step (THE MASTER-WEIGHT ADAM STEPS, below).
+ * Out of scope: multi-table, stochastically rounded and max-mode forms of the Adam steps; amsgrad, weight_decay and
  * maximize; state in anything but fp32; the ranged / sharded paths. */
 typedef enum { EMB_ADAM = 1, EMB_ROWWISE_ADAM = 2 } emb_adam_kind;
 typedef struct emb_adam_spec {
@@ -630,6 +632,64 @@ int emb_adam_constants(const emb_adam_spec *spec, float out[3]);
 uint64_t emb_adam_state_floats(uint32_t kind, uint64_t nr_rows, uint32_t dim, int which);
 int emb_grad_adam_step(emb_grad *g, const emb_grad_desc *descs, float *const *exp_avg, float *const *exp_avg_sq, uint32_t n_descs,
                        emb_index_type itype, const emb_adam_spec *spec, void *stream);
+
+/* THE MASTER-WEIGHT ADAM STEPS: the Adam steps on fp32 master rows, fused (tests/master_adam_ref.py restates them as a loop; the kernels are
+ * compared with that, bit for bit).  The only way to train EMB_F8_E4M3, EMB_F8_E5M2 and EMB_MXFP4 tables with Adam in one call, and the way
+ * to train EMB_F16 / EMB_BF16 tables with Adam without losing every update below half an ulp of the stored value -- Adam's normalised steps
+ * are exactly that kind of update.  g[r], U, good / bad / padding positions, the order of additions (position or segmented, as the context
+ * was created) and the bad-position count are the ones defined at the top; om1, om2 and ss are emb_adam_constants' of the spec, and
+ * step_size_dev replaces ss as in THE ADAM STEPS; emb_adam_spec, emb_adam_kind and emb_adam_state_floats are those of THE ADAM STEPS,
+ * unchanged.  P is the master, float[nr_rows][dim], no padding; M (exp_avg) and V (exp_avg_sq) as there; all caller-owned, in device memory.
+ * For every r in U, every fp32 operation rounded on its own and never contracted into an FMA, the table row NOT READ:
+ *   EMB_ADAM            M', V', den and x exactly as in EMB_ADAM;               P'[r][d] = P[r][d] - (ss * x)
+ *   EMB_ROWWISE_ADAM    ms, V', rate and M' exactly as in EMB_ROWWISE_ADAM;     P'[r][d] = P[r][d] - (rate * M'[d])
+ *   Table row           W[r] = enc_T(P'[r]), enc_T the row writer's encoder as in THE MASTER-WEIGHT STEPS: EMB_F16, EMB_BF16, EMB_F8_E4M3,
+ *                       EMB_F8_E5M2 element by element; EMB_MXFP4 per block of 32, its scale bytes and zero padding where pimemb.h puts them.
+ *   P', M' and V' are stored (csrc/pimemb_grad_adam.h: adam_moments / rowwise_adam_moment / adam_master -- the moments' half of the Adam
+ *   arithmetic, split out of adam_step and shared with it, and the master subtract).
+ * An EMB_MXFP4 row whose P'[r] holds an inf or a NaN anywhere keeps its table bytes; its P', M' and V' are stored all the same, and the row
+ * is counted in emb_grad_master_report's counter (no counter and no scratch of its own).  For the other dtypes every value has an encoding.
+ * Rows outside U keep their table, P, M and V bytes.  g is never written to memory.
+ *
+ * emb_grad_master_adam_step runs descriptor after descriptor (a table named twice is stepped twice, in order, with the same t): DEVICE
+ * pointers only; masters[k], exp_avg[k], exp_avg_sq[k] belong to descs[k]'s table; everything is checked before anything is enqueued -- a
+ * refused call leaves everything as it was; no allocation, no copy, no host wait: it can be captured in a graph (step_size_dev carries the
+ * new t between replays).  It works on a context of either order.
+ *   Tables               EMB_F16, EMB_BF16, EMB_F8_E4M3, EMB_F8_E5M2, EMB_MXFP4 (up to dim 512).  EMB_F32 is EMB_ERR_UNSUPPORTED: the table is
+ *                        its own master, use emb_grad_adam_step.  EMB_FIXED32, EMB_POOL_MAX, a staged hot set and the context's limits
+ *                        refuse as in emb_grad_master_step.
+ *   EMB_ERR_INVALID      whatever emb_grad_adam_step refuses about the spec, with its texts, checked before the context is looked at; a NULL
+ *                        or not 4-byte aligned master, M or V where n_indices > 0.
+ *   Kernel shape         the lane-group kernel runs where dim % 4 == 0, dim <= 512, grad, master and M (EMB_ADAM: V too) 16-byte aligned,
+ *                        grad_ld % 4 == 0.  Off that shape the 2-byte and 1-byte dtypes run an element-wise kernel with EMB_ADAM, the same
+ *                        bits; EMB_ROWWISE_ADAM and EMB_MXFP4 are EMB_ERR_UNSUPPORTED there (no row-wide and no block-wide view).
+ * How the tail runs.  A lane owns 4 elements per piece and moves four streams per piece: the master piece, the M piece and (EMB_ADAM) the V
+ * piece -- three 16-byte loads issued together BEHIND the run walk (hoisted before it they cost the Adam kernels two waves per SIMD and 10 %)
+ * and three 16-byte stores; row-wise, V[r] is loaded by every lane at the run head and stored by lane 0 -- and the encoded piece: one 8-byte
+ * (fp16 / bf16) or 4-byte (fp8) store, adjacent lanes adjacent bytes.  No table load.  MXFP4: eight adjacent lanes hold a block; amax and the
+ * zeros rule by the xor butterfly over distances 1, 2 and 4, the block's 16 bytes and the row's scale piece assembled with shuffles and stored
+ * by one lane per block and by lane 0 -- the master tail's own functions.  The row's inf / NaN flag is reduced over the whole lane group
+ * before the first table store of the row: every lane of a run-head group stays through the shuffles, lanes without a piece hold +0.
+ * Beyond dim 256, where a lane owns two pieces: EMB_ADAM takes them one after the other on every dtype -- walk, step, P' M' V' to memory --
+ * and on MXFP4 keeps each piece's P' (8 floats) until both are known, then reduces the flag, then encodes and stores both table pieces;
+ * EMB_ROWWISE_ADAM walks both pieces, keeps both sums, gets the rate and steps piece after piece, as in the Adam steps.
+ * No LDS, no scratch, no spills; grad_master_adam_rows_group takes 61 / 62 VGPRs (EMB_ADAM: position / segmented order) and 64 / 65
+ * (row-wise), against 65 / 70 and 63 / 64 for the in-place Adam kernels and 63 - 68 for Adagrad: 8 and 7 waves per SIMD.
+ * The kernels (grad_master_adam_rows_group: two kinds, two orders; grad_master_adam_rows_elem: two orders) have a code object of their own,
+ * libpimemb_grad_master_adam.so, built from the same source and found next to libpimemb_grad.so, which links against it; every other
+ * library's code object holds the machine code it held (the in-place Adam kernels' hashes were compared before and after the split of
+ * adam_step).
+ * Speed, measured on MI355X (tools/master_adam_probe.py, profiles/master_adam/README.md; medians of five alternating rounds, device pointers,
+ * the neighbours measured again in the same run; dim 128, 2048 bags x 32, 4 M rows).  Uniform ids, EMB_ADAM: 90.9 / 91.1 / 99.9 us on bf16 /
+ * e4m3 / MXFP4 tables; 1.04x SLOWER than the in-place bf16 emb_grad_adam_step (87.2 us), 1.09 - 1.10x SLOWER than emb_grad_master_step with
+ * Adagrad on bf16 / e4m3 (83.0 / 83.7 us) and 1.02x on MXFP4 (97.5), 5.8 - 6.2x faster than the unfused recipe (fill, emb_grad_sparse, torch ops on
+ * master / M / V, emb_rows_update: 564 - 580 us).  EMB_ROWWISE_ADAM: 85.7 / 85.8 / 96.8 us.  Zipf ids, S = 64 context: 143.6 / 143.2 / 147.6 us,
+ * 1.02x SLOWER than in place (140.9) and than master Adagrad (140.3 - 144.0), 4.8 - 5.3x faster than the recipe.  The Kaggle shape (dim 16, 39 292
+ * one-index bags): 59.4 / 63.3 us on bf16 / e4m3 against 51.9 / 52.2 for master Adagrad (1.14x / 1.21x SLOWER) and 238 for the recipe; the in-place
+ * bf16 Adam step measured 65.9 us there with a spread of 61 - 72.
+ * Out of scope: a multi-table, stochastically rounded or max-mode form; masters and states in anything but fp32; the ranged / sharded paths. */
+int emb_grad_master_adam_step(emb_grad *g, const emb_grad_desc *descs, float *const *masters, float *const *exp_avg, float *const *exp_avg_sq,
+                              uint32_t n_descs, emb_index_type itype, const emb_adam_spec *spec, void *stream);
 
 /* The number of EMB_MXFP4 rows master steps left unwritten (an inf or a NaN in the new master row) since the last such report;
  * resets the count.  Waits for the device first, like emb_grad_report, whose count of bad positions is a separate one. */

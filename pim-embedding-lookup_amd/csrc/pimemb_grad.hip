@@ -35,6 +35,11 @@
 // The Adam steps (emb_grad_adam_step; csrc/pimemb_grad_adam.h; a code object of their own, libpimemb_grad_adam.so):
 //   grad_adam_rows_group / grad_adam_rows_elem     the hot kernels' twins in both orders with the SparseAdam and row-wise Adam tails: the
 //                       table piece, the piece of exp_avg and the piece of exp_avg_sq (row-wise: V[r]) loaded together behind the walk
+// The master-weight Adam steps (emb_grad_master_adam_step; a code object of their own, libpimemb_grad_master_adam.so):
+//   grad_master_adam_rows_group / grad_master_adam_rows_elem     the same walks and exits with a tail of four streams: the pieces of the fp32
+//                       master, of exp_avg and of exp_avg_sq (row-wise: V[r]) loaded together behind the walk and stored as 16-byte vectors,
+//                       and the table piece ENCODED from the new master -- the table is never read; MXFP4 rows through the master tail's
+//                       block butterfly, once the whole row's new master is known
 // The max-mode backward (emb_grad_max_*; csrc/pimemb_grad_max.h; a code object of its own, libpimemb_grad_max.so):
 //   grad_max_winners_group / grad_max_winners_elem     one lane group per BAG (or one thread per bag element): the position that won
 //                       every element of the forward's max, the row gathers of eight positions in flight before the first compare
@@ -64,10 +69,12 @@
 #include "pimemb_grad_sr.h"
 #include "pimemb_grad_step.h"
 
-// This file is compiled five times (csrc/Makefile): as libpimemb_grad.so, and with -DPIMEMB_GRAD_MASTER_UNIT / -DPIMEMB_GRAD_SR_UNIT /
-// -DPIMEMB_GRAD_MAX_UNIT / -DPIMEMB_GRAD_ADAM_UNIT as the code objects of the master-weight steps, the stochastically rounded steps, the
-// max-mode backward and the Adam steps, which hold their own kernels and launchers alone.
-#if defined(PIMEMB_GRAD_MASTER_UNIT) || defined(PIMEMB_GRAD_SR_UNIT) || defined(PIMEMB_GRAD_MAX_UNIT) || defined(PIMEMB_GRAD_ADAM_UNIT)
+// This file is compiled six times (csrc/Makefile): as libpimemb_grad.so, and with -DPIMEMB_GRAD_MASTER_UNIT / -DPIMEMB_GRAD_SR_UNIT /
+// -DPIMEMB_GRAD_MAX_UNIT / -DPIMEMB_GRAD_ADAM_UNIT / -DPIMEMB_GRAD_MASTER_ADAM_UNIT as the code objects of the master-weight steps, the
+// stochastically rounded steps, the max-mode backward, the Adam steps and the master-weight Adam steps, which hold their own kernels and
+// launchers alone.
+#if defined(PIMEMB_GRAD_MASTER_UNIT) || defined(PIMEMB_GRAD_SR_UNIT) || defined(PIMEMB_GRAD_MAX_UNIT) || defined(PIMEMB_GRAD_ADAM_UNIT) || \
+    defined(PIMEMB_GRAD_MASTER_ADAM_UNIT)
 #define PIMEMB_GRAD_KERNEL_UNIT 1
 #endif
 
@@ -974,6 +981,11 @@ __device__ __forceinline__ float4 master_piece(const RowArgs &a, const MasterArg
     return m;
 }
 
+#endif      // PIMEMB_GRAD_MASTER_UNIT
+// (the encoding half of the tail -- from here to master_mx_row -- is text the master-weight Adam unit compiles too: inlined device functions,
+//  no kernel of either unit changes for it)
+#if defined(PIMEMB_GRAD_MASTER_UNIT) || defined(PIMEMB_GRAD_MASTER_ADAM_UNIT)
+
 // The encoded piece c of a 2-byte or 1-byte table row: ONE vector store of 8 or 4 bytes, adjacent lanes adjacent bytes.
 __device__ __forceinline__ void master_store_piece(const RowArgs &a, const MasterArgs &ma, uint32_t row, uint32_t c, float4 m) {
     const uint32_t bits[4] = {f32_bits(m.x), f32_bits(m.y), f32_bits(m.z), f32_bits(m.w)};
@@ -1050,6 +1062,9 @@ __device__ __forceinline__ void master_mx_row(const RowArgs &a, const MasterArgs
     }
     if (lg == 0) dst[nb] = u32x4{t[0], t[1], t[2], t[3]};
 }
+
+#endif      // PIMEMB_GRAD_MASTER_UNIT || PIMEMB_GRAD_MASTER_ADAM_UNIT
+#ifdef PIMEMB_GRAD_MASTER_UNIT
 
 // grad_rows_group / grad_seg_rows_group with the master tail.  The row-wise kind and MXFP4 need the whole row before the first
 // table store (the row's step size; the blocks' amax and the row's inf / NaN flag): there every lane of a run-head group stays
@@ -1351,10 +1366,11 @@ enum AdamKind : int { ADAM_ELEMENTS = EMB_ADAM, ADAM_ROWWISE = EMB_ROWWISE_ADAM 
 
 // Like the master, SR and max kernels these live in a code object of their own: this file compiled with -DPIMEMB_GRAD_ADAM_UNIT into
 // libpimemb_grad_adam.so (csrc/Makefile), which exports their launch function; libpimemb_grad.so's host side calls it.
-#ifdef PIMEMB_GRAD_ADAM_UNIT
-
+#if defined(PIMEMB_GRAD_ADAM_UNIT) || defined(PIMEMB_GRAD_MASTER_ADAM_UNIT)      // (the master-weight Adam unit reads its step size the same way)
 // The step size of this launch: one uniform load (or none), the same word in every lane.
 __device__ __forceinline__ float adam_step_size(const AdamArgs &ad) { return ad.step_size_dev ? *ad.step_size_dev : ad.ss; }
+#endif
+#ifdef PIMEMB_GRAD_ADAM_UNIT
 
 // What a lane loads of piece c of a stepped row for the tail: the table piece as it lies in memory (16 bytes of an fp32 row, or 8 bytes
 // of an fp16 / bf16 row in w.x and w.y), the piece of M, and (ADAM_ELEMENTS) the piece of V.
@@ -1521,6 +1537,207 @@ namespace {
 }  // namespace
 extern "C" void pimemb_grad_adam_launch(const void *row_args, const void *seg_args, const void *adam_args, int kind, int seg, int lane, uint32_t lanes,
                                         uint32_t lanes_log2, uint32_t chunks, uint32_t blocks, uint32_t elem_blocks, uint32_t S, void *stream);
+namespace {
+#endif
+
+// ---- the master-weight Adam steps: M', V' as in the Adam steps, P' = P - (ss * x) or P - (rate * M'), W = enc_T(P') ---------------------------
+// (include/pimemb_grad.h, THE MASTER-WEIGHT ADAM STEPS.)  The same pre-pass, sort, segment launch, run walk and exits; the row-wise butterfly
+// and V[r] as in the Adam kernels; the encoders and the MXFP4 row assembly as in the master kernels (master_store_piece, master_mx_row).  What
+// is this section's own is the tail between them.  Per piece a lane moves FOUR streams: the piece of the fp32 master P, the piece of M and
+// (SparseAdam) the piece of V -- three independent 16-byte loads issued together BEHIND the walk (at the head they would be 12 registers held
+// across it: the Adam kernels lost two waves per SIMD and 10 % that way), three 16-byte stores -- and the encoded table piece, one 8-, 4- or
+// (MXFP4, one lane per block) 16-byte store.  The table is never loaded: the Adam tail's AdamRaw does not exist here.
+// Two forms of the tail, chosen per launch (uniform):
+//   narrow   SparseAdam on the 2-byte and 1-byte dtypes: nothing of a row depends on another piece, so a lane takes its pieces one after
+//            the other -- walk, load, step, store P' M' V', encode, store -- and lanes without a piece leave at once.
+//   wide     row-wise Adam (the rate needs the whole row's g) and every MXFP4 row (the inf / NaN flag needs the whole row's P' BEFORE the first
+//            table store): every lane of a run-head group stays through the shuffles, lanes without a piece hold +0.  Beyond dim 256 row-wise
+//            Adam walks both pieces and keeps both sums, as today.  SparseAdam on MXFP4 does NOT: its pieces are independent until the
+//            encoder, so it goes through the narrow form's very loop -- walk, step, P' M' V' to memory -- and keeps only the piece's P' (4
+//            floats across the second walk, where two walks first would hold a whole accumulator as well), then the flag is reduced and both
+//            table pieces are encoded and stored (master_mx_row).  Both SparseAdam forms share their two walk sites, written out piece by
+//            piece: 61 / 62 VGPRs (position / segmented order), 73 / 82 SGPRs, nothing spilled.  Two variants of this were built and lost at
+//            compile time: a narrow loop beside a wide two-walk path (three walk sites) took 70 / 75 VGPRs and, segmented, 106 SGPRs with 24
+//            spilled to lanes; one rolled loop over the two pieces took 77 / 83 VGPRs and still spilled 2.  Row-wise Adam: 64 / 65 VGPRs.
+// AdamArgs and MasterArgs travel as they are, beside RowArgs, of which a.table / a.stride / a.dim are used.
+
+// Like the other units' kernels these live in a code object of their own: this file compiled with -DPIMEMB_GRAD_MASTER_ADAM_UNIT into
+// libpimemb_grad_master_adam.so (csrc/Makefile), which exports their launch function; libpimemb_grad.so's host side calls it.
+#ifdef PIMEMB_GRAD_MASTER_ADAM_UNIT
+
+// What a lane loads of piece c of a stepped row: the master piece, the piece of M and (ADAM_ELEMENTS) the piece of V.
+struct MasterAdamPiece {
+    float4 p, m, v;
+};
+
+// The loads of the tail: two or three independent 16-byte loads, issued together -- nothing here uses what they return.
+template <int KIND>
+__device__ __forceinline__ MasterAdamPiece master_adam_load(const RowArgs &a, const AdamArgs &ad, const MasterArgs &ma, uint32_t row, uint32_t c) {
+    MasterAdamPiece h;
+    h.v = make_float4(0.f, 0.f, 0.f, 0.f);
+    h.p = reinterpret_cast<const float4 *>(ma.master + (uint64_t)row * a.dim)[c];
+    h.m = reinterpret_cast<const float4 *>(ad.m + (uint64_t)row * a.dim)[c];
+    if (KIND == ADAM_ELEMENTS) h.v = reinterpret_cast<const float4 *>(ad.v + (uint64_t)row * a.dim)[c];
+    return h;
+}
+
+// One element of the tail: the moments by the Adam steps' own functions, then the master subtract.  `scale` is the call's step size ss
+// (ADAM_ELEMENTS) or the row's rate (ADAM_ROWWISE, whose V is the row's).  Returns P'.
+template <int KIND>
+__device__ __forceinline__ float master_adam_elem(const AdamArgs &ad, float p, float g, float *m, float *v, float scale) {
+    if (KIND == ADAM_ELEMENTS) return adam_master(p, adam_moments(g, m, v, ad.om1, ad.om2, ad.eps), scale);
+    return adam_master(p, rowwise_adam_moment(g, m, ad.om1), scale);
+}
+
+// The fp32 half of the tail of piece c: the loads, the step, and the 16-byte stores of P', M' (and V').  Returns P'[row][4c .. 4c + 3], which
+// the caller encodes.
+template <int KIND>
+__device__ __forceinline__ float4 master_adam_piece(const RowArgs &a, const AdamArgs &ad, const MasterArgs &ma, uint32_t row, uint32_t c, float4 g,
+                                                    float scale) {
+    MasterAdamPiece h = master_adam_load<KIND>(a, ad, ma, row, c);
+    h.p.x = master_adam_elem<KIND>(ad, h.p.x, g.x, &h.m.x, &h.v.x, scale);
+    h.p.y = master_adam_elem<KIND>(ad, h.p.y, g.y, &h.m.y, &h.v.y, scale);
+    h.p.z = master_adam_elem<KIND>(ad, h.p.z, g.z, &h.m.z, &h.v.z, scale);
+    h.p.w = master_adam_elem<KIND>(ad, h.p.w, g.w, &h.m.w, &h.v.w, scale);
+    reinterpret_cast<float4 *>(ma.master + (uint64_t)row * a.dim)[c] = h.p;
+    reinterpret_cast<float4 *>(ad.m + (uint64_t)row * a.dim)[c] = h.m;
+    if (KIND == ADAM_ELEMENTS) reinterpret_cast<float4 *>(ad.v + (uint64_t)row * a.dim)[c] = h.v;
+    return h.p;
+}
+
+// One unique row per lane group, as grad_rows_group is launched (SEG: behind grad_seg_partials).  All shuffles -- the row-wise pair tree, the
+// MXFP4 block butterfly, the row's flag and the scale piece -- sit behind the walk, with xor distances and source lanes inside the group.
+template <int KIND, bool SEG>
+__global__ __launch_bounds__(kBlock) void grad_master_adam_rows_group(RowArgs a, SegArgs sg, AdamArgs ad, MasterArgs ma, uint32_t lanes, uint32_t lanes_log2,
+                                                                      uint32_t chunks) {
+    static_assert(KIND == ADAM_ELEMENTS || KIND == ADAM_ROWWISE, "an Adam kind");
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    const bool mx = ma.enc == kMasterMXFP4;                               // (uniform over the launch)
+    const bool wide = KIND == ADAM_ROWWISE || mx;
+    if (i64 >= a.n || (!wide && lg >= chunks)) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;      // (uniform over the lane group)
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 p0 = zero, p1 = zero;                                          // the new master pieces a wide tail keeps for the encoder
+    if (KIND == ADAM_ELEMENTS) {
+        // SparseAdam: a piece's P', M' and V' depend on that piece alone, so a lane takes its (up to two) pieces one after the other -- ONE
+        // walk site for both forms.  Narrow: the piece is encoded and stored at once.  MXFP4: P', M' and V' are stored as they become ready,
+        // the piece's P' stays in registers (4 floats across the second walk, 8 behind it), and the table waits for the row's flag.
+        if (lg < chunks) {
+            const float4 acc = SEG ? seg_walk_piece(a, sg, i, row, lg, chunks) : walk_piece(a, i, row, lg);
+            p0 = master_adam_piece<KIND>(a, ad, ma, row, lg, acc, adam_step_size(ad));
+            if (!mx) master_store_piece(a, ma, row, lg, p0);
+        }
+        if (lg + lanes < chunks) {                                        // (beyond dim 256 only, where lanes == 64)
+            const float4 acc = SEG ? seg_walk_piece(a, sg, i, row, lg + lanes, chunks) : walk_piece(a, i, row, lg + lanes);
+            p1 = master_adam_piece<KIND>(a, ad, ma, row, lg + lanes, acc, adam_step_size(ad));
+            if (!mx) master_store_piece(a, ma, row, lg + lanes, p1);
+        }
+        if (mx) master_mx_row(a, ma, row, lg, lanes, p0, p1);             // (every lane of the group is here again; lanes without a piece hold +0)
+        return;
+    }
+    // Row-wise Adam: the rate needs the whole row's g.  Both walks, both sums kept, the pair tree, then piece after piece.
+    const bool own0 = lg < chunks, own1 = lg + lanes < chunks;            // (own1: beyond dim 256 only, where lanes == 64)
+    float vr = ad.v[row];                                                 // (every lane's own copy of V[r]: loaded before lane 0 stores V')
+    float4 acc0 = zero, acc1 = zero;
+    if (own0) acc0 = SEG ? seg_walk_piece(a, sg, i, row, lg, chunks) : walk_piece(a, i, row, lg);
+    if (own1) acc1 = SEG ? seg_walk_piece(a, sg, i, row, lg + lanes, chunks) : walk_piece(a, i, row, lg + lanes);
+    float sum = piece_squares(acc0);                                      // (+0 in a lane without a piece)
+    if (own1) sum = adagrad_add(sum, piece_squares(acc1));
+    for (uint32_t h = 1; h < lanes; h <<= 1) sum = adagrad_add(sum, __shfl_xor(sum, (int)h));      // the pair tree: the same bits in every lane
+    const float rate = rowwise_adam_rate(sum, a.dim, &vr, ad.om2, adam_step_size(ad), ad.eps);
+    if (lg == 0) ad.v[row] = vr;
+    if (own0) p0 = master_adam_piece<KIND>(a, ad, ma, row, lg, acc0, rate);
+    if (own1) p1 = master_adam_piece<KIND>(a, ad, ma, row, lg + lanes, acc1, rate);
+    if (mx) {
+        master_mx_row(a, ma, row, lg, lanes, p0, p1);                     // (reduces the row's flag over the group before its first table store)
+        return;
+    }
+    if (own0) master_store_piece(a, ma, row, lg, p0);
+    if (own1) master_store_piece(a, ma, row, lg + lanes, p1);
+}
+
+// grad_rows_elem / grad_seg_rows_elem with the tail: one thread per (sorted place, element), SparseAdam on the 2-byte and 1-byte dtypes.
+// (No row-wise kind and no MXFP4: no thread here sees a whole row, or a whole block.)  The three loads sit behind the walk here too.
+template <bool SEG>
+__global__ __launch_bounds__(kBlock) void grad_master_adam_rows_elem(RowArgs a, AdamArgs ad, MasterArgs ma, uint32_t S) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid / a.dim;
+    const uint32_t c = (uint32_t)(gid - i64 * a.dim);
+    if (i64 >= a.n) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t row = a.keys[i];
+    if (row >= a.nr_rows || (i > 0 && a.keys[i - 1] == row)) return;
+    float acc = 0.f, t = 0.f;
+    uint32_t in_seg = 0;
+    bool first = true;                           // (SEG) t_0 is taken as it is: the sum of the partials starts from it
+    for (uint32_t j = i; j < a.n && a.keys[j] == row; j++) {
+        const uint32_t p = min(a.vals[j], a.n - 1u);
+        const uint32_t b = min(a.bagof[p], a.n_bags - 1u);
+        const float cp = contribution(a.coef, a.grad[(uint64_t)b * a.ld + c], coef_of(a, p, b));
+        if (!SEG) {
+            acc = add_in_order(acc, cp);
+            continue;
+        }
+        t = add_in_order(t, cp);
+        if (++in_seg == S) {
+            acc = first ? t : add_in_order(acc, t);
+            first = false;
+            t = 0.f;
+            in_seg = 0;
+        }
+    }
+    if (SEG && in_seg) acc = first ? t : add_in_order(acc, t);
+    const uint64_t at = (uint64_t)row * a.dim + c;
+    float *pp = ma.master + at, *mp = ad.m + at, *vp = ad.v + at;
+    float m = *mp, v = *vp;
+    const float p1 = master_adam_elem<ADAM_ELEMENTS>(ad, *pp, acc, &m, &v, adam_step_size(ad));
+    *pp = p1;
+    *mp = m;
+    *vp = v;
+    const uint32_t o = master_enc(ma.enc, f32_bits(p1));
+    char *w = a.table + (uint64_t)row * a.stride;
+    if (ma.enc == kMasterF16 || ma.enc == kMasterBF16) reinterpret_cast<uint16_t *>(w)[c] = (uint16_t)o;
+    else reinterpret_cast<uint8_t *>(w)[c] = (uint8_t)o;
+}
+
+}  // namespace
+
+// The launch function libpimemb_grad_master_adam.so exports (plain C; RowArgs, SegArgs, AdamArgs and MasterArgs are this file's own, which every
+// compilation lays out alike).  The hot launch of a master-weight Adam step (a chain of one): the lane-group kernel or the element-wise one,
+// in the context's order.  kind: an emb_adam_kind.  Errors are left to the caller's hipGetLastError().
+extern "C" __attribute__((visibility("default"))) void pimemb_grad_master_adam_launch(const void *row_args, const void *seg_args, const void *adam_args,
+                                                                                       const void *master_args, int kind, int seg, int lane, uint32_t lanes,
+                                                                                       uint32_t lanes_log2, uint32_t chunks, uint32_t blocks,
+                                                                                       uint32_t elem_blocks, uint32_t S, void *stream) {
+    const RowArgs &a = *static_cast<const RowArgs *>(row_args);
+    const SegArgs &sg = *static_cast<const SegArgs *>(seg_args);
+    const AdamArgs &ad = *static_cast<const AdamArgs *>(adam_args);
+    const MasterArgs &ma = *static_cast<const MasterArgs *>(master_args);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 block(kBlock);
+    if (lane) {
+        const dim3 grid(blocks);
+        if (kind == ADAM_ELEMENTS && seg) grad_master_adam_rows_group<ADAM_ELEMENTS, true><<<grid, block, 0, s>>>(a, sg, ad, ma, lanes, lanes_log2, chunks);
+        else if (kind == ADAM_ELEMENTS) grad_master_adam_rows_group<ADAM_ELEMENTS, false><<<grid, block, 0, s>>>(a, sg, ad, ma, lanes, lanes_log2, chunks);
+        else if (seg) grad_master_adam_rows_group<ADAM_ROWWISE, true><<<grid, block, 0, s>>>(a, sg, ad, ma, lanes, lanes_log2, chunks);
+        else grad_master_adam_rows_group<ADAM_ROWWISE, false><<<grid, block, 0, s>>>(a, sg, ad, ma, lanes, lanes_log2, chunks);
+        return;
+    }
+    const dim3 grid(elem_blocks);                // (the row-wise kind and MXFP4 never get here: the plan refused them)
+    if (seg) grad_master_adam_rows_elem<true><<<grid, block, 0, s>>>(a, ad, ma, S);
+    else grad_master_adam_rows_elem<false><<<grid, block, 0, s>>>(a, ad, ma, 0u);
+}
+
+namespace {
+#else      // libpimemb_grad.so (and the other units, which never call it): the launcher is libpimemb_grad_master_adam.so's
+}  // namespace
+extern "C" void pimemb_grad_master_adam_launch(const void *row_args, const void *seg_args, const void *adam_args, const void *master_args, int kind, int seg,
+                                               int lane, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks, uint32_t blocks, uint32_t elem_blocks,
+                                               uint32_t S, void *stream);
 namespace {
 #endif
 
@@ -2490,6 +2707,16 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
         GRAD_HIP(hipGetLastError());
         return EMB_OK;
     }
+    if (spec.masters && spec.adam) {             // emb_grad_master_adam_step: both records, one launch
+        if (seg && c.lane) grad_seg_partials<<<dim3(l.blocks), block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
+        AdamArgs ad = spec.adam->consts;
+        ad.m = spec.adam->m[first], ad.v = spec.adam->v[first];
+        const MasterArgs ma{spec.masters[first], c.t.dtype, &g->counters[1]};
+        pimemb_grad_master_adam_launch(&a, &sg, &ad, &ma, spec.adam->kind, seg, c.lane, l.lanes, l.lanes_log2, l.chunks, l.blocks, c.elem_blocks,
+                                       g->cfg.segment, s);
+        GRAD_HIP(hipGetLastError());
+        return EMB_OK;
+    }
     if (spec.masters) {
         if (seg && c.lane) grad_seg_partials<<<dim3(l.blocks), block, 0, s>>>(a, sg, l.lanes, l.lanes_log2, l.chunks);
         const MasterArgs ma{spec.masters[first], c.t.dtype, &g->counters[1]};
@@ -2540,6 +2767,30 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
     return EMB_OK;
 }
 
+// What the master-weight steps (emb_grad_master_step, emb_grad_master_adam_step) check of a descriptor, its table and its master, and the
+// table's row stride as their encoders write it; *master_out = the master, NULL for an empty descriptor.
+int check_master_desc(emb_grad *g, const emb_grad_desc &d, emb_index_type itype, float *const *masters, uint32_t k, const char *alt, const char *who,
+                      TableShape &t, float **master_out) {
+    if (int rc = check_desc(g, d, itype, nullptr, who, &t)) return rc;
+    if (t.dtype == kF32) return fail(EMB_ERR_UNSUPPORTED, "%s: table %u is EMB_F32: the table is its own master, use %s", who, d.table_id, alt);
+    if (t.dtype != kMasterF16 && t.dtype != kMasterBF16 && t.dtype != kMasterE4M3 && t.dtype != kMasterE5M2 && t.dtype != kMasterMXFP4)
+        return fail(EMB_ERR_UNSUPPORTED, "%s: table %u has dtype %d, which no master step encodes", who, d.table_id, t.dtype);
+    uint32_t n_hot = 0;
+    if (int rc = emb_table_hot_count(g->e, d.table_id, &n_hot)) return fail_engine(rc, who);
+    if (n_hot)
+        return fail(EMB_ERR_UNSUPPORTED,
+                    "%s: table %u has a hot set of %u rows staged, a copy taken when it was set that lookups would go on serving: "
+                    "clear the set (emb_set_hot_rows with n_rows = 0), step, then set it again", who, d.table_id, n_hot);
+    const bool mx = t.dtype == kMasterMXFP4;
+    if (mx && t.dim > 512) return fail(EMB_ERR_UNSUPPORTED, "%s: table %u is MXFP4 of dim %u, the master step takes MXFP4 rows up to dim 512", who, d.table_id, t.dim);
+    t.stride = mx ? EMB_MXFP4_ROW_STRIDE(t.dim) : t.dim * (t.dtype == kMasterF16 || t.dtype == kMasterBF16 ? 2u : 1u);
+    float *master = d.n_indices ? masters[k] : nullptr;
+    if (d.n_indices && (!master || (uintptr_t)master % 4))
+        return fail(EMB_ERR_INVALID, "%s: the master of table %u is NULL or not 4-byte aligned", who, d.table_id);
+    *master_out = master;
+    return EMB_OK;
+}
+
 // The plan of emb_grad_master_step: every descriptor, master and state checked, in order; then one chain per non-empty descriptor.
 int plan_master(emb_grad *g, const emb_grad_desc *descs, float *const *masters, float *const *states, uint32_t n_descs, emb_index_type itype,
                 const StepSpec &spec, const char *who, Planned *plan) {
@@ -2547,23 +2798,9 @@ int plan_master(emb_grad *g, const emb_grad_desc *descs, float *const *masters, 
         const emb_grad_desc &d = descs[k];
         Planned &p = plan[k];
         TableShape &t = p.t;
-        if (int rc = check_desc(g, d, itype, nullptr, who, &t)) return rc;
-        if (t.dtype == kF32)
-            return fail(EMB_ERR_UNSUPPORTED, "%s: table %u is EMB_F32: the table is its own master, use emb_grad_sgd / emb_grad_step", who, d.table_id);
-        if (t.dtype != kMasterF16 && t.dtype != kMasterBF16 && t.dtype != kMasterE4M3 && t.dtype != kMasterE5M2 && t.dtype != kMasterMXFP4)
-            return fail(EMB_ERR_UNSUPPORTED, "%s: table %u has dtype %d, which no master step encodes", who, d.table_id, t.dtype);
-        uint32_t n_hot = 0;
-        if (int rc = emb_table_hot_count(g->e, d.table_id, &n_hot)) return fail_engine(rc, who);
-        if (n_hot)
-            return fail(EMB_ERR_UNSUPPORTED,
-                        "%s: table %u has a hot set of %u rows staged, a copy taken when it was set that lookups would go on serving: "
-                        "clear the set (emb_set_hot_rows with n_rows = 0), step, then set it again", who, d.table_id, n_hot);
+        float *master = nullptr;
+        if (int rc = check_master_desc(g, d, itype, masters, k, "emb_grad_sgd / emb_grad_step", who, t, &master)) return rc;
         const bool mx = t.dtype == kMasterMXFP4;
-        if (mx && t.dim > 512) return fail(EMB_ERR_UNSUPPORTED, "%s: table %u is MXFP4 of dim %u, the master step takes MXFP4 rows up to dim 512", who, d.table_id, t.dim);
-        t.stride = mx ? EMB_MXFP4_ROW_STRIDE(t.dim) : t.dim * (t.dtype == kMasterF16 || t.dtype == kMasterBF16 ? 2u : 1u);
-        float *master = d.n_indices ? masters[k] : nullptr;
-        if (d.n_indices && (!master || (uintptr_t)master % 4))
-            return fail(EMB_ERR_INVALID, "%s: the master of table %u is NULL or not 4-byte aligned", who, d.table_id);
         float *state = d.n_indices && states ? states[k] : nullptr;
         if (d.n_indices && spec.kind != RES_SGD && (!state || (uintptr_t)state % 4))
             return fail(EMB_ERR_INVALID, "%s: the state of table %u is NULL or not 4-byte aligned", who, d.table_id);
@@ -3021,6 +3258,67 @@ int emb_grad_adam_step(emb_grad *g, const emb_grad_desc *descs, float *const *ex
     st.adam = &call;
     std::vector<Planned> plan(n_descs);
     if (int rc = plan_adam(g, descs, call, n_descs, itype, who, plan.data())) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    for (uint32_t k = 0; k < n_descs; k++)
+        if (plan[k].k)
+            if (int rc = run_chain(g, descs, nullptr, plan.data(), k, itype == EMB_IDX_I64, st, SparseOut{}, s)) return rc;
+    return EMB_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The plan of emb_grad_master_adam_step: every descriptor, master and both states checked, in order -- the master steps' checks of the table,
+// the Adam steps' of the states -- then one chain per non-empty descriptor.
+int plan_master_adam(emb_grad *g, const emb_grad_desc *descs, float *const *masters, const AdamCall &call, uint32_t n_descs, emb_index_type itype,
+                     const char *who, Planned *plan) {
+    const bool rowwise = call.kind == EMB_ROWWISE_ADAM;
+    for (uint32_t k = 0; k < n_descs; k++) {
+        const emb_grad_desc &d = descs[k];
+        Planned &p = plan[k];
+        float *master = nullptr;
+        if (int rc = check_master_desc(g, d, itype, masters, k, "emb_grad_adam_step", who, p.t, &master)) return rc;
+        if (d.n_indices == 0) continue;
+        const float *m = call.m[k], *v = call.v[k];
+        if (!m || !v || (uintptr_t)m % 4 || (uintptr_t)v % 4)
+            return fail(EMB_ERR_INVALID, "%s: exp_avg or exp_avg_sq of table %u is NULL or not 4-byte aligned", who, d.table_id);
+        p.lane = lane_group_path(d, p.t, RES_SGD, nullptr, nullptr) && (uintptr_t)master % 16 == 0 && (uintptr_t)m % 16 == 0 &&
+                 (rowwise || (uintptr_t)v % 16 == 0);
+        const bool mx = p.t.dtype == kMasterMXFP4;
+        if (!p.lane && (rowwise || mx))
+            return fail(EMB_ERR_UNSUPPORTED,
+                        "%s: %s needs the lane-group shape (dim %% 4 == 0, dim <= 512, grad, master, exp_avg%s 16-byte aligned, grad_ld %% 4 == 0): "
+                        "table %u has dim %u, grad %p, grad_ld %llu, master %p, exp_avg %p, exp_avg_sq %p -- the element-wise kernel has no row-wide or "
+                        "block-wide view", who, rowwise ? "row-wise Adam" : "an MXFP4 table", rowwise ? "" : " and exp_avg_sq", d.table_id, p.t.dim,
+                        (const void *)d.grad, (unsigned long long)d.grad_ld, (const void *)master, (const void *)m, (const void *)v);
+    }
+    for (uint32_t k = 0; k < n_descs; k++)
+        if (descs[k].n_indices)
+            if (int rc = plan_chain(g, descs, plan, k, k + 1)) return rc;
+    return EMB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int emb_grad_master_adam_step(emb_grad *g, const emb_grad_desc *descs, float *const *masters, float *const *exp_avg, float *const *exp_avg_sq,
+                              uint32_t n_descs, emb_index_type itype, const emb_adam_spec *spec, void *stream) {
+    const char *who = "emb_grad_master_adam_step";
+    if (const char *fault = adam_fault(spec)) return fail(EMB_ERR_INVALID, "%s: %s", who, fault);
+    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
+    if (n_descs && (!descs || !masters || !exp_avg || !exp_avg_sq)) return fail(EMB_ERR_INVALID, "%s: descs, masters, exp_avg or exp_avg_sq is NULL", who);
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    float c[3];
+    adam_constants(spec->lr, spec->beta1, spec->beta2, spec->step, c);
+    const AdamCall call{exp_avg, exp_avg_sq, (int)spec->kind, AdamArgs{nullptr, nullptr, c[0], c[1], c[2], spec->eps, spec->step_size_dev}};
+    StepSpec st{spec->kind == EMB_ROWWISE_ADAM ? RES_ROWWISE : RES_ADAGRAD, 0.f, spec->eps};
+    st.adam = &call;
+    st.masters = masters;
+    std::vector<Planned> plan(n_descs);
+    if (int rc = plan_master_adam(g, descs, masters, call, n_descs, itype, who, plan.data())) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(g->device);
     for (uint32_t k = 0; k < n_descs; k++)

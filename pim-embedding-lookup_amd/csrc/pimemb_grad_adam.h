@@ -4,6 +4,8 @@
 //     EMB_ROWWISE_ADAM   once per row: ms = v / (float)dim;  dv = ms - V;  uv = dv * om2;  V' = V + uv;  rate = ss / (sqrt(V') + eps)
 //                        (v = the row-wise Adagrad pair tree over the row's g * g: the kernel's, from adagrad_square / adagrad_add);
 //                        per element: M' as above;  stored' = enc(dec(stored) - (rate * M'))
+// and of their master-weight forms (THE MASTER-WEIGHT ADAM STEPS), which take the moments' half of the above as it is -- adam_moments,
+// rowwise_adam_moment -- and subtract from the fp32 master element instead:  P' = P - (ss * x)  or  P' = P - (rate * M')  (adam_master);
 // built from pimemb_grad_optim.h's helpers: every fp32 operation is a statement of its own, never contracted into an FMA, division and
 // square root the correctly rounded ones.  om1, om2 and ss are computed once per call on the HOST, in double, and rounded to fp32
 // (adam_constants below: what torch.optim.SparseAdam computes in Python floats and then casts).
@@ -34,13 +36,19 @@ PIMEMB_ROWS_HD float adam_mul(float a, float b) {
 // A moving average stepped towards x: avg + ((x - avg) * om), three roundings.
 PIMEMB_ROWS_HD float adam_average(float avg, float x, float om) { return adagrad_add(avg, adam_mul(adam_sub(x, avg), om)); }
 
-// EMB_ADAM on one element: *m and *v become M' and V'; returns the stored bits after the step.
-PIMEMB_ROWS_HD uint32_t adam_step(int dtype, uint32_t stored_bits, float g, float *m, float *v, float om1, float om2, float ss, float eps) {
+// The moments of EMB_ADAM on one element, without the stored value: *m and *v become M' and V'; returns x = M' / (sqrt(V') + eps).
+// (The in-place tail and the master-weight tail -- THE MASTER-WEIGHT ADAM STEPS -- differ only in what they subtract ss * x from.)
+PIMEMB_ROWS_HD float adam_moments(float g, float *m, float *v, float om1, float om2, float eps) {
     const float m1 = adam_average(*m, g, om1);
     const float v1 = adam_average(*v, adagrad_square(g), om2);
     *m = m1;
     *v = v1;
-    const float x = adagrad_div(m1, adagrad_den(v1, eps));
+    return adagrad_div(m1, adagrad_den(v1, eps));
+}
+
+// EMB_ADAM on one element: *m and *v become M' and V'; returns the stored bits after the step.
+PIMEMB_ROWS_HD uint32_t adam_step(int dtype, uint32_t stored_bits, float g, float *m, float *v, float om1, float om2, float ss, float eps) {
+    const float x = adam_moments(g, m, v, om1, om2, eps);
     return step(dtype, stored_bits, x, ss);
 }
 
@@ -51,12 +59,21 @@ PIMEMB_ROWS_HD float rowwise_adam_rate(float sum, uint32_t dim, float *v, float 
     return adagrad_div(ss, adagrad_den(v1, eps));
 }
 
-// ... and per element: *m becomes M'; returns the stored bits after the step.
-PIMEMB_ROWS_HD uint32_t rowwise_adam_step(int dtype, uint32_t stored_bits, float g, float *m, float om1, float rate) {
+// ... and per element, without the stored value: *m becomes M', which is returned (the step subtracts rate * M').
+PIMEMB_ROWS_HD float rowwise_adam_moment(float g, float *m, float om1) {
     const float m1 = adam_average(*m, g, om1);
     *m = m1;
+    return m1;
+}
+
+// ... and per element: *m becomes M'; returns the stored bits after the step.
+PIMEMB_ROWS_HD uint32_t rowwise_adam_step(int dtype, uint32_t stored_bits, float g, float *m, float om1, float rate) {
+    const float m1 = rowwise_adam_moment(g, m, om1);
     return step(dtype, stored_bits, m1, rate);
 }
+
+// The master element of THE MASTER-WEIGHT ADAM STEPS: P' = P - (scale * x), with (scale, x) = (ss, adam_moments' x) or (rate, M').
+PIMEMB_ROWS_HD float adam_master(float p, float x, float scale) { return step_f32(p, x, scale); }
 
 // The three constants of a call, on the host: out = {om1, om2, ss}, each computed in double and rounded to fp32 once.
 inline void adam_constants(double lr, double beta1, double beta2, uint64_t t, float out[3]) {

@@ -261,17 +261,18 @@ class EmbeddingBagCollection:
         self._fused_adagrad, self._fused_lr, self._fused_adam = (float(lr), float(eps), bool(rowwise)), None, None
         return self
 
-    def enable_fused_adam(self, lr, betas=(0.9, 0.999), eps: float = 1e-8, rowwise: bool = False):
+    def enable_fused_adam(self, lr, betas=(0.9, 0.999), eps: float = 1e-8, rowwise: bool = False, master_weights: bool = False):
         """As enable_fused_sgd, with the fused Adam step (torch.optim.SparseAdam; rowwise=True: row-wise Adam, one second moment per row;
         GradContext.adam_step).  The fp32 states -- self.adam_exp_avg / self.adam_exp_avg_sq, one tensor each per table -- are allocated
-        here as zeros, once per flavour, and self.adam_step counts the steps.  lr=None switches it off.  Switches the other fused steps,
-        master weights and stochastic rounding off: the Adam steps have no such forms, and no multi-table one."""
+        here as zeros, once per flavour, and self.adam_step counts the steps.  lr=None switches it off.  Switches the other fused steps
+        and stochastic rounding off: the Adam steps have no such form, and no multi-table one.  master_weights=True: the master-weight
+        Adam step (GradContext.master_adam_step) on fp32 masters, the way to train f16, bf16, fp8 and MXFP4 tables with Adam."""
         import torch
         if lr is None:
             self._fused_adam = None
             return self
         self._set_sr(False, 0, False)
-        self._set_masters(False)
+        self._set_masters(bool(master_weights))
         if self.adam_exp_avg is None or (self.adam_exp_avg_sq[0].dim() == 1) != bool(rowwise):
             zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)  # noqa: E731
             self.adam_exp_avg = [zeros(int(n), self.m) for n in self.ln_emb]
@@ -309,7 +310,12 @@ class EmbeddingBagCollection:
                 if multi:
                     raise ValueError("multi_table_step does not go with the fused Adam steps: there is no multi-table Adam step")
                 self.adam_step += 1
-                ctx.adam_step(*args, [self.adam_exp_avg[k] for k in live], [self.adam_exp_avg_sq[k] for k in live], adam[0], betas=adam[1], eps=adam[2],
+                if self.master_weight is not None:      # ... on fp32 masters (emb_grad_master_adam_step): every table dtype but fp32
+                    ctx.master_adam_step(*args, [self.master_weight[k] for k in live], [self.adam_exp_avg[k] for k in live],
+                                         [self.adam_exp_avg_sq[k] for k in live], adam[0], betas=adam[1], eps=adam[2], step=self.adam_step,
+                                         rowwise=adam[3], per_sample_weights=w_live)
+                    return
+                ctx.adam_step(*args,[self.adam_exp_avg[k] for k in live], [self.adam_exp_avg_sq[k] for k in live], adam[0], betas=adam[1], eps=adam[2],
                               step=self.adam_step, rowwise=adam[3], per_sample_weights=w_live)
                 return
             masters = self.master_weight
@@ -531,9 +537,9 @@ def main(argv=None):
                                          ("Adam", args.fused_adam), ("row-wise Adam", args.fused_rowwise_adam)) if lr is not None]
     if len(fused) > 1:
         raise SystemExit("--fused-sgd, --fused-adagrad and --fused-rowwise-adagrad are mutually exclusive, and so are --fused-adam and --fused-rowwise-adam")
-    if fused and "Adam" in fused[0][0] and (args.multi_table_step or args.master_weights or args.stochastic_rounding is not None):
-        raise SystemExit("--fused-adam and --fused-rowwise-adam do not go with --multi-table-step, --master-weights or --stochastic-rounding: "
-                         "the Adam steps have no such forms")
+    if fused and "Adam" in fused[0][0] and (args.multi_table_step or args.stochastic_rounding is not None):
+        raise SystemExit("--fused-adam and --fused-rowwise-adam do not go with --multi-table-step or --stochastic-rounding: the Adam steps have no such "
+                         "forms (with --master-weights they run as the master-weight Adam step)")
     if args.multi_table_step and not fused:
         raise SystemExit("--multi-table-step goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
     if args.master_weights and not fused:
@@ -611,7 +617,7 @@ def main(argv=None):
         if opt_name == "SGD":
             ebc.enable_fused_sgd(opt_lr, master_weights=args.master_weights, **sr_kw)
         elif opt_name is not None and "Adam" in opt_name:
-            ebc.enable_fused_adam(opt_lr, rowwise=opt_name != "Adam")
+            ebc.enable_fused_adam(opt_lr, rowwise=opt_name != "Adam", master_weights=args.master_weights)
         elif opt_name is not None:
             ebc.enable_fused_adagrad(opt_lr, rowwise=opt_name != "Adagrad", master_weights=args.master_weights, **sr_kw)
         w_opt = None

@@ -927,6 +927,51 @@ class GradContext:
         finally:
             self._free(keep)
 
+    def master_adam_step(self, table_ids, indices, offsets, grads, masters, exp_avgs, exp_avg_sqs, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                         step: int = 1, rowwise: bool = False, step_size_dev=None, modes="sum", per_sample_weights=None, padding_idx=None,
+                         fixed_pooling: int = 0, stream: int | None = None) -> None:
+        """The fused master-weight Adam step (emb_grad_master_adam_step), table after table: adam_step's moments -- SparseAdam, or
+        rowwise=True row-wise Adam -- with the update subtracted from masters[k][r] in fp32, and the table row written as the new master row
+        encoded in the table's dtype (fp16, bf16, e4m3, e5m2, MXFP4); the table row itself is never read.  masters as master_step takes
+        them (master_of makes one), exp_avgs / exp_avg_sqs / step / step_size_dev as adam_step takes them (adam_state_shapes,
+        adam_constants).  Conventions as sgd_step.  An MXFP4 row whose new master holds an inf or a NaN keeps its table bytes and is counted
+        for master_report(); its master and moments are stored all the same."""
+        n_t = len(table_ids)
+        if len(masters) != n_t or len(exp_avgs) != n_t or len(exp_avg_sqs) != n_t:
+            raise ValueError(f"{len(masters)} masters, {len(exp_avgs)} exp_avg and {len(exp_avg_sqs)} exp_avg_sq states for {n_t} tables")
+        spec = self._adam_spec(lr, betas, eps, step, rowwise, step_size_dev)
+        keep, back = [], []
+        try:
+            arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, grads, modes, per_sample_weights, padding_idx, fixed_pooling,
+                                                          stream, keep)
+            ptrs = [(C.c_void_p * max(n, 1))() for _ in range(3)]
+            for k in range(n):
+                _ptr, rows, dim, _dt = self.engine.table_info(table_ids[k])
+                wants = (rows * dim,) + tuple(int(np.prod(s)) for s in self.adam_state_shapes(table_ids[k], rowwise))
+                for which, x in enumerate((masters[k], exp_avgs[k], exp_avg_sqs[k])):
+                    what, want = f"{('master', 'exp_avg', 'exp_avg_sq')[which]} {k}", wants[which]
+                    if x is None:
+                        ptrs[which][k] = None
+                    elif dev:
+                        import torch
+                        if not (_is_torch(x) and x.is_cuda) or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != want:
+                            raise TypeError(f"{what} must be a contiguous float32 CUDA tensor of {want} values")
+                        ptrs[which][k] = x.data_ptr()
+                    else:
+                        if not isinstance(x, np.ndarray) or x.dtype != np.float32 or x.size != want or not x.flags.c_contiguous or not x.flags.writeable:
+                            raise TypeError(f"{what} must be a writeable C-contiguous float32 numpy array of {want} values")
+                        buf = DeviceBuffer.from_numpy(self.engine, x)
+                        keep.append(buf)
+                        back.append((x, buf))
+                        ptrs[which][k] = buf.ptr
+            _l.check_grad(self._G.emb_grad_master_adam_step(self._h, arr, ptrs[0], ptrs[1], ptrs[2], n, itype, C.byref(spec), stream))
+            if not dev:
+                self.engine.synchronize(stream)
+                for x, buf in back:
+                    x[...] = buf.numpy().reshape(x.shape)
+        finally:
+            self._free(keep)
+
     def master_report(self) -> int:
         """MXFP4 rows that master steps left unwritten -- an inf or a NaN in the new master row -- since the last such report
         (waits for the device; resets the count)."""

@@ -34,6 +34,9 @@ stepped on its own, through the same call).
 (emb_grad_adam_step); the fp32 states are `module.adam_exp_avg` / `adam_exp_avg_sq`, the counter `module.adam_step`, and all three
 are in state_dict() once they exist.  Enabling one fused optimizer disables the others; master_weights, stochastic_rounding,
 multi_table and mode="max" raise ValueError with Adam.
+`enable_fused_master_adam(lr, betas, eps, rowwise, order)` / `master_adam_step_` are the Adam steps on fp32 master rows
+(emb_grad_master_adam_step): the module keeps `master_weight` beside the Adam states and the table row is the new master row's
+encoding -- fp16, bf16, fp8 and MXFP4 tables; fp32 tables and mode="max" raise ValueError.
 Not there: momentum SGD / amsgrad, weight decay, fp8 / MXFP4 weights, a second-order gradient.  max_norm is not supported
 by any module.
 
@@ -343,18 +346,23 @@ class PoolingEmbeddingBag(torch.nn.Module):
             return self.engine.lookup_pooled(self._id_list, [idx], [off], self.mode, per_sample_weights=None if w is None else [w],
                                              padding_idx=self.padding_idx, check=self._check(), out_dtype=self._engine_out)[0]
         lr, ada, adam = getattr(self, "_fused_lr", None), getattr(self, "_fused_adagrad", None), getattr(self, "_fused_adam", None)
+        madam = getattr(self, "_fused_master_adam", None)
         if w is not None and per_sample_weights.requires_grad and torch.is_grad_enabled():
             # the weights are trained: the result joins the graph on them, and backward enqueues their gradient FIRST -- at the
             # table this forward read -- and the fused step, if one is enabled, behind it
             w = w.detach()
             step = None
-            if adam is not None:
+            if madam is not None:
+                step = lambda g: self._master_adam(idx, off, g, *madam, w)  # noqa: E731
+            elif adam is not None:
                 step = lambda g: self._adam(idx, off, g, *adam, w)  # noqa: E731
             elif ada is not None:
                 step = lambda g: self._adagrad(idx, off, g, ada[0], ada[1], w)  # noqa: E731
             elif lr is not None:
                 step = lambda g: self._step(idx, off, g, lr, w)  # noqa: E731
             return _WeightedLookup.apply(_anchor(self, idx.device), lookup, lambda g: [self._weights_grad(idx, off, g)], step, per_sample_weights)
+        if madam is not None:
+            return _FusedSGD.apply(_anchor(self, idx.device), lookup, lambda g: self._master_adam(idx, off, g, *madam, w))
         if adam is not None:
             return _FusedSGD.apply(_anchor(self, idx.device), lookup, lambda g: self._adam(idx, off, g, *adam, w))
         if ada is not None:
@@ -381,6 +389,7 @@ class PoolingEmbeddingBag(torch.nn.Module):
         _no_max_variants([self.mode], master_weights, stochastic_rounding)
         _set_sr(self, stochastic_rounding, sr_seed, [self._table_dtype], master_weights)
         object.__setattr__(self, "_fused_order", _order(order))
+        object.__setattr__(self, "_fused_master_adam", None)
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
         object.__setattr__(self, "_fused_adagrad", None)
         object.__setattr__(self, "_fused_adam", None)
@@ -412,6 +421,7 @@ class PoolingEmbeddingBag(torch.nn.Module):
         _no_max_variants([self.mode], master_weights, stochastic_rounding)
         _set_sr(self, stochastic_rounding and lr is not None, sr_seed, [self._table_dtype], master_weights)
         object.__setattr__(self, "_fused_order", _order(order))
+        object.__setattr__(self, "_fused_master_adam", None)
         if lr is None:
             object.__setattr__(self, "_fused_adagrad", None)
             return self
@@ -438,6 +448,7 @@ class PoolingEmbeddingBag(torch.nn.Module):
         master-weight, stochastically rounded, multi-table or max-mode Adam step: ValueError.  Returns self."""
         _no_adam_variants([self.mode], master_weights, stochastic_rounding, multi_table)
         object.__setattr__(self, "_fused_order", _order(order))
+        object.__setattr__(self, "_fused_master_adam", None)
         if lr is None:
             object.__setattr__(self, "_fused_adam", None)
             return self
@@ -481,6 +492,48 @@ class PoolingEmbeddingBag(torch.nn.Module):
         flavour enable_fused_adam chose, or SparseAdam's zeros if there are none yet) at t = adam_step + 1.  Returns self."""
         idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
         self._adam(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), (float(betas[0]), float(betas[1])), float(eps), w, order)
+        return self
+
+    def enable_fused_master_adam(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, rowwise: bool = False, order: str = "position"):
+        """As enable_fused_adam, with the fused master-weight Adam step of include/pimemb_grad.h (emb_grad_master_adam_step): the moments of
+        SparseAdam -- or, rowwise=True, row-wise Adam -- step the fp32 master rows (master_weight, made from the table by exact widening on
+        first use), and the table row is the new master row's encoding.  The way to train fp16, bf16, fp8 and MXFP4 tables with Adam: fp32
+        tables (the table is its own master: enable_fused_adam) and mode='max' raise ValueError.  The module keeps master_weight,
+        adam_exp_avg, adam_exp_avg_sq and adam_step, saved by state_dict() under those names.  lr=None switches the step off (masters and
+        moments stay).  Switches every other fused optimizer and stochastic rounding off, as they switch this one off.  Returns self."""
+        _master_adam_tables([self.mode], [self._table_dtype])
+        object.__setattr__(self, "_fused_order", _order(order))
+        if lr is None:
+            object.__setattr__(self, "_fused_master_adam", None)
+            return self
+        _adam_state(self, bool(rowwise))
+        object.__setattr__(self, "_fused_lr", None)
+        object.__setattr__(self, "_fused_adagrad", None)
+        object.__setattr__(self, "_fused_adam", None)
+        _set_sr(self, False, 0, [self._table_dtype], False)
+        _set_master(self, True)
+        object.__setattr__(self, "_fused_master_adam", (float(lr), (float(betas[0]), float(betas[1])), float(eps)))
+        return self
+
+    def _master_adam(self, idx, off, grad_output, lr, betas, eps, w, order=None):
+        if grad_output is None:
+            return
+        _master_adam_tables([self.mode], [self._table_dtype])
+        if self.master_weight is None:
+            _set_master(self, True)
+        g = _grad_view(grad_output, self.embedding_dim)
+        m, v = _adam_state(self)
+        t = self.adam_step + 1
+        self._context(idx, off, order).master_adam_step(self._id_list, [idx], [off], [g], [self.master_weight], [m], [v], lr, betas=betas, eps=eps, step=t,
+                                                        rowwise=v.dim() == 1, modes=self.mode, per_sample_weights=w, padding_idx=self.padding_idx)
+        object.__setattr__(self, "_adam_step", t)
+
+    def master_adam_step_(self, input, offsets, grad_output, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, per_sample_weights=None,
+                          order: str = "position"):
+        """One fused master-weight Adam step on the rows the batch names, in stream order with forward(), on the module's master and
+        moments (made on first use: the table widened, SparseAdam's zeros) at t = adam_step + 1.  Returns self."""
+        idx, off, w = self._bags_on_device(input, offsets, per_sample_weights)
+        self._master_adam(idx, off, torch.as_tensor(grad_output).to(idx.device), float(lr), (float(betas[0]), float(betas[1])), float(eps), w, order)
         return self
 
     def _context(self, idx, off, order=None):
@@ -802,6 +855,15 @@ def _no_adam_variants(modes, master_weights, stochastic_rounding, multi_table) -
         raise ValueError("the fused Adam steps have no master-weight, stochastically rounded, multi-table or mode='max' form")
 
 
+def _master_adam_tables(modes, table_dtypes) -> None:
+    """What the master-weight Adam step does not go with (include/pimemb_grad.h, THE MASTER-WEIGHT ADAM STEPS)."""
+    if "max" in modes:
+        raise ValueError("the master-weight Adam step has no mode='max' form: a mode='max' table trains with the plain fused SGD / Adagrad steps")
+    if any(dt == torch.float32 for dt in table_dtypes):
+        raise ValueError("the master-weight Adam step goes with fp16, bf16, fp8 and MXFP4 tables: an fp32 table is its own master, use "
+                         "enable_fused_adam")
+
+
 def _no_max_variants(modes, master_weights, stochastic_rounding, multi_table=False) -> None:
     """The max-mode backward has the plain fused steps alone (include/pimemb_grad.h names what is not built)."""
     if "max" in modes and (master_weights or stochastic_rounding or multi_table):
@@ -948,11 +1010,14 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             return self.engine.lookup_pooled(self._ids, idx, off, self._modes, per_sample_weights=wl, padding_idx=self._pads, check=check,
                                              out_dtype=self._outs)
         lr, ada, adam = getattr(self, "_fused_lr", None), getattr(self, "_fused_adagrad", None), getattr(self, "_fused_adam", None)
+        madam = getattr(self, "_fused_master_adam", None)
         trained = [] if lS_w is None or not torch.is_grad_enabled() else [k for k, w in enumerate(lS_w) if w is not None and w.requires_grad]
         if trained:      # as PoolingEmbeddingBag.forward: the weights' gradients first, then the fused step if there is one
             wl = [None if w is None else w.detach() for w in ws]
             step = None
-            if adam is not None:
+            if madam is not None:
+                step = lambda g: self._master_adam(idx, off, g, *madam, wl, col)  # noqa: E731
+            elif adam is not None:
                 step = lambda g: self._adam(idx, off, g, *adam, wl, col)  # noqa: E731
             elif ada is not None:
                 step = lambda g: self._adagrad(idx, off, g, ada[0], ada[1], wl, col)  # noqa: E731
@@ -960,6 +1025,8 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
                 step = lambda g: self._step(idx, off, g, lr, wl, col)  # noqa: E731
             return _WeightedLookup.apply(_anchor(self, idx[0].device), lookup, lambda g: self._weights_grads(idx, off, g, col, trained), step,
                                          *[lS_w[k] for k in trained])
+        if madam is not None:
+            return _FusedSGD.apply(_anchor(self, idx[0].device), lookup, lambda g: self._master_adam(idx, off, g, *madam, wl, col))
         if adam is not None:
             return _FusedSGD.apply(_anchor(self, idx[0].device), lookup, lambda g: self._adam(idx, off, g, *adam, wl, col))
         if ada is not None:
@@ -985,6 +1052,7 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         _set_sr(self, stochastic_rounding, sr_seed, [b._table_dtype for b in self.bags], master_weights, multi_table)
         self._set_masters(master_weights, multi_table)
         object.__setattr__(self, "_fused_order", _order(order))
+        object.__setattr__(self, "_fused_master_adam", None)
         object.__setattr__(self, "_fused_multi", bool(multi_table))
         object.__setattr__(self, "_fused_lr", None if lr is None else float(lr))
         object.__setattr__(self, "_fused_adagrad", None)
@@ -1021,6 +1089,7 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         _set_sr(self, stochastic_rounding and lr is not None, sr_seed, [b._table_dtype for b in self.bags], master_weights, multi_table)
         self._set_masters(master_weights, multi_table)
         object.__setattr__(self, "_fused_order", _order(order))
+        object.__setattr__(self, "_fused_master_adam", None)
         object.__setattr__(self, "_fused_multi", bool(multi_table))
         if lr is None:
             object.__setattr__(self, "_fused_adagrad", None)
@@ -1044,6 +1113,7 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         Returns self."""
         _no_adam_variants(self._modes, master_weights, stochastic_rounding, multi_table)
         object.__setattr__(self, "_fused_order", _order(order))
+        object.__setattr__(self, "_fused_master_adam", None)
         if lr is None:
             object.__setattr__(self, "_fused_adam", None)
             return self
@@ -1065,6 +1135,39 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
             if g is not None:
                 self.bags[k]._adam(idx[k], off[k], g, lr, betas, eps, None if ws is None else ws[k],
                                    getattr(self, "_fused_order", "position") if order is None else order)
+
+    def enable_fused_master_adam(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, rowwise: bool = False, order: str = "position"):
+        """As PoolingEmbeddingBag.enable_fused_master_adam, for every table of the model: each bag holds its own master, moments and counter,
+        one call steps them all, table after table.  Returns self."""
+        _master_adam_tables(self._modes, [b._table_dtype for b in self.bags])
+        object.__setattr__(self, "_fused_order", _order(order))
+        if lr is None:
+            object.__setattr__(self, "_fused_master_adam", None)
+            return self
+        for b in self.bags:
+            _adam_state(b, bool(rowwise))
+        object.__setattr__(self, "_fused_lr", None)
+        object.__setattr__(self, "_fused_adagrad", None)
+        object.__setattr__(self, "_fused_adam", None)
+        object.__setattr__(self, "_fused_multi", False)
+        _set_sr(self, False, 0, [b._table_dtype for b in self.bags], False)
+        self._set_masters(True, False)
+        object.__setattr__(self, "_fused_master_adam", (float(lr), (float(betas[0]), float(betas[1])), float(eps)))
+        return self
+
+    def _master_adam(self, idx, off, grad_output, lr, betas, eps, ws, col=0, order=None):
+        """Table after table through the bags, which own the masters, the moments and the counters."""
+        _master_adam_tables(self._modes, [b._table_dtype for b in self.bags])
+        for k, g in enumerate(self._table_grads(grad_output, col)):
+            if g is not None:
+                self.bags[k]._master_adam(idx[k], off[k], g, lr, betas, eps, None if ws is None else ws[k],
+                                          getattr(self, "_fused_order", "position") if order is None else order)
+
+    def master_adam_step_(self, lS_o, lS_i, grad_output, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, lS_w=None, order: str = "position"):
+        """PoolingEmbeddingBag.master_adam_step_ for all tables in one call, on the bags' masters and moments; grad_output as sgd_step_ takes it."""
+        idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
+        self._master_adam(idx, off, g, float(lr), (float(betas[0]), float(betas[1])), float(eps), ws, order=order)
+        return self
 
     def adam_step_(self, lS_o, lS_i, grad_output, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, lS_w=None, order: str = "position"):
         """PoolingEmbeddingBag.adam_step_ for all tables in one call, on the bags' states; grad_output as sgd_step_ takes it."""
