@@ -613,7 +613,8 @@ int emb_grad_max_step(emb_grad *g, const emb_grad_desc *descs, uint32_t *const *
  * libpimemb_grad_adam.so, built from the same source and found next to libpimemb_grad.so, which links against it; the other libraries'
  * code objects hold the machine code they held.
  * The master-weight form is emb_grad_master_adam_step (THE MASTER-WEIGHT ADAM STEPS, below).
- * Out of scope: multi-table, stochastically rounded and max-mode forms of the Adam steps; amsgrad, weight_decay and
+ * The multi-table form is emb_grad_adam_step_multi (THE MULTI-TABLE ADAM STEPS, below).
+ * Out of scope: stochastically rounded and max-mode forms of the Adam steps; amsgrad, weight_decay and
  * maximize; state in anything but fp32; the ranged / sharded paths. */
 typedef enum { EMB_ADAM = 1, EMB_ROWWISE_ADAM = 2 } emb_adam_kind;
 typedef struct emb_adam_spec {
@@ -632,6 +633,48 @@ int emb_adam_constants(const emb_adam_spec *spec, float out[3]);
 uint64_t emb_adam_state_floats(uint32_t kind, uint64_t nr_rows, uint32_t dim, int which);
 int emb_grad_adam_step(emb_grad *g, const emb_grad_desc *descs, float *const *exp_avg, float *const *exp_avg_sq, uint32_t n_descs,
                        emb_index_type itype, const emb_adam_spec *spec, void *stream);
+
+/* THE MULTI-TABLE ADAM STEPS: emb_grad_adam_step with one pre-pass and one launch of the hot kernel per GROUP of descriptors instead of per
+ * descriptor -- what THE MULTI-TABLE STEPS are to emb_grad_sgd / emb_grad_step.  Same arguments, checks, refusals and error texts as
+ * emb_grad_adam_step; every descriptor and both states of each are checked before anything is enqueued; DEVICE pointers only; a pure enqueue
+ * on `stream` (no allocation, no copy, no host wait: the records of a group AND its state pointers are kernel arguments, nothing must outlive
+ * the call); step_size_dev as there, so a captured graph replays with a new t; the bad-position count is the same.  Every table, every M
+ * and every V ends with exactly the bytes emb_grad_adam_step leaves over the same descriptors, in a context of either order.
+ *
+ * Groups are formed by emb_grad_multi_groups, the very function, with rules 2 - 6 of THE MULTI-TABLE STEPS as they are and rule 1, the
+ * lane-group shape, read for Adam as:
+ *   1. the gradient's shape (dim % 4 == 0, dim <= 512, grad 16-byte aligned, grad_ld % 4 == 0), M 16-byte aligned, and for EMB_ADAM V 16-byte
+ *      aligned as well (the V of EMB_ROWWISE_ADAM is one float per row: 4-byte alignment does).
+ * A group of one descriptor runs emb_grad_adam_step's single-table chain, the element-wise kernel of EMB_ADAM included.  A table named twice
+ * opens a new group and is stepped twice, in order, with the same t.  EMB_ROWWISE_ADAM off the lane-group shape is EMB_ERR_UNSUPPORTED for
+ * the whole call, as in emb_grad_adam_step, and nothing is touched.  The dtype is per descriptor: one group may hold EMB_F32, EMB_F16 and
+ * EMB_BF16 tables.
+ * How it runs.  The pre-pass of a group is THE MULTI-TABLE STEPS' (grad_multi_classify, one sort over the composite keys; in a segmented
+ * context grad_seg_multi_partials, that library's own launch).  The hot kernel, grad_adam_multi_rows<kind, order>, is grad_multi_rows /
+ * grad_seg_multi_rows in how it finds its work -- one lane group per sorted place, working where a run of a composite key starts, the run's
+ * descriptor found once per run among up to 16 ascending key bases -- and grad_adam_rows_group in what it does with it: the run walk with that
+ * descriptor's gradient, cnt and weights, then THE ADAM STEPS' tail on that descriptor's table, M and V, through the same device functions
+ * (the same bits by construction).  The group's records travel by value: the 16 descriptors of THE MULTI-TABLE STEPS and, beside them, 16 M
+ * and 16 V pointers with om1, om2, ss, eps and step_size_dev -- 2.1 KB of the 4 KB a launch takes.  A lane reads its descriptor in two
+ * halves, what the walk needs at the run head and what the tail needs (table, stride, dtype, M, V) behind the walk, where the three loads of
+ * a piece are issued together; row-wise, V[r] is loaded by every lane at the run head, before lane 0 stores V'.  Beyond dim 256 SparseAdam
+ * takes its two pieces one after the other, row-wise Adam holds both sums until the row's rate is known.
+ * Resources on gfx950 (profiles/adam_multi/README.md): no LDS, no scratch, no spills.  grad_adam_multi_rows takes 76 / 80 VGPRs (EMB_ADAM:
+ * position / segmented order) and 76 / 77 (EMB_ROWWISE_ADAM) against 65 / 70 and 63 / 64 for grad_adam_rows_group: what a run needs of its
+ * descriptor -- gradient, row stride, cnt, weights, bag count, mode, and the descriptor's number for the tail -- lives in vector registers
+ * here, where the single-table kernel holds it in scalar ones (grad_multi_rows pays the same 11 over grad_rows_group: 71 - 79 against
+ * 60 - 68).  That is 6 waves per SIMD for all four instantiations against 7 / 7 and 8 / 8: every one of them runs BELOW the occupancy of
+ * its single-table twin, by one wave (SparseAdam) and by two (row-wise).  Not hidden, and not yet bought back.
+ * The kernels have a code object of their own, libpimemb_grad_adam_multi.so, built from the same source and found next to libpimemb_grad.so,
+ * which links against it; every other library's code object holds the machine code it held.
+ * Speed, measured on MI355X (tools/adam_multi_probe.py, profiles/adam_multi/README.md; medians of five alternating rounds, device pointers,
+ * emb_grad_adam_step measured again in the same run as the yardstick; fp32 tables).  8 Kaggle tables without long runs, dim 16, 39 292
+ * one-index bags each: 200.8 us against 481.1 (18 launches against 112); 8 tables of dim 128, 2048 bags x 32: 635.9 against 851.9 us,
+ * row-wise 562.2 against 811.3; the 26 Kaggle tables on an S = 64 context: 573 us against 1 960 (34 launches against 286), in the position
+ * order 14.0 against 20.8 ms (the long-run chain).  No measured case is slower than the per-table call.
+ * Out of scope: multi-table forms of the master-weight, stochastically rounded and max-mode steps; amsgrad and weight_decay. */
+int emb_grad_adam_step_multi(emb_grad *g, const emb_grad_desc *descs, float *const *exp_avg, float *const *exp_avg_sq, uint32_t n_descs,
+                             emb_index_type itype, const emb_adam_spec *spec, void *stream);
 
 /* THE MASTER-WEIGHT ADAM STEPS: the Adam steps on fp32 master rows, fused (tests/master_adam_ref.py restates them as a loop; the kernels are
  * compared with that, bit for bit).  The only way to train EMB_F8_E4M3, EMB_F8_E5M2 and EMB_MXFP4 tables with Adam in one call, and the way

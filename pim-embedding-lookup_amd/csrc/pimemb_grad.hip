@@ -35,6 +35,10 @@
 // The Adam steps (emb_grad_adam_step; csrc/pimemb_grad_adam.h; a code object of their own, libpimemb_grad_adam.so):
 //   grad_adam_rows_group / grad_adam_rows_elem     the hot kernels' twins in both orders with the SparseAdam and row-wise Adam tails: the
 //                       table piece, the piece of exp_avg and the piece of exp_avg_sq (row-wise: V[r]) loaded together behind the walk
+// The multi-table Adam steps (emb_grad_adam_step_multi; a code object of their own, libpimemb_grad_adam_multi.so):
+//   grad_adam_multi_rows     grad_multi_rows / grad_seg_multi_rows in how a lane group finds its run and that run's descriptor, and
+//                       grad_adam_rows_group in what it does with it: the Adam tails over the runs of a group's composite keys, the
+//                       states of up to 16 tables travelling by value beside the group's records
 // The master-weight Adam steps (emb_grad_master_adam_step; a code object of their own, libpimemb_grad_master_adam.so):
 //   grad_master_adam_rows_group / grad_master_adam_rows_elem     the same walks and exits with a tail of four streams: the pieces of the fp32
 //                       master, of exp_avg and of exp_avg_sq (row-wise: V[r]) loaded together behind the walk and stored as 16-byte vectors,
@@ -69,12 +73,12 @@
 #include "pimemb_grad_sr.h"
 #include "pimemb_grad_step.h"
 
-// This file is compiled six times (csrc/Makefile): as libpimemb_grad.so, and with -DPIMEMB_GRAD_MASTER_UNIT / -DPIMEMB_GRAD_SR_UNIT /
-// -DPIMEMB_GRAD_MAX_UNIT / -DPIMEMB_GRAD_ADAM_UNIT / -DPIMEMB_GRAD_MASTER_ADAM_UNIT as the code objects of the master-weight steps, the
-// stochastically rounded steps, the max-mode backward, the Adam steps and the master-weight Adam steps, which hold their own kernels and
-// launchers alone.
+// This file is compiled seven times (csrc/Makefile): as libpimemb_grad.so, and with -DPIMEMB_GRAD_MASTER_UNIT / -DPIMEMB_GRAD_SR_UNIT /
+// -DPIMEMB_GRAD_MAX_UNIT / -DPIMEMB_GRAD_ADAM_UNIT / -DPIMEMB_GRAD_MASTER_ADAM_UNIT / -DPIMEMB_GRAD_ADAM_MULTI_UNIT as the code objects of
+// the master-weight steps, the stochastically rounded steps, the max-mode backward, the Adam steps, the master-weight Adam steps and the
+// multi-table Adam steps, which hold their own kernels and launchers alone.
 #if defined(PIMEMB_GRAD_MASTER_UNIT) || defined(PIMEMB_GRAD_SR_UNIT) || defined(PIMEMB_GRAD_MAX_UNIT) || defined(PIMEMB_GRAD_ADAM_UNIT) || \
-    defined(PIMEMB_GRAD_MASTER_ADAM_UNIT)
+    defined(PIMEMB_GRAD_MASTER_ADAM_UNIT) || defined(PIMEMB_GRAD_ADAM_MULTI_UNIT)
 #define PIMEMB_GRAD_KERNEL_UNIT 1
 #endif
 
@@ -1366,11 +1370,14 @@ enum AdamKind : int { ADAM_ELEMENTS = EMB_ADAM, ADAM_ROWWISE = EMB_ROWWISE_ADAM 
 
 // Like the master, SR and max kernels these live in a code object of their own: this file compiled with -DPIMEMB_GRAD_ADAM_UNIT into
 // libpimemb_grad_adam.so (csrc/Makefile), which exports their launch function; libpimemb_grad.so's host side calls it.
-#if defined(PIMEMB_GRAD_ADAM_UNIT) || defined(PIMEMB_GRAD_MASTER_ADAM_UNIT)      // (the master-weight Adam unit reads its step size the same way)
+#if defined(PIMEMB_GRAD_ADAM_UNIT) || defined(PIMEMB_GRAD_MASTER_ADAM_UNIT) || defined(PIMEMB_GRAD_ADAM_MULTI_UNIT)
+// (the master-weight Adam unit and the multi-table Adam unit read their step size the same way)
 // The step size of this launch: one uniform load (or none), the same word in every lane.
 __device__ __forceinline__ float adam_step_size(const AdamArgs &ad) { return ad.step_size_dev ? *ad.step_size_dev : ad.ss; }
 #endif
-#ifdef PIMEMB_GRAD_ADAM_UNIT
+// (the tail's device functions -- from here to adam_store_piece -- are text the multi-table Adam unit compiles too: inlined, no kernel of
+//  the Adam unit changes for it)
+#if defined(PIMEMB_GRAD_ADAM_UNIT) || defined(PIMEMB_GRAD_ADAM_MULTI_UNIT)
 
 // What a lane loads of piece c of a stepped row for the tail: the table piece as it lies in memory (16 bytes of an fp32 row, or 8 bytes
 // of an fp16 / bf16 row in w.x and w.y), the piece of M, and (ADAM_ELEMENTS) the piece of V.
@@ -1426,6 +1433,9 @@ __device__ __forceinline__ void adam_store_piece(const RowArgs &a, const AdamArg
     reinterpret_cast<float4 *>(ad.m + (uint64_t)row * a.dim)[c] = h.m;
     if (KIND == ADAM_ELEMENTS) reinterpret_cast<float4 *>(ad.v + (uint64_t)row * a.dim)[c] = h.v;
 }
+
+#endif      // PIMEMB_GRAD_ADAM_UNIT || PIMEMB_GRAD_ADAM_MULTI_UNIT
+#ifdef PIMEMB_GRAD_ADAM_UNIT
 
 // grad_rows_group / grad_seg_rows_group with the Adam tails: the same exits, the same walks, the same row-wise butterfly (idle lanes hold
 // +0 and take part).  Row-wise, every lane loads V[r] at the head of the run -- before lane 0 stores V' -- and nothing else is loaded before
@@ -1537,6 +1547,120 @@ namespace {
 }  // namespace
 extern "C" void pimemb_grad_adam_launch(const void *row_args, const void *seg_args, const void *adam_args, int kind, int seg, int lane, uint32_t lanes,
                                         uint32_t lanes_log2, uint32_t chunks, uint32_t blocks, uint32_t elem_blocks, uint32_t S, void *stream);
+namespace {
+#endif
+
+// ---- the multi-table Adam steps: the Adam tails over the runs of a group's composite keys (emb_grad_adam_step_multi) ----------------------
+// grad_multi_rows / grad_seg_multi_rows in how the work is found -- one lane group per sorted place of the group's concatenation, working
+// where a run of a composite key starts, the same exits, uniform over the lane group; the run's descriptor found ONCE per run from its key
+// among the up to 16 ascending key bases -- and grad_adam_rows_group in what is done with it: walk_piece / seg_walk_piece with the RowArgs of
+// that descriptor (cnt at its bag_base, weights rebased by its pos_base, as multi_row_args builds them), then the Adam tail of that
+// descriptor's table, M and V through the device functions the single-table kernels call: adam_load_piece (the table piece, the M piece and
+// the V piece issued together BEHIND the walk -- before it they lost, see above), adam_store_piece, rowwise_adam_rate, piece_squares and the
+// xor pair tree with idle lanes holding +0.  The bits are the single-table kernels' by construction; the dtype is the descriptor's, so one
+// group may hold fp32, fp16 and bf16 tables.  In a segmented context the partials are grad_seg_multi_partials' (libpimemb_grad.so's own
+// launch, enqueued before this one).
+// The group's records travel by value: MultiArgs as it is (the state pointer of a MultiDesc is not used) and AdamMultiArgs beside it, 1808 +
+// 280 bytes of the 4 KB a launch takes.  What a run needs of its descriptor is read in two halves: the walk's half (grad, ld, cnt, weights,
+// n_bags, coef) at the run head, the tail's half (table, stride, dtype, M, V) behind the walk -- row-wise, V alone at the head, for V[r].
+// Resources (gfx950, no LDS, no scratch, no spills; profiles/adam_multi/README.md): include/pimemb_grad.h states the VGPR counts of the four
+// instantiations beside their single-table twins'.
+
+struct AdamMultiArgs {
+    float *m[kMultiMax];         // exp_avg of descriptor j of the group (the j of MultiArgs::d)
+    float *v[kMultiMax];         // exp_avg_sq of it
+    float om1, om2, ss, eps;
+    const float *step_size_dev;  // or NULL: as in AdamArgs
+};
+
+// Like the other units' kernels these live in a code object of their own: this file compiled with -DPIMEMB_GRAD_ADAM_MULTI_UNIT into
+// libpimemb_grad_adam_multi.so (csrc/Makefile), which exports their launch function; libpimemb_grad.so's host side calls it.
+#ifdef PIMEMB_GRAD_ADAM_MULTI_UNIT
+
+template <int KIND, bool SEG>
+__global__ __launch_bounds__(kBlock) void grad_adam_multi_rows(const MultiArgs m, const AdamMultiArgs am, const uint32_t *keys, const uint32_t *vals,
+                                                               const uint32_t *bagof, const uint32_t *cnt, SegArgs sg, uint32_t lanes, uint32_t lanes_log2,
+                                                               uint32_t chunks) {
+    static_assert(KIND == ADAM_ELEMENTS || KIND == ADAM_ROWWISE, "an Adam kind");
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= m.n || (KIND != ADAM_ROWWISE && lg >= chunks)) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t key = keys[i];
+    if (key >= m.key_end || (i > 0 && keys[i - 1] == key)) return;        // (uniform over the lane group)
+    uint32_t k = 0;
+    for (uint32_t j = 1; j < m.k; j++)           // (uniform trip count; the bases ascend)
+        if (m.d[j].key_base <= key) k = j;
+    const MultiDesc &d = m.d[k];
+    const uint32_t row = key - d.key_base;
+    RowArgs a{};                                 // the walk's half; a.lr / a.eps / a.state stay unused, as in the single-table Adam kernels
+    a.keys = keys;
+    a.vals = vals;
+    a.bagof = bagof;
+    a.cnt = cnt + d.bag_base;
+    a.weights = d.weights ? d.weights - d.pos_base : nullptr;             // (vals[] hold positions of the group)
+    a.grad = d.grad;
+    a.ld = d.ld;
+    a.n = m.n;
+    a.n_bags = d.n_bags;
+    a.nr_rows = d.nr_rows;
+    a.dim = m.dim;
+    a.coef = d.coef;
+    AdamArgs ad{nullptr, nullptr, am.om1, am.om2, am.ss, am.eps, am.step_size_dev};
+    const float ss = adam_step_size(ad);         // read once per lane group
+    if (KIND == ADAM_ROWWISE) {
+        const bool own0 = lg < chunks, own1 = lg + lanes < chunks;        // (own1: beyond dim 256 only, where lanes == 64)
+        ad.v = am.v[k];
+        float vr = ad.v[row];                                             // (every lane's own copy of V[r]: loaded before lane 0 stores V')
+        float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
+        if (own0) acc0 = SEG ? seg_walk_piece(a, sg, i, key, lg, chunks) : walk_piece(a, i, key, lg);
+        if (own1) acc1 = SEG ? seg_walk_piece(a, sg, i, key, lg + lanes, chunks) : walk_piece(a, i, key, lg + lanes);
+        float sum = piece_squares(acc0);                                  // (+0 in a lane without a piece)
+        if (own1) sum = adagrad_add(sum, piece_squares(acc1));
+        for (uint32_t h = 1; h < lanes; h <<= 1) sum = adagrad_add(sum, __shfl_xor(sum, (int)h));      // the pair tree: the same bits in every lane
+        const float rate = rowwise_adam_rate(sum, a.dim, &vr, ad.om2, ss, ad.eps);
+        if (lg == 0) ad.v[row] = vr;
+        a.table = d.table, a.stride = d.stride, a.dtype = d.dtype;        // the tail's half
+        ad.m = am.m[k];
+        if (own0) adam_store_piece<KIND>(a, ad, row, lg, adam_load_piece<KIND>(a, ad, row, lg), acc0, rate);
+        if (own1) adam_store_piece<KIND>(a, ad, row, lg + lanes, adam_load_piece<KIND>(a, ad, row, lg + lanes), acc1, rate);
+        return;
+    }
+    for (uint32_t c = lg; c < chunks; c += lanes) {                       // (two rounds beyond dim 256 only: SparseAdam takes its pieces one after the other)
+        const float4 acc = SEG ? seg_walk_piece(a, sg, i, key, c, chunks) : walk_piece(a, i, key, c);
+        a.table = d.table, a.stride = d.stride, a.dtype = d.dtype;        // the tail's half
+        ad.m = am.m[k], ad.v = am.v[k];
+        adam_store_piece<KIND>(a, ad, row, c, adam_load_piece<KIND>(a, ad, row, c), acc, ss);
+    }
+}
+
+}  // namespace
+
+// The launch function libpimemb_grad_adam_multi.so exports (plain C; MultiArgs, AdamMultiArgs and SegArgs are this file's own, which every
+// compilation lays out alike).  The hot launch of a group's Adam step, in the context's order (seg: behind grad_seg_multi_partials).
+// kind: an emb_adam_kind.  Errors are left to the caller's hipGetLastError().
+extern "C" __attribute__((visibility("default"))) void pimemb_grad_adam_multi_launch(const void *multi_args, const void *adam_multi_args, const uint32_t *keys,
+                                                                                      const uint32_t *vals, const uint32_t *bagof, const uint32_t *cnt,
+                                                                                      const void *seg_args, int kind, int seg, uint32_t lanes, uint32_t lanes_log2,
+                                                                                      uint32_t chunks, uint32_t blocks, void *stream) {
+    const MultiArgs &m = *static_cast<const MultiArgs *>(multi_args);
+    const AdamMultiArgs &am = *static_cast<const AdamMultiArgs *>(adam_multi_args);
+    const SegArgs &sg = *static_cast<const SegArgs *>(seg_args);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid(blocks), block(kBlock);
+    if (kind == ADAM_ELEMENTS && seg) grad_adam_multi_rows<ADAM_ELEMENTS, true><<<grid, block, 0, s>>>(m, am, keys, vals, bagof, cnt, sg, lanes, lanes_log2, chunks);
+    else if (kind == ADAM_ELEMENTS) grad_adam_multi_rows<ADAM_ELEMENTS, false><<<grid, block, 0, s>>>(m, am, keys, vals, bagof, cnt, sg, lanes, lanes_log2, chunks);
+    else if (seg) grad_adam_multi_rows<ADAM_ROWWISE, true><<<grid, block, 0, s>>>(m, am, keys, vals, bagof, cnt, sg, lanes, lanes_log2, chunks);
+    else grad_adam_multi_rows<ADAM_ROWWISE, false><<<grid, block, 0, s>>>(m, am, keys, vals, bagof, cnt, sg, lanes, lanes_log2, chunks);
+}
+
+namespace {
+#else      // libpimemb_grad.so (and the other units, which never call it): the launcher is libpimemb_grad_adam_multi.so's
+}  // namespace
+extern "C" void pimemb_grad_adam_multi_launch(const void *multi_args, const void *adam_multi_args, const uint32_t *keys, const uint32_t *vals,
+                                              const uint32_t *bagof, const uint32_t *cnt, const void *seg_args, int kind, int seg, uint32_t lanes,
+                                              uint32_t lanes_log2, uint32_t chunks, uint32_t blocks, void *stream);
 namespace {
 #endif
 
@@ -2666,6 +2790,17 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
         sg.S = g->cfg.segment, sg.S_log2 = g->seg_log2;
         sg.n_slots = (uint32_t)seg_slots(g->max_indices, sg.S);      // (l.chunks <= seg_pieces(max_dim): check_desc; max_indices <= 2^30)
     }
+    if (group && spec.adam) {                    // emb_grad_adam_step_multi: the group's states by value beside its records, one launch
+        if (seg) grad_seg_multi_partials<<<dim3(l.blocks), block, 0, s>>>(m, keys, vals, sc.bagof, sc.cnt, sg, l.lanes, l.lanes_log2, l.chunks);
+        const AdamArgs &ac = spec.adam->consts;
+        AdamMultiArgs am{};
+        am.om1 = ac.om1, am.om2 = ac.om2, am.ss = ac.ss, am.eps = ac.eps, am.step_size_dev = ac.step_size_dev;
+        for (uint32_t at = first, j = 0; at < c.end; at++)      // (the j of fill_multi: the non-empty descriptors in order)
+            if (descs[at].n_indices) am.m[j] = spec.adam->m[at], am.v[j] = spec.adam->v[at], j++;
+        pimemb_grad_adam_multi_launch(&m, &am, keys, vals, sc.bagof, sc.cnt, &sg, spec.adam->kind, seg, l.lanes, l.lanes_log2, l.chunks, l.blocks, s);
+        GRAD_HIP(hipGetLastError());
+        return EMB_OK;
+    }
     if (group && seg) {
         const dim3 grid(l.blocks);
         grad_seg_multi_partials<<<grid, block, 0, s>>>(m, keys, vals, sc.bagof, sc.cnt, sg, l.lanes, l.lanes_log2, l.chunks);
@@ -3204,13 +3339,17 @@ const char *adam_fault(const emb_adam_spec *sp) {
     return nullptr;
 }
 
-// The plan of emb_grad_adam_step: every descriptor and both states checked, in order; then one chain per non-empty descriptor.
-int plan_adam(emb_grad *g, const emb_grad_desc *descs, const AdamCall &call, uint32_t n_descs, emb_index_type itype, const char *who, Planned *plan) {
+// The plan of emb_grad_adam_step(_multi): every descriptor and both states checked, in order; then one chain per non-empty descriptor, or
+// one per group (ms != NULL: the multi call; ms and group_of have n_descs entries like `plan`).  Rule 1 of the grouping is p.lane as it is
+// computed here: the gradient's shape, M 16-byte aligned, and for EMB_ADAM V 16-byte aligned as well.
+int plan_adam(emb_grad *g, const emb_grad_desc *descs, const AdamCall &call, uint32_t n_descs, emb_index_type itype, const char *who, Planned *plan,
+              emb_grad_multi_shape *ms = nullptr, uint32_t *group_of = nullptr) {
     const bool rowwise = call.kind == EMB_ROWWISE_ADAM;
     for (uint32_t k = 0; k < n_descs; k++) {
         const emb_grad_desc &d = descs[k];
         Planned &p = plan[k];
         if (int rc = check_desc(g, d, itype, "an Adam", who, &p.t)) return rc;
+        if (ms) ms[k] = emb_grad_multi_shape{d.table_id, p.t.dim, 0u, p.t.nr_rows, d.n_indices, d.n_bags};
         if (d.n_indices == 0) continue;
         const float *m = call.m[k], *v = call.v[k];
         if (!m || !v || (uintptr_t)m % 4 || (uintptr_t)v % 4)
@@ -3221,10 +3360,40 @@ int plan_adam(emb_grad *g, const emb_grad_desc *descs, const AdamCall &call, uin
                         "%s: row-wise Adam needs the lane-group shape (dim %% 4 == 0, dim <= 512, grad and exp_avg 16-byte aligned, grad_ld %% 4 == 0): "
                         "table %u has dim %u, grad %p, grad_ld %llu, exp_avg %p -- the element-wise kernel has no row-wide view of g", who, d.table_id,
                         p.t.dim, (const void *)d.grad, (unsigned long long)d.grad_ld, (const void *)m);
+        if (ms) ms[k].lane_group = p.lane ? 1u : 0u;
     }
+    if (ms) emb_grad_multi_groups(ms, n_descs, g->max_indices, g->max_bags, group_of);
+    for (uint32_t k = 0, end; k < n_descs; k = end) {
+        end = k + 1;             // (a group's members are consecutive but for the empty descriptors among them)
+        if (descs[k].n_indices == 0) continue;
+        while (ms && end < n_descs && (group_of[end] == group_of[k] || descs[end].n_indices == 0)) end++;
+        if (int rc = plan_chain(g, descs, plan, k, end)) return rc;
+    }
+    return EMB_OK;
+}
+
+// What emb_grad_adam_step and emb_grad_adam_step_multi share: the spec and the arguments checked, the plan of the whole call, then chain
+// after chain enqueued.
+int adam_call(emb_grad *g, const emb_grad_desc *descs, float *const *exp_avg, float *const *exp_avg_sq, uint32_t n_descs, emb_index_type itype,
+              const emb_adam_spec *spec, bool multi, const char *who, void *stream) {
+    if (const char *fault = adam_fault(spec)) return fail(EMB_ERR_INVALID, "%s: %s", who, fault);
+    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
+    if (n_descs && (!descs || !exp_avg || !exp_avg_sq)) return fail(EMB_ERR_INVALID, "%s: descs, exp_avg or exp_avg_sq is NULL", who);
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    float c[3];
+    adam_constants(spec->lr, spec->beta1, spec->beta2, spec->step, c);
+    const AdamCall call{exp_avg, exp_avg_sq, (int)spec->kind, AdamArgs{nullptr, nullptr, c[0], c[1], c[2], spec->eps, spec->step_size_dev}};
+    StepSpec st{spec->kind == EMB_ROWWISE_ADAM ? RES_ROWWISE : RES_ADAGRAD, 0.f, spec->eps};
+    st.adam = &call;
+    std::vector<Planned> plan(n_descs);
+    std::vector<emb_grad_multi_shape> ms(multi ? n_descs : 0);
+    std::vector<uint32_t> group_of(multi ? n_descs : 0);
+    if (int rc = plan_adam(g, descs, call, n_descs, itype, who, plan.data(), multi ? ms.data() : nullptr, group_of.data())) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
     for (uint32_t k = 0; k < n_descs; k++)
-        if (descs[k].n_indices)
-            if (int rc = plan_chain(g, descs, plan, k, k + 1)) return rc;
+        if (plan[k].k)
+            if (int rc = run_chain(g, descs, nullptr, plan.data(), k, itype == EMB_IDX_I64, st, SparseOut{}, s)) return rc;
     return EMB_OK;
 }
 
@@ -3246,24 +3415,12 @@ uint64_t emb_adam_state_floats(uint32_t kind, uint64_t nr_rows, uint32_t dim, in
 
 int emb_grad_adam_step(emb_grad *g, const emb_grad_desc *descs, float *const *exp_avg, float *const *exp_avg_sq, uint32_t n_descs, emb_index_type itype,
                        const emb_adam_spec *spec, void *stream) {
-    const char *who = "emb_grad_adam_step";
-    if (const char *fault = adam_fault(spec)) return fail(EMB_ERR_INVALID, "%s: %s", who, fault);
-    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
-    if (n_descs && (!descs || !exp_avg || !exp_avg_sq)) return fail(EMB_ERR_INVALID, "%s: descs, exp_avg or exp_avg_sq is NULL", who);
-    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
-    float c[3];
-    adam_constants(spec->lr, spec->beta1, spec->beta2, spec->step, c);
-    const AdamCall call{exp_avg, exp_avg_sq, (int)spec->kind, AdamArgs{nullptr, nullptr, c[0], c[1], c[2], spec->eps, spec->step_size_dev}};
-    StepSpec st{spec->kind == EMB_ROWWISE_ADAM ? RES_ROWWISE : RES_ADAGRAD, 0.f, spec->eps};
-    st.adam = &call;
-    std::vector<Planned> plan(n_descs);
-    if (int rc = plan_adam(g, descs, call, n_descs, itype, who, plan.data())) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DeviceGuard guard(g->device);
-    for (uint32_t k = 0; k < n_descs; k++)
-        if (plan[k].k)
-            if (int rc = run_chain(g, descs, nullptr, plan.data(), k, itype == EMB_IDX_I64, st, SparseOut{}, s)) return rc;
-    return EMB_OK;
+    return adam_call(g, descs, exp_avg, exp_avg_sq, n_descs, itype, spec, false, "emb_grad_adam_step", stream);
+}
+
+int emb_grad_adam_step_multi(emb_grad *g, const emb_grad_desc *descs, float *const *exp_avg, float *const *exp_avg_sq, uint32_t n_descs,
+                             emb_index_type itype, const emb_adam_spec *spec, void *stream) {
+    return adam_call(g, descs, exp_avg, exp_avg_sq, n_descs, itype, spec, true, "emb_grad_adam_step_multi", stream);
 }
 
 }  // extern "C"

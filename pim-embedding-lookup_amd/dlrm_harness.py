@@ -265,7 +265,8 @@ class EmbeddingBagCollection:
         """As enable_fused_sgd, with the fused Adam step (torch.optim.SparseAdam; rowwise=True: row-wise Adam, one second moment per row;
         GradContext.adam_step).  The fp32 states -- self.adam_exp_avg / self.adam_exp_avg_sq, one tensor each per table -- are allocated
         here as zeros, once per flavour, and self.adam_step counts the steps.  lr=None switches it off.  Switches the other fused steps
-        and stochastic rounding off: the Adam steps have no such form, and no multi-table one.  master_weights=True: the master-weight
+        and stochastic rounding off: the Adam steps have no such form.  With multi_table_step the tables go through the multi-table Adam
+        step (one pre-pass and one launch per group; not with master_weights).  master_weights=True: the master-weight
         Adam step (GradContext.master_adam_step) on fp32 masters, the way to train f16, bf16, fp8 and MXFP4 tables with Adam."""
         import torch
         if lr is None:
@@ -306,9 +307,9 @@ class EmbeddingBagCollection:
             ctx = tm._grad_context(self.engine, size(i.shape[0] for i in lS_i), size(o.shape[0] for o in lS_o), *order)
             args = ([self._ids[k] for k in live], [lS_i[k] for k in live], [lS_o[k] for k in live], [grads[k] for k in live])
             w_live = [None if ws is None else ws[k] for k in live]
-            if adam is not None:         # the fused Adam step (emb_grad_adam_step): table after table, one t for the whole model
-                if multi:
-                    raise ValueError("multi_table_step does not go with the fused Adam steps: there is no multi-table Adam step")
+            if adam is not None:         # the fused Adam step (emb_grad_adam_step, or its multi-table form): one t for the whole model
+                if multi and self.master_weight is not None:
+                    raise ValueError("multi_table_step does not go with master weights: there is no multi-table master-weight Adam step")
                 self.adam_step += 1
                 if self.master_weight is not None:      # ... on fp32 masters (emb_grad_master_adam_step): every table dtype but fp32
                     ctx.master_adam_step(*args, [self.master_weight[k] for k in live], [self.adam_exp_avg[k] for k in live],
@@ -316,7 +317,7 @@ class EmbeddingBagCollection:
                                          rowwise=adam[3], per_sample_weights=w_live)
                     return
                 ctx.adam_step(*args,[self.adam_exp_avg[k] for k in live], [self.adam_exp_avg_sq[k] for k in live], adam[0], betas=adam[1], eps=adam[2],
-                              step=self.adam_step, rowwise=adam[3], per_sample_weights=w_live)
+                              step=self.adam_step, rowwise=adam[3], per_sample_weights=w_live, multi=multi)
                 return
             masters = self.master_weight
             if masters is not None:      # the fused master-weight step (emb_grad_master_step): every table dtype but fp32, table after table
@@ -504,7 +505,8 @@ def main(argv=None):
                     help="as --fused-sgd, with the fused row-wise Adagrad step (one fp32 accumulator per row; feature size a multiple of 4)")
     ap.add_argument("--fused-adam", type=float, default=None, metavar="LR",
                     help="as --fused-sgd, with the fused SparseAdam step (betas 0.9 / 0.999, eps 1e-8, two fp32 states of the tables' shape); "
-                         "not with --multi-table-step, --master-weights or --stochastic-rounding")
+                         "not with --stochastic-rounding; with --multi-table-step through the multi-table Adam step, with --master-weights "
+                         "as the master-weight Adam step")
     ap.add_argument("--fused-rowwise-adam", type=float, default=None, metavar="LR",
                     help="as --fused-adam, with the fused row-wise Adam step (one fp32 second moment per row; feature size a multiple of 4)")
     ap.add_argument("--multi-table-step", action="store_true",
@@ -537,11 +539,11 @@ def main(argv=None):
                                          ("Adam", args.fused_adam), ("row-wise Adam", args.fused_rowwise_adam)) if lr is not None]
     if len(fused) > 1:
         raise SystemExit("--fused-sgd, --fused-adagrad and --fused-rowwise-adagrad are mutually exclusive, and so are --fused-adam and --fused-rowwise-adam")
-    if fused and "Adam" in fused[0][0] and (args.multi_table_step or args.stochastic_rounding is not None):
-        raise SystemExit("--fused-adam and --fused-rowwise-adam do not go with --multi-table-step or --stochastic-rounding: the Adam steps have no such "
-                         "forms (with --master-weights they run as the master-weight Adam step)")
+    if fused and "Adam" in fused[0][0] and args.stochastic_rounding is not None:
+        raise SystemExit("--fused-adam and --fused-rowwise-adam do not go with --stochastic-rounding: the Adam steps have no such form (with "
+                         "--master-weights they run as the master-weight Adam step)")
     if args.multi_table_step and not fused:
-        raise SystemExit("--multi-table-step goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
+        raise SystemExit("--multi-table-step goes with one of the --fused-* flags")
     if args.master_weights and not fused:
         raise SystemExit("--master-weights goes with one of --fused-sgd, --fused-adagrad and --fused-rowwise-adagrad")
     if args.master_weights and args.multi_table_step:

@@ -571,7 +571,9 @@ class GradContext:
     def multi_groups(self, table_ids, n_indices, n_bags, lane_group=True) -> list:
         """How a multi=True step over these tables would be split in this context (emb_grad_multi_groups): the group number of
         every entry, None for an empty one.  n_indices / n_bags: one count per table; lane_group: one bool for all or one per
-        table -- whether its gradient (and Adagrad state) has the lane-group shape of include/pimemb_grad.h."""
+        table -- whether its gradient (and Adagrad state) has the lane-group shape of include/pimemb_grad.h.  For adam_step(multi=True)
+        lane_group means: the gradient's shape (dim % 4 == 0, dim <= 512, 16-byte aligned, row stride % 4 == 0), exp_avg 16-byte aligned,
+        and for SparseAdam exp_avg_sq 16-byte aligned as well (torch allocations are)."""
         n = len(table_ids)
         lg = list(lane_group) if isinstance(lane_group, (list, tuple)) else [lane_group] * n
         shapes, out = (_l.EmbGradMultiShape * max(n, 1))(), (C.c_uint32 * max(n, 1))()
@@ -672,12 +674,13 @@ class GradContext:
 
     def adam_step(self, table_ids, indices, offsets, grads, exp_avgs, exp_avg_sqs, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, step: int = 1,
                   rowwise: bool = False, step_size_dev=None, modes="sum", per_sample_weights=None, padding_idx=None, fixed_pooling: int = 0,
-                  stream: int | None = None) -> None:
+                  stream: int | None = None, multi: bool = False) -> None:
         """The fused SparseAdam step (rowwise=True: row-wise Adam, one second moment per row) of include/pimemb_grad.h, table after table:
         conventions as sgd_step.  exp_avgs / exp_avg_sqs: one state each per table, adam_state_shapes(table, rowwise) float32 values, read
         and written in place -- CUDA tensors with torch inputs, numpy arrays (copied to the device and back) with numpy inputs; the caller
         initialises them (zeros).  step: t >= 1, the same for every table of the call.  step_size_dev: a float32 CUDA tensor of one element
-        the kernels read instead of the step size of `step` (adam_constants(...)[2]): what a captured graph replays with."""
+        the kernels read instead of the step size of `step` (adam_constants(...)[2]): what a captured graph replays with.  multi=True: the
+        multi-table Adam step (emb_grad_adam_step_multi) -- one pre-pass and one launch per group of tables (multi_groups), the same bytes."""
         if len(exp_avgs) != len(table_ids) or len(exp_avg_sqs) != len(table_ids):
             raise ValueError(f"{len(exp_avgs)} exp_avg and {len(exp_avg_sqs)} exp_avg_sq states for {len(table_ids)} tables")
         spec = self._adam_spec(lr, betas, eps, step, rowwise, step_size_dev)
@@ -706,7 +709,8 @@ class GradContext:
                         back.append((st, buf))
                         p[k] = buf.ptr
                 ptrs.append(p)
-            _l.check_grad(self._G.emb_grad_adam_step(self._h, arr, ptrs[0], ptrs[1], n, itype, C.byref(spec), stream))
+            call = self._G.emb_grad_adam_step_multi if multi else self._G.emb_grad_adam_step
+            _l.check_grad(call(self._h, arr, ptrs[0], ptrs[1], n, itype, C.byref(spec), stream))
             if not dev:
                 self.engine.synchronize(stream)
                 for st, buf in back:

@@ -296,6 +296,7 @@ GRAD_SIGNATURES = {
     "emb_adam_constants": (C.c_int, [C.POINTER(EmbAdamSpec), C.POINTER(C.c_float)]),
     "emb_adam_state_floats": (_u64, [_u32, _u64, _u32, C.c_int]),
     "emb_grad_adam_step": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbAdamSpec), _vp]),
+    "emb_grad_adam_step_multi": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbAdamSpec), _vp]),
     "emb_grad_master_adam_step": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _u32, C.c_int, C.POINTER(EmbAdamSpec),
                                             _vp]),
 }
@@ -371,8 +372,10 @@ def load_grad() -> C.CDLL:
     load()
     if _grad_lib is not None:          # (load() came here itself)
         return _grad_lib
-    from .build import GRAD_ADAM_LIB_PATH, GRAD_LIB_PATH, GRAD_MASTER_ADAM_LIB_PATH, GRAD_MASTER_LIB_PATH, GRAD_MAX_LIB_PATH, GRAD_SR_LIB_PATH
-    for dep in (GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH, GRAD_MAX_LIB_PATH, GRAD_ADAM_LIB_PATH, GRAD_MASTER_ADAM_LIB_PATH):      # libpimemb_grad.so links against all five (RUNPATH $ORIGIN): name the one that is missing
+    from .build import (GRAD_ADAM_LIB_PATH, GRAD_ADAM_MULTI_LIB_PATH, GRAD_LIB_PATH, GRAD_MASTER_ADAM_LIB_PATH, GRAD_MASTER_LIB_PATH, GRAD_MAX_LIB_PATH,
+                        GRAD_SR_LIB_PATH)
+    for dep in (GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH, GRAD_MAX_LIB_PATH, GRAD_ADAM_LIB_PATH, GRAD_MASTER_ADAM_LIB_PATH,
+                GRAD_ADAM_MULTI_LIB_PATH):      # libpimemb_grad.so links against all six (RUNPATH $ORIGIN): name the one that is missing
         if not os.path.exists(dep):
             raise FileNotFoundError(
                 f"{dep} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "

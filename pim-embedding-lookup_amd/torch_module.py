@@ -32,8 +32,9 @@ stochastic_rounding=True raise ValueError there, and so does multi_table=True of
 stepped on its own, through the same call).
 `enable_fused_adam(lr, betas, eps, rowwise)` / `adam_step_` are the same with the fused SparseAdam or row-wise Adam step
 (emb_grad_adam_step); the fp32 states are `module.adam_exp_avg` / `adam_exp_avg_sq`, the counter `module.adam_step`, and all three
-are in state_dict() once they exist.  Enabling one fused optimizer disables the others; master_weights, stochastic_rounding,
-multi_table and mode="max" raise ValueError with Adam.
+are in state_dict() once they exist.  Enabling one fused optimizer disables the others; master_weights, stochastic_rounding
+and mode="max" raise ValueError with Adam, and so does multi_table on a single bag.  A fused model takes
+`enable_fused_adam(..., multi_table=True)`: one multi-table call (emb_grad_adam_step_multi) steps all its tables, the same bytes.
 `enable_fused_master_adam(lr, betas, eps, rowwise, order)` / `master_adam_step_` are the Adam steps on fp32 master rows
 (emb_grad_master_adam_step): the module keeps `master_weight` beside the Adam states and the table row is the new master row's
 encoding -- fp16, bf16, fp8 and MXFP4 tables; fp32 tables and mode="max" raise ValueError.
@@ -1110,8 +1111,10 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
                           master_weights: bool = False, stochastic_rounding: bool = False, multi_table: bool = False):
         """As PoolingEmbeddingBag.enable_fused_adam, for every table of the model: each bag holds its own states and counter
         (bags[k].adam_exp_avg / adam_exp_avg_sq / adam_step, saved as `bags.<k>.adam_*`), one call steps them all, table after table.
-        Returns self."""
-        _no_adam_variants(self._modes, master_weights, stochastic_rounding, multi_table)
+        multi_table=True: by the multi-table Adam step (emb_grad_adam_step_multi: one pre-pass and one launch per group of up to 16 tables
+        instead of per table; the same bytes) -- the states and counters stay the bags' own.  It does not go with master_weights or
+        stochastic_rounding: ValueError.  Returns self."""
+        _no_adam_variants(self._modes, master_weights, stochastic_rounding, False)
         object.__setattr__(self, "_fused_order", _order(order))
         object.__setattr__(self, "_fused_master_adam", None)
         if lr is None:
@@ -1122,15 +1125,33 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         object.__setattr__(self, "_fused_adam", (float(lr), (float(betas[0]), float(betas[1])), float(eps)))
         object.__setattr__(self, "_fused_lr", None)
         object.__setattr__(self, "_fused_adagrad", None)
-        object.__setattr__(self, "_fused_multi", False)
+        object.__setattr__(self, "_fused_multi", bool(multi_table))
         _set_sr(self, False, 0, [b._table_dtype for b in self.bags], False)
         self._set_masters(False, False)
         return self
 
-    def _adam(self, idx, off, grad_output, lr, betas, eps, ws, col=0, order=None):
+    def _adam(self, idx, off, grad_output, lr, betas, eps, ws, col=0, order=None, multi=None):
         """Table after table through the bags, which own the states and the counters: bags that have taken different numbers of steps run
-        with different t."""
+        with different t.  multi: ONE multi-table call over the tables that share t and the flavour of V (all of them, in a model whose
+        bags were stepped together), on a context sized by the sums of their indices and bags."""
         _no_adam_variants(self._modes, False, False, False)
+        multi = getattr(self, "_fused_multi", False) if multi is None else bool(multi)
+        if multi:
+            if self._masters_on():
+                raise ValueError("multi_table=True does not go with master weights: there is no multi-table master-weight Adam step")
+            call = self._live_grads(idx, off, grad_output, ws, col, True, order)
+            if call is None:
+                return
+            ctx, args, kw, live = call
+            states = [_adam_state(self.bags[k]) for k in live]
+            for key in sorted({(self.bags[k].adam_step + 1, v.dim() == 1) for k, (_m, v) in zip(live, states)}):
+                sel = [j for j, k in enumerate(live) if (self.bags[k].adam_step + 1, states[j][1].dim() == 1) == key]
+                pick = lambda v: [v[j] for j in sel]  # noqa: E731
+                ctx.adam_step(*[pick(a) for a in args], [states[j][0] for j in sel], [states[j][1] for j in sel], lr, betas=betas, eps=eps,
+                              step=key[0], rowwise=key[1], multi=True, **{n: pick(v) for n, v in kw.items()})
+                for j in sel:
+                    object.__setattr__(self.bags[live[j]], "_adam_step", key[0])
+            return
         for k, g in enumerate(self._table_grads(grad_output, col)):
             if g is not None:
                 self.bags[k]._adam(idx[k], off[k], g, lr, betas, eps, None if ws is None else ws[k],
@@ -1169,10 +1190,12 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         self._master_adam(idx, off, g, float(lr), (float(betas[0]), float(betas[1])), float(eps), ws, order=order)
         return self
 
-    def adam_step_(self, lS_o, lS_i, grad_output, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, lS_w=None, order: str = "position"):
-        """PoolingEmbeddingBag.adam_step_ for all tables in one call, on the bags' states; grad_output as sgd_step_ takes it."""
+    def adam_step_(self, lS_o, lS_i, grad_output, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, lS_w=None, order: str = "position",
+                   multi_table: bool = False):
+        """PoolingEmbeddingBag.adam_step_ for all tables in one call, on the bags' states; grad_output as sgd_step_ takes it.  multi_table:
+        as enable_fused_adam."""
         idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
-        self._adam(idx, off, g, float(lr), (float(betas[0]), float(betas[1])), float(eps), ws, order=order)
+        self._adam(idx, off, g, float(lr), (float(betas[0]), float(betas[1])), float(eps), ws, order=order, multi=multi_table)
         return self
 
     @property
