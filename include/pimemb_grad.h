@@ -56,8 +56,7 @@
  * Out of scope: optimizers other than SGD, Adagrad, row-wise Adagrad, SparseAdam and row-wise Adam (no momentum SGD, no amsgrad),
  * weight decay and lr_decay, optimizer state in anything but fp32; row-wise Adagrad off the
  * lane-group shape (the element-wise kernel has no row-wide view of g, and a second reduction is not built for it:
- * EMB_ERR_UNSUPPORTED); a multi-table emb_grad_sparse (it stays single; emb_grad_sgd_multi / emb_grad_step_multi below fuse the
- * steps of several tables); fusing descriptors of different dim, or of the element-wise shape, into one launch (they run on
+ * EMB_ERR_UNSUPPORTED); fusing descriptors of different dim, or of the element-wise shape, into one launch (they run on
  * their own, as before); splitting long runs IN THE POSITION ORDER (there a row that occurs thousands of times is one chain walked
  * by one lane group, in the multi-table step as well: a context of EMB_GRAD_ORDER_SEGMENTED, below, sums such a row in parallel, in
  * a second order that is as fixed as this one -- it is opt-in per context and nothing chooses it for the caller); a third level
@@ -295,6 +294,57 @@ uint32_t emb_grad_multi_groups(const emb_grad_multi_shape *shapes, uint32_t n, u
 int emb_grad_sgd_multi(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, float lr, void *stream);
 int emb_grad_step_multi(emb_grad *g, const emb_grad_desc *descs, float *const *states, uint32_t n_descs, emb_index_type itype,
                         const emb_opt_spec *opt, void *stream);
+
+/* THE MULTI-TABLE SPARSE GRADIENT: emb_grad_sparse over n_descs descriptors with one pre-pass per GROUP of them instead of per descriptor --
+ * the way out for every optimizer this library does not fuse, and the first half of the master-row recipe, at the launch count of THE
+ * MULTI-TABLE STEPS.
+ *   rows_out[k], grads_out[k], capacity[k]   HOST arrays of n_descs entries: what emb_grad_sparse takes for descs[k] (DEVICE buffers)
+ *   n_unique_dev                             a DEVICE uint64_t[n_descs]: entry k receives |U_k|
+ * rows_out[k], grads_out[k] and n_unique_dev[k] end with exactly the bytes emb_grad_sparse(g, &descs[k], itype, rows_out[k], grads_out[k],
+ * capacity[k], &n_unique_dev[k], stream) leaves, in a context of either order and for every table dtype that call takes: rows local to
+ * their table, ascending, int64; entries beyond |U_k| untouched; |U_k| = 0 for an empty descriptor; bad positions counted once, in the same
+ * counter.  DEVICE pointers only; a pure enqueue on `stream` (no allocation, no copy, no host wait: the records of a group AND its output
+ * pointers are kernel arguments, nothing must outlive the call; nothing is cleared by a memset node): it can be captured in a graph.
+ * Everything is checked before anything is enqueued, with emb_grad_sparse's checks and texts -- EMB_FIXED32 tables, EMB_POOL_MAX, the
+ * context's limits, tables of 2^32 - 1 rows or more; a NULL rows_out, grads_out, capacity or n_unique_dev; a NULL or misaligned rows_out[k]
+ * or grads_out[k] where n_indices > 0; capacity[k] < n_indices -- and a refused call writes nothing.  A staged hot set does not refuse:
+ * nothing in a table is read.
+ * Groups are formed by emb_grad_multi_groups, the very function, with rules 2 - 6 of THE MULTI-TABLE STEPS as they are and rule 1 read as:
+ *   1. the gradient's shape (dim % 4 == 0, dim <= 512, grad 16-byte aligned, grad_ld % 4 == 0) and grads_out[k] 16-byte aligned.
+ * A group of one descriptor runs emb_grad_sparse's single-table chain, the element-wise kernel included; a table named twice opens a new
+ * group.  A group is laid out in the context's scratch like one descriptor of that many positions (emb_grad_scratch_bytes is what it was).
+ * How it runs.  The pre-pass of a group is THE MULTI-TABLE STEPS' (grad_multi_classify, one sort over the composite keys key_base[k] + id; in
+ * a segmented context grad_seg_multi_partials) and the head-flag scan of emb_grad_sparse over the sorted composite keys, which numbers the
+ * unique (descriptor, row) runs of the whole group in key order: descriptor 0's rows, then descriptor 1's, ...  Two launches follow.
+ * grad_multi_sparse_bounds, ONE wavefront: lane k <= K binary-searches the sorted keys for the first place whose key is >= key_base[k]
+ * (key_base[K] = the key of every position that is not good: they sort behind everything and belong to no descriptor) and reads the scan
+ * there: ubase[k], the unique runs before descriptor k; a shuffle gives |U_k| = ubase[k + 1] - ubase[k], stored to n_unique_dev[k]; a
+ * descriptor without a good position finds its successor's place and gets 0.  The up to 17 ubase words stay in the context's 256-byte counter
+ * block (bytes 128 .. 195; the scan's total in bytes 64 .. 71; the bad and the unencodable count are bytes 0 .. 15).
+ * grad_multi_sparse_rows<order>: one lane group per sorted place, working where a run of a composite key starts, the run's descriptor found
+ * once among up to 16 ascending key bases as in grad_multi_rows; the run walk is emb_grad_sparse's -- eight 16-byte loads of G in flight, the
+ * adds in position order; segmented: the fold of the stored partials for runs longer than S -- through the device functions grad_rows_group /
+ * grad_seg_rows_group call, so the bits agree by construction; then lane l stores its 16-byte piece (two beyond dim 256) to grads_out[k] +
+ * (u - ubase[k]) * dim, u the run's number from the scan, and the lane of piece 0 stores rows_out[k][u - ubase[k]] = key - key_base[k].
+ * Plain vector stores; no atomics.  A lane reads its descriptor in two halves: the walk's at the run head, the output pointers and ubase[k]
+ * behind the walk.
+ * Resources on gfx950 (profiles/grad_sparse_multi/README.md): no LDS, no scratch, no spills.  grad_multi_sparse_rows takes 78 VGPRs in the position
+ * order and 82 in the segmented one, against 71 - 75 / 76 - 79 for grad_multi_rows / grad_seg_multi_rows and 63 / 67 for the single-table
+ * grad_rows_group / grad_seg_rows_group of emb_grad_sparse: 6 and 5 waves per SIMD against 7 - 6 / 6 and 8 / 7.  The segmented instantiation
+ * runs one wave BELOW the multi-table steps' kernel and both run two BELOW their single-table twins: what a run needs of its descriptor lives
+ * in vector registers, as in grad_multi_rows, and the run's place stays live across the walk for the scan read behind it.  An empty asm
+ * statement behind the walk keeps the output half's loads from being hoisted above it (81 / 85 VGPRs without it).  Not hidden, and not yet
+ * bought back.  grad_multi_sparse_bounds is one wavefront of 10 VGPRs.
+ * The kernels have a code object of their own, libpimemb_grad_sparse_multi.so, built from the same source and found next to
+ * libpimemb_grad.so, which links against it; every other library's code object holds the machine code it held.
+ * Speed, measured on MI355X (tools/grad_sparse_multi_probe.py, profiles/grad_sparse_multi/README.md; medians of five alternating rounds,
+ * device pointers, the per-table emb_grad_sparse loop measured again in the same run as the yardstick; fp32 tables; the two compared byte for byte before the first round).  8 Kaggle tables without long runs, dim 16, 39 292 one-index bags each,
+ * 298 925 unique rows: 124.1 us against 443.0 (one group: 21 launches, counted from the enqueue path, not traced); 8 tables of dim 128,
+ * 2048 bags x 32, 520 209 unique rows: 391.1 against 619.9 us; the 26 Kaggle tables on an S = 64 context (groups of 16 and 10): 541 us
+ * against 2 018.  No measured case is slower than the per-table loop; the spread of the five rounds stayed below 0.4 %.
+ * Out of scope: a multi-table emb_grad_max_sparse; compacting the per-table lists into one buffer; the ranged / sharded paths. */
+int emb_grad_sparse_multi(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, int64_t *const *rows_out,
+                          float *const *grads_out, const uint64_t *capacity, uint64_t *n_unique_dev, void *stream);
 
 /* THE GRADIENT OF PER_SAMPLE_WEIGHTS (tests/psw_ref.py restates it as a loop over positions; the kernels are compared with that, bit
  * for bit).  The second gradient of nn.EmbeddingBag(mode="sum", per_sample_weights=w): one fp32 value per position of the batch,

@@ -15,6 +15,7 @@ GRAD_MAX_LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb_grad_max.so")     # 
 GRAD_ADAM_LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb_grad_adam.so")     # the kernels of the Adam steps: libpimemb_grad.so links against it as well
 GRAD_MASTER_ADAM_LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb_grad_master_adam.so")     # the kernels of the master-weight Adam steps: likewise
 GRAD_ADAM_MULTI_LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb_grad_adam_multi.so")     # the kernels of the multi-table Adam steps: likewise
+GRAD_SPARSE_MULTI_LIB_PATH = os.path.join(PKG_DIR, "lib", "libpimemb_grad_sparse_multi.so")     # the kernels of the multi-table sparse gradient: likewise
 MARSHAL_PATH =os.path.join(PKG_DIR, "lib", "_pimemb_marshal.so")
 SOURCES = ["pimemb_kernels.hip", "pimemb_strided_kernels.hip", "pimemb_engine.cpp", "pimemb_compat.cpp", "pimemb_comm.cpp", "pimemb_shard.cpp", "pimemb_peer.cpp", "pimemb_peer.h", "pimemb_internal.h", "pimemb_torch_marshal.cpp",
            "pimemb_bag_kernels.h", "pimemb_pool_kernels.inc", "pimemb_sum_kernels.inc", "pimemb_mx4_kernels.inc", "pimemb_xcd_map.h", "pimemb_hot_rows.h", "pimemb_hostcopy.h", "Makefile",
@@ -25,7 +26,7 @@ SOURCES = ["pimemb_kernels.hip", "pimemb_strided_kernels.hip", "pimemb_engine.cp
 
 def is_stale() -> bool:
     libs = (LIB_PATH, ROWS_LIB_PATH, GRAD_LIB_PATH, GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH, GRAD_MAX_LIB_PATH, GRAD_ADAM_LIB_PATH, GRAD_MASTER_ADAM_LIB_PATH,
-            GRAD_ADAM_MULTI_LIB_PATH)
+            GRAD_ADAM_MULTI_LIB_PATH, GRAD_SPARSE_MULTI_LIB_PATH)
     if not all(os.path.exists(p) for p in libs):
         return True
     built = min(os.path.getmtime(p) for p in libs)
@@ -90,6 +91,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("libpimemb_grad_master_adam.so missing after build")
     if not os.path.exists(GRAD_ADAM_MULTI_LIB_PATH):
         raise RuntimeError("libpimemb_grad_adam_multi.so missing after build")
+    if not os.path.exists(GRAD_SPARSE_MULTI_LIB_PATH):
+        raise RuntimeError("libpimemb_grad_sparse_multi.so missing after build")
     build_marshal(verbose)          # optional: a failure is a warning, never an error
     return LIB_PATH
 

@@ -39,6 +39,11 @@
 //   grad_adam_multi_rows     grad_multi_rows / grad_seg_multi_rows in how a lane group finds its run and that run's descriptor, and
 //                       grad_adam_rows_group in what it does with it: the Adam tails over the runs of a group's composite keys, the
 //                       states of up to 16 tables travelling by value beside the group's records
+// The multi-table sparse gradient (emb_grad_sparse_multi; a code object of its own, libpimemb_grad_sparse_multi.so):
+//   grad_multi_sparse_bounds one wavefront: where each descriptor's share of the group's unique-run numbering starts (a binary search in the
+//                       sorted composite keys per descriptor, the head scan read there), and so every descriptor's |U|
+//   grad_multi_sparse_rows   grad_multi_rows / grad_seg_multi_rows in how a lane group finds its run and that run's descriptor; the walked sum
+//                       and the row id go to that descriptor's own output arrays, at the run's number minus the descriptor's start
 // The master-weight Adam steps (emb_grad_master_adam_step; a code object of their own, libpimemb_grad_master_adam.so):
 //   grad_master_adam_rows_group / grad_master_adam_rows_elem     the same walks and exits with a tail of four streams: the pieces of the fp32
 //                       master, of exp_avg and of exp_avg_sq (row-wise: V[r]) loaded together behind the walk and stored as 16-byte vectors,
@@ -73,12 +78,13 @@
 #include "pimemb_grad_sr.h"
 #include "pimemb_grad_step.h"
 
-// This file is compiled seven times (csrc/Makefile): as libpimemb_grad.so, and with -DPIMEMB_GRAD_MASTER_UNIT / -DPIMEMB_GRAD_SR_UNIT /
-// -DPIMEMB_GRAD_MAX_UNIT / -DPIMEMB_GRAD_ADAM_UNIT / -DPIMEMB_GRAD_MASTER_ADAM_UNIT / -DPIMEMB_GRAD_ADAM_MULTI_UNIT as the code objects of
-// the master-weight steps, the stochastically rounded steps, the max-mode backward, the Adam steps, the master-weight Adam steps and the
-// multi-table Adam steps, which hold their own kernels and launchers alone.
+// This file is compiled eight times (csrc/Makefile): as libpimemb_grad.so, and with -DPIMEMB_GRAD_MASTER_UNIT / -DPIMEMB_GRAD_SR_UNIT /
+// -DPIMEMB_GRAD_MAX_UNIT / -DPIMEMB_GRAD_ADAM_UNIT / -DPIMEMB_GRAD_MASTER_ADAM_UNIT / -DPIMEMB_GRAD_ADAM_MULTI_UNIT /
+// -DPIMEMB_GRAD_SPARSE_MULTI_UNIT as the code objects of the master-weight steps, the stochastically rounded steps, the max-mode backward,
+// the Adam steps, the master-weight Adam steps, the multi-table Adam steps and the multi-table sparse gradient, which hold their own kernels
+// and launchers alone.
 #if defined(PIMEMB_GRAD_MASTER_UNIT) || defined(PIMEMB_GRAD_SR_UNIT) || defined(PIMEMB_GRAD_MAX_UNIT) || defined(PIMEMB_GRAD_ADAM_UNIT) || \
-    defined(PIMEMB_GRAD_MASTER_ADAM_UNIT) || defined(PIMEMB_GRAD_ADAM_MULTI_UNIT)
+    defined(PIMEMB_GRAD_MASTER_ADAM_UNIT) || defined(PIMEMB_GRAD_ADAM_MULTI_UNIT) || defined(PIMEMB_GRAD_SPARSE_MULTI_UNIT)
 #define PIMEMB_GRAD_KERNEL_UNIT 1
 #endif
 
@@ -1664,6 +1670,120 @@ extern "C" void pimemb_grad_adam_multi_launch(const void *multi_args, const void
 namespace {
 #endif
 
+// ---- the multi-table sparse gradient: the runs of a group's composite keys written out per table (emb_grad_sparse_multi) -------------------
+// The pre-pass of a group is the multi-table steps' (grad_multi_classify, one sort over the composite keys) followed by the head-flag scan of
+// emb_grad_sparse over the SORTED COMPOSITE keys: uidx[i] + usums[i / 1024] numbers the unique (descriptor, row) runs of the whole group,
+// 0, 1, 2, ... in key order -- all of descriptor 0's rows, then descriptor 1's, and so on.  What is missing is where each descriptor's share of
+// that numbering starts, and two launches of this unit supply it:
+//   grad_multi_sparse_bounds   ONE wavefront.  Lane j <= k finds the first sorted place whose key is >= key_base[j] (key_base[k] = key_end:
+//                       the keys of positions that are not good) by binary search and reads the scan there (behind the last place: the
+//                       scan's total): ubase[j], the number of unique runs before descriptor j.  A shuffle hands lane j its neighbour's:
+//                       n_unique_dev[j] = ubase[j + 1] - ubase[j].  A descriptor without a good position finds the place its successor
+//                       finds: count 0.  The k + 1 words are left in the context's counter block for the next launch.
+//   grad_multi_sparse_rows<SEG>   grad_multi_rows / grad_seg_multi_rows in how a lane group finds its run and that run's descriptor, and
+//                       grad_rows_group<RES_SPARSE> in what it does with it: walk_piece / seg_walk_piece with the RowArgs of that descriptor
+//                       (the same device functions: the same bits), then lane l stores its 16-byte piece to grads_out[j] + (u - ubase[j]) * dim
+//                       and the lane of piece 0 stores rows_out[j][u - ubase[j]] = key - key_base[j].  Plain vector stores; no atomics, no LDS.
+// The group's records travel by value: MultiArgs as it is (table, stride, dtype and state of a MultiDesc are not used) and SparseMultiArgs
+// beside it, 1808 + 384 bytes of the 4 KB a launch takes.  A lane reads its descriptor in two halves: the walk's half at the run head, the
+// output pointers and ubase[j] behind the walk.  The local number is clamped below the descriptor's n_indices <= capacity: it lies below it
+// anyway (a descriptor has no more unique rows than positions), and the clamp is the bound of the stores all the same.
+
+struct SparseMultiArgs {
+    long long *rows[kMultiMax];             // rows_out of descriptor j of the group (the j of MultiArgs::d)
+    float *grads[kMultiMax];                // grads_out of it
+    unsigned long long *n_unique[kMultiMax];      // where its |U| goes
+};
+
+// Like the other units' kernels these live in a code object of their own: this file compiled with -DPIMEMB_GRAD_SPARSE_MULTI_UNIT into
+// libpimemb_grad_sparse_multi.so (csrc/Makefile), which exports their launch function; libpimemb_grad.so's host side calls it.
+#ifdef PIMEMB_GRAD_SPARSE_MULTI_UNIT
+
+__global__ __launch_bounds__(64) void grad_multi_sparse_bounds(const MultiArgs m, const SparseMultiArgs so, const uint32_t *keys, const uint32_t *uidx,
+                                                               const uint32_t *usums, const unsigned long long *total, uint32_t *ubase) {
+    const uint32_t j = min(threadIdx.x, m.k);    // (lanes beyond k repeat lane k's search: every lane reaches the shuffle)
+    const uint32_t base = j < m.k ? m.d[min(j, kMultiMax - 1u)].key_base : m.key_end;
+    uint32_t lo = 0, hi = m.n;                   // the first place whose key is >= base lies in [lo, hi]; hi == n: there is none
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] < base) lo = mid + 1;
+        else hi = mid;
+    }
+    const uint32_t ub = lo < m.n ? uidx[lo] + usums[lo / kTile] : (uint32_t)*total;
+    const uint32_t next = (uint32_t)__shfl_down((int)ub, 1);
+    if (threadIdx.x <= m.k) ubase[j] = ub;
+    if (threadIdx.x < m.k) *so.n_unique[j] = (unsigned long long)(next - ub);
+}
+
+template <bool SEG>
+__global__ __launch_bounds__(kBlock) void grad_multi_sparse_rows(const MultiArgs m, const SparseMultiArgs so, const uint32_t *keys, const uint32_t *vals,
+                                                                 const uint32_t *bagof, const uint32_t *cnt, const uint32_t *uidx, const uint32_t *usums,
+                                                                 const uint32_t *ubase, SegArgs sg, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t i64 = gid >> lanes_log2;
+    const uint32_t lg = (uint32_t)gid & (lanes - 1);
+    if (i64 >= m.n || lg >= chunks) return;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t key = keys[i];
+    if (key >= m.key_end || (i > 0 && keys[i - 1] == key)) return;        // (uniform over the lane group)
+    uint32_t k = 0;
+    for (uint32_t j = 1; j < m.k; j++)           // (uniform trip count; the bases ascend)
+        if (m.d[j].key_base <= key) k = j;
+    const MultiDesc &d = m.d[k];
+    RowArgs a{};                                 // the walk's half; what a step uses of RowArgs stays unused
+    a.keys = keys;
+    a.vals = vals;
+    a.bagof = bagof;
+    a.cnt = cnt + d.bag_base;
+    a.weights = d.weights ? d.weights - d.pos_base : nullptr;             // (vals[] hold positions of the group)
+    a.grad = d.grad;
+    a.ld = d.ld;
+    a.n = m.n;
+    a.n_bags = d.n_bags;
+    a.nr_rows = d.nr_rows;
+    a.dim = m.dim;
+    a.coef = d.coef;
+    for (uint32_t c = lg; c < chunks; c += lanes) {                       // (two rounds beyond dim 256 only)
+        const float4 acc = SEG ? seg_walk_piece(a, sg, i, key, c, chunks) : walk_piece(a, i, key, c);
+        asm volatile("" ::: "memory");           // (no instruction: the loads below stay below the walk, out of its registers)
+        const uint32_t u = min(uidx[i] + usums[i / kTile] - ubase[k], d.n - 1u);      // the output's half: this run's number in ITS table's list
+        if (c == 0) so.rows[k][u] = (long long)(key - d.key_base);
+        *reinterpret_cast<float4 *>(so.grads[k] + (uint64_t)u * m.dim + 4u * c) = acc;
+    }
+}
+
+}  // namespace
+
+// The launch function libpimemb_grad_sparse_multi.so exports (plain C; MultiArgs, SparseMultiArgs and SegArgs are this file's own, which every
+// compilation lays out alike).  The two launches that end a group's chain, in the context's order (seg: behind grad_seg_multi_partials):
+// the bounds, then the rows.  `total` is where the head scan left the group's number of unique runs, `ubase` 17 words of the context's own.
+// Errors are left to the caller's hipGetLastError().
+extern "C" __attribute__((visibility("default"))) void pimemb_grad_sparse_multi_launch(const void *multi_args, const void *sparse_multi_args, const uint32_t *keys,
+                                                                                        const uint32_t *vals, const uint32_t *bagof, const uint32_t *cnt,
+                                                                                        const uint32_t *uidx, const uint32_t *usums,
+                                                                                        const unsigned long long *total, uint32_t *ubase, const void *seg_args,
+                                                                                        int seg, uint32_t lanes, uint32_t lanes_log2, uint32_t chunks,
+                                                                                        uint32_t blocks, void *stream) {
+    const MultiArgs &m = *static_cast<const MultiArgs *>(multi_args);
+    const SparseMultiArgs &so = *static_cast<const SparseMultiArgs *>(sparse_multi_args);
+    const SegArgs &sg = *static_cast<const SegArgs *>(seg_args);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid(blocks), block(kBlock);
+    grad_multi_sparse_bounds<<<dim3(1), dim3(64), 0, s>>>(m, so, keys, uidx, usums, total, ubase);
+    if (seg) grad_multi_sparse_rows<true><<<grid, block, 0, s>>>(m, so, keys, vals, bagof, cnt, uidx, usums, ubase, sg, lanes, lanes_log2, chunks);
+    else grad_multi_sparse_rows<false><<<grid, block, 0, s>>>(m, so, keys, vals, bagof, cnt, uidx, usums, ubase, sg, lanes, lanes_log2, chunks);
+}
+
+namespace {
+#else      // libpimemb_grad.so (and the other units, which never call it): the launcher is libpimemb_grad_sparse_multi.so's
+}  // namespace
+extern "C" void pimemb_grad_sparse_multi_launch(const void *multi_args, const void *sparse_multi_args, const uint32_t *keys, const uint32_t *vals,
+                                                const uint32_t *bagof, const uint32_t *cnt, const uint32_t *uidx, const uint32_t *usums,
+                                                const unsigned long long *total, uint32_t *ubase, const void *seg_args, int seg, uint32_t lanes,
+                                                uint32_t lanes_log2, uint32_t chunks, uint32_t blocks, void *stream);
+namespace {
+#endif
+
 // ---- the master-weight Adam steps: M', V' as in the Adam steps, P' = P - (ss * x) or P - (rate * M'), W = enc_T(P') ---------------------------
 // (include/pimemb_grad.h, THE MASTER-WEIGHT ADAM STEPS.)  The same pre-pass, sort, segment launch, run walk and exits; the row-wise butterfly
 // and V[r] as in the Adam kernels; the encoders and the MXFP4 row assembly as in the master kernels (master_store_piece, master_mx_row).  What
@@ -2589,7 +2709,16 @@ struct SparseOut {               // where emb_grad_sparse writes; all NULL for a
     long long *rows = nullptr;
     float *grads = nullptr;
     unsigned long long *n_unique = nullptr;
+    // emb_grad_sparse_multi: the call's arrays, one entry per descriptor (a group takes its members'; a chain of one gets the three above)
+    int64_t *const *rows_of = nullptr;
+    float *const *grads_of = nullptr;
+    uint64_t *n_unique_of = nullptr;
 };
+
+// Where a group of emb_grad_sparse_multi keeps its words in the context's 256-byte counter block (uint64 words 0 and 1 are the bad and the
+// unencodable count): the head scan's total in uint64 word 8, the up to 17 ubase words from byte 128 on.
+constexpr uint32_t kSparseTotalWord = 8, kSparseUbaseByte = 128;
+static_assert(kSparseTotalWord * 8 + 8 <= kSparseUbaseByte && kSparseUbaseByte + (kMultiMax + 1) * 4 <= kCounterBytes, "inside the counter block");
 
 // THE predicate for "this descriptor runs on the lane-group kernel" (for RES_ROWWISE: whether it runs at all).  Evaluated once per
 // descriptor, into Planned::lane: the row-wise refusal, emb_grad_multi_shape::lane_group and the chain's kernel all read that.
@@ -2764,7 +2893,7 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
     const dim3 block(kBlock), pos_grid((n + kBlock - 1) / kBlock);
     unsigned long long *bad = &g->counters[0];
     MultiArgs m;                                 // (filled for a group only)
-    if (c.mean && c.n_bags && (spec.masters || spec.sr || spec.adam)) pimemb_grad_master_clear(sc.cnt, c.n_bags, s);      // (a kernel: the note at grad_master_clear)
+    if (c.mean && c.n_bags && (spec.masters || spec.sr || spec.adam || out.n_unique_of)) pimemb_grad_master_clear(sc.cnt, c.n_bags, s);      // (a kernel: the note at grad_master_clear)
     else if (c.mean && c.n_bags) GRAD_HIP(hipMemsetAsync(sc.cnt, 0, (size_t)c.n_bags * 4, s));
     if (group) {
         fill_multi(m, descs, states, p, first);
@@ -2798,6 +2927,24 @@ int run_chain(emb_grad *g, const emb_grad_desc *descs, float *const *states, con
         for (uint32_t at = first, j = 0; at < c.end; at++)      // (the j of fill_multi: the non-empty descriptors in order)
             if (descs[at].n_indices) am.m[j] = spec.adam->m[at], am.v[j] = spec.adam->v[at], j++;
         pimemb_grad_adam_multi_launch(&m, &am, keys, vals, sc.bagof, sc.cnt, &sg, spec.adam->kind, seg, l.lanes, l.lanes_log2, l.chunks, l.blocks, s);
+        GRAD_HIP(hipGetLastError());
+        return EMB_OK;
+    }
+    if (group && spec.kind == RES_SPARSE) {      // emb_grad_sparse_multi: the head scan over the composite keys, then the unit's two launches
+        const uint32_t tiles = (uint32_t)tiles_of(n);
+        unsigned long long *total = &g->counters[kSparseTotalWord];
+        grad_scan_chunks<true><<<dim3(tiles), block, 0, s>>>(keys, n, c.key_end, sc.uidx, sc.sums);
+        grad_scan_sums<<<dim3(1), block, 0, s>>>(sc.sums, tiles, total);
+        if (seg) grad_seg_multi_partials<<<dim3(l.blocks), block, 0, s>>>(m, keys, vals, sc.bagof, sc.cnt, sg, l.lanes, l.lanes_log2, l.chunks);
+        GRAD_HIP(hipGetLastError());
+        SparseMultiArgs so{};
+        for (uint32_t at = first, j = 0; at < c.end; at++)      // (the j of fill_multi: the non-empty descriptors in order)
+            if (descs[at].n_indices)
+                so.rows[j] = reinterpret_cast<long long *>(out.rows_of[at]), so.grads[j] = out.grads_of[at],
+                so.n_unique[j] = reinterpret_cast<unsigned long long *>(out.n_unique_of + at), j++;
+        pimemb_grad_sparse_multi_launch(&m, &so, keys, vals, sc.bagof, sc.cnt, sc.uidx, sc.sums, total,
+                                        reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(g->counters) + kSparseUbaseByte), &sg, seg, l.lanes,
+                                        l.lanes_log2, l.chunks, l.blocks, s);
         GRAD_HIP(hipGetLastError());
         return EMB_OK;
     }
@@ -3029,6 +3176,55 @@ int emb_grad_sparse(emb_grad *g, const emb_grad_desc *desc, emb_index_type itype
     }
     const SparseOut out{reinterpret_cast<long long *>(rows_out), grads_out, reinterpret_cast<unsigned long long *>(n_unique_dev)};
     return run_chain(g, desc, nullptr, &p, 0, itype == EMB_IDX_I64, StepSpec{}, out, s);
+}
+
+int emb_grad_sparse_multi(emb_grad *g, const emb_grad_desc *descs, uint32_t n_descs, emb_index_type itype, int64_t *const *rows_out,
+                          float *const *grads_out, const uint64_t *capacity, uint64_t *n_unique_dev, void *stream) {
+    const char *who = "emb_grad_sparse_multi";
+    if (!g) return fail(EMB_ERR_INVALID, "%s: context is NULL", who);
+    if (n_descs && (!descs || !rows_out || !grads_out || !capacity)) return fail(EMB_ERR_INVALID, "%s: descs, rows_out, grads_out or capacity is NULL", who);
+    if (itype != EMB_IDX_U32 && itype != EMB_IDX_I64) return fail(EMB_ERR_INVALID, "%s: bad index type", who);
+    if (!n_unique_dev || (uintptr_t)n_unique_dev % 8) return fail(EMB_ERR_INVALID, "%s: n_unique_dev is NULL or not 8-byte aligned", who);
+    // the plan: emb_grad_sparse's checks on every descriptor, in order, then the groups; rule 1 is lane_group_path with this descriptor's grads_out
+    std::vector<Planned> plan(n_descs);
+    std::vector<emb_grad_multi_shape> ms(n_descs);
+    std::vector<uint32_t> group_of(n_descs);
+    bool any_empty = false;
+    for (uint32_t k = 0; k < n_descs; k++) {
+        const emb_grad_desc &d = descs[k];
+        Planned &p = plan[k];
+        if (int rc = check_desc(g, d, itype, nullptr, who, &p.t)) return rc;
+        if (capacity[k] < d.n_indices)
+            return fail(EMB_ERR_INVALID, "%s: room for %llu rows, %llu indices may name as many", who, (unsigned long long)capacity[k],
+                        (unsigned long long)d.n_indices);
+        if (d.n_indices && (!rows_out[k] || !grads_out[k] || (uintptr_t)rows_out[k] % 8 || (uintptr_t)grads_out[k] % 4))
+            return fail(EMB_ERR_INVALID, "%s: rows_out or grads_out is NULL or not naturally aligned", who);
+        p.lane = lane_group_path(d, p.t, RES_SPARSE, nullptr, d.n_indices ? grads_out[k] : nullptr);
+        ms[k] = emb_grad_multi_shape{d.table_id, p.t.dim, p.lane ? 1u : 0u, p.t.nr_rows, d.n_indices, d.n_bags};
+        any_empty = any_empty || d.n_indices == 0;
+    }
+    emb_grad_multi_groups(ms.data(), n_descs, g->max_indices, g->max_bags, group_of.data());
+    for (uint32_t k = 0, end; k < n_descs; k = end) {
+        end = k + 1;             // (a group's members are consecutive but for the empty descriptors among them)
+        if (descs[k].n_indices == 0) continue;
+        while (end < n_descs && (group_of[end] == group_of[k] || descs[end].n_indices == 0)) end++;
+        if (int rc = plan_chain(g, descs, plan.data(), k, end)) return rc;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(g->device);
+    if (any_empty) {             // |U| = 0 for the empty descriptors: the whole array cleared by a kernel (the note at grad_master_clear), the rest rewritten
+        pimemb_grad_master_clear(reinterpret_cast<uint32_t *>(n_unique_dev), 2u * n_descs, s);
+        GRAD_HIP(hipGetLastError());
+    }
+    SparseOut out{};
+    out.rows_of = rows_out, out.grads_of = grads_out, out.n_unique_of = n_unique_dev;
+    for (uint32_t k = 0; k < n_descs; k++) {
+        if (!plan[k].k) continue;
+        out.rows = reinterpret_cast<long long *>(rows_out[k]), out.grads = grads_out[k];      // (what a chain of one writes)
+        out.n_unique = reinterpret_cast<unsigned long long *>(n_unique_dev + k);
+        if (int rc = run_chain(g, descs, nullptr, plan.data(), k, itype == EMB_IDX_I64, StepSpec{}, out, s)) return rc;
+    }
+    return EMB_OK;
 }
 
 }  // extern "C"

@@ -523,6 +523,42 @@ class GradContext:
         finally:
             self._free((rows_b, grads_b, count_b, *keep))
 
+    def sparse_grads(self, table_ids, indices, offsets, grads, modes="sum", per_sample_weights=None, padding_idx=None, stream: int | None = None,
+                     fixed_pooling: int = 0) -> list:
+        """[(rows, grads), ...]: sparse_grad of every table, by the multi-table call (emb_grad_sparse_multi) -- one pre-pass and one launch
+        chain per group of tables (multi_groups; here lane_group also asks for a 16-byte aligned output, which the buffers made here are), the
+        same bytes as sparse_grad table after table.  Arguments as sgd_step takes them: one entry per table; modes, per_sample_weights and
+        padding_idx one value for all or one per table; a gradient may be a column view of a [B, T*dim] buffer.  Torch CUDA tensors: read
+        in place, tensors come back after ONE wait, for all counts; numpy arrays: copied to the device and back."""
+        keep, outs = [], []
+        try:
+            arr, n, itype, dev, stream = self._step_descs(table_ids, indices, offsets, grads, modes, per_sample_weights, padding_idx, fixed_pooling,
+                                                          stream, keep)
+            sizes = [(int(arr[k].n_indices), self.engine.table_info(table_ids[k])[2]) for k in range(n)]
+            rows_p, grads_p, caps = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))(), (C.c_uint64 * max(n, 1))()
+            if dev:
+                import torch
+                device = indices[0].device
+                outs = [(torch.empty((m,), dtype=torch.int64, device=device), torch.empty((m, dim), dtype=torch.float32, device=device)) for m, dim in sizes]
+                counts = torch.zeros((max(n, 1),), dtype=torch.int64, device=device)
+                for k, (r, g) in enumerate(outs):
+                    rows_p[k], grads_p[k], caps[k] = r.data_ptr(), g.data_ptr(), sizes[k][0]
+                _l.check_grad(self._G.emb_grad_sparse_multi(self._h, arr, n, itype, rows_p, grads_p, caps, counts.data_ptr(), stream))
+                us = counts.tolist()         # the one wait
+                return [(r[:u], g[:u]) for (r, g), u in zip(outs, us)]
+            outs = [(DeviceBuffer(self.engine, max(m, 1) * 8, np.int64, (max(m, 1),)),
+                     DeviceBuffer(self.engine, max(m * dim, 1) * 4, np.float32, (max(m, 1), dim))) for m, dim in sizes]
+            counts_b = DeviceBuffer(self.engine, max(n, 1) * 8, np.uint64, (max(n, 1),))
+            keep.append(counts_b)
+            for k, (r, g) in enumerate(outs):
+                rows_p[k], grads_p[k], caps[k] = r.ptr, g.ptr, sizes[k][0]
+            _l.check_grad(self._G.emb_grad_sparse_multi(self._h, arr, n, itype, rows_p, grads_p, caps, counts_b.ptr, stream))
+            self.engine.synchronize(stream)
+            us = [int(u) for u in counts_b.numpy()]
+            return [(r.numpy()[:u].copy(), g.numpy()[:u].copy()) for (r, g), u in zip(outs, us)]
+        finally:
+            self._free([b for pair in outs for b in pair] + keep)
+
     def sgd_step(self, table_ids, indices, offsets, grads, lr: float, modes="sum", per_sample_weights=None, padding_idx=None,
                  stream: int | None = None, fixed_pooling: int = 0, multi: bool = False, sr=None) -> None:
         """W[r] = enc(dec(W[r]) - lr * g[r]) for every row r the batch of its table names, in place, table after table (fp32,

@@ -276,6 +276,7 @@ GRAD_SIGNATURES = {
     "emb_grad_create_ex": (C.c_int, [_vp, _u64, _u64, C.POINTER(EmbGradConfig), _pp]),
     "emb_grad_config_of": (C.c_int, [_vp, C.POINTER(EmbGradConfig)]),
     "emb_grad_sparse": (C.c_int, [_vp, C.POINTER(EmbGradDesc), C.c_int, _vp, _vp, _u64, _vp, _vp]),
+    "emb_grad_sparse_multi": (C.c_int, [_vp, C.POINTER(EmbGradDesc), _u32, C.c_int, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _vp, _vp]),
     "emb_grad_sgd": (C.c_int, [_vp, C.POINTER(EmbGradDesc), _u32, C.c_int, C.c_float, _vp]),
     "emb_grad_report": (C.c_int, [_vp, C.POINTER(_u64)]),
     "emb_opt_state_floats": (_u64, [_u32, _u64, _u32]),
@@ -373,9 +374,9 @@ def load_grad() -> C.CDLL:
     if _grad_lib is not None:          # (load() came here itself)
         return _grad_lib
     from .build import (GRAD_ADAM_LIB_PATH, GRAD_ADAM_MULTI_LIB_PATH, GRAD_LIB_PATH, GRAD_MASTER_ADAM_LIB_PATH, GRAD_MASTER_LIB_PATH, GRAD_MAX_LIB_PATH,
-                        GRAD_SR_LIB_PATH)
+                        GRAD_SPARSE_MULTI_LIB_PATH, GRAD_SR_LIB_PATH)
     for dep in (GRAD_MASTER_LIB_PATH, GRAD_SR_LIB_PATH, GRAD_MAX_LIB_PATH, GRAD_ADAM_LIB_PATH, GRAD_MASTER_ADAM_LIB_PATH,
-                GRAD_ADAM_MULTI_LIB_PATH):      # libpimemb_grad.so links against all six (RUNPATH $ORIGIN): name the one that is missing
+                GRAD_ADAM_MULTI_LIB_PATH, GRAD_SPARSE_MULTI_LIB_PATH):      # libpimemb_grad.so links against all seven (RUNPATH $ORIGIN): name the one that is missing
         if not os.path.exists(dep):
             raise FileNotFoundError(
                 f"{dep} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "

@@ -1372,6 +1372,22 @@ class FusedPoolingEmbeddingBags(torch.nn.Module):
         self._adagrad(idx, off, g, float(lr), float(eps), ws, multi=multi_table, order=order, sr_seed=int(sr_seed) if stochastic_rounding else False)
         return self
 
+    def sparse_grads(self, lS_o, lS_i, grad_output, lS_w=None, col: int = 0, order: str = "position"):
+        """The sparse gradient of every table in ONE multi-table call (emb_grad_sparse_multi): a list of (rows, grads) in module order -- rows
+        int64 ascending, grads float32 [len(rows), m_k], what nn.EmbeddingBag(sparse=True) leaves in weight.grad after .coalesce() -- None where
+        a table has no gradient.  For the optimizers this library does not fuse.  grad_output as sgd_step_ takes it: the ONE [B, sum(m)]
+        gradient of a concat=True forward is read in place (from column col).  One host wait, for all counts."""
+        if "max" in self._modes:
+            raise ValueError("sparse_grads covers the sum / mean tables: a mode='max' table has no multi-table form of the max-mode backward")
+        idx, off, ws, g = self._inputs_on_device(lS_o, lS_i, grad_output, lS_w)
+        out = [None] * len(self.bags)
+        call = self._live_grads(idx, off, g, ws, col, True, order)
+        if call is not None:
+            ctx, args, kw, live = call
+            for k, pair in zip(live, ctx.sparse_grads(*args, **kw)):
+                out[k] = pair
+        return out
+
     def update_rows_(self, table: int, ids, rows):
         """PoolingEmbeddingBag.update_rows_ on table number `table` of the model (its position in the module list)."""
         self.bags[table].update_rows_(ids, rows)
